@@ -13,8 +13,14 @@ reported separately. The B GCs of the online phase are garbled once and
 re-encoded every step; a step's work (encode, H2D, evaluate, D2H, decode for B
 inferences) is the same as on fresh GCs. (A rolling per-group pipeline of the
 steps, each group's decode and next encode overlapping the others' runs, measured
-no faster: 2246 vs 2300 inf/s, the GPU is the bound.) Two further phases run after the
-timed loop and are reported beside the headline, never instead of it:
+no faster: 2246 vs 2300 inf/s, the GPU is the bound.)
+
+A plain run (``--gpus N --steps K --warmup W``) garbles the GCs, warms up, times the K
+steps and prints the record; ``--dump-outputs DIR`` also writes the last timed step's
+decoded outputs to ``DIR/logits.npy``. Everything else is behind ``--full``: the check of
+the outputs against the plaintext model, the host-thread sweep, the batch-1 latencies, and
+two further phases that run after the timed loop and are reported beside the headline,
+never instead of it:
 
 * ``reference``: the same loop with the reference's gadget constructions
   (legacy l-fold sign-base-extension rescale rescale_gadget.h:115-242,
@@ -47,6 +53,8 @@ import numpy as np
 
 BASELINE_LATENCY_MS = 1443.0  # RTX 4090, DASH GPU, MiniONN, batch 1, fresh GC
 BASELINE_INF_PER_S = 1000.0 / BASELINE_LATENCY_MS
+
+FULL_PHASES = "main,threads,latency,latency_ref,reference,served"  # what --full runs by default
 
 CONSTRUCTIONS = {
     # the framework's fastest exact-on-the-guarded-range constructions (headline)
@@ -86,8 +94,17 @@ def parse_args(argv=None) -> argparse.Namespace:
                     default=os.environ.get("DASH_BENCH_REHEARSAL", "") == "1",
                     help="allow more ranks than visible GPUs (ranks share devices over gloo). A rehearsal of the "
                          "multi-rank path, never a scaling measurement; the record says so")
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps of the headline loop")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the check of the outputs against the plaintext "
+                         "model (--verify) and the phases of --phases. Without it a run sets up, warms up, times "
+                         "--steps steps and prints the record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/logits.npy: the "
+                         "decoded output values of every GC, float64, shape (ranks, GCs per GPU, outputs). The "
+                         "inputs are seeded: two runs with the same arguments and the same number of GCs (--batch "
+                         "pins it) write equal files")
     ap.add_argument("--batch", type=int, default=int(os.environ.get("DASH_BENCH_BATCH", "0")),
                     help="GCs evaluated together per GPU (0: as many as HBM holds, a multiple of --streams)")
     ap.add_argument("--constructions", default=os.environ.get("DASH_BENCH_CONSTRUCTIONS", "flagship"),
@@ -108,18 +125,19 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--no-mfma", action="store_true")
     ap.add_argument("--profile", action="store_true", help="print per-layer GPU times")
     ap.add_argument("--threads", type=int, default=0, help="host threads per rank (0: cores / local ranks)")
-    ap.add_argument("--verify", type=int, default=1)
+    ap.add_argument("--verify", type=int, default=None,
+                    help="1: the first warm-up step's and the last timed step's outputs are checked against the exact "
+                         "plaintext model (the default with --full, and only there); 0: no check")
     ap.add_argument("--pipeline", type=int, default=int(os.environ.get("DASH_BENCH_PIPELINE", "1")),
                     help="1: a group's next step is encoded and launched as soon as its outputs of the current step "
                          "are fetched and decoded (the other groups keep the GPU busy meanwhile); 0: step by step")
     ap.add_argument("--garble-device", type=int, default=int(os.environ.get("DASH_BENCH_GARBLE_DEVICE", "1")),
                     help="garble on this rank's GPU (byte-identical to the host garbler)")
-    ap.add_argument("--phases",
-                    default=os.environ.get("DASH_BENCH_PHASES", "main,threads,latency,latency_ref,reference,served"),
-                    help="comma list of main, threads, latency (flagship, batch 1: device and wire-form input "
-                         "encoding), latency_ref (batch 1, the reference's constructions and encoding, wire-form "
+    ap.add_argument("--phases", default=None,
+                    help="with --full: comma list of main, threads, latency (flagship, batch 1: device and wire-form "
+                         "input encoding), latency_ref (batch 1, the reference's constructions and encoding, wire-form "
                          "input: the like-for-like comparison with its 1443 ms), reference, served (main is always "
-                         "run)")
+                         f"run; default: DASH_BENCH_PHASES or {FULL_PHASES}). Without --full only main runs")
     ap.add_argument("--thread-sweep", default="4,8",
                     help="host thread budgets of the threads phase (headline loop re-timed at each)")
     ap.add_argument("--latency-gcs", type=int, default=8, help="fresh GCs timed one by one in the latency phase")
@@ -136,7 +154,22 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--served-requests", type=int, default=64, help="online batches of the served phase")
     ap.add_argument("--served-min-s", type=float, default=10.0,
                     help="the served phase keeps issuing requests until it has run this long (steady state)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.full:
+        args.phases = args.phases or os.environ.get("DASH_BENCH_PHASES", FULL_PHASES)
+        args.verify = 1 if args.verify is None else args.verify
+    else:
+        # a plain run does what the headline figure needs and nothing else; asking for more without --full is an
+        # error, never silently dropped
+        extra = sorted({p.strip() for p in (args.phases or "").split(",") if p.strip()} - {"main"})
+        if extra:
+            ap.error(f"--phases {','.join(extra)} needs --full")
+        if args.verify:
+            ap.error("--verify needs --full")
+        args.phases, args.verify = "main", 0
+    return args
 
 
 # ----------------------------------------------------------------------------------------- rank launcher
@@ -767,6 +800,11 @@ def run(argv=None) -> Optional[dict]:
     elapsed = r["elapsed"]
     gathered = all_gather_array(ctx, np.stack(r["last"]))  # decoded logits of the last step onto every rank
     assert gathered.shape[0] == world
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received in the last timed step: every GC's decoded outputs (signed
+        # integers below the CRT modulus, 510510 for the headline: float64 holds them exactly); a few KB
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), np.asarray(gathered, dtype=np.float64))
     total_inf = world * B * args.steps
     value = total_inf / elapsed
     ms_step = 1000.0 * elapsed / args.steps
@@ -843,6 +881,7 @@ def run(argv=None) -> Optional[dict]:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(ms_step, 3),
             "ms_per_inference": round(1000.0 * elapsed / (B * args.steps), 3),
             "latency_ms_per_batch": round(ms_step, 3),
@@ -899,7 +938,9 @@ def run(argv=None) -> Optional[dict]:
                                  "hardened encoding); vs_baseline_b1_reference = 1443 ms / latency_b1_reference_ms "
                                  "(the reference's constructions and encoding, host-encoded input labels: the exact "
                                  "like-for-like); vs_baseline_throughput = value / (1 / 1.443 s), batched throughput "
-                                 "over the reference's batch-1 rate"),
+                                 "over the reference's batch-1 rate") if lat is not None else
+                                "vs_baseline = vs_baseline_throughput = value / (1 / 1.443 s), batched throughput over "
+                                "the reference's batch-1 rate (no latency phase in this run; --full measures it)",
             "dist_backend": ctx.backend if ctx.distributed else "none",
             "world_size": world,
             "rehearsal_shared_device": rehearsal and world > 1,

@@ -7,10 +7,10 @@ T=${1:-ab}; shift
 OUT=gpurun_out/$T
 mkdir -p "$OUT"
 PH=${PHASES:-main,latency}
-timeout -k 10 300 python bench.py --steps "${STEPS:-20}" --warmup 5 --phases "$PH" > "$OUT/a.json" 2> "$OUT/a.err" \
+timeout -k 10 300 python bench.py --steps "${STEPS:-20}" --warmup 5 --full --phases "$PH" > "$OUT/a.json" 2> "$OUT/a.err" \
     || { tail -20 "$OUT/a.err"; exit 1; }
 if [ $# -gt 0 ]; then
-    env "$@" timeout -k 10 300 python bench.py --steps "${STEPS:-20}" --warmup 5 --phases "$PH" > "$OUT/b.json" \
+    env "$@" timeout -k 10 300 python bench.py --steps "${STEPS:-20}" --warmup 5 --full --phases "$PH" > "$OUT/b.json" \
         2> "$OUT/b.err" || { tail -20 "$OUT/b.err"; exit 1; }
 fi
 for f in a b; do

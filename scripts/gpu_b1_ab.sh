@@ -10,7 +10,7 @@ OUT=gpurun_out/$T
 mkdir -p "$OUT"
 for i in $(seq 1 "$PAIRS"); do
     for v in "$A" "$B"; do
-        env "$VAR=$v" timeout -k 10 300 python bench.py --steps 3 --warmup 1 --batch 16 --phases latency --latency-gcs 16 \
+        env "$VAR=$v" timeout -k 10 300 python bench.py --steps 3 --warmup 1 --batch 16 --full --phases latency --latency-gcs 16 \
             > "$OUT/${VAR}_${v}_$i.json" 2> "$OUT/${VAR}_${v}_$i.err" || { tail -20 "$OUT/${VAR}_${v}_$i.err"; exit 1; }
         python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d.get('latency_b1_ms'), d['value'])" \
             "$OUT/${VAR}_${v}_$i.json" "$VAR=$v"

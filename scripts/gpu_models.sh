@@ -10,7 +10,7 @@ for mc in MODEL_F_GNNP_POOL_REPL:DASH MODEL_F_MINIONN_POOL_REPL:REDASH_OPT MODEL
           LENET5:DASH MODEL_A:DASH VGG16:DASH RESNET18:DASH; do
     m=${mc%%:*} c=${mc##*:}
     timeout -k 10 420 python bench.py --model "$m" --config "$c" --steps "${STEPS:-10}" --warmup 2 \
-        --phases main,latency --latency-gcs 4 > "$OUT/$m.$c.json" 2> "$OUT/$m.$c.err" \
+        --full --phases main,latency --latency-gcs 4 > "$OUT/$m.$c.json" 2> "$OUT/$m.$c.err" \
         || { echo "$m $c failed"; tail -15 "$OUT/$m.$c.err"; exit 1; }
     cat "$OUT/$m.$c.json" >> "$OUT/models.jsonl"
     python3 -c "

@@ -24,7 +24,7 @@ if [ "${SKIP_GARBLE:-0}" != 1 ]; then
     cat "$OUT/garble_models.jsonl"
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-    timeout -k 10 900 python bench.py --steps "${STEPS:-20}" --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+    timeout -k 10 900 python bench.py --steps "${STEPS:-20}" --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
         || { tail -20 "$OUT/bench.err"; exit 1; }
     cat "$OUT/bench.json"
 fi

@@ -7,7 +7,7 @@ ROOT=$(pwd)
 RE='k_sign_chain|k_rescale_update_approx|k_sign_castsum|k_sign_approx'
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 1 --warmup 0 --batch 1 --streams 1 --verify 0 --phases latency_ref --latency-gcs 2"
+ARGS="--steps 1 --warmup 0 --batch 1 --streams 1 --verify 0 --full --phases latency_ref --latency-gcs 2"
 timeout -s KILL 300 rocprofv3 --kernel-trace --kernel-include-regex "$RE" \
     --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU \
     --output-format csv -d "$ROOT/$OUT/a" -o run -- python3 "$ROOT/bench.py" $ARGS > "$ROOT/$OUT/a.log" 2>&1

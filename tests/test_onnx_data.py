@@ -1,10 +1,11 @@
 """ONNX import/export and dataset readers.
 
 Reference coverage: dash/test/test_onnx_modelloader.h (fixture
-dash/test/fixtures/model_dense.onnx, read here in place — it is a data file,
-decoded by our own protobuf reader; expected weights copied from the test).
+dash/test/fixtures/model_dense.onnx, kept as tests/golden/model_dense.onnx — it
+is a data file, decoded by our own protobuf reader; expected weights copied
+from the test).
 """
-import os
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -16,10 +17,9 @@ from dash_amd.ir.circuit import Circuit
 from dash_amd.ir.onnx import load_onnx_model, parse_onnx, save_onnx_model
 from dash_amd.ir.quant import QuantizationMethod as Q
 
-FIXTURE = "/root/reference/dash/test/fixtures/model_dense.onnx"
+FIXTURE = str(Path(__file__).resolve().parent / "golden" / "model_dense.onnx")
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference fixture not mounted")
 def test_reference_dense_fixture():
     c = load_onnx_model(FIXTURE, Q.SimpleQuant, 10)
     assert c.input_dims == (1, 28, 28)
@@ -35,7 +35,6 @@ def test_reference_dense_fixture():
     assert b[-1] == np.float32(-0.02649968676269054412841796875)
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference fixture not mounted")
 def test_reference_fixture_scalequant_inserts_rescale():
     c = load_onnx_model(FIXTURE, Q.ScaleQuant, 3)
     assert [type(l).__name__ for l in c.layers] == ["Flatten", "Dense", "Rescale"]

@@ -58,7 +58,7 @@ def _bench_worker(rank, world, port, q, local_rank=None, env=None):
     from dash_amd import benchcore
 
     out = benchcore.run(["--backend", "cpu", "--gpus", str(world), "--model", "MODEL_A", "--batch", "2", "--streams",
-                         "1", "--steps", "2", "--warmup", "1", "--phases", "main,served", "--served-slots", "2",
+                         "1", "--steps", "2", "--warmup", "1", "--full", "--phases", "main,served", "--served-slots", "2",
                          "--served-groups", "2", "--served-requests", "1", "--served-min-s", "0"])
     q.put((rank, out))
 
@@ -217,7 +217,7 @@ def test_bench_cli_spawns_ranks():
     import json
 
     p = _run_bench_cli(["--backend", "cpu", "--gpus", "4", "--model", "MODEL_A", "--batch", "2", "--streams", "1",
-                        "--steps", "2", "--warmup", "1", "--phases", "main,latency", "--latency-gcs", "2"])
+                        "--steps", "2", "--warmup", "1", "--full", "--phases", "main,latency", "--latency-gcs", "2"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -261,7 +261,7 @@ def test_bench_pipelined_groups_verified(pipeline, monkeypatch):
     from dash_amd import benchcore
 
     out = benchcore.run(["--backend", "cpu", "--gpus", "1", "--model", "MODEL_A", "--batch", "4", "--streams", "2",
-                         "--steps", "3", "--warmup", "2", "--phases", "main", "--pipeline", str(pipeline)])
+                         "--steps", "3", "--warmup", "2", "--full", "--phases", "main", "--pipeline", str(pipeline)])
     assert out["pipelined_steps"] == bool(pipeline)
     assert out["config"]["streams"] == 2 and out["config"]["global_batch"] == 4
     assert out["verified_vs_plaintext"] and out["verified_last_timed_step"]
