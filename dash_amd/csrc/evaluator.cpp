@@ -182,7 +182,8 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                             const i64 f = o / (G.OH * G.OW), r = o % (G.OH * G.OW), oy = r / G.OW, ox = r % G.OW;
                             std::fill(acc.begin(), acc.end(), 0);
                             const int32_t* wf = wm.data() + f * G.K();
-                            for (i64 c = 0; c < G.C; ++c)
+                            const i64 c0 = (f / G.Fg()) * G.Cg();  // the filter's group of input channels
+                            for (i64 c = 0; c < G.Cg(); ++c)
                                 for (i64 dy = 0; dy < G.kh; ++dy)
                                     for (i64 dx = 0; dx < G.kw; ++dx) {
                                         const int32_t wv = wf[(c * G.kh + dy) * G.kw + dx];
@@ -190,7 +191,7 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                                         const i64 iy = oy * G.sh - G.ph + dy, ix = ox * G.sw - G.pw + dx;
                                         const comp_t* x = (iy < 0 || iy >= G.H || ix < 0 || ix >= G.W)
                                                               ? Zp
-                                                              : I.at((c * G.H + iy) * G.W + ix);
+                                                              : I.at(((c0 + c) * G.H + iy) * G.W + ix);
                                         for (int cc = 0; cc < mi.n; ++cc) acc[cc] += wv * x[cc];
                                     }
                             comp_t* y = O.at(o);

@@ -52,7 +52,9 @@ ConvGeom::ConvGeom(const Params& p) {
     sw = param1(p, "sw", 1);
     ph = param1(p, "ph", 0);
     pw = param1(p, "pw", 0);
+    g = param1(p, "g", 1);
     DASH_CHECK(C > 0 && H > 0 && W > 0 && F > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0, "bad conv geometry");
+    DASH_CHECK(g > 0 && C % g == 0 && F % g == 0, "conv groups must divide both C and F");
     OH = (H + 2 * ph - kh) / sh + 1;
     OW = (W + 2 * pw - kw) / sw + 1;
 }
@@ -669,7 +671,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 const auto& w = paramv(spec.p, "w");
                 const auto& b = paramv(spec.p, "b");
                 DASH_CHECK(static_cast<i64>(w.size()) == G.F * G.K() && static_cast<i64>(b.size()) == G.F, "conv weight shape");
-                const auto rw = reduced_weights(li, w, {G.F, G.C, G.kh, G.kw});
+                const auto rw = reduced_weights(li, w, {G.F, G.Cg(), G.kh, G.kw});
                 const Array& wa = rw.first;
                 g.a["w"] = wa;
                 CrtLabels nxt;
@@ -703,7 +705,8 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                             i64 zc = hard ? 0 : 1;
                             const i64 bneg = hard ? pmod(-pmod(b[f], M_), p) : 0;
                             const i64* wf = wa.ptr<i64>() + f * G.K();
-                            for (i64 c = 0; c < G.C; ++c)
+                            const i64 c0 = (f / G.Fg()) * G.Cg();  // the filter's group of input channels
+                            for (i64 c = 0; c < G.Cg(); ++c)
                                 for (i64 dy = 0; dy < G.kh; ++dy)
                                     for (i64 dx = 0; dx < G.kw; ++dx) {
                                         const i64 wv = wf[(c * G.kh + dy) * G.kw + dx] % p;
@@ -714,7 +717,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                                         const i64 iy = oy * G.sh - G.ph + dy, ix = ox * G.sw - G.pw + dx;
                                         const comp_t* x = (iy < 0 || iy >= G.H || ix < 0 || ix >= G.W)
                                                               ? Zp
-                                                              : I.at((c * G.H + iy) * G.W + ix);
+                                                              : I.at(((c0 + c) * G.H + iy) * G.W + ix);
                                         for (int cc = 0; cc < mi.n; ++cc) acc[cc] += wv * x[cc];
                                     }
                             comp_t* y = O.at(o);

@@ -3063,7 +3063,7 @@ void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, C
     std::vector<DevBlock> out = I.alloc_labels(mods, Nout);
     dev::ConvArgs a{};
     {
-        ConvPlanKey key{I.device, wh, {G.C, G.H, G.W, G.F, G.kh, G.kw, G.sh, G.sw, G.ph, G.pw}, mods};
+        ConvPlanKey key{I.device, wh, {G.C, G.H, G.W, G.F, G.kh, G.kw, G.sh, G.sw, G.ph, G.pw, G.g}, mods};
         std::lock_guard<std::mutex> lk(conv_plans_mutex());
         auto it = conv_plans().find(key);
         if (it != conv_plans().end()) {
@@ -3083,9 +3083,20 @@ void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, C
             a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
             a.Kpad = (K + 63) / 64 * 64;
             a.use_mfma = 1;
+            a.groups = static_cast<int>(G.g);
             int max_p = 0;
             for (int j = 0; j < a.crt.k; ++j) max_p = std::max(max_p, mods[j]);
-            dev::conv_plan(a, max_p, true);
+            if (G.g > 1) {
+                // grouped conv: the byte-stencil kernel, no MFMA plan
+                a.use_mfma = 0;
+                DASH_CHECK(max_p <= dev::kActMaxModulus, "gpu garbler: conv residue modulus above 255");
+                DASH_CHECK(static_cast<uint64_t>(K) * (max_p - 1) * (max_p - 1) < (1ull << 32),
+                           "grouped conv: (C/g)*kh*kw*(p-1)^2 must stay below 2^32 (32-bit accumulator)");
+                DASH_CHECK(dev::conv_grp_geometry(a) > 0,
+                           "grouped conv: one output row of a group exceeds 64 KiB of LDS");
+            } else {
+                dev::conv_plan(a, max_p, true);
+            }
             a.lab_stride = 0;
             a.img_off[0] = 0;
             for (int j = 0; j < a.crt.k; ++j) {
@@ -3093,23 +3104,29 @@ void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, C
                 DASH_CHECK(p <= dev::kActMaxModulus, "gpu garbler: conv residue modulus above 255");
                 a.lab_off[j] = p * gg::kW;
                 a.img_off[j + 1] = a.img_off[j] + n;
-                std::vector<int16_t> wm(static_cast<size_t>(F) * K);
-                std::vector<int8_t> w8(static_cast<size_t>(F) * a.Kpad, 0);
+                const bool grp = G.g > 1;  // k_conv_grp reads its own image (wg) only
+                std::vector<int16_t> wm(grp ? 0 : static_cast<size_t>(F) * K);
+                std::vector<int8_t> w8(grp ? 0 : static_cast<size_t>(F) * a.Kpad, 0);
                 std::vector<int32_t> zc(F, 1);
                 for (int f = 0; f < F; ++f)
                     for (int q = 0; q < K; ++q) {
                         const int v = static_cast<int>(w[static_cast<size_t>(f) * K + q] % p);
-                        wm[static_cast<size_t>(f) * K + q] = static_cast<int16_t>(v);
                         if (v == 0) ++zc[f];
+                        if (grp) continue;
+                        wm[static_cast<size_t>(f) * K + q] = static_cast<int16_t>(v);
                         w8[static_cast<size_t>(f) * a.Kpad + q] = static_cast<int8_t>(v > p / 2 ? v - p : v);
                     }
-                a.w[j] = gg::dconst(wm.data(), wm.size());
+                a.w[j] = grp ? nullptr : gg::dconst(wm.data(), wm.size());
                 a.zc[j] = gg::dconst(zc.data(), zc.size());
                 std::vector<int16_t> zb(static_cast<size_t>(F) * n, 0);
                 a.bias[j] = gg::dconst(zb.data(), zb.size());
                 a.w8[j] = nullptr;
                 a.w8r[j] = nullptr;
-                if (a.nbands > 0) {
+                a.wg[j] = nullptr;
+                if (G.g > 1) {
+                    const std::vector<uint32_t> wg = dev::conv_grp_weights(w, G.F, G.Cg(), a.kh, a.kw, p);
+                    a.wg[j] = gg::dconst(wg.data(), wg.size());
+                } else if (a.nbands > 0) {
                     const std::vector<int8_t> w8r = dev::conv_w8r(a, w8, F);
                     a.w8r[j] = gg::dconst(w8r.data(), w8r.size());
                 } else {

@@ -90,10 +90,11 @@ __device__ __forceinline__ int64_t run_post(const Post& P, int64_t v, bool& bad)
 struct ConvP {
     const int64_t* x;
     int64_t* y;
-    const int32_t* w;  // [F][C][kh][kw]
+    const int32_t* w;  // [F][C/groups][kh][kw]
     const int64_t* bias;
     int* flags;
     int C, H, W, F, kh, kw, sh, sw, ph, pw, OH, OW;
+    int groups;  // group q: filters [q F/g, (q+1) F/g) over channels [q C/g, (q+1) C/g)
     int64_t in_size, out_size;
     int64_t asafe;  // I24: operands |x| <= asafe keep every partial sum inside int32 (host bound, see Layer)
     Post post;
@@ -104,13 +105,16 @@ constexpr int kFB = 8;  // filters per lane (one input load feeds kFB multiply-a
 // Lanes = output pixels, padded to whole waves per (input, filter block): the filter block is wave-uniform, so
 // its weights are scalar loads (KH x KW > 0: the taps unrolled, a channel's taps merged into wide scalar loads).
 // PAD = false: no tap of a valid output pixel leaves the image (no bounds checks).
+// A filter block never spans a group: ceil((F/g) / kFB) blocks per group, the filter index clamped to the
+// group's last filter (groups = 1: the dense blocks).
 template <int KH, int KW, bool I24, bool PAD>
 __global__ __launch_bounds__(256) void k_g_conv(ConvP p, int64_t total) {
     const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (t >= total) return;
     const int OHW = p.OH * p.OW;
     const int OHWp = (OHW + 63) & ~63;
-    const int nfb = (p.F + kFB - 1) / kFB;
+    const int Fg = p.F / p.groups, Cg = p.C / p.groups;
+    const int nfbg = (Fg + kFB - 1) / kFB, nfb = p.groups * nfbg;
     const int pix = static_cast<int>(t % OHWp);
     const int64_t r = t / OHWp;
     const int fb = __builtin_amdgcn_readfirstlane(static_cast<int>(r % nfb));
@@ -118,8 +122,9 @@ __global__ __launch_bounds__(256) void k_g_conv(ConvP p, int64_t total) {
     if (pix >= OHW) return;
     const int kh = KH ? KH : p.kh, kw = KW ? KW : p.kw;
     const int oy = pix / p.OW, ox = pix - oy * p.OW;
-    const int f0 = fb * kFB;
-    const int K = p.C * kh * kw;
+    const int q = fb / nfbg;
+    const int f0 = q * Fg + (fb - q * nfbg) * kFB, flast = (q + 1) * Fg - 1;
+    const int K = Cg * kh * kw;
     const int64_t* xb = p.x + b * p.in_size;
     int64_t acc[kFB];
     int32_t a32[kFB];
@@ -127,13 +132,13 @@ __global__ __launch_bounds__(256) void k_g_conv(ConvP p, int64_t total) {
     for (int j = 0; j < kFB; ++j) acc[j] = 0, a32[j] = 0;
     const int32_t* wf[kFB];
 #pragma unroll
-    for (int j = 0; j < kFB; ++j) wf[j] = p.w + static_cast<int64_t>(min(f0 + j, p.F - 1)) * K;
+    for (int j = 0; j < kFB; ++j) wf[j] = p.w + static_cast<int64_t>(min(f0 + j, flast)) * K;
     bool wide = false;
     const int iy0 = oy * p.sh - p.ph, ix0 = ox * p.sw - p.pw;
     const int64_t HW = static_cast<int64_t>(p.H) * p.W;
 #pragma unroll 2
-    for (int c = 0; c < p.C; ++c) {
-        const int64_t* xc = xb + c * HW;
+    for (int c = 0; c < Cg; ++c) {
+        const int64_t* xc = xb + (q * Cg + c) * HW;
         const int kc = c * kh * kw;
 #pragma unroll
         for (int dy = 0; dy < kh; ++dy) {
@@ -164,7 +169,7 @@ __global__ __launch_bounds__(256) void k_g_conv(ConvP p, int64_t total) {
 #pragma unroll
     for (int j = 0; j < kFB; ++j) {
         const int f = f0 + j;
-        if (f < p.F)
+        if (f <= flast)
             yb[static_cast<int64_t>(f) * OHW + pix] =
                 run_post(p.post, (I24 ? static_cast<int64_t>(a32[j]) : acc[j]) + p.bias[f], bad);
     }
@@ -280,6 +285,7 @@ struct Layer {
     int64_t lo = 0, hi = 0, span_max = 0, S = 1, c = 0;
     int l = 0;
     int C = 0, H = 0, W = 0, F = 0, kh = 0, kw = 0, sh = 1, sw = 1, ph = 0, pw = 0, OH = 0, OW = 0;
+    int g = 1;  // conv groups
     int add_src = -1;  // G_ADD: context index of the residual
     int32_t* w = nullptr;
     int64_t* bias = nullptr;
@@ -327,6 +333,7 @@ class DevRangeGuard {
             L.C = geti("C", 0), L.H = geti("H", 0), L.W = geti("W", 0), L.F = geti("F", 0);
             L.kh = geti("kh", 0), L.kw = geti("kw", 0), L.sh = geti("sh", 1), L.sw = geti("sw", 1);
             L.ph = geti("ph", 0), L.pw = geti("pw", 0), L.OH = geti("OH", 0), L.OW = geti("OW", 0);
+            L.g = geti("g", 1);
             L.add_src = geti("add_src", -1);
             if (d.contains("post")) {
                 py::list ops = d["post"].cast<py::list>();
@@ -357,6 +364,7 @@ class DevRangeGuard {
             if (L.kind == G_CONV) {
                 DASH_CHECK(L.C > 0 && L.H > 0 && L.W > 0 && L.F > 0 && L.kh > 0 && L.kw > 0 && L.OH > 0 && L.OW > 0,
                            "DevRangeGuard: conv geometry");
+                DASH_CHECK(L.g > 0 && L.C % L.g == 0 && L.F % L.g == 0, "DevRangeGuard: conv groups must divide C and F");
                 DASH_CHECK(L.in_size == static_cast<int64_t>(L.C) * L.H * L.W &&
                                L.out_size == static_cast<int64_t>(L.F) * L.OH * L.OW,
                            "DevRangeGuard: conv sizes");
@@ -373,7 +381,7 @@ class DevRangeGuard {
                 auto w = d["w"].cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
                 auto b = d["b"].cast<py::array_t<int64_t, py::array::c_style | py::array::forcecast>>();
                 const int64_t rows = L.kind == G_CONV ? L.F : L.out_size;
-                const int64_t K = L.kind == G_CONV ? static_cast<int64_t>(L.C) * L.kh * L.kw : L.in_size;
+                const int64_t K = L.kind == G_CONV ? static_cast<int64_t>(L.C / L.g) * L.kh * L.kw : L.in_size;
                 DASH_CHECK(w.size() == rows * K && b.size() == rows, "DevRangeGuard: weight / bias shape");
                 L.w = upload(w.data(), w.size());
                 L.bias = upload(b.data(), b.size());
@@ -574,9 +582,9 @@ class DevRangeGuard {
             switch (L.kind) {
                 case G_CONV: {
                     ConvP p{in.first, y, L.w, L.bias, flags, L.C, L.H, L.W, L.F, L.kh, L.kw, L.sh, L.sw, L.ph, L.pw,
-                            L.OH, L.OW, in.second, ys, L.asafe, L.post};
+                            L.OH, L.OW, L.g, in.second, ys, L.asafe, L.post};
                     const int64_t ohwp = (static_cast<int64_t>(L.OH) * L.OW + 63) & ~int64_t(63);
-                    const int64_t total = B * ((L.F + kFB - 1) / kFB) * ohwp;
+                    const int64_t total = B * L.g * ((L.F / L.g + kFB - 1) / kFB) * ohwp;
                     hipLaunchKernelGGL(conv_kernel(L), dim3(blocks_of(total)), dim3(256), 0, st_, p, total);
                     break;
                 }

@@ -919,7 +919,221 @@ void launch_dense(const DenseArgs& a, const Act& x, const Act& y, int B, hipStre
     hipLaunchKernelGGL(k_dense, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
 }
 
+// ---------------------------------------------------------------------------
+// Grouped / depthwise conv (ConvArgs::groups > 1): a per-plane byte stencil, not a GEMM (depthwise: K = kh*kw).
+// Block = one image (gc, residue, component) x gpb consecutive groups x a band of gband output rows
+// (conv_grp_geometry). The groups' input rows are staged into LDS once, 16 bytes per load, padding written
+// with the image's Z_p byte; the tap loop then reads LDS only, without bounds checks. A lane owns 4 adjacent
+// output columns of one (filter, row): per input row it reads the covering dwords, forms the 4 windows with
+// v_alignbyte_b32 and accumulates v_dot4_u32_u8 against the weight dword of 4 dx taps (raw residues times
+// raw weights: unsigned, nothing to center). The host bounds (C/g)*kh*kw*(p-1)^2 < 2^32, so the one reduction
+// is the epilogue's. The block's weight dwords and per-filter epilogue constants (zc[f] * Z + bias) are staged
+// into LDS with the rows, so nothing after the barrier loads from global memory. Slots per filter are padded to
+// a multiple of 64 where a plane has that many: the filter is then wave-uniform and its weight reads are LDS
+// broadcasts. (Scalar loads of the weights from global memory are not what the compiler selects here: with
+// the output stores in the same loop it keeps them as vector loads with a full wait ahead of the dot4s.)
+struct __attribute__((packed, aligned(1))) Row16u {
+    u32x4c v;
+};
+// n / d from m = floor((2^32 - 1) / d) + 1 >= 2^32 / d (d > 1): the multiply-high never undershoots and
+// overshoots by at most one while n * d < 2^32, which the compare takes back
+__device__ __forceinline__ int grp_div(int n, int d, uint32_t m) {
+    if (d <= 1) return n;
+    const int q = static_cast<int>(__umulhi(static_cast<uint32_t>(n), m));
+    return q * d > n ? q - 1 : q;
+}
+__device__ __forceinline__ uint32_t grp_bmask(int nb) {  // low nb bytes set (nb <= 0: none, >= 4: all)
+    return nb <= 0 ? 0u : (nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u);
+}
+// the 4 windows of one input row against the row's weight dwords. I: the lane's first byte of the row (dword
+// aligned); KW, SW: compile-time taps per row and column stride (0: runtime kw, sw)
+template <int KW, int SW>
+__device__ __forceinline__ void grp_row(const uint8_t* I, const uint32_t* w, int kw, int sw, uint32_t (&acc)[4]) {
+    if constexpr (KW == 1 && SW > 0) {
+        // one tap: output t is byte t*SW of the row; the weight moves to that byte of its dword
+        constexpr int ND = (3 * SW) / 4 + 1;
+        uint32_t D[ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) D[i] = *reinterpret_cast<const uint32_t*>(I + 4 * i);
+        const uint32_t w0 = w[0];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            acc[t] = __builtin_amdgcn_udot4(D[(t * SW) / 4], w0 << (8 * ((t * SW) % 4)), acc[t], false);
+    } else if constexpr (KW > 0 && SW > 0) {
+        constexpr int KWD = (KW + 3) / 4, ND = (3 * SW + 4 * KWD + 3) / 4;
+        uint32_t D[ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) D[i] = *reinterpret_cast<const uint32_t*>(I + 4 * i);
+#pragma unroll
+        for (int d = 0; d < KWD; ++d) {
+            const uint32_t wd = w[d];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int o = t * SW + 4 * d;  // constant after unrolling
+                const uint32_t win = (o % 4) ? __builtin_amdgcn_alignbyte(D[(o / 4 + 1) < ND ? o / 4 + 1 : ND - 1],
+                                                                           D[o / 4], o % 4)
+                                             : D[o / 4];
+                acc[t] = __builtin_amdgcn_udot4(win, wd, acc[t], false);
+            }
+        }
+    } else {
+        const int kwd = (kw + 3) >> 2;
+        for (int d = 0; d < kwd; ++d) {
+            const uint32_t wd = w[d];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int o = t * sw + 4 * d;
+                const uint32_t lo = *reinterpret_cast<const uint32_t*>(I + (o & ~3));
+                const uint32_t hi = *reinterpret_cast<const uint32_t*>(I + (o & ~3) + 4);
+                acc[t] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(hi, lo, o & 3), wd, acc[t], false);
+            }
+        }
+    }
+}
+// one lane's 4 outputs: all channels and rows of the filter's group
+template <int KH, int KW, int SW>
+__device__ __forceinline__ void grp_item(const uint8_t* I, const uint32_t* w, int Cg, int kh, int kw, int sw, int chs,
+                                         int R, uint32_t (&acc)[4]) {
+    const int khh = KH ? KH : kh;
+    const int kwd = ((KW ? KW : kw) + 3) >> 2;
+    for (int c = 0; c < Cg; ++c) {
+#pragma unroll
+        for (int dy = 0; dy < khh; ++dy) grp_row<KW, SW>(I + dy * R, w + dy * kwd, kw, sw, acc);
+        I += chs;
+        w += khh * kwd;
+    }
+}
+
+// KH, KW, SW: compile-time taps and column stride; 0, 0, 0: the runtime-tap instance
+template <int KH, int KW, int SW>
+__global__ __launch_bounds__(256) void k_conv_grp(ConvArgs a, Act x, Act y) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t gimg[];
+    const int kh = KH ? KH : a.kh, kw = KW ? KW : a.kw, sw = SW ? SW : a.sw;
+    const int kwd = (kw + 3) >> 2;
+    unsigned bid = blockIdx.x;
+    const int band = static_cast<int>(bid % static_cast<unsigned>(a.gnbands));
+    bid /= static_cast<unsigned>(a.gnbands);
+    const int gb = static_cast<int>(bid % static_cast<unsigned>(a.gngb));
+    const int64_t gi = bid / static_cast<unsigned>(a.gngb);
+    int j = 0;
+    while (j + 1 < a.crt.k && gi >= a.img_off[j + 1]) ++j;
+    const int n = a.crt.n[j], p = a.crt.p[j];
+    const int64_t r0 = gi - a.img_off[j];
+    const int b = static_cast<int>(r0 / n), c = static_cast<int>(r0 % n);
+    const int Cg = a.C / a.groups, Fg = a.F / a.groups;
+    const int q0 = gb * a.gpb, nq = min(a.gpb, a.groups - q0);
+    const int ch0 = q0 * Cg, nch = nq * Cg, f0 = q0 * Fg, nf = nq * Fg;
+    const int oy0 = band * a.gband, nrows = min(a.OH, oy0 + a.gband) - oy0;
+    const int iy0 = oy0 * a.sh - a.ph, in_rows = (nrows - 1) * a.sh + kh;
+    const int R = a.gR, R16 = R >> 4, chs = in_rows * R;
+    const int CHW = a.C * a.H * a.W;
+    const act_t* X = x.p[j] + (static_cast<int64_t>(b) * n + c) * CHW;
+    const uint32_t zv = static_cast<uint32_t>(a.zero[static_cast<int64_t>(b) * a.lab_stride + a.lab_off[j] + c]) & 0xffu;
+    const uint32_t pad4 = zv * 0x01010101u;
+    const int tid = threadIdx.x;
+
+    // stage: item = 16 LDS bytes = padded columns [16 k16, 16 k16 + 16) of one (channel, input row)
+    // item -> (chl, row, k16) and slot -> (filter, row, column quad) by multiply-high (grp_div; the runtime
+    // divisions cost ~25 VALU each)
+    const int nstage = nch * in_rows * R16;
+    const uint32_t m16 = R16 > 1 ? 0xffffffffu / static_cast<uint32_t>(R16) + 1u : 0u;
+    const uint32_t mir = in_rows > 1 ? 0xffffffffu / static_cast<uint32_t>(in_rows) + 1u : 0u;
+    for (int it = tid; it < nstage; it += 256) {
+        const int t2 = grp_div(it, R16, m16);
+        const int k16 = it - t2 * R16;
+        const int chl = grp_div(t2, in_rows, mir);
+        const int row = t2 - chl * in_rows;
+        const int iy = iy0 + row, ix0 = k16 * 16 - a.pw;
+        const int lo = max(0, -ix0), hi = min(16, a.W - ix0);  // bytes [lo, hi) are input columns
+        uint32_t v[4] = {pad4, pad4, pad4, pad4};
+        if (iy >= 0 && iy < a.H && hi > lo) {
+            const int off = ((ch0 + chl) * a.H + iy) * a.W + ix0;
+            if (off >= 0 && off + 16 <= CHW) {
+                // the 16 bytes lie inside the image (their tail may be the next row's): one load, any
+                // alignment, the bytes outside the row masked to padding
+                const u32x4c d = reinterpret_cast<const Row16u*>(X + off)->v;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t m = grp_bmask(hi - 4 * i) & ~grp_bmask(lo - 4 * i);
+                    v[i] = (d[i] & m) | (pad4 & ~m);
+                }
+            } else {
+                // first / last bytes of the image: byte by byte
+#pragma unroll
+                for (int t = 0; t < 16; ++t)
+                    if (t >= lo && t < hi)
+                        v[t >> 2] = (v[t >> 2] & ~(0xffu << (8 * (t & 3)))) |
+                                    (static_cast<uint32_t>(X[off + t]) << (8 * (t & 3)));
+            }
+        }
+        *reinterpret_cast<u32x4c*>(gimg + static_cast<size_t>(chl * in_rows + row) * R + k16 * 16) =
+            u32x4c{v[0], v[1], v[2], v[3]};
+    }
+    // the block's weight dwords and, per filter, the epilogue constant zc[f] * Z + bias, behind the image
+    const int npp = a.gnpp;
+    const int wper = Cg * kh * kwd;  // weight dwords per filter
+    uint32_t* wl = reinterpret_cast<uint32_t*>(gimg + static_cast<size_t>(nch) * ((a.gband - 1) * a.sh + kh) * R);
+    uint32_t* kl = wl + nf * wper;
+    {
+        const uint32_t* wsrc = a.wg[j] + static_cast<int64_t>(f0) * wper;
+        for (int it = tid; it < nf * wper; it += 256) wl[it] = wsrc[it];
+        for (int it = tid; it < nf; it += 256) {
+            const int f = f0 + it;
+            const uint32_t bv = static_cast<uint16_t>(a.bias[j][(static_cast<int64_t>(b) * a.F + f) * n + c]);
+            kl[it] = static_cast<uint32_t>(a.zc[j][f]) * zv + bv;
+        }
+    }
+    __syncthreads();
+
+    const int OWq = (a.OW + 3) >> 2, nposv = nrows * OWq, nitems = nf * npp;
+    const int npos = a.OH * a.OW;
+    const uint32_t pq = static_cast<uint32_t>(p), mq = a.mq[j];
+    const uint32_t mnpp = npp > 1 ? 0xffffffffu / static_cast<uint32_t>(npp) + 1u : 0u;
+    const uint32_t mowq = OWq > 1 ? 0xffffffffu / static_cast<uint32_t>(OWq) + 1u : 0u;
+    for (int it0 = (tid & ~63); it0 < nitems; it0 += 256) {
+        const int it = it0 + (tid & 63);
+        int fl = grp_div(it, npp, mnpp);
+        int pos = it - fl * npp;
+        const bool live = it < nitems && pos < nposv;
+        if (!live) pos = 0;
+        if (fl >= nf) fl = 0;
+        const int oyl = grp_div(pos, OWq, mowq);
+        const int ox4 = pos - oyl * OWq;
+        uint32_t acc[4] = {0u, 0u, 0u, 0u};
+        const uint8_t* I = gimg + static_cast<size_t>((fl / Fg) * Cg) * chs + oyl * a.sh * R + ox4 * 4 * sw;
+        grp_item<KH, KW, SW>(I, wl + fl * wper, Cg, kh, kw, sw, chs, R, acc);
+        if (!live) continue;
+        const int f = f0 + fl;
+        const uint32_t k0 = kl[fl];
+        uint32_t o[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) o[t] = modq_conv(modq_conv(acc[t], pq, mq) + k0, pq, mq);
+        const int ox0 = ox4 * 4;
+        act_t* Y = y.p[j] + ((static_cast<int64_t>(b) * n + c) * a.F + f) * npos + (oy0 + oyl) * a.OW + ox0;
+        if (ox0 + 4 <= a.OW && (reinterpret_cast<uintptr_t>(Y) & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(Y) = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (ox0 + t < a.OW) Y[t] = static_cast<act_t>(o[t]);
+        }
+    }
+}
+
 void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream_t st) {
+    if (a.groups > 1) {
+        const size_t lds = conv_grp_lds(a, a.gpb, a.gband);
+        dim3 g(static_cast<unsigned>(a.img_off[a.crt.k] * a.gngb * a.gnbands), 1, 1);
+        if (a.kh == 3 && a.kw == 3 && a.sw == 1)
+            hipLaunchKernelGGL((k_conv_grp<3, 3, 1>), g, dim3(256), lds, st, a, x, y);
+        else if (a.kh == 3 && a.kw == 3 && a.sw == 2)
+            hipLaunchKernelGGL((k_conv_grp<3, 3, 2>), g, dim3(256), lds, st, a, x, y);
+        else if (a.kh == 1 && a.kw == 1 && a.sw == 1)
+            hipLaunchKernelGGL((k_conv_grp<1, 1, 1>), g, dim3(256), lds, st, a, x, y);
+        else
+            hipLaunchKernelGGL((k_conv_grp<0, 0, 0>), g, dim3(256), lds, st, a, x, y);
+        return;
+    }
     if (a.use_mfma && a.nbands > 0) {
         const int64_t nimg = a.img_off[a.crt.k];
         const int in_rows = (min(a.band, a.OH) - 1) * a.sh + a.kh;

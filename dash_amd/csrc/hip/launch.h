@@ -112,6 +112,14 @@ struct ConvArgs {
     // u* hold the layer's own geometry for the staging; the fields above describe the unrolled view.
     int ur = 0;
     int uC = 0, uH = 0, uW = 0, ukh = 0, ukw = 0, ush = 0, usw = 0, uph = 0, upw = 0;
+    // grouped conv (k_conv_grp, groups > 1; 0 and 1 are the dense paths above): group q holds filters
+    // [q F/g, (q+1) F/g) and reads channels [q C/g, (q+1) C/g). wg: weights mod p_j as unsigned bytes (not
+    // centered), [F][C/g][kh][ceil(kw/4)] dwords of 4 dx taps each, zero filled. Block geometry from
+    // conv_grp_geometry: gpb groups and gband output rows per block, gR bytes per LDS image row, gnpp padded
+    // lane slots per filter.
+    int groups = 0;
+    const uint32_t* wg[kMaxRes];
+    int gpb = 0, gngb = 0, gband = 0, gnbands = 0, gR = 0, gnpp = 0;
 };
 void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream_t st);
 
@@ -264,6 +272,69 @@ inline void conv_plan(ConvArgs& a, int max_p, bool unroll) {
         a = own;
         conv_img_geometry(a);
     }
+}
+
+// k_conv_grp geometry. A lane owns 4 adjacent output columns of one (filter, row); a block owns one image,
+// gband output rows and gpb consecutive groups:
+//   * band rule: the whole plane if its OH * ceil(OW/4) lane slots fit the block's 256 lanes, else the most
+//     rows that do (at least one);
+//   * gnpp: a filter's slots padded to a multiple of 64 (the filter is then wave-uniform: its weight reads
+//     from LDS are broadcasts) or, below 64, to a power of two (several filters per wave);
+//   * gpb: as many groups as fill the 256 lanes kGrpPasses times over (a lane loops over its slots: one
+//     staging pass and one barrier then serve several outputs per lane; one pass per block left the layer
+//     bound by block start-up), at most kGrpMaxGroups, shrunk until the staged rows and weights fit 16 KiB of LDS
+//     (several blocks per CU);
+//   * the band then shrinks until a single group's rows and weights fit 64 KiB.
+// gR covers the padded row and the furthest dword any lane reads, in 16-byte staging chunks.
+// Returns the dynamic LDS bytes (rows, weights, constants), or 0 when even one group and one output row do not fit.
+constexpr int kGrpPasses = 8, kGrpMaxGroups = 32;
+inline size_t conv_grp_lds(const ConvArgs& a, int gpb, int band) {
+    const int Cg = a.C / a.groups, Fg = a.F / a.groups;
+    const size_t img = static_cast<size_t>(gpb) * Cg * ((band - 1) * a.sh + a.kh) * a.gR;
+    // the groups' weight dwords and one epilogue constant per filter
+    const size_t wl = static_cast<size_t>(gpb) * Fg * (static_cast<size_t>(Cg) * a.kh * ((a.kw + 3) / 4) + 1) * 4;
+    return img + wl;
+}
+inline int conv_grp_npp(const ConvArgs& a, int band) {
+    const int np = band * ((a.OW + 3) / 4);
+    if (np >= 64) return (np + 63) / 64 * 64;
+    int v = 1;
+    while (v < np) v *= 2;
+    return v;
+}
+inline size_t conv_grp_geometry(ConvArgs& a) {
+    for (int j = 0; j < a.crt.k; ++j)
+        a.mq[j] = static_cast<uint32_t>(0x100000000ull / static_cast<uint32_t>(a.crt.p[j]));
+    const int OWq = (a.OW + 3) / 4, kwd = (a.kw + 3) / 4, Fg = a.F / a.groups;
+    const int ext = 4 * (OWq - 1) * a.sw + 3 * a.sw + 4 * kwd + 4;
+    a.gR = (std::max(a.W + 2 * a.pw, ext) + 15) / 16 * 16;
+    const size_t budget = 64 * 1024;
+    int band = a.OH;
+    if (static_cast<int64_t>(a.OH) * OWq > 256) band = std::max(1, 256 / OWq);
+    int64_t lanes = static_cast<int64_t>(Fg) * conv_grp_npp(a, band);
+    int gpb = static_cast<int>(std::max<int64_t>(
+        1, std::min<int64_t>(std::min(a.groups, kGrpMaxGroups), (256 * kGrpPasses + lanes - 1) / lanes)));
+    while (gpb > 1 && conv_grp_lds(a, gpb, band) > 16 * 1024) --gpb;
+    while (band > 1 && conv_grp_lds(a, gpb, band) > budget) --band;
+    a.gpb = gpb;
+    a.gngb = (a.groups + gpb - 1) / gpb;
+    a.gband = band;
+    a.gnbands = (a.OH + band - 1) / band;
+    a.gnpp = conv_grp_npp(a, band);
+    const size_t lds = conv_grp_lds(a, gpb, band);
+    return lds > budget ? 0 : lds;
+}
+// k_conv_grp weight image of residue p from the [F][C/g][kh][kw] weights (reduced, non-negative)
+inline std::vector<uint32_t> conv_grp_weights(const int64_t* w, int64_t F, int64_t Cg, int kh, int kw, int p) {
+    const int kwd = (kw + 3) / 4;
+    std::vector<uint32_t> r(static_cast<size_t>(F * Cg) * kh * kwd, 0u);
+    for (int64_t fc = 0; fc < F * Cg; ++fc)
+        for (int dy = 0; dy < kh; ++dy)
+            for (int dx = 0; dx < kw; ++dx) {
+                const uint32_t v = static_cast<uint32_t>(w[(fc * kh + dy) * kw + dx] % p);
+                r[(static_cast<size_t>(fc) * kh + dy) * kwd + dx / 4] |= v << (8 * (dx % 4));
+            }
+    return r;
 }
 
 // MFMA weight image [F16][kh][kw][Cpad] from the centered im2col weights w8 [F][Kpad] (order ci*kh*kw + dy*kw

@@ -966,8 +966,19 @@ void HipEvaluator::build() {
                 const i64 K = G.K();
                 a.Kpad = static_cast<int>((K + 63) / 64 * 64);
                 a.use_mfma = mfma_ ? 1 : 0;
-                // LDS-image kernel geometry: 64-channel chunks, row bands that fit 64 KiB of LDS
-                {
+                a.groups = static_cast<int>(G.g);
+                if (G.g > 1) {
+                    // grouped conv: the byte-stencil kernel, no MFMA plan
+                    a.use_mfma = 0;
+                    for (int j = 0; j < k_; ++j) {
+                        const u64 pm = static_cast<u64>(crt_[j] - 1);
+                        DASH_CHECK(crt_[j] <= kActMaxModulus, "grouped conv: residue modulus above 255");
+                        DASH_CHECK(static_cast<u64>(K) * pm * pm < (1ull << 32),
+                                   "grouped conv: (C/g)*kh*kw*(p-1)^2 must stay below 2^32 (32-bit accumulator)");
+                    }
+                    DASH_CHECK(conv_grp_geometry(a) > 0, "grouped conv: one output row of a group exceeds 64 KiB of LDS");
+                } else {
+                    // LDS-image kernel geometry: 64-channel chunks, row bands that fit 64 KiB of LDS
                     static const bool img_ok = [] {
                         const char* e = std::getenv("DASH_CONV_IMG");
                         return !(e && e[0] == '0');
@@ -982,18 +993,25 @@ void HipEvaluator::build() {
                 const Array& w = g.arr("w");
                 for (int j = 0; j < k_; ++j) {
                     const int p = crt_[j];
-                    std::vector<int16_t> wm(static_cast<size_t>(G.F * K));
-                    std::vector<int8_t> w8(static_cast<size_t>(G.F) * a.Kpad, 0);
+                    const bool grp = G.g > 1;  // k_conv_grp reads its own image (wg) only
+                    std::vector<int16_t> wm(grp ? 0 : static_cast<size_t>(G.F * K));
+                    std::vector<int8_t> w8(grp ? 0 : static_cast<size_t>(G.F) * a.Kpad, 0);
                     std::vector<int32_t> zc(G.F, 0);
                     for (i64 f = 0; f < G.F; ++f)
                         for (i64 q = 0; q < K; ++q) {
                             const int v = static_cast<int>(w.ptr<i64>()[f * K + q] % p);
-                            wm[f * K + q] = static_cast<int16_t>(v);
                             if (v == 0) ++zc[f];
+                            if (grp) continue;
+                            wm[f * K + q] = static_cast<int16_t>(v);
                             w8[f * a.Kpad + q] = static_cast<int8_t>(v > p / 2 ? v - p : v);
                         }
-                    a.w[j] = upload(wm.data(), wm.size());
-                    a.w8[j] = (mfma_ && p <= 255) ? upload(w8.data(), w8.size()) : nullptr;
+                    a.w[j] = grp ? nullptr : upload(wm.data(), wm.size());
+                    a.w8[j] = (mfma_ && p <= 255 && !grp) ? upload(w8.data(), w8.size()) : nullptr;
+                    a.wg[j] = nullptr;
+                    if (grp) {
+                        const std::vector<uint32_t> wg = conv_grp_weights(w.ptr<i64>(), G.F, G.Cg(), a.kh, a.kw, p);
+                        a.wg[j] = upload(wg.data(), wg.size());
+                    }
                     if (a.nbands > 0 && p <= 255) {
                         // [F16][kh][kw][Cpad] centered int8 (im2col order ci*kh*kw + dy*kw + dx -> (dy, dx, ci))
                         const std::vector<int8_t> w8r = conv_w8r(a, w8, static_cast<int>(G.F));

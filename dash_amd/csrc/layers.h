@@ -6,10 +6,14 @@
 namespace dash {
 
 struct ConvGeom {
-    i64 C, H, W, F, kh, kw, sh, sw, ph, pw, OH, OW;
+    // g channel groups: group q holds filters [q*F/g, (q+1)*F/g) and reads
+    // channels [q*C/g, (q+1)*C/g); weights are [F][C/g][kh][kw]
+    i64 C, H, W, F, kh, kw, sh, sw, ph, pw, OH, OW, g;
     explicit ConvGeom(const Params& p);
     explicit ConvGeom(const GLayer& g) : ConvGeom(g.p) {}
-    i64 K() const { return C * kh * kw; }
+    i64 Cg() const { return C / g; }
+    i64 Fg() const { return F / g; }
+    i64 K() const { return (C / g) * kh * kw; }
     i64 out_size() const { return F * OH * OW; }
 };
 

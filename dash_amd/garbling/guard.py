@@ -156,7 +156,12 @@ class RangeGuard:
                 W, b = ws[i]
                 cols = F.unfold(inp.to(torch.float64).view(B, l.C, l.H, l.W), (l.kh, l.kw), padding=(l.ph, l.pw),
                                 stride=(l.sh, l.sw))
-                y = torch.matmul(W, cols) + b[:, None]
+                if l.groups == 1:
+                    y = torch.matmul(W, cols) + b[:, None]
+                else:  # grouped unfold: the group's filters against the group's own rows of cols
+                    g = l.groups
+                    y = torch.matmul(W.view(1, g, l.F // g, -1), cols.view(B, g, W.shape[1], -1))
+                    y = y.reshape(B, l.F, -1) + b[:, None]
                 out = y.reshape(B, -1).to(torch.int64)
             elif isinstance(l, L.Dense):
                 W, b, perm = ws[i]
@@ -291,7 +296,7 @@ class RangeGuard:
             post = [op_of(j) for j in g[1:]]
             if isinstance(head, L.Conv2d):
                 d.update(kind=0, C=head.C, H=head.H, W=head.W, F=head.F, kh=head.kh, kw=head.kw, sh=head.sh,
-                         sw=head.sw, ph=head.ph, pw=head.pw, OH=head.OH, OW=head.OW,
+                         sw=head.sw, ph=head.ph, pw=head.pw, OH=head.OH, OW=head.OW, g=head.groups,
                          w=_i32(head.q_weights.reshape(head.F, -1)), b=np.asarray(head.q_biases, np.int64))
             elif isinstance(head, L.Dense):
                 perm = None

@@ -200,8 +200,10 @@ def _im2col(x: np.ndarray, C, H, W, kh, kw, sh, sw, ph, pw):
 
 
 class Conv2d(Layer):
-    """2-D convolution, weights [F][C][kh][kw]; optional zero padding (an
-    extension over the reference's 'valid'-only conv, needed by VGG/ResNet).
+    """2-D convolution, weights [F][C/groups][kh][kw]; optional zero padding
+    and channel groups (extensions over the reference's 'valid'-only dense
+    conv, needed by VGG/ResNet and by depthwise-separable networks). Group q
+    holds filters [q*F/g, (q+1)*F/g) and reads channels [q*C/g, (q+1)*C/g).
     Reference: circuit/layer/conv2d.h (index bug §2.7 #2 fixed)."""
 
     kind = Kind.CONV
@@ -210,14 +212,18 @@ class Conv2d(Layer):
     def __init__(self, weights: np.ndarray, biases: np.ndarray, input_width: int, input_height: int, channel: int,
                  filter: int, filter_width: int, filter_height: int, stride_width: int = 1, stride_height: int = 1,
                  q_parameter: int = -1, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
-                 q_const: float = 10.0, pad_width: int = 0, pad_height: int = 0):
+                 q_const: float = 10.0, pad_width: int = 0, pad_height: int = 0, groups: int = 1):
         self.C, self.H, self.W, self.F = int(channel), int(input_height), int(input_width), int(filter)
+        self.groups = int(groups)
+        if self.groups < 1 or self.C % self.groups or self.F % self.groups:
+            raise ValueError(f"groups={groups} must be positive and divide channel={channel} and filter={filter}")
+        self.Cg, self.Fg = self.C // self.groups, self.F // self.groups
         self.kh, self.kw, self.sh, self.sw = int(filter_height), int(filter_width), int(stride_height), int(stride_width)
         self.ph, self.pw = int(pad_height), int(pad_width)
         self.OH = (self.H + 2 * self.ph - self.kh) // self.sh + 1
         self.OW = (self.W + 2 * self.pw - self.kw) // self.sw + 1
         super().__init__((self.C, self.H, self.W), (self.F, self.OH, self.OW))
-        w = np.asarray(weights, dtype=np.float32).reshape(self.F, self.C, self.kh, self.kw)
+        w = np.asarray(weights, dtype=np.float32).reshape(self.F, self.Cg, self.kh, self.kw)
         b = np.asarray(biases, dtype=np.float32).reshape(self.F)
         self.weights, self.biases = w, b
         self.q_method, self.q_parameter, self.q_const = QuantizationMethod(q_method), q_parameter, q_const
@@ -226,11 +232,15 @@ class Conv2d(Layer):
 
     @classmethod
     def from_quantized(cls, q_weights, q_biases, input_width, input_height, channel, filter, filter_width,
-                       filter_height, stride_width=1, stride_height=1, pad_width=0, pad_height=0):
-        c = cls(np.zeros((filter, channel, filter_height, filter_width), np.float32), np.zeros(filter, np.float32),
+                       filter_height, stride_width=1, stride_height=1, pad_width=0, pad_height=0, groups=1):
+        if groups < 1 or channel % groups or filter % groups:
+            raise ValueError(f"groups={groups} must be positive and divide channel={channel} and filter={filter}")
+        c = cls(np.zeros((filter, channel // groups, filter_height, filter_width), np.float32),
+                np.zeros(filter, np.float32),
                 input_width, input_height, channel, filter, filter_width, filter_height, stride_width, stride_height,
-                q_const=1.0, pad_width=pad_width, pad_height=pad_height)
-        c.q_weights = np.asarray(q_weights, dtype=np.int64).reshape(filter, channel, filter_height, filter_width)
+                q_const=1.0, pad_width=pad_width, pad_height=pad_height, groups=groups)
+        c.q_weights = np.asarray(q_weights, dtype=np.int64).reshape(filter, channel // groups, filter_height,
+                                                                    filter_width)
         c.q_biases = np.asarray(q_biases, dtype=np.int64).reshape(filter)
         c.weights = c.q_weights.astype(np.float32)
         c.biases = c.q_biases.astype(np.float32)
@@ -249,7 +259,13 @@ class Conv2d(Layer):
 
     def _conv(self, x, w, b):
         cols, OH, OW = _im2col(x, self.C, self.H, self.W, self.kh, self.kw, self.sh, self.sw, self.ph, self.pw)
-        y = w.reshape(self.F, -1) @ cols + b[:, None]
+        if self.groups == 1:
+            y = w.reshape(self.F, -1) @ cols + b[:, None]
+            return y.reshape(-1), cols
+        # per group: the group's filters against the group's own rows of cols
+        wg = w.reshape(self.groups, self.Fg, -1)
+        cg = cols.reshape(self.groups, self.Cg * self.kh * self.kw, -1)
+        y = np.matmul(wg, cg).reshape(self.F, -1) + b[:, None]
         return y.reshape(-1), cols
 
     def plain_eval(self, x, track=True, ctx=None):
@@ -263,9 +279,12 @@ class Conv2d(Layer):
         y, cols = self._conv(x, self.q_weights, self.q_biases)
         if track:
             wf = self.q_weights.reshape(self.F, -1)
-            # products and running partial sums (conv2d.h:85-140)
+            # products and running partial sums (conv2d.h:85-140), over the
+            # filter's own group of C/g*kh*kw terms
+            Kg = self.Cg * self.kh * self.kw
             for f in range(self.F):
-                prod = wf[f][:, None] * cols
+                q = f // self.Fg
+                prod = wf[f][:, None] * cols[q * Kg:(q + 1) * Kg]
                 self._track_q(prod, np.cumsum(prod, axis=0))
             self._track_q(y)
         return y
@@ -277,9 +296,12 @@ class Conv2d(Layer):
         return max(self.max_q, int(self.q_weights.max()), int(self.q_biases.max()))
 
     def garble_spec(self):
-        return self.kind, {"C": self.C, "H": self.H, "W": self.W, "F": self.F, "kh": self.kh, "kw": self.kw,
-                           "sh": self.sh, "sw": self.sw, "ph": self.ph, "pw": self.pw,
-                           "w": self.q_weights.reshape(-1), "b": self.q_biases.reshape(-1)}
+        spec = {"C": self.C, "H": self.H, "W": self.W, "F": self.F, "kh": self.kh, "kw": self.kw,
+                "sh": self.sh, "sw": self.sw, "ph": self.ph, "pw": self.pw,
+                "w": self.q_weights.reshape(-1), "b": self.q_biases.reshape(-1)}
+        if self.groups > 1:  # groups == 1 keeps the dense wire bytes
+            spec["g"] = self.groups
+        return self.kind, spec
 
 
 class Relu(Layer):

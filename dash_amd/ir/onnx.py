@@ -139,15 +139,18 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             dims = (w.shape[0],)
         elif op == "Conv":
             w = arr(ins[1])
-            F, C, kh, kw = (int(v) for v in w.shape)
-            assert int(a.get("group", 1)) == 1, "onnx: grouped convolutions are not supported"
+            F, Cg, kh, kw = (int(v) for v in w.shape)
+            group = int(a.get("group", 1))
+            C = Cg * group  # weights are [F][C/group][kh][kw]
+            if group < 1 or F % group or (len(dims) == 3 and dims[0] % group):
+                raise ValueError(f"onnx: conv group {group} must divide the input channels and the {F} filters")
             assert all(int(v) == 1 for v in a.get("dilations", [1, 1])), "onnx: dilated convolutions are not supported"
             st = [int(v) for v in a.get("strides", [1, 1])]
             pads = [int(v) for v in a.get("pads", [0, 0, 0, 0])]
             assert pads[0] == pads[2] and pads[1] == pads[3], "onnx: only symmetric padding is supported"
             bias = arr(ins[2]).reshape(-1) if len(ins) > 2 and ins[2] else np.zeros(F, np.float32)
             assert len(dims) == 3 and dims[0] == C, f"onnx: conv expects {C} input channels, got dims {dims}"
-            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1])), outs[0])
+            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group), outs[0])
             H = (dims[1] + 2 * pads[0] - kh) // st[0] + 1
             W = (dims[2] + 2 * pads[1] - kw) // st[1] + 1
             dims = (F, H, W)
@@ -196,7 +199,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             C, H, W = kw["dims"]
             F, _, kh, kw_ = kw["w"].shape
             layers.append(Conv2d(kw["w"], kw["b"], W, H, C, F, kw_, kh, kw["stride"][1], kw["stride"][0],
-                                 q_parameter, q_method, q_const, pad_width=kw["pads"][1], pad_height=kw["pads"][0]))
+                                 q_parameter, q_method, q_const, pad_width=kw["pads"][1], pad_height=kw["pads"][0],
+                                 groups=kw["group"]))
         elif s.kind == "maxpool":
             C, H, W = kw["dims"]
             layers.append(MaxPool2d(W, H, C, kw["k"][1], kw["k"][0], kw["stride"][1], kw["stride"][0]))
@@ -304,7 +308,7 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
                                _attr_float("alpha", 1.0) + _attr_float("beta", 1.0) + _attr_int("transB", 1)))
         elif isinstance(l, Conv2d):
             inits += [_tensor(f"{name}.weight", l.weights), _tensor(f"{name}.bias", l.biases)]
-            attrs = (_attr_ints("dilations", [1, 1]) + _attr_int("group", 1) + _attr_ints("kernel_shape", [l.kh, l.kw])
+            attrs = (_attr_ints("dilations", [1, 1]) + _attr_int("group", l.groups) + _attr_ints("kernel_shape", [l.kh, l.kw])
                      + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + _attr_ints("strides", [l.sh, l.sw]))
             nodes.append(_node("Conv", [cur, f"{name}.weight", f"{name}.bias"], [out], name, attrs))
         elif isinstance(l, MaxPool2d):

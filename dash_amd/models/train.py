@@ -56,7 +56,7 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
         def forward(self, x):
             return nn.functional.linear(fq(x), fq(self.weight), fq(self.bias))
 
-    class FQConv(nn.Conv2d):
+    class FQConv(nn.Conv2d):  # nn.Conv2d's own `groups` keyword (depthwise: groups = in channels)
         def forward(self, x):
             return self._conv_forward(fq(x), fq(self.weight), fq(self.bias))
 
@@ -72,6 +72,10 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             _, cout, ks, s, p = op
             mods.append(FQConv(dims[0], cout, ks, stride=s, padding=p))
             dims = [cout, (dims[1] + 2 * p - ks) // s + 1, (dims[2] + 2 * p - ks) // s + 1]
+        elif k == "dwconv":
+            _, ks, s, p = op
+            mods.append(FQConv(dims[0], dims[0], ks, stride=s, padding=p, groups=dims[0]))
+            dims = [dims[0], (dims[1] + 2 * p - ks) // s + 1, (dims[2] + 2 * p - ks) // s + 1]
         elif k == "relu":
             mods.append(nn.ReLU())
         elif k == "sign":
@@ -116,9 +120,10 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
             rescale(dims)
         elif isinstance(m, nn.Conv2d):
             w = m.weight.detach().cpu().numpy()
-            F, Cin, kh, kw = w.shape
-            c = Conv2d(w, m.bias.detach().cpu().numpy(), dims[2], dims[1], Cin, F, kw, kh, m.stride[1], m.stride[0],
-                       q_parameter, qm, q_const, pad_width=m.padding[1], pad_height=m.padding[0])
+            F, Cg, kh, kw = w.shape  # [F][C/groups][kh][kw]
+            c = Conv2d(w, m.bias.detach().cpu().numpy(), dims[2], dims[1], Cg * m.groups, F, kw, kh, m.stride[1],
+                       m.stride[0], q_parameter, qm, q_const, pad_width=m.padding[1], pad_height=m.padding[0],
+                       groups=m.groups)
             layers.append(c)
             dims = c.out_dims
             rescale(dims)

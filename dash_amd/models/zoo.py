@@ -17,6 +17,7 @@ from ..ir.quant import QuantizationMethod, quantize_input
 
 # architecture ops: ("conv", out_ch, k, stride, pad) | ("relu",) | ("sign",) | ("flatten",) | ("fc", out)
 #                   | ("maxpool", k, s) | ("res", [ops...]) residual block | ("sumpool", k)
+#                   | ("dwconv", k, stride, pad) depthwise conv (groups = channels, F = C)
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     "MODEL_B_POOL_REPL": {"input": (1, 28, 28), "ops": [
@@ -55,6 +56,13 @@ ARCHS: dict[str, dict] = {
         ("conv", 64, 3, 1, 1), ("relu",),
         ("res", 64, 1), ("res", 64, 1), ("res", 128, 2), ("res", 128, 1),
         ("res", 256, 2), ("res", 256, 1), ("res", 512, 2), ("res", 512, 1),
+        ("sumpool", 4), ("flatten",), ("fc", 10)]},
+    # depthwise-separable CIFAR net (MobileNet style): dense stem, then depthwise 3x3 / 1x1 blocks
+    "MODEL_DWSEP_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 1, 1), ("relu",),
+        ("dwconv", 3, 2, 1), ("relu",), ("conv", 32, 1, 1, 0), ("relu",),
+        ("dwconv", 3, 2, 1), ("relu",), ("conv", 64, 1, 1, 0), ("relu",),
+        ("dwconv", 3, 1, 1), ("relu",), ("conv", 64, 1, 1, 0), ("relu",),
         ("sumpool", 4), ("flatten",), ("fc", 10)]},
 }
 
@@ -98,10 +106,12 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         elif qm == QuantizationMethod.ScaleQuantPlus:
             layers.append(Rescale([q_parameter], d))
 
-    def conv(cout, k, s, p, cin, h, w):
-        wt = _init(rng, (cout, cin, k, k), cin * k * k)
-        bs = _init(rng, (cout,), cin * k * k)
-        c = Conv2d(wt, bs, w, h, cin, cout, k, k, s, s, q_parameter, qm, q_const, pad_width=p, pad_height=p)
+    def conv(cout, k, s, p, cin, h, w, groups=1):
+        fan_in = cin // groups * k * k
+        wt = _init(rng, (cout, cin // groups, k, k), fan_in)
+        bs = _init(rng, (cout,), fan_in)
+        c = Conv2d(wt, bs, w, h, cin, cout, k, k, s, s, q_parameter, qm, q_const, pad_width=p, pad_height=p,
+                   groups=groups)
         layers.append(c)
         rescale_after(c.out_dims)
         return c.out_dims
@@ -122,6 +132,9 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         elif kind == "conv":
             _, cout, k, s, p = op
             dims = conv(cout, k, s, p, dims[0], dims[1], dims[2])
+        elif kind == "dwconv":
+            _, k, s, p = op
+            dims = conv(dims[0], k, s, p, dims[0], dims[1], dims[2], groups=dims[0])
         elif kind == "relu":
             layers.append(Relu(dims))
         elif kind == "sign":
@@ -189,5 +202,7 @@ BENCH_CONFIGS = {
     "MODEL_F_MINIONN_POOL_REPL/REDASH_CPM": dict(model="MODEL_F_MINIONN_POOL_REPL",
                                                 q_method=QuantizationMethod.ScaleQuantPlus, q_parameter=32,
                                                 crt=[32, 3, 5, 7, 11, 13, 17], mrs=[10, 9, 9, 8, 7, 7, 6]),
+    "MODEL_DWSEP_CIFAR/DASH": dict(model="MODEL_DWSEP_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
+                                   crt=7, mrs=100.0),
     "MODEL_A/SIMPLE": dict(model="MODEL_A", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8, mrs=100.0),
 }
