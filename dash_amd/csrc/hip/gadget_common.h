@@ -44,14 +44,7 @@ constexpr int kSignApproxChunk = DASH_SA_CHUNK;  // label loads in flight per la
 // AES kernels stride over their elements so the LDS image is filled once per
 // resident block: resident blocks per CU (register budget: waves per SIMD x 4
 // SIMDs x 64 lanes / block size; LDS: 160 KiB / image), x4 for tail balance.
-static int num_cus() {
-    static int cus = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
-    return cus;
-}
+// num_cus() is the planning CU count (launch.h, one definition in launch_plan.hip).
 static int aes_block_cap(int bs) {
     const int waves = std::max(kAesMinBlocks, kSignApproxMinWaves);
     const int resident = std::max(1, std::min(waves * 256 / bs, 160 * 1024 / DASH_AES_LDS_BYTES));
@@ -73,7 +66,25 @@ static inline int aes_bs(int64_t n, int y, int z) {
     while (bs > 64 && lanes < static_cast<int64_t>(bs) * num_cus()) bs >>= 1;
     return bs;
 }
-#define AES_LAUNCH(n, y, z) grid_aes((n), aes_bs((n), (y), (z)), (y), (z)), dim3(aes_bs((n), (y), (z)))
+// grid and block of the AES kernel `kernel` over n x y x z lanes (the launch log gets "aes.<kernel>")
+struct LaunchDims {
+    dim3 grid, block;
+};
+static inline LaunchDims aes_dims(const char* kernel, int64_t n, int y, int z) {
+    const int bs = aes_bs(n, y, z);
+    const LaunchDims d{grid_aes(n, bs, y, z), dim3(bs)};
+    if (launch_log_on()) {
+        std::string name(kernel);  // a template-id arrives in parentheses
+        if (!name.empty() && name.front() == '(') name = name.substr(1, name.size() - 2);
+        launch_log_add("aes." + name, d.grid, d.block);
+    }
+    return d;
+}
+#define AES_LAUNCH_GGL(kernel, n, y, z, lds, st, ...)                        \
+    do {                                                                     \
+        const LaunchDims d_ = aes_dims(#kernel, (n), (y), (z));              \
+        hipLaunchKernelGGL(kernel, d_.grid, d_.block, lds, st, __VA_ARGS__); \
+    } while (0)
 
 // static (not dynamic) LDS: its address is a link-time constant, so the
 // table base folds into the ds_read offset field

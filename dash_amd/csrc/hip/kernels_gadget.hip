@@ -720,7 +720,7 @@ __global__ __launch_bounds__(kAesBlock, DASH_UA_MINBLOCKS) void k_rescale_update
 
 void launch_rescale_hash_sign(const u128* signP, const u128* du, int64_t N, int B, u128* h0, uint16_t* col0,
                               const AesGlobals& g, hipStream_t st) {
-    hipLaunchKernelGGL(k_rescale_hash_sign, AES_LAUNCH(N, 1, B), kAesLds, st, signP, du, N, h0, col0, g.te0, g.rk);
+    AES_LAUNCH_GGL(k_rescale_hash_sign, N, 1, B, kAesLds, st, signP, du, N, h0, col0, g.te0, g.rk);
 }
 void launch_rescale_update_approx(const RescaleArgs& r, const SignArgs& a, const Act& x, const int16_t* delta,
                                   const u128* zh, int B, const ModC* mc, const AesGlobals& g, hipStream_t st) {
@@ -731,18 +731,19 @@ void launch_rescale_update_approx(const RescaleArgs& r, const SignArgs& a, const
     }();
     // at most two waves per SIMD: the lanes are serial chains of round trips
     const bool small = small_on && r.N * r.crt.k * B <= static_cast<int64_t>(2 * 4 * 64) * num_cus();
+    const LaunchDims d = aes_dims(small ? "update_approx.small" : "update_approx.large", r.N, r.crt.k, B);
     if (a.t <= 5 && small)
-        hipLaunchKernelGGL((k_rescale_update_approx<5, 16>), AES_LAUNCH(r.N, r.crt.k, B), kAesLds, st, r, a, x,
-                           delta, zh, mc, g.te0, g.rk);
+        hipLaunchKernelGGL((k_rescale_update_approx<5, 16>), d.grid, d.block, kAesLds, st, r, a, x, delta, zh, mc,
+                           g.te0, g.rk);
     else if (a.t <= 5)
-        hipLaunchKernelGGL((k_rescale_update_approx<5, kChunkUA>), AES_LAUNCH(r.N, r.crt.k, B), kAesLds, st, r, a, x,
-                           delta, zh, mc, g.te0, g.rk);
+        hipLaunchKernelGGL((k_rescale_update_approx<5, kChunkUA>), d.grid, d.block, kAesLds, st, r, a, x, delta, zh,
+                           mc, g.te0, g.rk);
     else if (small)
-        hipLaunchKernelGGL((k_rescale_update_approx<8, 16>), AES_LAUNCH(r.N, r.crt.k, B), kAesLds, st, r, a, x,
-                           delta, zh, mc, g.te0, g.rk);
+        hipLaunchKernelGGL((k_rescale_update_approx<8, 16>), d.grid, d.block, kAesLds, st, r, a, x, delta, zh, mc,
+                           g.te0, g.rk);
     else
-        hipLaunchKernelGGL((k_rescale_update_approx<8, kChunkUA>), AES_LAUNCH(r.N, r.crt.k, B), kAesLds, st, r, a,
-                           x, delta, zh, mc, g.te0, g.rk);
+        hipLaunchKernelGGL((k_rescale_update_approx<8, kChunkUA>), d.grid, d.block, kAesLds, st, r, a, x, delta, zh,
+                           mc, g.te0, g.rk);
 }
 
 
@@ -1363,17 +1364,19 @@ void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x,
         return !(e && e[0] == '0');
     }();
     if (out_quad_fits(a, B)) {
-        hipLaunchKernelGGL(k_rescale_relu_out_q, dim3(static_cast<unsigned>((a.N + kRroQE - 1) / kRroQE), a.crt.k, B),
-                           dim3(256), 0, st, a, sa, x, y, gtab, etab, mc);
+        const dim3 gq(static_cast<unsigned>((a.N + kRroQE - 1) / kRroQE), a.crt.k, B);
+        if (launch_log_on()) launch_log_add("relu_out.quad", gq, dim3(256));
+        hipLaunchKernelGGL(k_rescale_relu_out_q, gq, dim3(256), 0, st, a, sa, x, y, gtab, etab, mc);
         return;
     }
     if (rro_stage && stage_ok(a.N, kRroBS)) {
-        hipLaunchKernelGGL(k_rescale_relu_out_s, dim3(static_cast<unsigned>((a.N + kRroBS - 1) / kRroBS), a.crt.k, B),
-                           dim3(kRroBS), 0, st, a, sa, x, y, gtab, etab, mc, g.te0, g.rk);
+        const dim3 gs(static_cast<unsigned>((a.N + kRroBS - 1) / kRroBS), a.crt.k, B);
+        if (launch_log_on()) launch_log_add("relu_out.staged", gs, dim3(kRroBS));
+        hipLaunchKernelGGL(k_rescale_relu_out_s, gs, dim3(kRroBS), 0, st, a, sa, x, y, gtab, etab, mc, g.te0, g.rk);
         return;
     }
-    hipLaunchKernelGGL(k_rescale_relu_out, AES_LAUNCH(a.N, a.crt.k, B), kAesLds, st, a, sa, x, y, gtab, etab, mc,
-                       g.te0, g.rk);
+    const LaunchDims d = aes_dims("relu_out.lane", a.N, a.crt.k, B);
+    hipLaunchKernelGGL(k_rescale_relu_out, d.grid, d.block, kAesLds, st, a, sa, x, y, gtab, etab, mc, g.te0, g.rk);
 }
 
 // hx[b][j][e] = H(compress(x_j)), colx = color: the ReLU multiply's garbler half gates (exact-sign path;
@@ -1416,8 +1419,8 @@ static void dispatch_mrs_chain(const MrsArgs& a, const Act& x, int B, const ModC
 
 void launch_relu_mrs(const MrsArgs& a, const SignArgs& sa, const Act& x, const Act& y, const u128* gtab,
                      const u128* etab, int B, const ModC* mc, const AesGlobals& g, hipStream_t st) {
-    hipLaunchKernelGGL(k_label_hash, AES_LAUNCH(a.N, a.crt.k, B), kAesLds, st, x, a.crt, a.N,
-                       sa.hx, sa.colx, mc, g.te0, g.rk, sa.hard, sa.mgate0);
+    AES_LAUNCH_GGL(k_label_hash, a.N, a.crt.k, B, kAesLds, st, x, a.crt, a.N, sa.hx, sa.colx, mc, g.te0, g.rk,
+                   sa.hard, sa.mgate0);
     dispatch_mrs_chain(a, x, B, mc, g, st);
     launch_relu_mult(sa, x, y, gtab, etab, mc, st);
 }
@@ -1492,17 +1495,22 @@ void launch_rescale_mrs(const MrsArgs& a, const Act& x, int B, const ModC* mc, c
                         bool chain_only) {
     dispatch_mrs_chain(a, x, B, mc, g, st);
     if (chain_only) return;  // the joint ReLU's k_rescale_relu_out writes the outputs
-    if (a.mode == 2 && stage_ok(a.N, kOhBS))
-        hipLaunchKernelGGL(k_rescale_mrs_out_hash_s, grid_aes(a.N, kOhBS, a.crt.k, B), dim3(kOhBS), 0, st, a, x, mc,
-                           g.te0, g.rk);
-    else if (a.mode == 2)
-        hipLaunchKernelGGL(k_rescale_mrs_out_hash, AES_LAUNCH(a.N, a.crt.k, B), kAesLds, st, a, x, mc, g.te0, g.rk);
-    else if (out_quad_fits(a, B))
-        hipLaunchKernelGGL(k_rescale_mrs_out_q, dim3(static_cast<unsigned>((a.N + kRroQE - 1) / kRroQE), a.crt.k, B),
-                           dim3(256), 0, st, a, x, mc);
-    else
-        hipLaunchKernelGGL(k_rescale_mrs_out, dim3(static_cast<unsigned>((a.N + 255) / 256), a.crt.k, B), dim3(256), 0,
-                           st, a, x, mc);
+    if (a.mode == 2 && stage_ok(a.N, kOhBS)) {
+        const dim3 gs = grid_aes(a.N, kOhBS, a.crt.k, B);
+        if (launch_log_on()) launch_log_add("out_hash.staged", gs, dim3(kOhBS));
+        hipLaunchKernelGGL(k_rescale_mrs_out_hash_s, gs, dim3(kOhBS), 0, st, a, x, mc, g.te0, g.rk);
+    } else if (a.mode == 2) {
+        const LaunchDims d = aes_dims("out_hash.lane", a.N, a.crt.k, B);
+        hipLaunchKernelGGL(k_rescale_mrs_out_hash, d.grid, d.block, kAesLds, st, a, x, mc, g.te0, g.rk);
+    } else if (out_quad_fits(a, B)) {
+        const dim3 gq(static_cast<unsigned>((a.N + kRroQE - 1) / kRroQE), a.crt.k, B);
+        if (launch_log_on()) launch_log_add("mrs_out.quad", gq, dim3(256));
+        hipLaunchKernelGGL(k_rescale_mrs_out_q, gq, dim3(256), 0, st, a, x, mc);
+    } else {
+        const dim3 gl(static_cast<unsigned>((a.N + 255) / 256), a.crt.k, B);
+        if (launch_log_on()) launch_log_add("mrs_out.lane", gl, dim3(256));
+        hipLaunchKernelGGL(k_rescale_mrs_out, gl, dim3(256), 0, st, a, x, mc);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1665,15 +1673,14 @@ static inline dim3 grid_for(int64_t n, int bs, int y, int z) {
 
 void launch_sign_approx(const SignArgs& a, const Act& x, const ModC* mc, const AesGlobals& g, hipStream_t st) {
     if (a.t <= 5)
-        hipLaunchKernelGGL(k_sign_approx<5>, AES_LAUNCH(a.N, a.crt.k, a.B), kAesLds, st, a, x, mc, g.te0,
-                           g.rk);
+        AES_LAUNCH_GGL(k_sign_approx<5>, a.N, a.crt.k, a.B, kAesLds, st, a, x, mc, g.te0, g.rk);
     else
-        hipLaunchKernelGGL(k_sign_approx<8>, AES_LAUNCH(a.N, a.crt.k, a.B), kAesLds, st, a, x, mc, g.te0,
-                           g.rk);
+        AES_LAUNCH_GGL(k_sign_approx<8>, a.N, a.crt.k, a.B, kAesLds, st, a, x, mc, g.te0, g.rk);
 }
 void launch_sign_chain(const SignArgs& a, int maxn, const ModC* mc, const AesGlobals& g, hipStream_t st) {
     const dim3 gs = grid_for(a.N, 256, a.t, a.B);
-    const dim3 gr = grid_aes(a.N, aes_bs(a.N, 1, a.B), 1, a.B), br(aes_bs(a.N, 1, a.B));
+    const LaunchDims dr = aes_dims(a.fused ? "k_sign_chain_fused" : "k_sign_chain", a.N, 1, a.B);
+    const dim3 gr = dr.grid, br = dr.block;
     // (measured: folding the castsum pass into the chain lanes is slower, 334 vs 356 inf/s on
     // MiniONN B=24: the chain is latency bound and the castsum's t-fold lane parallelism wins)
     if (maxn <= 24) {  // k = 7 DASH configs (cast outputs mod 8 m_d: <= 22 components)
@@ -1705,15 +1712,17 @@ void launch_relu_mult(const SignArgs& a, const Act& x, const Act& y, const u128*
     if (stage_ok(a.N, kRmBS) && x.p[0] != y.p[0]) {
         const unsigned nx = static_cast<unsigned>(std::min<int64_t>((a.N + kRmBS - 1) / kRmBS,
                                                                    std::max(1, 16 * num_cus() / (a.crt.k * a.B))));
+        if (launch_log_on()) launch_log_add("relu_mult.staged", dim3(nx, a.crt.k, a.B), dim3(kRmBS));
         hipLaunchKernelGGL(k_relu_mult_s, dim3(nx, a.crt.k, a.B), dim3(kRmBS), 0, st, a, x, y, gtab, etab, mc);
         return;
     }
+    if (launch_log_on()) launch_log_add("relu_mult.lane", grid_for(a.N, 256, a.crt.k, a.B), dim3(256));
     hipLaunchKernelGGL(k_relu_mult, grid_for(a.N, 256, a.crt.k, a.B), dim3(256), 0, st, a, x, y, gtab, etab, mc);
 }
 void launch_rescale_hash(const Act& x, int fi, int s, const int16_t* up, int up_stride, int add_up, int64_t N, int B,
                          u128* h0, uint16_t* col0, const ModC* mc, const AesGlobals& g, hipStream_t st, int hard) {
-    hipLaunchKernelGGL(k_rescale_hash, AES_LAUNCH(N, 1, B), kAesLds, st, x, fi, s, up, up_stride,
-                       add_up, N, h0, col0, mc, g.te0, g.rk, hard);
+    AES_LAUNCH_GGL(k_rescale_hash, N, 1, B, kAesLds, st, x, fi, s, up, up_stride, add_up, N, h0, col0, mc, g.te0,
+                   g.rk, hard);
 }
 void launch_rescale_update(const RescaleArgs& a, const Act& x, int B, const ModC* mc, hipStream_t st) {
     hipLaunchKernelGGL(k_rescale_update, grid_for(a.N, 256, a.crt.k, B), dim3(256), 0, st, a, x, mc);
@@ -1728,11 +1737,11 @@ void launch_base_ext(const BEArgs& a, const Act& x, int B, const ModC* mc, const
 }
 void launch_proj(const ProjArgs& a, const Act& x, const Act& y, int B, const ModC* mc, const AesGlobals& g,
                  hipStream_t st) {
-    hipLaunchKernelGGL(k_proj, AES_LAUNCH(a.N, a.k, B), kAesLds, st, a, x, y, mc, g.te0, g.rk);
+    AES_LAUNCH_GGL(k_proj, a.N, a.k, B, kAesLds, st, a, x, y, mc, g.te0, g.rk);
 }
 void launch_mult(const MultArgs& a, const Act& x, const Act& y, int B, const ModC* mc, const AesGlobals& g,
                  hipStream_t st) {
-    hipLaunchKernelGGL(k_mult, AES_LAUNCH(a.No, a.crt.k, B), kAesLds, st, a, x, y, mc, g.te0, g.rk);
+    AES_LAUNCH_GGL(k_mult, a.No, a.crt.k, B, kAesLds, st, a, x, y, mc, g.te0, g.rk);
 }
 
 }  // namespace dev

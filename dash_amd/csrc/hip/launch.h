@@ -4,15 +4,32 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "kargs.h"
 
 namespace dash {
 namespace dev {
+
+// Launch planning (launch_plan.hip). num_cus() is the CU count the pickers of the gadget launches compare a
+// launch with: the device's count, or the override a test set with set_planning_cus (n = 0 restores the device's
+// value; nothing else sets it, no environment variable either). It changes only which kernel form, block size and
+// grid a picker chooses, never where the work runs, and none of the pickers' correctness preconditions.
+int num_cus();
+void set_planning_cus(int n);
+int planning_cus_override();  // 0: none
+// Launch log: off by default (one relaxed load per host-side launch, nothing under graph replay, where no picker
+// runs). When on, every picker appends the form it launched as "<form> grid=(x,y,z) block=n".
+extern std::atomic<bool> g_launch_log_on;
+inline bool launch_log_on() { return g_launch_log_on.load(std::memory_order_relaxed); }
+void launch_log_enable(bool on);
+void launch_log_add(const std::string& form, dim3 grid, dim3 block);
+std::vector<std::string> launch_log_take();
 
 
 void launch_sign_approx(const SignArgs& a, const Act& x, const ModC* mc, const AesGlobals& g, hipStream_t st);

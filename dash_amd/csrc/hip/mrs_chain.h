@@ -1031,6 +1031,11 @@ static inline bool mrs_quad_on() {
     }();
     return on;
 }
+// launch log entry of a chain form: "chain.<form> K=<K> mode=<MODE> grid=(x,y,z) block=n"
+static inline void chain_log(const char* form, int K, int mode, dim3 grid, dim3 block) {
+    if (!launch_log_on()) return;
+    launch_log_add(std::string("chain.") + form + " K=" + std::to_string(K) + " mode=" + std::to_string(mode), grid, block);
+}
 // launches k_mrs_chain_w<K, MODE> (or its quad form) with wl bytes of dynamic LDS (the per-kernel limit is raised
 // once)
 template <int K, int MODE>
@@ -1047,6 +1052,7 @@ static void launch_chain_w(const MrsArgs& a, const Act& x, int B, size_t wl, con
         aq.qpack = qpack;
         const size_t ql = wl / kMrsWBS * kMrsQE;  // every residue's rows for kMrsQE elements
         const dim3 gq(static_cast<unsigned>((a.N + kMrsQE - 1) / kMrsQE), 1, B);
+        chain_log("quad", K, MODE, gq, dim3(kMrsQBS));
         hipLaunchKernelGGL((k_mrs_chain_q<K, MODE>), gq, dim3(kMrsQBS), ql, st, aq, x, mc);
         return;
     }
@@ -1057,6 +1063,7 @@ static void launch_chain_w(const MrsArgs& a, const Act& x, int B, size_t wl, con
     }();
     (void)raised;
     const dim3 gw(static_cast<unsigned>((a.N + kMrsWBS - 1) / kMrsWBS), 1, B);
+    chain_log("wave", K, MODE, gw, dim3(kMrsWBS));
     hipLaunchKernelGGL((k_mrs_chain_w<K, MODE>), gw, dim3(kMrsWBS), wl, st, a, x, mc, g.te0, g.rk);
 }
 
@@ -1075,6 +1082,7 @@ void launch_mrs_chain_k(const MrsArgs& a, const Act& x, int B, const ModC* mc, c
     const size_t wl = stg ? 0 : mrs_wave_lds(a, B);
     const dim3 gc = stg ? grid_aes(a.N, kMrsBS, 1, B) : grid_aes(a.N, aes_bs(a.N, 1, B), 1, B);
     const dim3 bc(stg ? kMrsBS : aes_bs(a.N, 1, B));
+    if (!wl) chain_log(stg ? "staged" : "lane", K, a.mode == 1 || a.mode == 2 ? a.mode : 0, gc, bc);
     if (a.mode == 1) {
         if (wl) launch_chain_w<K, 1>(a, x, B, wl, mc, g, st);
         else if (stg) hipLaunchKernelGGL((k_mrs_chain_s<K, 1>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);

@@ -1829,6 +1829,17 @@ void register_hip_bindings(py::module_& m) {
     // Reset the thread's sticky last-error (e.g. after a handled out-of-memory), so a later
     // hipGetLastError() launch check does not report it again. Returns the cleared code.
     m.def("hip_clear_last_error", []() { return static_cast<int>(hipGetLastError()); });
+    // Launch planning for tests (launch.h): the CU count the gadget launch pickers plan with (0 restores the
+    // device's count; it picks kernel forms, block sizes and grids, never where work runs), and the launch log.
+    // An evaluator's picks freeze when its graph is captured: set the count before building the evaluator.
+    m.def("hip_set_planning_cus", [](int n) {
+        DASH_CHECK(n >= 0, "hip_set_planning_cus: n must be >= 0 (0 restores the device's count)");
+        dev::set_planning_cus(n);
+    }, py::arg("n"));
+    m.def("hip_planning_cus", []() { return dev::num_cus(); });
+    m.def("hip_planning_override", []() { return dev::planning_cus_override(); });
+    m.def("hip_launch_log", [](bool on) { dev::launch_log_enable(on); }, py::arg("on"));
+    m.def("hip_launch_log_take", []() { return dev::launch_log_take(); });
     m.def("hip_device_count", []() {
         int n = 0;
         if (hipGetDeviceCount(&n) != hipSuccess) return 0;
