@@ -3081,7 +3081,6 @@ void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, C
             a.sh = static_cast<int>(G.sh); a.sw = static_cast<int>(G.sw);
             a.ph = static_cast<int>(G.ph); a.pw = static_cast<int>(G.pw);
             a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
-            a.Kpad = (K + 63) / 64 * 64;
             a.use_mfma = 1;
             a.groups = static_cast<int>(G.g);
             int max_p = 0;
@@ -3095,7 +3094,7 @@ void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, C
                 DASH_CHECK(dev::conv_grp_geometry(a) > 0,
                            "grouped conv: one output row of a group exceeds 64 KiB of LDS");
             } else {
-                dev::conv_plan(a, max_p, true);
+                dev::conv_layer_plan(a, true);
             }
             a.lab_stride = 0;
             a.img_off[0] = 0;

@@ -911,11 +911,13 @@ void launch_dense(const DenseArgs& a, const Act& x, const Act& y, int B, hipStre
         for (int j = 0; j < a.crt.k; ++j) maxn = max(maxn, a.crt.n[j]);
         dim3 g(static_cast<unsigned>((static_cast<int64_t>(B) * maxn + 63) / 64), static_cast<unsigned>((a.O + 63) / 64),
                static_cast<unsigned>(a.crt.k));
+        if (launch_log_on()) launch_log_add("dense.mfma", g, dim3(256));
         hipLaunchKernelGGL(k_dense_mfma, g, dim3(256), 0, st, a, x, y, B);
         return;
     }
     const ZTab& z = ztab_for(a.crt);
     dim3 g(static_cast<unsigned>((a.O + 255) / 256), 1, static_cast<unsigned>(B * z.sumn));
+    if (launch_log_on()) launch_log_add("dense.valu", g, dim3(256));
     hipLaunchKernelGGL(k_dense, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
 }
 
@@ -1124,14 +1126,21 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
     if (a.groups > 1) {
         const size_t lds = conv_grp_lds(a, a.gpb, a.gband);
         dim3 g(static_cast<unsigned>(a.img_off[a.crt.k] * a.gngb * a.gnbands), 1, 1);
-        if (a.kh == 3 && a.kw == 3 && a.sw == 1)
+        const char* form;
+        if (a.kh == 3 && a.kw == 3 && a.sw == 1) {
+            form = "conv.grp<3,3,1>";
             hipLaunchKernelGGL((k_conv_grp<3, 3, 1>), g, dim3(256), lds, st, a, x, y);
-        else if (a.kh == 3 && a.kw == 3 && a.sw == 2)
+        } else if (a.kh == 3 && a.kw == 3 && a.sw == 2) {
+            form = "conv.grp<3,3,2>";
             hipLaunchKernelGGL((k_conv_grp<3, 3, 2>), g, dim3(256), lds, st, a, x, y);
-        else if (a.kh == 1 && a.kw == 1 && a.sw == 1)
+        } else if (a.kh == 1 && a.kw == 1 && a.sw == 1) {
+            form = "conv.grp<1,1,1>";
             hipLaunchKernelGGL((k_conv_grp<1, 1, 1>), g, dim3(256), lds, st, a, x, y);
-        else
+        } else {
+            form = "conv.grp<0,0,0>";
             hipLaunchKernelGGL((k_conv_grp<0, 0, 0>), g, dim3(256), lds, st, a, x, y);
+        }
+        if (launch_log_on()) launch_log_add(form, g, dim3(256));
         return;
     }
     if (a.use_mfma && a.nbands > 0) {
@@ -1144,20 +1153,30 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
             return e ? std::atoi(e) : 2;
         }();
         const int KS = a.kh * a.kw * (a.Cpad / 64);
-        if (ver == 1 && a.ldsS == a.Cpad + 16 && a.ldsR == (a.W + 2 * a.pw) * a.ldsS)
+        const char* form;  // the kernel and its real template arguments, for the launch log
+        if (ver == 1 && a.ldsS == a.Cpad + 16 && a.ldsR == (a.W + 2 * a.pw) * a.ldsS) {
+            form = "conv.img";
             hipLaunchKernelGGL(k_conv_img, g, dim3(256), lds, st, a, x, y, B);  // A/B: its fixed layout only
-        else if (a.ur && KS == 1)
+        } else if (a.ur && KS == 1) {
+            form = "conv.img2<1,1>";
             hipLaunchKernelGGL((k_conv_img2<1, true>), g, dim3(256), lds, st, a, x, y, B);
-        else if (a.ur)
+        } else if (a.ur) {
+            form = "conv.img2<0,1>";
             hipLaunchKernelGGL((k_conv_img2<0, true>), g, dim3(256), lds, st, a, x, y, B);
-        else if (KS == 9)
+        } else if (KS == 9) {
+            form = "conv.img2<9,0>";
             hipLaunchKernelGGL((k_conv_img2<9, false>), g, dim3(256), lds, st, a, x, y, B);
-        else if (KS == 4)
+        } else if (KS == 4) {
+            form = "conv.img2<4,0>";
             hipLaunchKernelGGL((k_conv_img2<4, false>), g, dim3(256), lds, st, a, x, y, B);
-        else if (KS == 1)
+        } else if (KS == 1) {
+            form = "conv.img2<1,0>";
             hipLaunchKernelGGL((k_conv_img2<1, false>), g, dim3(256), lds, st, a, x, y, B);
-        else
+        } else {
+            form = "conv.img2<0,0>";
             hipLaunchKernelGGL((k_conv_img2<0, false>), g, dim3(256), lds, st, a, x, y, B);
+        }
+        if (launch_log_on()) launch_log_add(form, g, dim3(256));
         bool rest = false;
         for (int j = 0; j < a.crt.k; ++j) rest |= (a.w8r[j] == nullptr);
         if (!rest) return;
@@ -1166,6 +1185,7 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
             if (!a.w8[j]) continue;
             const int64_t ncols = static_cast<int64_t>(B) * a.crt.n[j] * a.OH * a.OW;
             dim3 g(static_cast<unsigned>((ncols + 63) / 64), static_cast<unsigned>((a.F + 63) / 64), 1);
+            if (launch_log_on()) launch_log_add("conv.im2col", g, dim3(256));
             hipLaunchKernelGGL(k_conv_mfma, g, dim3(256), 0, st, a, x, y, j, ncols);
         }
         // residues without an int8 image (p > 255) fall through to VALU below
@@ -1175,6 +1195,7 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
     }
     const ZTab& z = ztab_for(a.crt);
     dim3 g(static_cast<unsigned>((a.OH * a.OW + 255) / 256), static_cast<unsigned>(a.F), static_cast<unsigned>(B * z.sumn));
+    if (launch_log_on()) launch_log_add("conv.valu", g, dim3(256));
     hipLaunchKernelGGL(k_conv_valu, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
 }
 

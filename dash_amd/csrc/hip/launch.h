@@ -291,6 +291,26 @@ inline void conv_plan(ConvArgs& a, int max_p, bool unroll) {
     }
 }
 
+// The whole plan of a dense (groups <= 1) conv layer from its shape (C .. OW) and CRT base (a.crt): the padded
+// reduction length, then conv_plan with the base's largest modulus. img: the LDS-image kernels may run (the
+// evaluator's mfma switch and the DASH_CONV_IMG A/B knob; the GPU garbler always allows them); without them the
+// layer takes the im2col MFMA or the VALU kernel (nbands = 0). The evaluator, the GPU garbler and the test
+// binding hip_conv_plan all plan through this one function; it needs no device.
+inline bool conv_img_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("DASH_CONV_IMG");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+inline void conv_layer_plan(ConvArgs& a, bool img) {
+    a.Kpad = (a.C * a.kh * a.kw + 63) / 64 * 64;
+    int max_p = 0;
+    for (int j = 0; j < a.crt.k; ++j) max_p = std::max(max_p, a.crt.p[j]);
+    conv_plan(a, max_p, img);
+    if (!img) a.band = a.nbands = 0;
+}
+
 // k_conv_grp geometry. A lane owns 4 adjacent output columns of one (filter, row); a block owns one image,
 // gband output rows and gpb consecutive groups:
 //   * band rule: the whole plane if its OH * ceil(OW/4) lane slots fit the block's 256 lanes, else the most

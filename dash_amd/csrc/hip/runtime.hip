@@ -964,7 +964,6 @@ void HipEvaluator::build() {
                 a.ph = static_cast<int>(G.ph); a.pw = static_cast<int>(G.pw);
                 a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
                 const i64 K = G.K();
-                a.Kpad = static_cast<int>((K + 63) / 64 * 64);
                 a.use_mfma = mfma_ ? 1 : 0;
                 a.groups = static_cast<int>(G.g);
                 if (G.g > 1) {
@@ -978,15 +977,8 @@ void HipEvaluator::build() {
                     }
                     DASH_CHECK(conv_grp_geometry(a) > 0, "grouped conv: one output row of a group exceeds 64 KiB of LDS");
                 } else {
-                    // LDS-image kernel geometry: 64-channel chunks, row bands that fit 64 KiB of LDS
-                    static const bool img_ok = [] {
-                        const char* e = std::getenv("DASH_CONV_IMG");
-                        return !(e && e[0] == '0');
-                    }();
-                    int max_p = 0;
-                    for (int j = 0; j < k_; ++j) max_p = std::max(max_p, crt_[j]);
-                    conv_plan(a, max_p, mfma_ && img_ok);
-                    if (!(mfma_ && img_ok)) a.band = a.nbands = 0;
+                    // LDS-image kernel geometry: 64-channel chunks, row bands that fit the LDS budget
+                    conv_layer_plan(a, mfma_ && conv_img_enabled());
                 }
                 a.img_off[0] = 0;
                 for (int j = 0; j < k_; ++j) a.img_off[j + 1] = a.img_off[j] + static_cast<i64>(B_) * crt.n[j];
@@ -1840,6 +1832,41 @@ void register_hip_bindings(py::module_& m) {
     m.def("hip_planning_override", []() { return dev::planning_cus_override(); });
     m.def("hip_launch_log", [](bool on) { dev::launch_log_enable(on); }, py::arg("on"));
     m.def("hip_launch_log_take", []() { return dev::launch_log_take(); });
+    // The conv kernel plan of a dense-conv layer, exactly as the evaluator (mfma: its switch) and the GPU garbler
+    // plan it (launch.h conv_layer_plan). Host arithmetic only: works without a device.
+    m.def("hip_conv_plan", [](int C, int H, int W, int F, int kh, int kw, int sh, int sw, int ph, int pw,
+                              const std::vector<int>& crt_moduli, bool mfma) {
+        DASH_CHECK(C > 0 && H > 0 && W > 0 && F > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0,
+                   "hip_conv_plan: bad conv geometry");
+        DASH_CHECK(!crt_moduli.empty() && static_cast<int>(crt_moduli.size()) <= dev::kMaxRes,
+                   "hip_conv_plan: 1 .. 16 CRT moduli");
+        dev::ConvArgs a{};
+        a.crt.k = static_cast<int>(crt_moduli.size());
+        for (int j = 0; j < a.crt.k; ++j) {
+            DASH_CHECK(crt_moduli[j] >= 2, "hip_conv_plan: modulus below 2");
+            a.crt.p[j] = crt_moduli[j];
+            a.crt.n[j] = nr_comps(crt_moduli[j]);
+        }
+        a.C = C; a.H = H; a.W = W; a.F = F; a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
+        a.OH = (H + 2 * ph - kh) / sh + 1;
+        a.OW = (W + 2 * pw - kw) / sw + 1;
+        DASH_CHECK(a.OH > 0 && a.OW > 0, "hip_conv_plan: empty output");
+        dev::conv_layer_plan(a, mfma && dev::conv_img_enabled());
+        py::dict d;
+        d["ur"] = a.ur;
+        d["KS"] = a.kh * a.kw * (a.Cpad / 64);
+        d["Cpad"] = a.Cpad;
+        d["Kpad"] = a.Kpad;
+        d["ldsS"] = a.ldsS;
+        d["ldsR"] = a.ldsR;
+        d["band"] = a.band;
+        d["nbands"] = a.nbands;
+        d["OH"] = a.OH;
+        d["OW"] = a.OW;
+        d["sh24"] = std::vector<int>(a.sh24, a.sh24 + a.crt.k);
+        return d;
+    }, py::arg("C"), py::arg("H"), py::arg("W"), py::arg("F"), py::arg("kh"), py::arg("kw"), py::arg("sh"),
+       py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("crt_moduli"), py::arg("mfma") = true);
     m.def("hip_device_count", []() {
         int n = 0;
         if (hipGetDeviceCount(&n) != hipSuccess) return 0;

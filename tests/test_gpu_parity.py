@@ -114,8 +114,12 @@ def test_conv(mfma):
                                                (12, 9, 3, 3, 1, 2, 1), (10, 6, 70, 3, 1, 1, 1)])
 def test_conv_band_edges(W, H, C, k, sw, sh, pad):
     """Band staging of the MFMA conv: rows whose width is not a multiple of 8 (edge items as clamped loads),
-    left/right padding, strides; few input channels take the tap-unrolled image (C * k * k <= 64 patch bytes as
-    the channels of one 1x1 k-step), C = 70 the channel-chunked image. Labels bit-exact against the host."""
+    left/right padding, strides. Every stride-1 case here takes the tap-unrolled image: k_conv_img2<1,true> for the
+    3x3 cases (C * k * k <= 64 patch bytes as the channels of one 1x1 k-step), <0,true> for 5x5 (two k-steps) and
+    for C = 70 (ten: the unroll rule fires for every C outside 57..64 and 121..128 at 3x3). The two stride-2 cases
+    take the plain image, <4,false> and <9,false>. All residues (base 7) are raw operands on the 24-bit reduction.
+    The plain and channel-chunked kernels at stride 1 are covered in test_gpu_gemm_forms.py. Labels bit-exact
+    against the host."""
     rng = np.random.default_rng(W * 100 + H)
     F = 6
     Wt = rng.integers(-5, 6, (F, C, k, k)); b = rng.integers(-5, 6, F)
@@ -126,9 +130,11 @@ def test_conv_band_edges(W, H, C, k, sw, sh, pad):
 
 @pytest.mark.parametrize("crt", [7, [5, 7, 131]], ids=["base7", "p131_centered"])
 def test_conv_many_images(crt):
-    """Band conv over many images (3 GCs x every component of every residue) with the exact 24-bit epilogue
-    reduction (small accumulator bound) and, for p = 131, the centered-operand path and the 32-bit reduction
-    where the bound is too large; a 2x2 stride-2 conv follows. Labels bit-exact against the host."""
+    """Band conv over many images (3 GCs x every component of every residue): the 3x3 conv takes the tap-unrolled
+    k_conv_img2<0,true> (three k-steps), the 2x2 stride-2 conv after it the plain <4,false>. Every residue, p = 131
+    with its centered operands included, is on the exact 24-bit epilogue reduction (Kpad = 192 and 128 keep every
+    accumulator bound small); the 32-bit reduction is covered in test_gpu_gemm_forms.py. Labels bit-exact against
+    the host."""
     rng = np.random.default_rng(31)
     C, F, H, W = 16, 32, 7, 7
     Wt = rng.integers(-5, 6, (F, C, 3, 3)); b = rng.integers(-5, 6, F)
