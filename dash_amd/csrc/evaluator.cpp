@@ -92,6 +92,11 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
     std::vector<int> keep(m.layers.size() + 1, 0);
     for (const auto& l : m.layers) {
         if (l.kind == K_ADD) keep[l.param("src") + 1] = 1;
+        if (l.kind == K_CONCAT)
+            for (i64 s : l.vec("srcs")) {
+                DASH_CHECK(s >= -1 && s < static_cast<i64>(m.layers.size()), "concat: bad source layer");
+                keep[s + 1] = 1;
+            }
         if (l.p.count("in_src")) keep[l.param("in_src") + 1] = 1;
     }
     std::vector<CrtLabels> saved(m.layers.size() + 1);
@@ -436,7 +441,7 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 for (int j = 0; j < k; ++j) {
                     Labels O(crt[j], G.out_size());
                     for (i64 o = 0; o < G.out_size(); ++o) {
-                        G.window(o, w);
+                        G.window_inside(o, w);
                         std::memcpy(O.at(o), cur[j].at(w[0]), sizeof(comp_t) * O.n);
                         for (size_t s = 1; s < w.size(); ++s) lab_add(O.at(o), cur[j].at(w[s]), O.n, O.p);
                     }
@@ -450,6 +455,31 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 DASH_CHECK(!other.empty() && other[0].N == Nin, "add: operand size mismatch");
                 for (int j = 0; j < k; ++j)
                     for (i64 e = 0; e < Nin; ++e) lab_add(cur[j].at(e), other[j].at(e), cur[j].n, cur[j].p);
+                break;
+            }
+            case K_CONCAT: {
+                const auto& srcs = g.vec("srcs");
+                DASH_CHECK(!srcs.empty(), "concat: no operands");
+                for (i64 s : srcs) DASH_CHECK(s >= -1 && s < static_cast<i64>(li), "concat: bad source layer");
+                const CrtLabels& first = saved[srcs[0] + 1];
+                CrtLabels nxt;
+                for (size_t j = 0; j < first.size(); ++j) {
+                    i64 Ntot = 0;
+                    for (i64 s : srcs) {
+                        const CrtLabels& S = saved[s + 1];
+                        DASH_CHECK(S.size() == first.size() && S[j].p == first[j].p, "concat: operands on different moduli");
+                        Ntot += S[j].N;
+                    }
+                    Labels O(first[j].p, Ntot);
+                    i64 off = 0;
+                    for (i64 s : srcs) {
+                        const Labels& S = saved[s + 1][j];
+                        std::memcpy(O.at(off), S.at(0), sizeof(comp_t) * S.n * S.N);
+                        off += S.N;
+                    }
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
                 break;
             }
             case K_PROJ: {

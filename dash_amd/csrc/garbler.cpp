@@ -33,6 +33,7 @@ const char* kind_name(int kind) {
         case K_BASEEXT: return "base_extension";
         case K_ADD: return "add";
         case K_SUMPOOL: return "sum_pool";
+        case K_CONCAT: return "concat";
     }
     return "unknown";
 }
@@ -67,16 +68,41 @@ PoolGeom::PoolGeom(const Params& p) {
     kw = param1(p, "kw");
     sh = param1(p, "sh", kh);
     sw = param1(p, "sw", kw);
-    DASH_CHECK(C > 0 && H >= kh && W >= kw && kh > 0 && kw > 0, "bad pool geometry");
-    OH = (H - kh) / sh + 1;
-    OW = (W - kw) / sw + 1;
+    ph = param1(p, "ph", 0);
+    pw = param1(p, "pw", 0);
+    ceil = param1(p, "ceil", 0);
+    DASH_CHECK(C > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0, "bad pool geometry");
+    DASH_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "bad pool geometry");
+    DASH_CHECK(2 * ph <= kh && 2 * pw <= kw, "pool padding above half the kernel");
+    auto out = [&](i64 n, i64 k, i64 s, i64 pad) {
+        const i64 span = n + 2 * pad - k;
+        i64 o = (ceil ? (span + s - 1) / s : span / s) + 1;
+        if (ceil && (o - 1) * s >= n + pad) --o;  // the last window must start inside the image or its left pad
+        return o;
+    };
+    OH = out(H, kh, sh, ph);
+    OW = out(W, kw, sw, pw);
 }
 
 void PoolGeom::window(i64 o, std::vector<i64>& idx) const {
     idx.clear();
     const i64 c = o / (OH * OW), r = o % (OH * OW), oy = r / OW, ox = r % OW;
     for (i64 dy = 0; dy < kh; ++dy)
-        for (i64 dx = 0; dx < kw; ++dx) idx.push_back((c * H + oy * sh + dy) * W + ox * sw + dx);
+        for (i64 dx = 0; dx < kw; ++dx) {
+            const i64 y = std::min(std::max<i64>(oy * sh + dy - ph, 0), H - 1);
+            const i64 x = std::min(std::max<i64>(ox * sw + dx - pw, 0), W - 1);
+            idx.push_back((c * H + y) * W + x);
+        }
+}
+
+void PoolGeom::window_inside(i64 o, std::vector<i64>& idx) const {
+    idx.clear();
+    const i64 c = o / (OH * OW), r = o % (OH * OW), oy = r / OW, ox = r % OW;
+    for (i64 dy = 0; dy < kh; ++dy)
+        for (i64 dx = 0; dx < kw; ++dx) {
+            const i64 y = oy * sh + dy - ph, x = ox * sw + dx - pw;
+            if (y >= 0 && y < H && x >= 0 && x < W) idx.push_back((c * H + y) * W + x);
+        }
 }
 
 MaxTree::MaxTree(i64 K) {
@@ -505,6 +531,11 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
     std::vector<int> keep(layers.size() + 1, 0);
     for (const auto& l : layers) {
         if (l.kind == K_ADD) keep[param1(l.p, "src") + 1] = 1;
+        if (l.kind == K_CONCAT)
+            for (i64 s : paramv(l.p, "srcs")) {
+                DASH_CHECK(s >= -1 && s < static_cast<i64>(layers.size()), "concat: bad source layer");
+                keep[s + 1] = 1;
+            }
         auto it = l.p.find("in_src");
         if (it != l.p.end() && !it->second.empty()) keep[it->second[0] + 1] = 1;
     }
@@ -582,7 +613,8 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                                layers[li + 1].kind == K_RELU && param1(layers[li + 1].p, "in_src", -2) == -2;
         // every layer kind but the test-only projection / mult layers garbles on the device when a GPU garbler
         // is present (the legacy rescale's sign base extension needs residue 0 = 2)
-        const bool lin_kind = spec.kind == K_CONV || spec.kind == K_DENSE || spec.kind == K_SUMPOOL || spec.kind == K_ADD;
+        const bool lin_kind = spec.kind == K_CONV || spec.kind == K_DENSE || spec.kind == K_SUMPOOL ||
+                              spec.kind == K_ADD || spec.kind == K_CONCAT;
         const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
                                     (spec.kind == K_RELU || spec.kind == K_SIGN ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
@@ -1075,7 +1107,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 for (int j = 0; j < k; ++j) {
                     Labels O(crt_[j], G.out_size());
                     for (i64 o = 0; o < G.out_size(); ++o) {
-                        G.window(o, w);
+                        G.window_inside(o, w);
                         std::memcpy(O.at(o), cur[j].at(w[0]), sizeof(comp_t) * O.n);
                         for (size_t s = 1; s < w.size(); ++s) lab_add(O.at(o), cur[j].at(w[s]), O.n, O.p);
                     }
@@ -1096,6 +1128,49 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 DASH_CHECK(!other.empty() && other[0].N == Nin, "add: operand size mismatch");
                 for (int j = 0; j < k; ++j)
                     for (i64 e = 0; e < Nin; ++e) lab_add(cur[j].at(e), other[j].at(e), cur[j].n, cur[j].p);
+                break;
+            }
+            case K_CONCAT: {
+                // channel concatenation of saved outputs: with the [C][H][W] layout the flat label vectors, in order
+                const auto& srcs = paramv(spec.p, "srcs");
+                DASH_CHECK(!srcs.empty(), "concat: no operands");
+                i64 Ntot = 0, ch = 0;
+                std::vector<i64> d0;
+                for (i64 s : srcs) {
+                    DASH_CHECK(s >= -1 && s < static_cast<i64>(li), "concat: bad source layer");
+                    DASH_CHECK(saved_mod[s + 1] == saved_mod[srcs[0] + 1], "concat: operands on different moduli");
+                    const auto& d = saved_dims[s + 1];
+                    if (d0.empty()) d0 = d;
+                    DASH_CHECK(!d.empty() && d.size() == d0.size() && (d.size() != 3 || (d[1] == d0[1] && d[2] == d0[2])),
+                               "concat: operand dims mismatch");
+                    ch += d[0];
+                    i64 n = 1;
+                    for (i64 v : d) n *= v;
+                    Ntot += n;
+                }
+                cur_mod = saved_mod[srcs[0] + 1];
+                dims = d0;
+                dims[0] = ch;
+                if (on_gpu) {
+                    std::vector<size_t> slots;
+                    for (i64 s : srcs) slots.push_back(static_cast<size_t>(s + 1));
+                    gpu->concat_saved(slots, cur);
+                    DASH_CHECK(cur[0].N == Ntot, "concat: operand size mismatch");
+                    break;
+                }
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) {
+                    Labels O(cur_mod[j], Ntot);
+                    i64 off = 0;
+                    for (i64 s : srcs) {
+                        const Labels& S = saved[s + 1][j];
+                        std::memcpy(O.at(off), S.at(0), sizeof(comp_t) * S.n * S.N);
+                        off += S.N;
+                    }
+                    DASH_CHECK(off == Ntot, "concat: operand size mismatch");
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
                 break;
             }
             case K_PROJ: {

@@ -2931,6 +2931,7 @@ struct GpuGarbler::Impl {
 GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs, const std::string& seed16,
                        const LabelBank& R, const LabelBank& Z, int device, bool hardened)
     : impl_(new Impl(device)) {
+    concat_hook() = &GpuGarbler::concat_saved_dev;
     Impl& I = *impl_;
     I.enter();
     I.c.hard = hardened ? 1 : 0;
@@ -3957,6 +3958,38 @@ void GpuGarbler::add_saved(size_t idx, CrtLabels& cur) {
     HIPCHECK(hipGetLastError());
 }
 
+// channel concat (garbler.cpp K_CONCAT): cur = the saved outputs idx[0], idx[1], ... one after the other. The
+// chunked label layout depends on N, so each operand is gathered to its element offset (map -1 elsewhere: the
+// first pass leaves zeros there, the later ones accumulate onto them).
+void GpuGarbler::concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& idx, CrtLabels& cur) {
+    Impl& I = *self.impl_;
+    I.enter();
+    DASH_CHECK(!idx.empty(), "gpu garbler: concat without operands");
+    int64_t Ntot = 0;
+    for (size_t s : idx) {
+        auto it = I.saved.find(s);
+        DASH_CHECK(it != I.saved.end(), "gpu garbler: concat operand missing");
+        DASH_CHECK(it->second.mods == I.saved.find(idx[0])->second.mods, "gpu garbler: concat operands on different moduli");
+        Ntot += it->second.N;
+    }
+    const std::vector<int> mods = I.saved.find(idx[0])->second.mods;
+    std::vector<DevBlock> y = I.alloc_labels(mods, Ntot);
+    int64_t off = 0;
+    for (size_t q = 0; q < idx.size(); ++q) {
+        const Impl::Saved& sv = I.saved.find(idx[q])->second;
+        std::vector<int32_t> map(static_cast<size_t>(Ntot), -1);
+        for (int64_t e = 0; e < sv.N; ++e) map[static_cast<size_t>(off + e)] = static_cast<int32_t>(e);
+        launch_gsum(I.c, y, sv.L, mods, Ntot, sv.N, gg::dconst(map.data(), map.size()), 1, q > 0,
+                    [](int, int) { return 1; });
+        off += sv.N;
+    }
+    HIPCHECK(hipGetLastError());
+    I.cur = std::move(y);
+    I.cur_mod = mods;
+    I.cur_N = Ntot;
+    set_stale(cur, I.cur_mod, Ntot);
+}
+
 // dense base labels (garbler.cpp K_DENSE): y_o = sum_{w != 0 mod p} w x_src(i) + (1 + #zero weights) Z_p
 void GpuGarbler::dense(i64 in, i64 out, i64 ch, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur) {
     Impl& I = *impl_;
@@ -4044,11 +4077,12 @@ void GpuGarbler::sumpool(const PoolGeom& G, CrtLabels& cur) {
     DASH_CHECK(G.C * G.H * G.W == I.cur_N, "gpu garbler: sum pool input size");
     const int64_t Nout = G.out_size();
     const int K = static_cast<int>(G.kh * G.kw);
-    std::vector<int32_t> map(static_cast<size_t>(Nout) * K);
+    // in-image taps first, then -1 (k_gsum skips those): padded / ceil-mode windows have fewer than K taps
+    std::vector<int32_t> map(static_cast<size_t>(Nout) * K, -1);
     std::vector<i64> win;
     for (int64_t o = 0; o < Nout; ++o) {
-        G.window(o, win);
-        for (int s = 0; s < K; ++s) map[static_cast<size_t>(o) * K + s] = static_cast<int32_t>(win[s]);
+        G.window_inside(o, win);
+        for (size_t s = 0; s < win.size(); ++s) map[static_cast<size_t>(o) * K + s] = static_cast<int32_t>(win[s]);
     }
     std::vector<DevBlock> y = I.alloc_labels(I.cur_mod, Nout);
     // windows of more than kMaxTerms values: accumulate term groups (the map is re-cut per group)

@@ -60,6 +60,18 @@ class GpuGarbler {
     bool has_saved(size_t idx) const;
     void restore(size_t idx, CrtLabels& cur);
     void add_saved(size_t idx, CrtLabels& cur);
+    // cur = the saved outputs idx[0], idx[1], ... concatenated (channel concat of [C][H][W] tensors). The device
+    // translation unit registers the implementation, so host-only links of garbler.cpp (which never construct a
+    // GpuGarbler) need no definition of it.
+    using ConcatFn = void (*)(GpuGarbler&, const std::vector<size_t>&, CrtLabels&);
+    static ConcatFn& concat_hook() {
+        static ConcatFn f = nullptr;
+        return f;
+    }
+    void concat_saved(const std::vector<size_t>& idx, CrtLabels& cur) {
+        DASH_CHECK(concat_hook() != nullptr, "gpu garbler: concat is not linked in");
+        concat_hook()(*this, idx, cur);
+    }
     // max pool / max: window values, one ReLU-gadget tree level per call (relu_garble_elem on streams
     // 20 + 2 lv / 21 + 2 lv), then the reduced values become cur
     void maxpool_begin(const std::vector<std::vector<i64>>& win, CrtLabels& cur);
@@ -76,6 +88,7 @@ class GpuGarbler {
     struct Impl;
 
    private:
+    static void concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& idx, CrtLabels& cur);
     std::unique_ptr<Impl> impl_;
 };
 

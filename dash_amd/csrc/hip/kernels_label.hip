@@ -78,6 +78,38 @@ __global__ __launch_bounds__(256) void k_window_sum(Act in, int64_t Nin, Act out
     out.p[j][(static_cast<int64_t>(b) * n + c) * Nout + o] = static_cast<act_t>(acc % p);
 }
 
+// sum pool with padding / ceil_mode, straight from the geometry: out[c][oy][ox] = sum of the window's in-image
+// taps (taps in the padding or past the edge are skipped)            grid (ceil(C*OH*OW*n_max/256), k, B)
+__global__ __launch_bounds__(256) void k_pool_sum(Act in, Act out, PoolArgs g, CrtInfo crt) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int n = crt.n[j], p = crt.p[j];
+    const int64_t Nin = static_cast<int64_t>(g.C) * g.H * g.W, Nout = static_cast<int64_t>(g.C) * g.OH * g.OW;
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= Nout * n) return;
+    const int64_t c = t / Nout, o = t % Nout;
+    const int ch = static_cast<int>(o / (g.OH * g.OW)), r = static_cast<int>(o % (g.OH * g.OW));
+    const int y0 = (r / g.OW) * g.sh - g.ph, x0 = (r % g.OW) * g.sw - g.pw;
+    const int ya = y0 < 0 ? 0 : y0, yb = y0 + g.kh > g.H ? g.H : y0 + g.kh;
+    const int xa = x0 < 0 ? 0 : x0, xb = x0 + g.kw > g.W ? g.W : x0 + g.kw;
+    const act_t* I = in.p[j] + (static_cast<int64_t>(b) * n + c) * Nin + static_cast<int64_t>(ch) * g.H * g.W;
+    int32_t acc = 0;
+    for (int y = ya; y < yb; ++y)
+        for (int x = xa; x < xb; ++x) acc += I[y * g.W + x];
+    out.p[j][(static_cast<int64_t>(b) * n + c) * Nout + o] = static_cast<act_t>(acc % p);
+}
+
+// channel concat, one operand: out[b][j][c][off + e] = src[b][j][c][e], e < Ns. Row starts and operand offsets have
+// no alignment in general (one byte per element), so this copies bytes.   grid (ceil(Ns*n_max/256), k, B)
+__global__ __launch_bounds__(256) void k_concat_copy(Act src, int64_t Ns, Act out, int64_t Nout, int64_t off,
+                                                     CrtInfo crt) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int n = crt.n[j];
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= Ns * n) return;
+    const int64_t c = t / Ns, e = t % Ns;
+    out.p[j][(static_cast<int64_t>(b) * n + c) * Nout + off + e] = src.p[j][(static_cast<int64_t>(b) * n + c) * Ns + e];
+}
+
 __global__ __launch_bounds__(512) void k_aes_test(const u128* in, u128* out, int64_t n, const uint32_t* te0,
                                                   const uint32_t* rk) {
     __shared__ __attribute__((aligned(16))) uint32_t lds_aes[DASH_AES_LDS_WORDS];
@@ -160,6 +192,14 @@ void launch_window_sum(const Act& in, int64_t Nin, const Act& out, int64_t Nout,
                        const CrtInfo& crt, int B, hipStream_t st) {
     hipLaunchKernelGGL(k_window_sum, g1(Nout * nmax(crt), crt.k, B), dim3(256), 0, st, in, Nin, out, Nout, idx, K,
                        crt);
+}
+void launch_pool_sum(const Act& in, const Act& out, const PoolArgs& g, const CrtInfo& crt, int B, hipStream_t st) {
+    const int64_t Nout = static_cast<int64_t>(g.C) * g.OH * g.OW;
+    hipLaunchKernelGGL(k_pool_sum, g1(Nout * nmax(crt), crt.k, B), dim3(256), 0, st, in, out, g, crt);
+}
+void launch_concat_copy(const Act& src, int64_t Ns, const Act& out, int64_t Nout, int64_t off, const CrtInfo& crt,
+                        int B, hipStream_t st) {
+    hipLaunchKernelGGL(k_concat_copy, g1(Ns * nmax(crt), crt.k, B), dim3(256), 0, st, src, Ns, out, Nout, off, crt);
 }
 // out[c][r] = in[r][c]: 64x64 tiles through LDS (row pitch 65: conflict-free
 // column reads), both global sides coalesced; element types may differ (label

@@ -74,6 +74,14 @@ void launch_pair_add(const Act& v, int64_t Nv, const Act& r, const Act& nv, int6
 void launch_add(const Act& x, const Act& y, int64_t N, const CrtInfo& crt, int B, hipStream_t st);
 void launch_window_sum(const Act& in, int64_t Nin, const Act& out, int64_t Nout, const int64_t* idx, int K,
                        const CrtInfo& crt, int B, hipStream_t st);
+// padded / ceil-mode sum pool straight from the geometry (no index table; out-of-image taps are skipped)
+struct PoolArgs {
+    int C, H, W, kh, kw, sh, sw, ph, pw, OH, OW;
+};
+void launch_pool_sum(const Act& in, const Act& out, const PoolArgs& g, const CrtInfo& crt, int B, hipStream_t st);
+// one concat operand: rows of Ns elements into rows of Nout elements at element offset off
+void launch_concat_copy(const Act& src, int64_t Ns, const Act& out, int64_t Nout, int64_t off, const CrtInfo& crt,
+                        int B, hipStream_t st);
 void launch_aes_bench(u128* out, int blocks, int iters, const AesGlobals& g, hipStream_t st);
 void launch_aes_test(const u128* in, u128* out, int64_t n, const AesGlobals& g, hipStream_t st);
 void launch_hard_test(const u128* key, const uint64_t* gate, const uint32_t* sub, const uint32_t* blk, u128* out,

@@ -802,6 +802,13 @@ void HipEvaluator::build() {
                     N = 1;
                     break;
                 case K_SUMPOOL: N = PoolGeom(l.p).out_size(); break;
+                case K_CONCAT:
+                    N = 0;
+                    for (i64 s : l.vec("srcs")) {
+                        DASH_CHECK(s >= -1 && s < static_cast<i64>(li0), "concat: bad source layer");
+                        N += outN[s + 1];
+                    }
+                    break;
                 case K_MULT: case K_MMULT: N /= 2; break;
                 case K_PROJ: {
                     const auto& om = l.vec("out_mod");
@@ -848,6 +855,8 @@ void HipEvaluator::build() {
     std::vector<int> keep(m0.layers.size() + 1, 0);
     for (auto& l : m0.layers) {
         if (l.kind == K_ADD) keep[l.param("src") + 1] = 1;
+        if (l.kind == K_CONCAT)
+            for (i64 s : l.vec("srcs")) keep[s + 1] = 1;
         if (l.p.count("in_src")) keep[l.param("in_src") + 1] = 1;
     }
     saved_.assign(m0.layers.size() + 1, {});
@@ -1368,6 +1377,20 @@ void HipEvaluator::build() {
             }
             case K_SUMPOOL: {
                 PoolGeom G(g.p);
+                if (G.padded()) {
+                    // ragged windows: the geometry-direct kernel skips the taps outside the image
+                    const PoolArgs pa{static_cast<int>(G.C),  static_cast<int>(G.H),  static_cast<int>(G.W),
+                                      static_cast<int>(G.kh), static_cast<int>(G.kw), static_cast<int>(G.sh),
+                                      static_cast<int>(G.sw), static_cast<int>(G.ph), static_cast<int>(G.pw),
+                                      static_cast<int>(G.OH), static_cast<int>(G.OW)};
+                    DASH_CHECK(G.C * G.H * G.W == N, "sumpool input size mismatch");
+                    Act x = act_of(cur), y = act_of(nxt);
+                    const int B = B_;
+                    add_op(lname + ".geom", [x, y, pa, crt, B](hipStream_t st) { launch_pool_sum(x, y, pa, crt, B, st); });
+                    N = G.out_size();
+                    cur = nxt;
+                    break;
+                }
                 std::vector<i64> idx, w;
                 for (i64 o = 0; o < G.out_size(); ++o) {
                     G.window(o, w);
@@ -1392,6 +1415,34 @@ void HipEvaluator::build() {
                 const i64 NN = N;
                 const int B = B_;
                 add_op(lname, [x, y, NN, crt, B](hipStream_t st) { launch_add(x, y, NN, crt, B, st); });
+                break;
+            }
+            case K_CONCAT: {
+                // operands are saved copies (also the previous layer's output); each goes to its element offset
+                const auto& srcs = g.vec("srcs");
+                DASH_CHECK(!srcs.empty(), "concat: no operands");
+                i64 Ntot = 0;
+                for (i64 s : srcs) {
+                    DASH_CHECK(s >= -1 && s < static_cast<i64>(li) && !saved_[s + 1].empty(), "concat source not saved");
+                    DASH_CHECK(saved_mods[s + 1] == saved_mods[srcs[0] + 1], "concat: operands on different moduli");
+                    Ntot += saved_n[s + 1];
+                }
+                mods = saved_mods[srcs[0] + 1];
+                const CrtInfo ci = crt_info(mods);
+                Act y = act_of(nxt);
+                const int B = B_;
+                i64 off = 0;
+                for (i64 s : srcs) {
+                    Act x{};
+                    for (int j = 0; j < k_; ++j) x.p[j] = saved_[s + 1][j];
+                    const i64 Ns = saved_n[s + 1], o = off;
+                    add_op(lname, [x, Ns, y, Ntot, o, ci, B](hipStream_t st) {
+                        launch_concat_copy(x, Ns, y, Ntot, o, ci, B, st);
+                    });
+                    off += Ns;
+                }
+                N = Ntot;
+                cur = nxt;
                 break;
             }
             case K_PROJ: {

@@ -18,11 +18,16 @@ struct ConvGeom {
 };
 
 struct PoolGeom {
-    i64 C, H, W, kh, kw, sh, sw, OH, OW;
+    // ph/pw: symmetric padding (at most half the kernel); ceil: ONNX/PyTorch ceil_mode output size
+    i64 C, H, W, kh, kw, sh, sw, ph, pw, ceil, OH, OW;
     explicit PoolGeom(const Params& p);
     i64 out_size() const { return C * OH * OW; }
-    // flattened input indices of output element o's window (row-major)
+    bool padded() const { return ph || pw || ceil; }
+    // flattened input indices of output element o's window (row-major), always kh*kw of them: a tap outside
+    // the image is replaced by the tap at the clamped coordinate, which lies in the same window (max pooling)
     void window(i64 o, std::vector<i64>& idx) const;
+    // the in-image taps only (sum pooling); at least one, at most kh*kw
+    void window_inside(i64 o, std::vector<i64>& idx) const;
 };
 
 // Pairwise max-reduction schedule over a window of K values: level l has

@@ -32,6 +32,7 @@ enum Kind : int {
     K_BASEEXT = 11,
     K_ADD = 12,
     K_SUMPOOL = 13,
+    K_CONCAT = 14,
 };
 const char* kind_name(int kind);
 

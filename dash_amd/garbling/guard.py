@@ -23,7 +23,8 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
 
 * on a GPU, ``DevRangeGuard`` (csrc/hip/guard.hip): one HIP launch per layer over chunks of the batch,
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
-  evaluation; inputs whose activations exceed the int32 operand range are re-decided by the numpy model;
+  evaluation; inputs whose activations exceed the int32 operand range are re-decided by the numpy model. It
+  has no Concat and no padded / ceil-mode pooling: circuits with either take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
 * the per-input numpy model (``violations_np``), the exact reference of both and the path of layers without a
@@ -56,7 +57,12 @@ class RangeGuard:
         self.circuit, self.M, self.mrs = circuit, int(crt_modulus), bool(mrs)
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
-                                          L.SumPool2d, L.Add, L.Projection, L.BaseExtension)) for l in circuit.layers)
+                                          L.SumPool2d, L.Add, L.Concat, L.Projection, L.BaseExtension))
+                           for l in circuit.layers)
+        # DevRangeGuard (guard.hip) has no Concat and no padded / ceil-mode pooling: such circuits take the
+        # batched torch path
+        self.native_forms = not any(isinstance(l, L.Concat) or
+                                    (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
         self._stream = None
         self._dev = None  # DevRangeGuard (GPU), built on first use
@@ -184,13 +190,23 @@ class RangeGuard:
                 out = mn = None
                 for dy in range(l.kh):
                     for dx in range(l.kw):
-                        w = v[:, :, dy:dy + l.sh * (l.OH - 1) + 1:l.sh, dx:dx + l.sw * (l.OW - 1) + 1:l.sw]
+                        if l.padded:  # a tap outside the image reads the clamped coordinate (layers.MaxPool2d)
+                            ys, xs = l._coords(dy, dx)
+                            ys = torch.as_tensor(np.clip(ys, 0, l.H - 1), device=X.device)
+                            xs = torch.as_tensor(np.clip(xs, 0, l.W - 1), device=X.device)
+                            w = v[:, :, ys[:, None], xs[None, :]]
+                        else:
+                            w = v[:, :, dy:dy + l.sh * (l.OH - 1) + 1:l.sh, dx:dx + l.sw * (l.OW - 1) + 1:l.sw]
                         out = w if out is None else torch.maximum(out, w)
                         mn = w if mn is None else torch.minimum(mn, w)
                 bad |= ((out - mn).reshape(B, -1) > self.span_max()).any(dim=1)
                 out = out.reshape(B, -1)
             elif isinstance(l, L.SumPool2d):
                 v = inp.view(B, l.C, l.H, l.W)
+                if l.padded:  # zero padding up to the last window's end: skipped taps add nothing
+                    eh = max(0, (l.OH - 1) * l.sh + l.kh - l.ph - l.H)
+                    ew = max(0, (l.OW - 1) * l.sw + l.kw - l.pw - l.W)
+                    v = F.pad(v, (l.pw, ew, l.ph, eh))
                 out = 0
                 for dy in range(l.kh):
                     for dx in range(l.kw):
@@ -198,6 +214,8 @@ class RangeGuard:
                 out = out.reshape(B, -1)
             elif isinstance(l, L.Add):
                 out = inp + ctx[l.src + 1]
+            elif isinstance(l, L.Concat):
+                out = torch.cat([ctx[s + 1].reshape(B, -1) for s in l.srcs], dim=1)
             else:  # Flatten, Projection, BaseExtension: value-preserving
                 out = inp.reshape(B, -1)
             ctx.append(out)
@@ -333,7 +351,7 @@ class RangeGuard:
         return self._dev
 
     def _native_ok(self) -> bool:
-        if self.device is None or not self.batched:
+        if self.device is None or not self.batched or not self.native_forms:
             return False
         try:
             import torch

@@ -34,6 +34,7 @@ class Kind:
     BASEEXT = 11
     ADD = 12
     SUMPOOL = 13
+    CONCAT = 14
 
 
 def _size(d: Sequence[int]) -> int:
@@ -443,30 +444,79 @@ class Flatten(Layer):
         return np.asarray(x).reshape(-1)
 
 
-class MaxPool2d(Layer):
-    """Max pooling as a pairwise tree of max(a,b) = a + relu(b - a).
-    Reference: max_pool2d.h, garbled_maxpool2d.h (output dims use the stride,
-    fixing §2.7 #8)."""
+def _pool_out(n: int, k: int, s: int, p: int, ceil_mode: bool) -> int:
+    """PyTorch/ONNX pooled size of one axis: floor_or_ceil((n + 2p - k)/s) + 1; with
+    ceil_mode the last window must start inside the image or its left padding."""
+    span = n + 2 * p - k
+    if span < 0:
+        raise ValueError(f"pool kernel {k} larger than the padded input {n} + 2*{p}")
+    o = (-(-span // s) if ceil_mode else span // s) + 1
+    if ceil_mode and (o - 1) * s >= n + p:
+        o -= 1
+    return o
 
-    kind = Kind.MAXPOOL
-    name = "max_pool"
+
+class _Pool2d(Layer):
+    """Shared pooling geometry: symmetric padding (at most half the kernel) and
+    ceil_mode, with the PyTorch/ONNX output-size rule."""
 
     def __init__(self, input_width, input_height, channel, kernel_width, kernel_height, stride_width=None,
-                 stride_height=None):
+                 stride_height=None, pad_width=0, pad_height=0, ceil_mode=False):
         self.C, self.H, self.W = int(channel), int(input_height), int(input_width)
         self.kh, self.kw = int(kernel_height), int(kernel_width)
         self.sh = int(stride_height if stride_height is not None else kernel_height)
         self.sw = int(stride_width if stride_width is not None else kernel_width)
-        self.OH = (self.H - self.kh) // self.sh + 1
-        self.OW = (self.W - self.kw) // self.sw + 1
+        self.ph, self.pw, self.ceil_mode = int(pad_height), int(pad_width), bool(ceil_mode)
+        if self.ph < 0 or self.pw < 0 or 2 * self.ph > self.kh or 2 * self.pw > self.kw:
+            raise ValueError(f"pool padding ({self.ph}, {self.pw}) must be at most half the kernel "
+                             f"({self.kh}, {self.kw})")
+        self.OH = _pool_out(self.H, self.kh, self.sh, self.ph, self.ceil_mode)
+        self.OW = _pool_out(self.W, self.kw, self.sw, self.pw, self.ceil_mode)
         super().__init__((self.C, self.H, self.W), (self.C, self.OH, self.OW))
+
+    @property
+    def padded(self) -> bool:
+        return bool(self.ph or self.pw or self.ceil_mode)
+
+    def _coords(self, dy, dx):
+        """Image coordinates (unclamped) of tap (dy, dx) for every output row / column."""
+        return (np.arange(self.OH) * self.sh + dy - self.ph, np.arange(self.OW) * self.sw + dx - self.pw)
+
+    def garble_spec(self):
+        spec = {"C": self.C, "H": self.H, "W": self.W, "kh": self.kh, "kw": self.kw, "sh": self.sh, "sw": self.sw}
+        # emitted only when set: pools without padding keep their wire bytes
+        if self.ph:
+            spec["ph"] = self.ph
+        if self.pw:
+            spec["pw"] = self.pw
+        if self.ceil_mode:
+            spec["ceil"] = 1
+        return self.kind, spec
+
+
+class MaxPool2d(_Pool2d):
+    """Max pooling as a pairwise tree of max(a,b) = a + relu(b - a).
+    Reference: max_pool2d.h, garbled_maxpool2d.h (output dims use the stride,
+    fixing §2.7 #8).
+
+    With padding or ceil_mode a tap outside the image is replaced by the tap at
+    the clamped coordinate. Pads are at most half the kernel, so that tap lies in
+    the same window and the max is unchanged; every window keeps kh*kw values
+    and the max tree stays uniform. The duplicated taps of border windows cost
+    real ReLU gadgets (tables and evaluation work); that is accepted in place of
+    ragged trees."""
+
+    kind = Kind.MAXPOOL
+    name = "max_pool"
 
     def _windows(self, x):
         x = np.asarray(x).reshape(self.C, self.H, self.W)
         out = []
         for dy in range(self.kh):
             for dx in range(self.kw):
-                out.append(x[:, dy:dy + self.sh * (self.OH - 1) + 1:self.sh, dx:dx + self.sw * (self.OW - 1) + 1:self.sw])
+                ys, xs = self._coords(dy, dx)
+                ys, xs = np.clip(ys, 0, self.H - 1), np.clip(xs, 0, self.W - 1)
+                out.append(x[:, ys[:, None], xs[None, :]])
         return out
 
     def plain_eval(self, x, track=True, ctx=None):
@@ -479,38 +529,29 @@ class MaxPool2d(Layer):
         w = self._windows(np.asarray(x, dtype=np.int64))
         y = np.max(np.stack(w), axis=0).reshape(-1)
         if track:
-            # differences b - a feed the ReLU gadgets
+            # differences b - a feed the ReLU gadgets (duplicated border taps included)
             self._track_q(y, *[a - b for a in w for b in w])
         return y
 
-    def garble_spec(self):
-        return self.kind, {"C": self.C, "H": self.H, "W": self.W, "kh": self.kh, "kw": self.kw, "sh": self.sh,
-                           "sw": self.sw}
 
-
-class SumPool2d(Layer):
+class SumPool2d(_Pool2d):
     """Window sum (free in the label domain). Average pooling = SumPool2d + a
-    rescale or a weight fold into the next linear layer."""
+    rescale or a weight fold into the next linear layer. With padding or
+    ceil_mode the taps outside the image are skipped (zero padding)."""
 
     kind = Kind.SUMPOOL
     name = "sum_pool"
 
-    def __init__(self, input_width, input_height, channel, kernel_width, kernel_height, stride_width=None,
-                 stride_height=None):
-        self.C, self.H, self.W = int(channel), int(input_height), int(input_width)
-        self.kh, self.kw = int(kernel_height), int(kernel_width)
-        self.sh = int(stride_height if stride_height is not None else kernel_height)
-        self.sw = int(stride_width if stride_width is not None else kernel_width)
-        self.OH = (self.H - self.kh) // self.sh + 1
-        self.OW = (self.W - self.kw) // self.sw + 1
-        super().__init__((self.C, self.H, self.W), (self.C, self.OH, self.OW))
-
     def _sum(self, x):
         x = np.asarray(x).reshape(self.C, self.H, self.W)
-        acc = 0
+        acc = np.zeros((self.C, self.OH, self.OW), dtype=x.dtype)
         for dy in range(self.kh):
             for dx in range(self.kw):
-                acc = acc + x[:, dy:dy + self.sh * (self.OH - 1) + 1:self.sh, dx:dx + self.sw * (self.OW - 1) + 1:self.sw]
+                ys, xs = self._coords(dy, dx)
+                oy = np.nonzero((ys >= 0) & (ys < self.H))[0]
+                ox = np.nonzero((xs >= 0) & (xs < self.W))[0]
+                if oy.size and ox.size:
+                    acc[:, oy[:, None], ox[None, :]] += x[:, ys[oy][:, None], xs[ox][None, :]]
         return acc.reshape(-1)
 
     def plain_eval(self, x, track=True, ctx=None):
@@ -521,10 +562,6 @@ class SumPool2d(Layer):
         if track:
             self._track_q(y)
         return y
-
-    def garble_spec(self):
-        return self.kind, {"C": self.C, "H": self.H, "W": self.W, "kh": self.kh, "kw": self.kw, "sh": self.sh,
-                           "sw": self.sw}
 
 
 class Add(Layer):
@@ -549,6 +586,47 @@ class Add(Layer):
 
     def garble_spec(self):
         return self.kind, {"src": self.src}
+
+
+class Concat(Layer):
+    """Channel concatenation of the outputs of layers `srcs` (-1 = circuit
+    input), in that order; the previous layer is named like any other operand.
+    With the [C][H][W] layout this is the concatenation of the flat vectors, so
+    1-D operands concatenate too. Free in the label domain: no tables, no PRG
+    draws, no constants."""
+
+    kind = Kind.CONCAT
+    name = "concat"
+
+    def __init__(self, dims_list, srcs):
+        dims_list = [tuple(int(v) for v in d) for d in dims_list]
+        self.srcs = [int(s) for s in srcs]
+        if not dims_list or len(dims_list) != len(self.srcs):
+            raise ValueError("Concat needs one dims entry per source")
+        d0 = dims_list[0]
+        for d in dims_list:
+            if len(d) != len(d0) or d[1:] != d0[1:]:
+                raise ValueError(f"Concat operands must agree on all but the channel axis: {dims_list}")
+        self.dims_list = dims_list
+        super().__init__(d0, (sum(d[0] for d in dims_list),) + d0[1:])
+
+    def _cat(self, ctx, dtype):
+        parts = [np.asarray(ctx[s + 1], dtype=dtype).reshape(-1) for s in self.srcs]
+        for p, d in zip(parts, self.dims_list):
+            assert p.size == _size(d), "concat operand size mismatch"
+        return np.concatenate(parts)
+
+    def plain_eval(self, x, track=True, ctx=None):
+        return self._cat(ctx, np.float32)
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        y = self._cat(ctx, np.int64)
+        if track:
+            self._track_q(y)
+        return y
+
+    def garble_spec(self):
+        return self.kind, {"srcs": list(self.srcs)}
 
 
 # ---- test-only layers (reference: projection.h, mult_layer.h, mixed_mod_mult_layer.h, max.h, base_extension.h)

@@ -13,7 +13,25 @@ factor), q_const = 0.02 for SimpleQuant. Differences (deliberate):
   exporter-specific);
 * Conv `pads` (symmetric) are honoured, Gemm `transB`/`alpha`/`beta`,
   MatMul+Add, BatchNormalization folding into the preceding Conv/Gemm,
-  residual Add of two activations, Identity/Dropout are accepted.
+  residual Add of two activations, Identity/Dropout are accepted;
+* the import follows the graph: every node's data input is resolved through
+  the tensor it names, dims are tracked per tensor, and a layer that does not
+  read the previous layer's output gets `in_src` (projection shortcuts, the
+  branches of a fire / inception module). `Concat` along the channel axis
+  becomes a `Concat` layer; `MaxPool` takes symmetric `pads` and `ceil_mode`.
+
+`ReduceSum` over (2, 3) is the plane `SumPool2d` itself (the exporter writes a
+global sum pool that no linear layer follows this way).
+
+Averages. `AveragePool`, `GlobalAveragePool` and `ReduceMean` over (2, 3)
+import as a `SumPool2d` plus a *pending factor* 1/K on the tensor. The factor
+passes through Relu, MaxPool, Flatten, Identity and Dropout (all commute with a
+positive factor), a Sign drops it, and the next Conv / Gemm / MatMul multiplies
+it into its **weights** (never its bias) before quantization. A factor that
+reaches an Add, a Concat or a graph output has no linear layer to absorb it:
+that raises NotImplementedError naming the node. Refused as well, because no
+single factor exists: `AveragePool` with pads and `count_include_pad=0`, with
+pads and `ceil_mode`, or with a `ceil_mode` that cuts the last window.
 
 `save_onnx_model(path, circuit)` writes a pytorch-style ONNX graph of a float
 circuit with a small protobuf encoder (the python `onnx` package is not
@@ -30,7 +48,7 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import Add, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign
+from .layers import Add, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -71,6 +89,21 @@ class _Spec:
         self.kw = kw
 
 
+def _pool_attrs(node) -> tuple:
+    """(kernel, strides, symmetric pads, ceil_mode) of a MaxPool / AveragePool node."""
+    a, name = node["attrs"], node.get("name") or node["op_type"]
+    k = [int(v) for v in a["kernel_shape"]]
+    st = [int(v) for v in a.get("strides", [1, 1])]
+    pads = [int(v) for v in a.get("pads", [0, 0, 0, 0])]
+    if len(k) != 2 or any(int(v) != 1 for v in a.get("dilations", [1, 1])):
+        raise NotImplementedError(f"onnx: {name}: only undilated 2-D pooling is supported")
+    if pads[0] != pads[2] or pads[1] != pads[3]:
+        raise NotImplementedError(f"onnx: {name}: asymmetric pads {pads} are not supported")
+    if a.get("auto_pad", "NOTSET") not in ("NOTSET", b"NOTSET"):
+        raise NotImplementedError(f"onnx: {name}: auto_pad is not supported")
+    return k, st, (pads[0], pads[1]), bool(int(a.get("ceil_mode", 0)))
+
+
 def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
                              q_const: float = DEFAULT_Q_CONST, q_parameter: int = -1) -> Circuit:
     q_method = QuantizationMethod(q_method)
@@ -81,24 +114,49 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         t = inits[name]
         return np.asarray(t["values"], dtype=np.float32).reshape([int(v) for v in t["dims"]] or [-1])
 
-    dims = _input_dims(model, set(inits))
     specs: list[_Spec] = []
-    producer: dict[str, int] = {}  # tensor name -> index of the spec producing it (-1 = graph input)
+    # per tensor: the spec producing it (-1 = graph input), its dims and the pending average factor (see the
+    # module docstring)
+    producer: dict[str, int] = {}
+    tdims: dict[str, tuple] = {}
+    tfac: dict[str, float] = {}
     data_inputs = [i["name"] for i in model["inputs"] if i["name"] not in inits]
     producer[data_inputs[0]] = -1
+    tdims[data_inputs[0]] = _input_dims(model, set(inits))
+    tfac[data_inputs[0]] = 1.0
     alias: dict[str, str] = {}
     first_dense = True
     last_conv_filters = 0
     nodes = model["nodes"]
     skip = set()
 
-    def src_of(name: str) -> Optional[int]:
-        name = alias.get(name, name)
-        return producer.get(name)
+    def res(name: str) -> str:
+        return alias.get(name, name)
 
-    def emit(spec: _Spec, out_name: str):
+    def src_of(name: str) -> Optional[int]:
+        return producer.get(res(name))
+
+    def data_in(node, name: str) -> tuple:
+        """(producing spec, dims, pending factor) of a node's data input."""
+        r = res(name)
+        if r not in producer:
+            raise NotImplementedError(f"onnx: {node.get('name') or node['op_type']}: input {name!r} is produced by "
+                                      "an unsupported node")
+        return producer[r], tdims[r], tfac[r]
+
+    def emit(spec: _Spec, out_name: str, src: int, dims: tuple, fac: float = 1.0):
+        # a layer that does not read the previous layer's output names its source
+        spec.kw["in_src"] = None if src == len(specs) - 1 else src
         specs.append(spec)
         producer[out_name] = len(specs) - 1
+        tdims[out_name] = tuple(int(v) for v in dims)
+        tfac[out_name] = fac
+
+    def no_factor(node, fac: float):
+        if fac != 1.0:
+            raise NotImplementedError(
+                f"onnx: {node.get('name') or node['op_type']}: an average's 1/K factor reaches this "
+                f"{node['op_type']} before a Conv/Gemm could absorb it")
 
     for ni, node in enumerate(nodes):
         if ni in skip:
@@ -106,15 +164,16 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         op, a = node["op_type"], node["attrs"]
         ins, outs = node["inputs"], node["outputs"]
         if op in ("Identity", "Dropout"):
-            alias[outs[0]] = alias.get(ins[0], ins[0])
+            alias[outs[0]] = res(ins[0])
             continue
         if op == "Flatten" or op == "Reshape":
+            j, dims, fac = data_in(node, ins[0])
             if op == "Reshape" and len(dims) == 1:
-                alias[outs[0]] = alias.get(ins[0], ins[0])
+                alias[outs[0]] = res(ins[0])
                 continue
-            emit(_Spec("flatten", dims=dims), outs[0])
-            dims = (int(np.prod(dims)),)
+            emit(_Spec("flatten", dims=dims), outs[0], j, (int(np.prod(dims)),), fac)
         elif op in ("Gemm", "MatMul"):
+            j, dims, fac = data_in(node, ins[0])
             w = arr(ins[1])
             trans_b = int(a.get("transB", 0)) if op == "Gemm" else 0
             if not trans_b:
@@ -135,9 +194,11 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             if tf and first_dense and last_conv_filters > 0:
                 channel_tf = last_conv_filters
             first_dense = False
-            emit(_Spec("dense", w=w, b=bias, channel_tf=channel_tf), out_name)
-            dims = (w.shape[0],)
+            if fac != 1.0:  # pending average: into the weights, never the bias
+                w = (w * np.float32(fac)).astype(np.float32)
+            emit(_Spec("dense", w=w, b=bias, channel_tf=channel_tf), out_name, j, (w.shape[0],))
         elif op == "Conv":
+            j, dims, fac = data_in(node, ins[0])
             w = arr(ins[1])
             F, Cg, kh, kw = (int(v) for v in w.shape)
             group = int(a.get("group", 1))
@@ -150,10 +211,12 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             assert pads[0] == pads[2] and pads[1] == pads[3], "onnx: only symmetric padding is supported"
             bias = arr(ins[2]).reshape(-1) if len(ins) > 2 and ins[2] else np.zeros(F, np.float32)
             assert len(dims) == 3 and dims[0] == C, f"onnx: conv expects {C} input channels, got dims {dims}"
-            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group), outs[0])
+            if fac != 1.0:
+                w = (w * np.float32(fac)).astype(np.float32)
             H = (dims[1] + 2 * pads[0] - kh) // st[0] + 1
             W = (dims[2] + 2 * pads[1] - kw) // st[1] + 1
-            dims = (F, H, W)
+            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group), outs[0], j,
+                 (F, H, W))
             last_conv_filters = F
         elif op == "BatchNormalization":
             j = src_of(ins[0])
@@ -165,26 +228,90 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             s = specs[j]
             s.kw["w"] = s.kw["w"] * g.reshape((-1,) + (1,) * (s.kw["w"].ndim - 1))
             s.kw["b"] = (s.kw["b"] - mean) * g + shift
-            producer[outs[0]] = j
+            alias[outs[0]] = res(ins[0])
         elif op == "MaxPool":
-            k = [int(v) for v in a["kernel_shape"]]
-            st = [int(v) for v in a.get("strides", [1, 1])]
-            emit(_Spec("maxpool", dims=dims, k=k, stride=st), outs[0])
-            dims = (dims[0], (dims[1] - k[0]) // st[0] + 1, (dims[2] - k[1]) // st[1] + 1)
+            j, dims, fac = data_in(node, ins[0])
+            k, st, pads, ceil = _pool_attrs(node)
+            assert len(dims) == 3, f"onnx: MaxPool expects an image, got dims {dims}"
+            out = (dims[0], _pool_out(dims[1], k[0], st[0], pads[0], ceil), _pool_out(dims[2], k[1], st[1], pads[1], ceil))
+            emit(_Spec("maxpool", dims=dims, k=k, stride=st, pads=pads, ceil=ceil), outs[0], j, out, fac)
+        elif op in ("AveragePool", "GlobalAveragePool", "ReduceMean", "ReduceSum"):
+            j, dims, fac = data_in(node, ins[0])
+            name = node.get("name") or op
+            assert len(dims) == 3, f"onnx: {op} expects an image, got dims {dims}"
+            flat = False
+            if op == "AveragePool":
+                k, st, pads, ceil = _pool_attrs(node)
+                if any(pads) and not int(a.get("count_include_pad", 0)):
+                    raise NotImplementedError(f"onnx: {name}: pads with count_include_pad=0 divide every position "
+                                              "by its own tap count")
+                if ceil and any(pads):
+                    raise NotImplementedError(f"onnx: {name}: ceil_mode with pads is not supported")
+                if ceil:
+                    # a window cut at the edge divides by its own (smaller) tap count: only a ceil_mode that
+                    # cuts no window is a sum with one factor
+                    for n_, k_, s_ in ((dims[1], k[0], st[0]), (dims[2], k[1], st[1])):
+                        if (_pool_out(n_, k_, s_, 0, True) - 1) * s_ + k_ > n_:
+                            raise NotImplementedError(f"onnx: {name}: ceil_mode cuts the last window, whose "
+                                                      "divisor differs")
+                    ceil = False
+            else:
+                if op in ("ReduceMean", "ReduceSum"):
+                    axes = a.get("axes")
+                    if axes is None and len(ins) > 1 and ins[1] in inits:
+                        t = inits[ins[1]]  # opset 18: the axes are an int64 input
+                        axes = list(t["ivalues"]) or [int(v) for v in np.asarray(t["values"]).reshape(-1)]
+                    axes = [axes] if isinstance(axes, int) else (axes or [])
+                    axes = sorted(int(v) % 4 for v in axes)
+                    if tf or axes != [2, 3]:
+                        raise NotImplementedError(f"onnx: {name}: {op} is supported over axes (2, 3) only")
+                    flat = not int(a.get("keepdims", 1))
+                k, st, pads, ceil = [dims[1], dims[2]], [1, 1], (0, 0), False
+            out = (dims[0], _pool_out(dims[1], k[0], st[0], pads[0], ceil), _pool_out(dims[2], k[1], st[1], pads[1], ceil))
+            if op != "ReduceSum":  # the plane sum is the SumPool2d itself
+                fac = fac / float(k[0] * k[1])
+            emit(_Spec("sumpool", dims=dims, k=k, stride=st, pads=pads, ceil=ceil), outs[0], j, out, fac)
+            if flat:  # keepdims=0: (C, 1, 1) -> (C,)
+                emit(_Spec("flatten", dims=out), outs[0], len(specs) - 1, (out[0],), fac)
         elif op == "Relu":
-            emit(_Spec("relu", dims=dims), outs[0])
+            j, dims, fac = data_in(node, ins[0])
+            emit(_Spec("relu", dims=dims), outs[0], j, dims, fac)
         elif op in ("Tanh", "SignTanh", "Sign"):
-            emit(_Spec("sign", dims=dims), outs[0])
+            j, dims, fac = data_in(node, ins[0])
+            emit(_Spec("sign", dims=dims), outs[0], j, dims)  # the sign drops a positive factor
         elif op == "Add":
-            srcs = [src_of(x) for x in ins]
             if any(x in inits for x in ins):
                 raise NotImplementedError("onnx: Add of a constant is only supported directly after MatMul")
-            assert None not in srcs, "onnx: Add operand produced by an unsupported node"
-            prev = len(specs) - 1
-            other = srcs[0] if srcs[1] == prev else srcs[1]
-            emit(_Spec("add", dims=dims, src=other), outs[0])
+            (j0, d0, f0), (j1, d1, f1) = data_in(node, ins[0]), data_in(node, ins[1])
+            no_factor(node, f0)
+            no_factor(node, f1)
+            assert d0 == d1, f"onnx: Add operands of different dims {d0} and {d1}"
+            if j1 == len(specs) - 1:  # the current tensor is the previous layer's where possible
+                j0, j1 = j1, j0
+            emit(_Spec("add", dims=d0, src=j1), outs[0], j0, d0)
+        elif op == "Concat":
+            name = node.get("name") or op
+            ops_ = [data_in(node, x) for x in ins]
+            axis = int(a.get("axis", 1))
+            nd = len(ops_[0][1])
+            if tf or nd not in (1, 3) or axis % (nd + 1) != 1:
+                raise NotImplementedError(f"onnx: {name}: Concat is supported along the channel axis (axis=1 of "
+                                          "NCHW or 2-D tensors) only")
+            for _, d_, f_ in ops_:
+                no_factor(node, f_)
+                if len(d_) != nd or d_[1:] != ops_[0][1][1:]:
+                    raise ValueError(f"onnx: {name}: Concat operands of different H x W")
+            dl = [d_ for _, d_, _ in ops_]
+            out = (sum(d_[0] for d_ in dl),) + tuple(dl[0][1:])
+            emit(_Spec("concat", dims_list=dl, srcs=[j_ for j_, _, _ in ops_]), outs[0], len(specs) - 1, out)
         else:
             raise NotImplementedError(f"onnx: unsupported operator {op}")
+
+    for o in model.get("outputs", []):
+        r = res(o["name"])
+        if r in tfac and tfac[r] != 1.0:
+            raise NotImplementedError(f"onnx: graph output {o['name']!r} carries an average's 1/K factor that no "
+                                      "Conv/Gemm absorbs")
 
     # materialize: quantize weights, insert rescales, remap spec indices -> layer indices
     layers = []
@@ -201,15 +328,21 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             layers.append(Conv2d(kw["w"], kw["b"], W, H, C, F, kw_, kh, kw["stride"][1], kw["stride"][0],
                                  q_parameter, q_method, q_const, pad_width=kw["pads"][1], pad_height=kw["pads"][0],
                                  groups=kw["group"]))
-        elif s.kind == "maxpool":
+        elif s.kind in ("maxpool", "sumpool"):
             C, H, W = kw["dims"]
-            layers.append(MaxPool2d(W, H, C, kw["k"][1], kw["k"][0], kw["stride"][1], kw["stride"][0]))
+            cls = MaxPool2d if s.kind == "maxpool" else SumPool2d
+            layers.append(cls(W, H, C, kw["k"][1], kw["k"][0], kw["stride"][1], kw["stride"][0],
+                              pad_width=kw["pads"][1], pad_height=kw["pads"][0], ceil_mode=kw["ceil"]))
         elif s.kind == "relu":
             layers.append(Relu(kw["dims"]))
         elif s.kind == "sign":
             layers.append(Sign(kw["dims"]))
         elif s.kind == "add":
             layers.append(Add(kw["dims"], spec_to_layer[kw["src"]]))
+        elif s.kind == "concat":
+            layers.append(Concat(kw["dims_list"], [spec_to_layer[j] for j in kw["srcs"]]))
+        if kw.get("in_src") is not None:
+            layers[-1].in_src = spec_to_layer[kw["in_src"]]
         spec_to_layer[i] = len(layers) - 1
         if s.kind in ("dense", "conv"):
             out = layers[-1].out_dims
@@ -264,6 +397,11 @@ def _tensor(name: str, a: np.ndarray) -> bytes:
     return body
 
 
+def _tensor_i64(name: str, vals) -> bytes:
+    a = np.ascontiguousarray(vals, dtype=np.int64)
+    return b"".join(_i(1, d) for d in a.shape) + _i(2, 7) + _s(8, name) + _ld(9, a.tobytes())
+
+
 def _attr_ints(name: str, vals) -> bytes:
     return _ld(5, _s(1, name) + b"".join(_i(8, int(v)) for v in vals) + _i(20, 7))
 
@@ -288,43 +426,92 @@ def _value_info(name: str, dims) -> bytes:
 
 def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
     """Write the float weights of `circuit` as an ONNX (opset 13) graph in the
-    layout pytorch's exporter uses (NCHW input, Gemm with transB=1). Rescale
-    layers are quantization artefacts and are dropped; loading the file back
-    with the same q_method re-inserts them."""
+    layout pytorch's exporter uses (NCHW input, Gemm with transB=1). Tensors
+    are named by layer index, so `in_src`, `Add.src` and `Concat.srcs` become
+    real edges. Rescale layers are quantization artefacts and are dropped;
+    loading the file back with the same q_method re-inserts them. A SumPool2d
+    is written as an average (AveragePool / GlobalAveragePool) and the next
+    linear layer's weights are multiplied by its window size K: the inverse of
+    the import fold."""
     nodes, inits = [], []
-    cur = "input"
-    in_dims = circuit.input_dims
+    names = {-1: "input"}  # layer index -> name of the tensor holding its output
+    scale = {"input": 1}  # pending sum/average ratio K of a tensor (SumPool2d written as an average)
     for i, l in enumerate(circuit.layers):
         out = f"t{i}"
         name = f"{l.name}_{i}"
+        src = getattr(l, "in_src", None)
+        cur = names[src if src is not None else i - 1]
+        K = scale[cur]
         if isinstance(l, Rescale):
+            names[i] = cur
             continue
+        if isinstance(l, (Add, Concat)):
+            operands = [cur, names[l.src]] if isinstance(l, Add) else [names[s] for s in l.srcs]
+            if any(scale[o] != 1 for o in operands):
+                raise NotImplementedError(f"onnx export: the average before layer {i} ({l.name}) has no linear layer "
+                                          "to fold its window size into")
+        scale[out] = 1
         if isinstance(l, Flatten):
             nodes.append(_node("Flatten", [cur], [out], name, _attr_int("axis", 1)))
+            scale[out] = K
         elif isinstance(l, Dense):
             assert l.channel_tf == 0, "onnx export: TF channel order is not representable"
-            inits += [_tensor(f"{name}.weight", l.weights), _tensor(f"{name}.bias", l.biases)]
+            inits += [_tensor(f"{name}.weight", l.weights * np.float32(K)), _tensor(f"{name}.bias", l.biases)]
             nodes.append(_node("Gemm", [cur, f"{name}.weight", f"{name}.bias"], [out], name,
                                _attr_float("alpha", 1.0) + _attr_float("beta", 1.0) + _attr_int("transB", 1)))
         elif isinstance(l, Conv2d):
-            inits += [_tensor(f"{name}.weight", l.weights), _tensor(f"{name}.bias", l.biases)]
+            inits += [_tensor(f"{name}.weight", l.weights * np.float32(K)), _tensor(f"{name}.bias", l.biases)]
             attrs = (_attr_ints("dilations", [1, 1]) + _attr_int("group", l.groups) + _attr_ints("kernel_shape", [l.kh, l.kw])
                      + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + _attr_ints("strides", [l.sh, l.sw]))
             nodes.append(_node("Conv", [cur, f"{name}.weight", f"{name}.bias"], [out], name, attrs))
         elif isinstance(l, MaxPool2d):
-            attrs = _attr_ints("kernel_shape", [l.kh, l.kw]) + _attr_ints("pads", [0, 0, 0, 0]) + \
+            attrs = _attr_ints("kernel_shape", [l.kh, l.kw]) + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + \
                 _attr_ints("strides", [l.sh, l.sw])
+            if l.ceil_mode:
+                attrs += _attr_int("ceil_mode", 1)
             nodes.append(_node("MaxPool", [cur], [out], name, attrs))
+            scale[out] = K
+        elif isinstance(l, SumPool2d):
+            if l.ceil_mode and ((l.OH - 1) * l.sh + l.kh > l.H + l.ph or (l.OW - 1) * l.sw + l.kw > l.W + l.pw):
+                raise NotImplementedError(f"onnx export: layer {i}: a ceil-mode sum pool whose last window is cut "
+                                          "is no average with one divisor")
+            plane = (l.kh, l.kw) == (l.H, l.W) and not l.padded
+            if plane and not any(isinstance(m, (Conv2d, Dense)) for m in circuit.layers[i + 1:]):
+                # no later linear layer could absorb an average's K (a classifier conv + global pool head):
+                # the plane sum itself
+                inits.append(_tensor_i64(f"{name}.axes", [2, 3]))
+                nodes.append(_node("ReduceSum", [cur, f"{name}.axes"], [out], name, _attr_int("keepdims", 1)))
+                names[i] = out
+                scale[out] = K
+                continue
+            if plane:
+                nodes.append(_node("GlobalAveragePool", [cur], [out], name))
+            else:
+                attrs = _attr_ints("kernel_shape", [l.kh, l.kw]) + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + \
+                    _attr_ints("strides", [l.sh, l.sw])
+                if l.ph or l.pw:
+                    attrs += _attr_int("count_include_pad", 1)
+                nodes.append(_node("AveragePool", [cur], [out], name, attrs))
+            scale[out] = K * l.kh * l.kw
         elif isinstance(l, Relu):
             nodes.append(_node("Relu", [cur], [out], name))
+            scale[out] = K
         elif isinstance(l, Sign):
             nodes.append(_node("Sign", [cur], [out], name))
+        elif isinstance(l, Add):
+            nodes.append(_node("Add", [cur, names[l.src]], [out], name))
+        elif isinstance(l, Concat):
+            nodes.append(_node("Concat", [names[s] for s in l.srcs], [out], name, _attr_int("axis", 1)))
         else:
             raise NotImplementedError(f"onnx export: layer {l.name} has no ONNX equivalent")
-        cur = out
-    dims = (1,) + tuple(in_dims)
+        names[i] = out
+    last = names[len(circuit.layers) - 1]
+    if scale[last] != 1:
+        raise NotImplementedError("onnx export: the circuit ends in an average with no linear layer to fold its "
+                                  "window size into")
+    dims = (1,) + tuple(circuit.input_dims)
     graph = b"".join(nodes) + _s(2, "dash_amd") + b"".join(_ld(5, t) for t in inits)
     graph += _ld(11, _value_info("input", dims))
-    graph += _ld(12, _value_info(cur, (1,) + tuple(circuit.output_dims)))
+    graph += _ld(12, _value_info(last, (1,) + tuple(circuit.output_dims)))
     model = _i(1, 7) + _s(2, producer) + _s(3, "1") + _ld(7, graph) + _ld(8, _s(1, "") + _i(2, 13))
     Path(path).write_bytes(model)

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
+from ..ir.layers import Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
 from ..ir.quant import QuantizationMethod
 from .zoo import ARCHS, canonical
 
@@ -81,13 +81,15 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
         elif k == "sign":
             mods.append(nn.Tanh())  # trained as tanh, garbled as sign (onnx_modelloader.h Tanh -> Sign)
         elif k == "maxpool":
-            mods.append(nn.MaxPool2d(op[1], op[2]))
-            dims = [dims[0], (dims[1] - op[1]) // op[2] + 1, (dims[2] - op[1]) // op[2] + 1]
+            pad, ceil = (op[3], bool(op[4])) if len(op) > 3 else (0, False)  # ("maxpool", k, s[, pad, ceil_mode])
+            mods.append(nn.MaxPool2d(op[1], op[2], padding=pad, ceil_mode=ceil))
+            dims = [dims[0], _pool_out(dims[1], op[1], op[2], pad, ceil), _pool_out(dims[2], op[1], op[2], pad, ceil)]
         elif k == "sumpool":
             mods.append(nn.AvgPool2d(op[1]))
             dims = [dims[0], dims[1] // op[1], dims[2] // op[1]]
         else:
-            raise NotImplementedError(f"training: op {k} (residual blocks) not supported by the sequential trainer")
+            raise NotImplementedError(f"training: op {k} (residual blocks, fire modules, global pooling) not supported "
+                                      "by the sequential trainer")
     seq = nn.Sequential(*mods)
     seq.fq = fq  # set seq.fq.c = 0 to evaluate the float network
     return seq
@@ -132,8 +134,9 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
         elif isinstance(m, nn.Tanh):
             layers.append(Sign(dims))
         elif isinstance(m, nn.MaxPool2d):
-            k, s = int(m.kernel_size), int(m.stride)
-            mp = MaxPool2d(dims[2], dims[1], dims[0], k, k, s, s)
+            k, s, pad = int(m.kernel_size), int(m.stride), int(m.padding)
+            mp = MaxPool2d(dims[2], dims[1], dims[0], k, k, s, s, pad_width=pad, pad_height=pad,
+                           ceil_mode=bool(m.ceil_mode))
             layers.append(mp)
             dims = mp.out_dims
         elif isinstance(m, nn.AvgPool2d):

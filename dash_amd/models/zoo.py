@@ -12,12 +12,15 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import Add, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
+from ..ir.layers import Add, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
 from ..ir.quant import QuantizationMethod, quantize_input
 
 # architecture ops: ("conv", out_ch, k, stride, pad) | ("relu",) | ("sign",) | ("flatten",) | ("fc", out)
 #                   | ("maxpool", k, s) | ("res", [ops...]) residual block | ("sumpool", k)
 #                   | ("dwconv", k, stride, pad) depthwise conv (groups = channels, F = C)
+#                   | ("maxpool", k, s, pad, ceil_mode) | ("gap",) global sum pool (the average's 1/K is left to
+#                   the next linear layer) | ("fire", squeeze, e1, e3) SqueezeNet fire module: 1x1 squeeze + ReLU,
+#                   then a 1x1 and a padded 3x3 expand (each + ReLU) that both read the squeeze output, then Concat
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     "MODEL_B_POOL_REPL": {"input": (1, 28, 28), "ops": [
@@ -64,6 +67,12 @@ ARCHS: dict[str, dict] = {
         ("dwconv", 3, 2, 1), ("relu",), ("conv", 64, 1, 1, 0), ("relu",),
         ("dwconv", 3, 1, 1), ("relu",), ("conv", 64, 1, 1, 0), ("relu",),
         ("sumpool", 4), ("flatten",), ("fc", 10)]},
+    # SqueezeNet-style CIFAR net: a stride-2 stem (32 -> 16), ceil-mode 3x3/2 max pools whose last window is cut at
+    # the edge (16 -> 8 -> 4), two fire modules, a 1x1 classifier conv and a global average over the 4x4 plane
+    "SQUEEZENET_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 2, 1), ("relu",), ("maxpool", 3, 2, 0, True),
+        ("fire", 8, 16, 16), ("maxpool", 3, 2, 0, True), ("fire", 8, 16, 16),
+        ("conv", 10, 1, 1, 0), ("gap",), ("flatten",)]},
 }
 
 ALIASES = {"MINIONN": "MODEL_F_MINIONN_POOL_REPL", "GNNP": "MODEL_F_GNNP_POOL_REPL", "MLP": "MODEL_A",
@@ -140,14 +149,34 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         elif kind == "sign":
             layers.append(Sign(dims))
         elif kind == "maxpool":
-            _, k, s = op
-            mp = MaxPool2d(dims[2], dims[1], dims[0], k, k, s, s)
+            k, s = op[1], op[2]
+            pad, ceil = (op[3], op[4]) if len(op) > 3 else (0, False)
+            mp = MaxPool2d(dims[2], dims[1], dims[0], k, k, s, s, pad_width=pad, pad_height=pad, ceil_mode=ceil)
             layers.append(mp)
             dims = mp.out_dims
         elif kind == "sumpool":
             sp = SumPool2d(dims[2], dims[1], dims[0], op[1], op[1])
             layers.append(sp)
             dims = sp.out_dims
+        elif kind == "gap":
+            sp = SumPool2d(dims[2], dims[1], dims[0], dims[2], dims[1])
+            layers.append(sp)
+            dims = sp.out_dims
+        elif kind == "fire":
+            _, sq, e1, e3 = op
+            d_sq = conv(sq, 1, 1, 0, dims[0], dims[1], dims[2])
+            layers.append(Relu(d_sq))
+            squeeze = len(layers) - 1
+            d1 = conv(e1, 1, 1, 0, sq, d_sq[1], d_sq[2])
+            layers.append(Relu(d1))
+            left = len(layers) - 1
+            first3 = len(layers)
+            d3 = conv(e3, 3, 1, 1, sq, d_sq[1], d_sq[2])
+            layers[first3].in_src = squeeze  # the 3x3 expand reads the squeeze output, not the 1x1 expand
+            layers.append(Relu(d3))
+            cat = Concat([d1, d3], [left, len(layers) - 1])
+            layers.append(cat)
+            dims = cat.out_dims
         elif kind == "res":
             _, cout, stride = op
             cin = dims[0]
@@ -204,5 +233,7 @@ BENCH_CONFIGS = {
                                                 crt=[32, 3, 5, 7, 11, 13, 17], mrs=[10, 9, 9, 8, 7, 7, 6]),
     "MODEL_DWSEP_CIFAR/DASH": dict(model="MODEL_DWSEP_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
                                    crt=7, mrs=100.0),
+    "SQUEEZENET_CIFAR/DASH": dict(model="SQUEEZENET_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
+                                  crt=7, mrs=100.0),
     "MODEL_A/SIMPLE": dict(model="MODEL_A", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8, mrs=100.0),
 }
