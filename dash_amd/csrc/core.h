@@ -365,6 +365,7 @@ enum TweakKind : uint32_t {
     TW_PROJ = 11,   // projection layer
     TW_GME = 12,    // generalized half gate, evaluator half (key y_j)
     TW_MMT = 13,    // mixed-mult layer: the residue-j mod transform (key x_2e+1)
+    TW_CAP = 14,    // clip: the cap projection (key s_hi; slots: residues)
 };
 inline uint32_t tw_sub(TweakKind k, uint32_t idx) { return (static_cast<uint32_t>(k) << 16) | (idx & 0xffffu); }
 

@@ -66,6 +66,46 @@ void relu_eval_elem(const SignPlan& sp, const LabelBank& Z, const std::vector<in
                         T.ea->ptr<u128>() + (e * k + j) * 3, out[j], MMTw{hard, m_gate, j, k, true});
 }
 
+// Clip of one element (gadgets.h ClipPlan): the sign evaluation twice on the same labels, then multiply + cap
+struct ClipTabs {
+    const Array* s[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // [lo / hi]: approx, cast2, sign | mrs
+    const Array *g, *e, *cap;
+    ClipTabs(const GLayer& l, bool exact) : g(&l.arr("mm.g")), e(&l.arr("mm.e")), cap(&l.arr("cap")) {
+        for (int side = 0; side < 2; ++side) {
+            const std::string pre = side ? "hi." : "lo.";
+            if (exact) {
+                s[side][0] = &l.arr(pre + "mrs");
+            } else {
+                s[side][0] = &l.arr(pre + "s.approx");
+                s[side][1] = &l.arr(pre + "s.cast2");
+                s[side][2] = &l.arr(pre + "s.sign");
+            }
+        }
+    }
+};
+
+void clip_eval_elem(const ClipPlan& cp, const SignPlan* sp_a, const SignMrsPlan* sp_m, const LabelBank& Z,
+                    const comp_t* const* x, const ClipTabs& T, i64 e, comp_t* const* out, u64 lo_gate, u64 m_gate,
+                    u64 hi_gate) {
+    const int k = cp.k();
+    comp_t slo[128], shi[128];
+    for (int side = 0; side < 2; ++side) {
+        comp_t* sig = side ? shi : slo;
+        const u64 gate = side ? hi_gate : lo_gate;
+        const Array* const* a = T.s[side];
+        if (sp_m) {
+            sign_mrs_eval_elem(*sp_m, x, a[0]->ptr<u128>() + e * a[0]->shape[1], sig, true, gate);
+        } else {
+            comp_t* outs[1] = {sig};
+            sign_eval_elem(*sp_a, Z, x, a[0]->ptr<u128>() + e * a[0]->shape[1], nullptr,
+                           a[1]->ptr<u128>() + e * a[1]->shape[1], a[2]->ptr<u128>() + e * a[2]->shape[1], outs, true,
+                           gate);
+        }
+    }
+    clip_mult_eval(cp, x, slo, shi, T.g->ptr<u128>() + e * cp.sum_crt, T.e->ptr<u128>() + e * k * 3,
+                   T.cap->ptr<u128>() + e * k * 2, out, m_gate);
+}
+
 // a layer array that the hardened encoding does not ship (bias labels): all-zero rows of the same shape
 const comp_t* zeros_or(const GLayer& g, const std::string& name, bool hard, size_t n, std::vector<comp_t>& buf) {
     if (!hard) return g.arr(name).ptr<comp_t>();
@@ -277,6 +317,32 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                     }
                 }, nt);
                 if (trace) trace->relu_sign[li] = std::move(sigs);
+                cur = std::move(nxt);
+                break;
+            }
+            case K_CLIP: {
+                DASH_CHECK(hard, "clip: the Clip layer exists in the hardened encoding only");
+                const ClipPlan cp(crt, g.vec("lo").at(0), g.vec("hi").at(0));
+                const bool exact = g.param("smode", 0) == 1;
+                SignPlan sp_a;
+                SignMrsPlan sp_m;
+                if (exact) sp_m = SignMrsPlan(crt);
+                else sp_a = SignPlan(crt, m.h.mrs, {2}, 0, 1, fused);
+                const ClipTabs T(g, exact);
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) nxt.emplace_back(crt[j], Nin);
+                parallel_for(Nin, [&](i64 b0, i64 b1) {
+                    std::vector<const comp_t*> x(k);
+                    std::vector<comp_t*> y(k);
+                    for (i64 e = b0; e < b1; ++e) {
+                        for (int j = 0; j < k; ++j) {
+                            x[j] = cur[j].at(e);
+                            y[j] = nxt[j].at(e);
+                        }
+                        clip_eval_elem(cp, exact ? nullptr : &sp_a, exact ? &sp_m : nullptr, Z, x.data(), T, e, y.data(),
+                                       stream_id(L, 1, e), stream_id(L, 2, e), stream_id(L, 3, e));
+                    }
+                }, nt);
                 cur = std::move(nxt);
                 break;
             }

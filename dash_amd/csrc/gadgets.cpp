@@ -853,4 +853,54 @@ void sign_mrs_eval_elem(const SignMrsPlan& P, const comp_t* const* x, const u128
     std::memcpy(sig, key[P.ord[k - 1]], sizeof(comp_t) * nr_comps(2));
 }
 
+// ---------------------------------------------------------------------------
+void clip_shift_base(const ClipPlan& P, const LabelBank& R, const comp_t* const* x0, i64 q, comp_t* dst) {
+    for (int j = 0; j < P.k(); ++j) {
+        const int p = P.crt[j];
+        lab_affine(dst + static_cast<size_t>(128) * j, x0[j], pmod(q, p), R.get(p), nr_comps(p), p);
+    }
+}
+
+void clip_mult_garble(const ClipPlan& P, const LabelBank& R, const Prg& prg, u64 stream, const comp_t* const* x0,
+                      const comp_t* slo0, const comp_t* shi0, u128* g, u128* e, u128* cap, comp_t* const* out0) {
+    const int k = P.k();
+    const ModInfo& m2 = mod_info(2);
+    comp_t u0[128], xs[128], c0[128];
+    std::memcpy(u0, slo0, sizeof(comp_t) * m2.n);
+    lab_add(u0, shi0, m2.n, 2);
+    u64 ctr = 0;
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        lab_affine(xs, x0[j], pmod(P.lo, mp.p), R.get(mp.p), mp.n, mp.p);  // the wire x_j - q_lo
+        mixed_mult_garble(xs, mp, u0, m2, R, prg, stream, ctr, g + P.prefix[j], e + 3 * j, out0[j],
+                          MMTw{true, stream, j, k, true});
+    }
+    ProjKeys& K = proj_keys_scratch();
+    proj_keys(shi0, R.get(2), m2, K, true);
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        draw(prg, stream, ctr, mp.p, c0);
+        const i64 d = pmod(P.hi - P.lo, mp.p);
+        garble_proj_keys(K, c0, R.get(mp.p), mp, [d](int v) { return v * d; }, cap + 2 * j, 1,
+                         Mask{true, stream, tw_sub(TW_CAP, 0), j});
+        lab_add(out0[j], c0, mp.n, mp.p);
+        lab_axpy(out0[j], -pmod(P.lo, mp.p), R.get(mp.p), mp.n, mp.p);  // + q_lo: base - q_lo R
+    }
+}
+
+void clip_mult_eval(const ClipPlan& P, const comp_t* const* x, const comp_t* slo, const comp_t* shi, const u128* g,
+                    const u128* e, const u128* cap, comp_t* const* out, u64 gate) {
+    const int k = P.k();
+    const ModInfo& m2 = mod_info(2);
+    comp_t u[128], c[128];
+    std::memcpy(u, slo, sizeof(comp_t) * m2.n);
+    lab_add(u, shi, m2.n, 2);
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        mixed_mult_eval(x[j], mp, u, m2, g + P.prefix[j], e + 3 * j, out[j], MMTw{true, gate, j, k, true});
+        eval_proj(shi, m2, cap + 2 * j, mp, c, 1, Mask{true, gate, tw_sub(TW_CAP, 0), j});
+        lab_add(out[j], c, mp.n, mp.p);
+    }
+}
+
 }  // namespace dash

@@ -378,4 +378,63 @@ void sign_mrs_garble_elem(const SignMrsPlan& P, const LabelBank& R, const Prg& p
 void sign_mrs_eval_elem(const SignMrsPlan& P, const comp_t* const* x, const u128* tab, comp_t* sig, bool hard = false,
                         u64 gate = 0);
 
+// ---------------------------------------------------------------------------
+// Clip (clamp to public bounds q_lo < q_hi; ONNX Clip, ReLU6) per element
+//
+// Two signs of the same input and one multiply, instead of the two complete
+// ReLU gadgets of relu(x - lo) - relu(x - hi):
+//   s_lo = [x >= q_lo], s_hi = [x >= q_hi]   (mod-2 labels)
+// each from a sign gadget run on the SAME evaluator labels x_j: the public
+// shifts -q_lo / -q_hi are folded into the garbler's base labels of the two
+// gadgets (x0_j + q R_j is the base of the wire x - q with unchanged labels),
+// so the evaluator runs the sign evaluation twice, with two table sets, on one
+// input and does no shift work. The signs are the approximate fused gadget
+// (SignPlan, out {2}, 0/1) or the exact SignMrsPlan; both are exact on
+// x - q in [-M/2, M/2) up to the approximate gadget's own error.
+// q_hi > q_lo, so s_hi = 1 implies s_lo = 1 and the free label sum
+//   u = s_lo + s_hi (mod 2) = [q_lo <= x < q_hi].
+//   out_j = q_lo + u (x_j - q_lo) + s_hi (q_hi - q_lo)   (mod p_j)
+// The product is the mixed-modulus half gate of the ReLU keyed by the label of
+// u, on the wire x_j - q_lo (again a base-label fold): p_j garbler rows, 2
+// evaluator rows and the mini. The last term ("cap") is a 2-row projection
+// Z_2 -> Z_{p_j} keyed by the label of s_hi; q_lo is folded into the output
+// base label. Hardened encoding only: the folds are the hardened encoding's
+// public-constant rule, and the labels of u and s_hi each key k rows, which
+// needs the per-(gate, row, slot) pads (TW_MMY as the ReLU, TW_CAP slot j).
+// Tables: the two sign gadgets' arrays under "lo." / "hi.", mm.g [sum p_j],
+// mm.e [k][3], cap [k][2] (row = color of s_hi). Entries per element, with
+// n_sign the sign gadget's entries (approx: n_approx + n_cast + n_sign; exact:
+// SignMrsPlan::n_tab) and P = sum_j p_j:
+//   clip      2 n_sign + P + 3 k + 2 k
+//   two ReLUs 2 n_sign + 2 P + 6 k
+// (k = 7, first primes: exact 294 + 58 + 35 = 387 against 452.)
+// PRG streams: sign lo = slot 1, multiply and cap = slot 2 (the cap's base
+// label is drawn after the k half gates' draws), sign hi = slot 3.
+struct ClipPlan {
+    std::vector<int> crt;
+    i64 lo = 0, hi = 1;
+    i64 sum_crt = 0;
+    std::vector<i64> prefix;  // mm.g offset of residue j
+    ClipPlan() = default;
+    ClipPlan(const std::vector<int>& crt_, i64 lo_, i64 hi_) : crt(crt_), lo(lo_), hi(hi_) {
+        DASH_CHECK(lo < hi, "clip needs lo < hi");
+        for (int p : crt) {
+            prefix.push_back(sum_crt);
+            sum_crt += p;
+        }
+    }
+    int k() const { return static_cast<int>(crt.size()); }
+    // table entries per element given the sign gadget's entry count
+    i64 entries(i64 n_sign) const { return 2 * n_sign + sum_crt + 3 * k() + 2 * k(); }
+    static i64 two_relu_entries(i64 n_sign, i64 sum_crt, int k) { return 2 * n_sign + 2 * sum_crt + 6 * k; }
+};
+// Tables of one element: the multiply's g [sum_crt] and e [k][3] and the cap [k][2]. slo0 / shi0 (garbler) and
+// slo / shi (evaluator) are the two sign gadgets' mod-2 output (base) labels; gate = the slot-2 stream.
+void clip_mult_garble(const ClipPlan& P, const LabelBank& R, const Prg& prg, u64 stream, const comp_t* const* x0,
+                      const comp_t* slo0, const comp_t* shi0, u128* g, u128* e, u128* cap, comp_t* const* out0);
+void clip_mult_eval(const ClipPlan& P, const comp_t* const* x, const comp_t* slo, const comp_t* shi, const u128* g,
+                    const u128* e, const u128* cap, comp_t* const* out, u64 gate);
+// base labels of the wire x - q on the labels of x: x0_j + (q mod p_j) R_j (dst: k rows of 128 components)
+void clip_shift_base(const ClipPlan& P, const LabelBank& R, const comp_t* const* x0, i64 q, comp_t* dst);
+
 }  // namespace dash

@@ -34,6 +34,7 @@ const char* kind_name(int kind) {
         case K_ADD: return "add";
         case K_SUMPOOL: return "sum_pool";
         case K_CONCAT: return "concat";
+        case K_CLIP: return "clip";
     }
     return "unknown";
 }
@@ -198,6 +199,41 @@ void relu_garble_elem(const SignPlan& sp, const LabelBank& R, const LabelBank& Z
         mixed_mult_garble(x0[j], mp, sig, m2, R, prg, m_stream, ctr, t.g.ptr<u128>() + e * t.g.shape[1] + prefix[j],
                           t.e.ptr<u128>() + (e * k + j) * 3, out0[j], MMTw{hard, m_stream, j, k, true});
     }
+}
+
+// Clip of one element (gadgets.h ClipPlan): two signs of x - q_lo / x - q_hi on the labels of x, then the
+// multiply and the cap. sp_a: the approximate sign (tables lo / hi) or, with sp_m, the exact sign (mlo / mhi).
+struct ClipTables {
+    ReluTables lo, hi;  // approximate sign arrays (g / e unused)
+    Array mlo, mhi;     // exact sign rows
+    Array g, e, cap;
+};
+
+void clip_garble_elem(const ClipPlan& cp, const SignPlan* sp_a, const SignMrsPlan* sp_m, const LabelBank& R,
+                      const LabelBank& Z, const Prg& prg, u64 lo_stream, u64 m_stream, u64 hi_stream,
+                      const comp_t* const* x0, ClipTables& t, i64 e, comp_t* const* out0) {
+    const int k = cp.k();
+    comp_t xs[16 * 128], slo[128], shi[128];
+    DASH_CHECK(k <= 16, "clip: at most 16 residues");
+    const comp_t* xp[16];
+    for (int j = 0; j < k; ++j) xp[j] = xs + static_cast<size_t>(128) * j;
+    for (int side = 0; side < 2; ++side) {
+        clip_shift_base(cp, R, x0, side ? cp.hi : cp.lo, xs);
+        comp_t* sig = side ? shi : slo;
+        const u64 stream = side ? hi_stream : lo_stream;
+        if (sp_m) {
+            Array& tab = side ? t.mhi : t.mlo;
+            sign_mrs_garble_elem(*sp_m, R, prg, stream, xp, tab.ptr<u128>() + e * tab.shape[1], sig, true);
+        } else {
+            ReluTables& s = side ? t.hi : t.lo;
+            comp_t* outs[1] = {sig};
+            sign_garble_elem(*sp_a, R, Z, prg, stream, xp, s.approx.ptr<u128>() + e * sp_a->n_approx, nullptr,
+                             s.cast2.ptr<u128>() + e * s.cast2.shape[1], s.sign.ptr<u128>() + e * sp_a->n_sign, outs,
+                             true);
+        }
+    }
+    clip_mult_garble(cp, R, prg, m_stream, x0, slo, shi, t.g.ptr<u128>() + e * cp.sum_crt,
+                     t.e.ptr<u128>() + e * k * 3, t.cap.ptr<u128>() + e * k * 2, out0);
 }
 
 }  // namespace
@@ -618,6 +654,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
                                     (spec.kind == K_RELU || spec.kind == K_SIGN ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
+                                    spec.kind == K_CLIP ||
                                     (spec.kind == K_RESCALE && (param1(spec.p, "mode", 0) != 0 || crt_[0] == 2)))));
         const bool passthru = spec.kind == K_FLATTEN;
         if (on_gpu && !dev_ok) {
@@ -860,6 +897,87 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 }, nt);
                 put_relu_tables(g, "", t);
                 cur = std::move(nxt);
+                break;
+            }
+            case K_CLIP: {
+                DASH_CHECK(is_crt(), "clip needs CRT-base labels");
+                DASH_CHECK(hard, "clip: the Clip layer exists in the hardened encoding only");
+                const ClipPlan cp(crt_, paramv(spec.p, "lo").at(0), paramv(spec.p, "hi").at(0));
+                // the sign construction follows the ReLU's: exact with relu_mrs / relu_joint, else approximate
+                const bool exact = opt.relu_mrs || opt.relu_joint;
+                ClipTables t;
+                SignPlan sp_a;
+                SignMrsPlan sp_m;
+                if (exact) {
+                    sp_m = SignMrsPlan(crt_);
+                    t.mlo = Array(DType::u128, {Nin, std::max<i64>(sp_m.n_tab, 1)});
+                    t.mhi = Array(DType::u128, {Nin, std::max<i64>(sp_m.n_tab, 1)});
+                } else {
+                    sp_a = SignPlan(crt_, mrs_, {2}, 0, 1, fused);
+                    for (ReluTables* r : {&t.lo, &t.hi}) {
+                        r->approx = Array(DType::u128, {Nin, sp_a.n_approx});
+                        r->cast2 = Array(DType::u128, {Nin, std::max<i64>(sp_a.n_cast, 1)});
+                        r->sign = Array(DType::u128, {Nin, sp_a.n_sign});
+                    }
+                }
+                t.g = Array(DType::u128, {Nin, sum_crt});
+                t.e = Array(DType::u128, {Nin, static_cast<i64>(k), 3});
+                t.cap = Array(DType::u128, {Nin, static_cast<i64>(k), 2});
+                if (on_gpu) {
+                    Array* st[2][3] = {{&t.mlo, nullptr, nullptr}, {&t.mhi, nullptr, nullptr}};
+                    if (exact) {
+                        sinkify(t.mlo, "lo.mrs");
+                        sinkify(t.mhi, "hi.mrs");
+                    } else {
+                        ReluTables* rt[2] = {&t.lo, &t.hi};
+                        for (int side = 0; side < 2; ++side) {
+                            const std::string pre = side ? "hi." : "lo.";
+                            sinkify(rt[side]->approx, pre + "s.approx");
+                            sinkify(rt[side]->cast2, pre + "s.cast2");
+                            sinkify(rt[side]->sign, pre + "s.sign");
+                            st[side][0] = &rt[side]->approx;
+                            st[side][1] = &rt[side]->cast2;
+                            st[side][2] = &rt[side]->sign;
+                        }
+                    }
+                    sinkify(t.g, "mm.g");
+                    sinkify(t.e, "mm.e");
+                    sinkify(t.cap, "cap");
+                    gpu->clip(L, exact ? &sp_m : nullptr, exact ? nullptr : &sp_a, cp.lo, cp.hi, cur, st, &prefix, t.g,
+                              t.e, t.cap);
+                } else {
+                    CrtLabels nxt;
+                    for (int j = 0; j < k; ++j) nxt.emplace_back(crt_[j], Nin);
+                    parallel_for(Nin, [&](i64 b0, i64 b1) {
+                        std::vector<const comp_t*> x(k);
+                        std::vector<comp_t*> y(k);
+                        for (i64 e = b0; e < b1; ++e) {
+                            for (int j = 0; j < k; ++j) {
+                                x[j] = cur[j].at(e);
+                                y[j] = nxt[j].at(e);
+                            }
+                            clip_garble_elem(cp, exact ? nullptr : &sp_a, exact ? &sp_m : nullptr, R_, Z_, prg_,
+                                             stream_id(L, 1, e), stream_id(L, 2, e), stream_id(L, 3, e), x.data(), t,
+                                             e, y.data());
+                        }
+                    }, nt);
+                    cur = std::move(nxt);
+                }
+                if (exact) {
+                    g.a["lo.mrs"] = t.mlo;
+                    g.a["hi.mrs"] = t.mhi;
+                } else {
+                    g.a["lo.s.approx"] = t.lo.approx;
+                    g.a["lo.s.cast2"] = t.lo.cast2;
+                    g.a["lo.s.sign"] = t.lo.sign;
+                    g.a["hi.s.approx"] = t.hi.approx;
+                    g.a["hi.s.cast2"] = t.hi.cast2;
+                    g.a["hi.s.sign"] = t.hi.sign;
+                }
+                g.a["mm.g"] = t.g;
+                g.a["mm.e"] = t.e;
+                g.a["cap"] = t.cap;
+                g.p["smode"] = {exact ? 1 : 0};
                 break;
             }
             case K_SIGN: {

@@ -1826,6 +1826,53 @@ __global__ __launch_bounds__(256) void k_fold(Ctx c, FoldArgs a) {
     }
 }
 
+// Clip (gadgets.h ClipPlan): u = s_lo + s_hi (mod 2) of two sign-label slots into a third (whole slots, kW
+// components: mod-2 labels fill them)
+__global__ __launch_bounds__(256) void k_clip_u(Gadget g, int lo_slot, int hi_slot, int u_slot) {
+    const int64_t total = static_cast<int64_t>(kW / kCh) * g.N;
+    const int16_t* a = slot_base(g, lo_slot);
+    const int16_t* b = slot_base(g, hi_slot);
+    int16_t* u = slot_base(g, u_slot);
+    for (int64_t x = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; x < total;
+         x += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        uint32_t va[8], vb[8];
+        unpack8(*reinterpret_cast<const u32x4a*>(a + x * kCh), va);
+        unpack8(*reinterpret_cast<const u32x4a*>(b + x * kCh), vb);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) va[q] = (va[q] + vb[q]) & 1u;
+        st_chunk(u + x * kCh, pack8(va));
+    }
+}
+
+// Clip output base labels: out0_j (the half gate's sk04 - sk03) += c0_j (the cap's base label, slot cap0 + j)
+// + neg_j R_pj with neg_j = -q_lo mod p_j. Grid (element x chunk work, residue j).
+struct ClipFin {
+    int16_t* out[kMaxRes];
+    int p[kMaxRes], nc[kMaxRes], neg[kMaxRes];
+    int cap0;
+};
+__global__ __launch_bounds__(256) void k_clip_finish(Ctx c, Gadget g, ClipFin a) {
+    const int j = blockIdx.y;
+    const int p = a.p[j];
+    const ModC m = c.mc[p];
+    const int16_t* Rp = c.R + static_cast<int64_t>(p) * kW;
+    const int16_t* C0 = slot_base(g, a.cap0 + j);
+    const int64_t N = g.N, total = N * a.nc[j];
+    const uint32_t f = static_cast<uint32_t>(a.neg[j]);
+    for (int64_t x = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; x < total;
+         x += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int c8 = static_cast<int>(x / N);
+        int16_t* d = a.out[j] + x * kCh;  // chunk c8 of element e at (c8 * N + e) * 8 = x * 8
+        uint32_t acc[8], t[8], r[8];
+        unpack8(*reinterpret_cast<const u32x4a*>(d), acc);
+        unpack8(*reinterpret_cast<const u32x4a*>(C0 + x * kCh), t);
+        unpack8(*reinterpret_cast<const u32x4a*>(Rp + c8 * kCh), r);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] = modq(acc[q] + t[q] + f * r[q], m);
+        st_chunk(d, pack8(acc));
+    }
+}
+
 // Dense base labels y_o = sum_i w_oi x_i + zc_o Z_p (mod p), weights reduced mod p and transposed ([in][out],
 // rows already in the channel_tf source order), zc_o = 1 + #(w_oi = 0 mod p) (the reference's zero-weight Z
 // quirk, and the bias label's Z). Block: 64 outputs x 4 input groups for one (chunk, residue); the groups'
@@ -2932,6 +2979,7 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
                        const LabelBank& R, const LabelBank& Z, int device, bool hardened)
     : impl_(new Impl(device)) {
     concat_hook() = &GpuGarbler::concat_saved_dev;
+    clip_hook() = &GpuGarbler::clip_dev;
     Impl& I = *impl_;
     I.enter();
     I.c.hard = hardened ? 1 : 0;
@@ -3463,6 +3511,57 @@ static std::vector<DevBlock> relu_mult_gates(GpuGarbler::Impl& I, const gg::Gadg
     return out;
 }
 
+// Descriptors of one mixed-radix sign gadget (sign_mrs_garble_elem's order) with its slots from slot0: the
+// digit-target label draws, the k key slots, the fan-out rows of table 0. Shared by the ReLU and by a Clip's two
+// signs (which differ in the slot offset and the PRG stream only).
+struct MrsSignDesc {
+    std::vector<gg::Draw> dr;
+    std::vector<gg::Proj> pr;
+    std::vector<int> fan;
+    std::vector<int16_t> flut;
+    gg::MrsSG a{};
+    int sig_slot = 0, end_slot = 0;
+    int64_t entries = 0;
+};
+static MrsSignDesc mrs_sign_desc(const SignMrsPlan& P, int slot0) {
+    MrsSignDesc d;
+    const int k = P.k();
+    d.a.k = k;
+    int slot = slot0, ctr = 0;
+    std::vector<int> dig0(k, 0);
+    for (int i = 0; i + 1 < k; ++i) {
+        dig0[i] = slot;
+        for (int t = 0; t < P.targets(i); ++t) {
+            const int r = P.target_res(i, t);
+            d.a.sub[r][d.a.nsub[r]++] = slot;
+            d.dr.push_back({slot++, P.crt[r], ctr});
+            ctr += prg_blocks(P.crt[r]);
+        }
+    }
+    d.a.key0 = slot;
+    slot += k;
+    d.sig_slot = d.a.key0 + P.ord[k - 1];
+    d.end_slot = slot;
+    int64_t first = 0;
+    for (int i = 0; i + 1 < k; ++i) {
+        const int nt = P.targets(i), r0 = P.ord[i];
+        const int a0 = static_cast<int>(d.flut.size()), a1 = static_cast<int>(d.fan.size());
+        for (int v = 0; v < P.crt[r0]; ++v)
+            for (int t = 0; t < nt; ++t) d.flut.push_back(static_cast<int16_t>(P.digit_fn(i, t, v)));
+        for (int t = 0; t < nt; ++t) d.fan.push_back(P.crt[P.target_res(i, t)]);
+        gg::Proj p{};
+        p.in_kind = gg::S_SLOT; p.in_idx = d.a.key0 + r0; p.pin = P.crt[r0];
+        p.out_slot = dig0[i]; p.pout = P.crt[P.target_res(i, 0)]; p.fn = gg::F_FAN; p.a0 = a0; p.a1 = a1;
+        p.outr_kind = gg::R_BANK; p.table = 0; p.stride = nt; p.off = P.dig_off[i]; p.first = first;
+        p.hsub = tw_sub(kTwSmrs, static_cast<uint32_t>(i));
+        first += P.crt[r0];
+        d.pr.push_back(p);
+    }
+    for (int j = 0; j < k; ++j) d.a.crt[j] = P.crt[j];
+    d.entries = first;
+    return d;
+}
+
 // ReLU with the mixed-radix sign: draw the digit-target labels (sign_mrs_garble_elem order) -> keys ->
 // fan-out projections; residue 0's key slot is the sign label; then the mixed-modulus half gates exactly as
 // in sign_layer's ReLU branch.
@@ -3476,45 +3575,14 @@ void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, 
     const int64_t N = I.cur_N;
     const int k = I.k;
     DASH_CHECK(P.k() == k, "gpu garbler: mixed-radix sign plan mismatch");
-    std::vector<gg::Draw> dr;
-    std::vector<gg::Proj> pr;
-    std::vector<int> fan;
-    std::vector<int16_t> flut;
-    gg::MrsSG a{};
-    a.k = k;
-    int slot = 0, ctr = 0;
-    std::vector<int> dig0(k, 0);
-    for (int i = 0; i + 1 < k; ++i) {
-        dig0[i] = slot;
-        for (int t = 0; t < P.targets(i); ++t) {
-            const int r = P.target_res(i, t);
-            a.sub[r][a.nsub[r]++] = slot;
-            dr.push_back({slot++, P.crt[r], ctr});
-            ctr += prg_blocks(P.crt[r]);
-        }
-    }
-    a.key0 = slot;
-    slot += k;
-    const int sig_slot = a.key0 + P.ord[k - 1];
-    const int sk0 = slot;
-    slot += 2 * k;
-    const int nslots = slot;
-    int64_t first = 0;
-    for (int i = 0; i + 1 < k; ++i) {
-        const int nt = P.targets(i), r0 = P.ord[i];
-        const int a0 = static_cast<int>(flut.size()), a1 = static_cast<int>(fan.size());
-        for (int v = 0; v < P.crt[r0]; ++v)
-            for (int t = 0; t < nt; ++t) flut.push_back(static_cast<int16_t>(P.digit_fn(i, t, v)));
-        for (int t = 0; t < nt; ++t) fan.push_back(P.crt[P.target_res(i, t)]);
-        gg::Proj p{};
-        p.in_kind = gg::S_SLOT; p.in_idx = a.key0 + r0; p.pin = P.crt[r0];
-        p.out_slot = dig0[i]; p.pout = P.crt[P.target_res(i, 0)]; p.fn = gg::F_FAN; p.a0 = a0; p.a1 = a1;
-        p.outr_kind = gg::R_BANK; p.table = 0; p.stride = nt; p.off = P.dig_off[i]; p.first = first;
-        p.hsub = tw_sub(kTwSmrs, static_cast<uint32_t>(i));
-        first += P.crt[r0];
-        pr.push_back(p);
-    }
-    for (int j = 0; j < k; ++j) a.crt[j] = P.crt[j];
+    MrsSignDesc D = mrs_sign_desc(P, 0);
+    const std::vector<gg::Draw>& dr = D.dr;
+    const std::vector<gg::Proj>& pr = D.pr;
+    const std::vector<int>& fan = D.fan;
+    const std::vector<int16_t>& flut = D.flut;
+    const gg::MrsSG& a = D.a;
+    const int sig_slot = D.sig_slot, sk0 = D.end_slot, nslots = D.end_slot + 2 * k;
+    const int64_t first = D.entries;
     DevTable tT, tG, tE;
     tT.alloc(I.device, N, tab.shape[1], tab);
     tG.alloc(I.device, N, mmg.shape[1], mmg);
@@ -3558,6 +3626,174 @@ void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, 
     tT.to_array(tab, I.device);
     tG.to_array(mmg, I.device);
     tE.to_array(mme, I.device);
+    I.cur = std::move(out);
+    set_stale(cur, I.crt, N);
+}
+
+// Clip (garbler.cpp K_CLIP, clip_garble_elem's order): the sign gadget once per bound on the labels shifted by
+// the bound (folded into the device cur in place: x0 + q_lo R, then x0 + q_hi R, then back to x0 + q_lo R, the
+// wire the half gates multiply), PRG streams 1 and 3; u = s_lo + s_hi; the mixed-modulus half gates keyed by u
+// (stream 2) as a ReLU's; the cap rows keyed by s_hi, their base labels drawn on stream 2 after the half gates'
+// draws; out0_j = half gate + c0_j - q_lo R_j. The signs are the exact mixed-radix gadget (pm; tables st[side][0])
+// or the approximate fused one (pa; st[side] = approx, cast2, sign). Scratch slots: the two sign labels, u, the
+// 2k half-gate labels, the k cap labels; the exact sign's own slots come first (both sides side by side), the
+// approximate sign runs in sign_core's scratch and leaves a copy of its label.
+void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
+                          CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,
+                          Array& cap) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("clip");
+    const int64_t N = I.cur_N;
+    const int k = I.k;
+    DASH_CHECK((pm != nullptr) != (pa != nullptr), "gpu garbler: clip needs exactly one sign plan");
+    DASH_CHECK(!pm || pm->k() == k, "gpu garbler: mixed-radix sign plan mismatch");
+    auto fold = [&](i64 q) {  // cur_j += (q mod p_j) R_pj
+        gg::FoldArgs a{};
+        a.N = N;
+        a.group = N;
+        int ncmax = 1;
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            const int32_t cj = static_cast<int32_t>(pmod(q, p));
+            a.j[j] = gg::FoldJob{I.cur[j].as<int16_t>(), gg::dconst(&cj, 1), p, static_cast<int>(gg::chunks_of(nr_comps(p)))};
+            ncmax = std::max(ncmax, a.j[j].nc);
+        }
+        const int blocks = static_cast<int>(std::min<int64_t>((N * ncmax + 255) / 256, 4096));
+        hipLaunchKernelGGL(gg::k_fold, dim3(blocks, k), dim3(256), 0, gg::tl_st, I.c, a);
+    };
+    const gg::In in = labels_in(I.cur, I.crt, N);
+    std::vector<void*> tmp;
+    int sig[2] = {0, 1};
+    int base = 2;  // first slot after the sign stage
+    std::vector<DevBlock> sig_copy[2];
+    if (pa) {
+        // approximate sign: sign_core (out {2}) once per bound; its label comes back as a slot-sized copy
+        Array none;
+        for (int side = 0; side < 2; ++side) {
+            fold(side ? hi - lo : lo);
+            std::vector<int> omods;
+            sig_copy[side] = sign_core(I, layer, side ? 3 : 1, 2, *pa, in, N, *st[side][0], none, *st[side][1],
+                                       *st[side][2], nullptr, nullptr, nullptr, omods);
+            DASH_CHECK(omods.size() == 1 && omods[0] == 2, "gpu garbler: clip sign plan must output one mod-2 label");
+        }
+    } else {
+        base = 2 * mrs_sign_desc(*pm, 0).end_slot;
+    }
+    const int u_slot = base, sk0 = u_slot + 1, cap0 = sk0 + 2 * k, nslots = cap0 + k;
+    gg::Gadget g{};
+    g.layer = layer;
+    g.mask = 0;
+    g.S = I.scratch(static_cast<size_t>(N) * nslots * gg::kW * sizeof(int16_t));
+    g.N = N;
+    g.nslots = nslots;
+    DevTable tT[2], tG, tE, tC;
+    if (pa) {
+        const size_t bytes = static_cast<size_t>(gg::chunks_of(nr_comps(2))) * gg::kCh * N * sizeof(int16_t);
+        for (int side = 0; side < 2; ++side)
+            HIPCHECK(hipMemcpyAsync(gg::slot_base(g, sig[side]), sig_copy[side][0].p, bytes, hipMemcpyDeviceToDevice,
+                                    gg::tl_st));
+    } else {
+        for (int side = 0; side < 2; ++side) {
+            fold(side ? hi - lo : lo);
+            const MrsSignDesc D = mrs_sign_desc(*pm, side * (base / 2));
+            sig[side] = D.sig_slot;
+            tT[side].alloc(I.device, N, st[side][0]->shape[1], *st[side][0]);
+            gg::Tables tb{};
+            tb.t[0] = tT[side].p(); tb.row[0] = tT[side].row;
+            gg::Gadget gs = g;
+            gs.sslot = side ? 3 : 1;
+            gs.PB = I.pbank(2, N);
+            gs.draws = gg::dconst(D.dr.data(), D.dr.size());
+            gs.ndraws = static_cast<int>(D.dr.size());
+            gs.projs = gg::dconst(D.pr.data(), D.pr.size());
+            gs.nprojs = static_cast<int>(D.pr.size());
+            gs.entries = D.entries;
+            gs.nblk = draw_blocks(D.dr);
+            check_desc(gs);
+            hipLaunchKernelGGL(gg::draw_kernel(), dim3(draw_grid(gs)), dim3(gg::kGB), 0, gg::tl_st, I.c, gs);
+            hipLaunchKernelGGL(gg::k_mrs_sign_derive, dim3(blocks_for(N, 256), k), dim3(256), 0, gg::tl_st, I.c, gs, in,
+                               D.a);
+            project(I.c, gs, in, tb, D.pr, ProjFns{&D.flut, &D.fan});
+        }
+    }
+    fold(lo - hi);  // back to x0 + q_lo R: the wire x - q_lo
+    tG.alloc(I.device, N, mmg.shape[1], mmg);
+    tE.alloc(I.device, N, static_cast<int64_t>(k) * 3, mme, true);
+    tC.alloc(I.device, N, static_cast<int64_t>(k) * 2, cap);
+    hipLaunchKernelGGL(gg::k_clip_u, dim3(blocks_for(static_cast<int64_t>(gg::kW / gg::kCh) * N, 256, 4096)), dim3(256), 0,
+                       gg::tl_st, g, sig[0], sig[1], u_slot);
+    gg::Tables tbm{};
+    tbm.t[4] = tG.p(); tbm.row[4] = tG.row;
+    tbm.t[5] = tE.p(); tbm.row[5] = tE.row;
+    g.sslot = 2;
+    std::vector<DevBlock> out = relu_mult_gates(I, g, in, tbm, u_slot, sk0, *prefix);
+    // the cap: base labels c0_j drawn after the 2k half-gate labels, one 2-row projection of s_hi per residue
+    // (table row [k][2], pad slot j of row (TW_CAP, 0))
+    {
+        std::vector<gg::Draw> dc;
+        std::vector<gg::Proj> pc;
+        std::vector<int> fan;
+        std::vector<int16_t> flut;
+        int ctr = 0;
+        for (int j = 0; j < k; ++j) ctr += 2 * prg_blocks(I.crt[j]);
+        int64_t first = 0;
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            dc.push_back({cap0 + j, p, ctr});
+            ctr += prg_blocks(p);
+            const int a0 = static_cast<int>(flut.size()), a1 = static_cast<int>(fan.size());
+            flut.push_back(0);
+            flut.push_back(static_cast<int16_t>(pmod(hi - lo, p)));
+            fan.push_back(p);
+            gg::Proj q{};
+            q.in_kind = gg::S_SLOT; q.in_idx = sig[1]; q.pin = 2;
+            q.out_slot = cap0 + j; q.pout = p; q.fn = gg::F_FAN; q.a0 = a0; q.a1 = a1;
+            q.outr_kind = gg::R_BANK; q.table = 6; q.stride = 1; q.off = 2 * j; q.first = first;
+            q.hsub = tw_sub(kTwCap, 0);
+            q.hslot = j;
+            first += 2;
+            pc.push_back(q);
+        }
+        gg::Tables tbc{};
+        tbc.t[6] = tC.p(); tbc.row[6] = tC.row;
+        gg::Gadget gc = g;
+        gc.sslot = 2;
+        gc.PB = I.pbank(2, N);
+        gc.draws = gg::dconst(dc.data(), dc.size());
+        gc.ndraws = static_cast<int>(dc.size());
+        gc.projs = gg::dconst(pc.data(), pc.size());
+        gc.nprojs = static_cast<int>(pc.size());
+        gc.entries = first;
+        gc.nblk = draw_blocks(dc);
+        check_desc(gc);
+        hipLaunchKernelGGL(gg::draw_kernel(), dim3(draw_grid(gc)), dim3(gg::kGB), 0, gg::tl_st, I.c, gc);
+        project(I.c, gc, in, tbc, pc, ProjFns{&flut, &fan});
+        gg::ClipFin cf{};
+        int ncmax = 1;
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            cf.out[j] = out[j].as<int16_t>();
+            cf.p[j] = p;
+            cf.nc[j] = static_cast<int>(gg::chunks_of(nr_comps(p)));
+            cf.neg[j] = static_cast<int>(pmod(-lo, p));
+            ncmax = std::max(ncmax, cf.nc[j]);
+        }
+        cf.cap0 = cap0;
+        hipLaunchKernelGGL(gg::k_clip_finish, dim3(blocks_for(N * ncmax, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c,
+                           gc, cf);
+    }
+    HIPCHECK(hipGetLastError());
+    gg::end_layer(tmp);
+    tr_.mark("kernels");
+    if (pm) {
+        tT[0].to_array(*st[0][0], I.device);
+        tT[1].to_array(*st[1][0], I.device);
+    }
+    tG.to_array(mmg, I.device);
+    tE.to_array(mme, I.device);
+    tC.to_array(cap, I.device);
     I.cur = std::move(out);
     set_stale(cur, I.crt, N);
 }

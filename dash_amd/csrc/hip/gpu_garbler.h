@@ -44,6 +44,22 @@ class GpuGarbler {
     void relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, Array& tab, const std::vector<int>* relu_crt,
                   const std::vector<i64>* prefix, Array& mmg, Array& mme);
 
+    // Clip (gadgets.h ClipPlan): two signs, exact (pm; tables st[side][0] = mrs) or approximate (pa; st[side] =
+    // approx, cast2, sign), side 0 = lower bound; the half gates keyed by u = s_lo + s_hi and the cap rows keyed by
+    // s_hi; device cur -> next. Registered by the device translation unit like concat_saved, so host-only links
+    // need no definition.
+    using ClipFn = void (*)(GpuGarbler&, uint64_t, const SignMrsPlan*, const SignPlan*, i64, i64, CrtLabels&,
+                            Array* const (*)[3], const std::vector<i64>*, Array&, Array&, Array&);
+    static ClipFn& clip_hook() {
+        static ClipFn f = nullptr;
+        return f;
+    }
+    void clip(uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi, CrtLabels& cur,
+              Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme, Array& cap) {
+        DASH_CHECK(clip_hook() != nullptr, "gpu garbler: clip is not linked in");
+        clip_hook()(*this, layer, pm, pa, lo, hi, cur, st, prefix, mmg, mme, cap);
+    }
+
     // ReLU whose sign labels the preceding rescale_mrs (P.sign_last) left on the device: mixed-modulus half
     // gates only; device cur -> next
     void relu_mult(uint64_t layer, CrtLabels& cur, const std::vector<i64>* prefix, Array& mmg, Array& mme);
@@ -89,6 +105,9 @@ class GpuGarbler {
 
    private:
     static void concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& idx, CrtLabels& cur);
+    static void clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
+                         CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,
+                         Array& cap);
     std::unique_ptr<Impl> impl_;
 };
 

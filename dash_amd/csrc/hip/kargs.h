@@ -128,8 +128,23 @@ struct MrsArgs {
     uint64_t rgate0;  // modes 1, 2: the ReLU mixed-mult gadget's gate base (its y-row / g-row pads)
     int ny;           // y-row pad slots per element (k entries + packed minis)
     u128* ys;         // modes 1, 2: [B][ny][N] the sign label's y-row pads
+    u128* ks;         // mode 1, a Clip's sign: [B][N] the sign label itself (with ny = 0: no y-row pads); else null
     int qpack;        // k_mrs_chain_q: bit 0 four digits per quad reduction (moduli <= 63); >> 1: positions
                       // I < that value take chunk-split keys
+};
+
+// Clip multiply (gadgets.h ClipPlan): the two sign labels, the half gates' tables and the cap rows
+struct ClipArgs {
+    CrtInfo crt;
+    int64_t N;
+    const u128* hx;        // [B][k][N] pads of x_j's garbler half gate row (TW_MMG, j), gate mgate0
+    const uint16_t* colx;  // [B][k][N]
+    const u128* klo;       // [B][N] compressed sign label s_lo = [x >= q_lo]
+    const u128* khi;       // [B][N] compressed sign label s_hi = [x >= q_hi]
+    const u128* gtab;      // [B][N][sum]
+    const u128* etab;      // [B][N][k][3]
+    const u128* cap;       // [B][N][k][2]
+    uint64_t mgate0;       // gate base of the multiply (stream slot 2): rows (TW_MMY, 0) of u, (TW_CAP, 0) of s_hi
 };
 
 struct BEArgs {

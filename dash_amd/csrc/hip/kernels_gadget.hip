@@ -493,6 +493,155 @@ __global__ __launch_bounds__(kRmBS) void k_relu_mult_s(SignArgs a, Act x, Act y,
 }
 
 // ---------------------------------------------------------------------------
+// Clip multiply (gadgets.h ClipPlan): clip_j = E + ypr x_j - G + C, the ReLU multiply keyed by the label of
+// u = s_lo + s_hi plus the cap row C of s_hi, from the two sign labels themselves. Mod-2 labels compress to
+// their bit pack, so the compressed label of u is the XOR of the two sign labels; the lane derives u's
+// y-row pads (TW_MMY, 0: entry slot j, mini lane j % 8 of slot k + j / 8) and the cap pad (TW_CAP, 0: slot j).
+struct ClipLane {
+    u128 G, E, C;
+    uint32_t ypr;
+};
+__device__ __forceinline__ ClipLane clip_lane(const ClipArgs& a, int j, int b, int64_t e, int p, const ModC& m) {
+    const int k = a.crt.k;
+    const int64_t N = a.N;
+    const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
+    const int64_t be = static_cast<int64_t>(b) * N + e;
+    // the gathers go out before the pads are computed
+    const u128 Hx = a.hx[bke];
+    const uint32_t colx = a.colx[bke];
+    const u128 Khi = a.khi[be];
+    const u128 U = a.klo[be] ^ Khi;
+    const uint32_t cU = static_cast<uint32_t>(U) & 1u, cH = static_cast<uint32_t>(Khi) & 1u;
+    const u128* E3 = a.etab + (be * k + j) * 3;
+    const u128 Graw = a.gtab[be * a.crt.sum + a.crt.prefix[j] + colx];
+    const u128 Eraw = E3[cU];
+    const u128 mini = E3[2];
+    const u128 Craw = a.cap[(be * k + j) * 2 + cH];
+    const uint64_t mg = a.mgate0 ^ static_cast<uint64_t>(e);
+    const int sS = j, sM = k + j / 8;  // j is uniform per block: so is the choice of one or two pad blocks
+    u128 pd[4];
+    hard_block(U, mg, tw_sub(kTwMmy, 0), static_cast<uint32_t>(sS) >> 2, pd);
+    const u128 HS = pd[sS & 3];
+    if ((sM >> 2) != (sS >> 2)) hard_block(U, mg, tw_sub(kTwMmy, 0), static_cast<uint32_t>(sM) >> 2, pd);
+    const u128 HM = pd[sM & 3] >> (16 * (j % 8));
+    const u128 HC = hard_pad(Khi, mg, tw_sub(kTwCap, 0), j);
+    ClipLane r;
+    r.G = Graw - Hx;
+    r.E = Eraw - HS;
+    r.C = Craw - HC;
+    const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cU)));
+    const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
+    r.ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);  // p*2^15 > |ypr16|
+    return r;
+}
+
+// grid (ceil(N/256), k, B)
+__global__ __launch_bounds__(256) void k_clip_mult(ClipArgs a, Act x, Act y, const ModC* mc) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const ClipLane c = clip_lane(a, j, b, e, p, m);
+    const uint32_t ypr = c.ypr;
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    DigitStream sg, se, sc;
+    sg.init(c.G);
+    se.init(c.E);
+    sc.init(c.C);
+    const int n = static_cast<int>(m.n);
+    // the next chunk's loads go out before this chunk's stores (as k_relu_mult)
+    uint16_t cur[kChunk], nxt[kChunk];
+#pragma unroll
+    for (int u = 0; u < kChunk; ++u)
+        if (u < n) cur[u] = X[static_cast<int64_t>(u) * N];
+    for (int i0 = 0; i0 < n; i0 += kChunk) {
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u)
+            if (i0 + kChunk + u < n) nxt[u] = X[static_cast<int64_t>(i0 + kChunk + u) * N];
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u)
+            if (i0 + u < n) {
+                const uint32_t g = sg.next(m);
+                const uint32_t ev = se.next(m);
+                const uint32_t cv = sc.next(m);
+                // all terms in [0, p): ev + ypr * x + (p - g) + cv < p^2 + 3p
+                Y[static_cast<int64_t>(i0 + u) * N] = static_cast<act_t>(
+                    modq(ev + ypr * static_cast<uint32_t>(cur[u]) + static_cast<uint32_t>(p) - g + cv, m));
+            }
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
+    }
+}
+
+// k_clip_mult with the label staged in LDS (stage_ok; as k_relu_mult_s): a block = (256-element tile, residue
+// j, GC b); the per-element gathers go out first, the block's x_j rows come in as 16-byte loads, each lane
+// rewrites its column in place and the block stores the y_j rows back as 16-byte stores.
+__global__ __launch_bounds__(kRmBS) void k_clip_mult_s(ClipArgs a, Act x, Act y, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[128 * kRmBS];
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int n = static_cast<int>(m.n);
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * n * N;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N;
+    for (int64_t e0 = static_cast<int64_t>(blockIdx.x) * kRmBS; e0 < N; e0 += static_cast<int64_t>(gridDim.x) * kRmBS) {
+        const int64_t e = min(e0 + tid, N - 1);  // lanes past the end redo the last element (their column is not stored)
+        const ClipLane c = clip_lane(a, j, b, e, p, m);
+        const uint32_t ypr = c.ypr;
+        __syncthreads();  // the previous tile's stores have read the image
+        lds_stage_rows<kRmBS, 4>(stg, X, N, e0, 0, n);
+        __syncthreads();
+        if (m.bits == 1) {
+            // p = 2: digits are bits, (e + ypr x + 2 - g + c) mod 2 = e ^ g ^ c ^ (ypr & x)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t gec = static_cast<uint32_t>(c.G >> (32 * w)) ^ static_cast<uint32_t>(c.E >> (32 * w)) ^
+                                     static_cast<uint32_t>(c.C >> (32 * w));
+#pragma unroll 8
+                for (int u = 0; u < 32; ++u) {
+                    const int cc = 32 * w + u;
+                    if (cc >= n) break;
+                    uint8_t& v = stg[cc * kRmBS + tid];
+                    v = static_cast<uint8_t>(((gec >> u) & 1u) ^ (static_cast<uint32_t>(v) & ypr));
+                }
+            }
+        } else if (m.bits) {
+            DigitStream sg, se, sc;
+            sg.init(c.G);
+            se.init(c.E);
+            sc.init(c.C);
+            for (int cc = 0; cc < n; ++cc) {
+                const uint32_t g = sg.next(m);
+                const uint32_t ev = se.next(m);
+                const uint32_t cv = sc.next(m);
+                uint8_t& v = stg[cc * kRmBS + tid];
+                v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g + cv, m));
+            }
+        } else {  // chunk-major (chunk_digit): one divmod per stream per chunk, uniform digit loops
+            u128 QG = c.G, QE = c.E, QC = c.C;
+            for (int c0 = 0; c0 < n; c0 += static_cast<int>(m.c)) {
+                uint32_t rg = divmod128(QG, m), re = divmod128(QE, m), rc = divmod128(QC, m);
+                const int cnt = min(static_cast<int>(m.c), n - c0);
+                for (int t = 0; t < cnt; ++t) {
+                    const uint32_t g = chunk_digit(rg, m);
+                    const uint32_t ev = chunk_digit(re, m);
+                    const uint32_t cv = chunk_digit(rc, m);
+                    uint8_t& v = stg[(c0 + t) * kRmBS + tid];
+                    v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g + cv, m));
+                }
+            }
+        }
+        __syncthreads();
+        lds_store_rows<kRmBS>(Y, stg, N, e0, 0, n);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Rescale step 1+2 for one factor: hash the factor residue (optionally after
 // the upshift). grid (ceil(N/256), 1, B)
 __global__ __launch_bounds__(kAesBlock, kAesMinBlocks) void k_rescale_hash(Act x, int fi, int s, const int16_t* up, int up_stride,
@@ -1718,6 +1867,26 @@ void launch_relu_mult(const SignArgs& a, const Act& x, const Act& y, const u128*
     }
     if (launch_log_on()) launch_log_add("relu_mult.lane", grid_for(a.N, 256, a.crt.k, a.B), dim3(256));
     hipLaunchKernelGGL(k_relu_mult, grid_for(a.N, 256, a.crt.k, a.B), dim3(256), 0, st, a, x, y, gtab, etab, mc);
+}
+// Clip: the half gates' keys of x (as launch_relu_mrs), then one sign per bound into its own scratch, then the
+// multiply. The multiply's picker is launch_relu_mult's.
+void launch_clip_hash(const ClipArgs& a, u128* hx, uint16_t* colx, const Act& x, int B, const ModC* mc,
+                      const AesGlobals& g, hipStream_t st) {
+    AES_LAUNCH_GGL(k_label_hash, a.N, a.crt.k, B, kAesLds, st, x, a.crt, a.N, hx, colx, mc, g.te0, g.rk, 1, a.mgate0);
+}
+void launch_clip_sign_mrs(const MrsArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g, hipStream_t st) {
+    dispatch_mrs_chain(a, x, B, mc, g, st);
+}
+void launch_clip_mult(const ClipArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st) {
+    if (stage_ok(a.N, kRmBS) && x.p[0] != y.p[0]) {
+        const unsigned nx = static_cast<unsigned>(std::min<int64_t>((a.N + kRmBS - 1) / kRmBS,
+                                                                   std::max(1, 16 * num_cus() / (a.crt.k * B))));
+        if (launch_log_on()) launch_log_add("clip_mult.staged", dim3(nx, a.crt.k, B), dim3(kRmBS));
+        hipLaunchKernelGGL(k_clip_mult_s, dim3(nx, a.crt.k, B), dim3(kRmBS), 0, st, a, x, y, mc);
+        return;
+    }
+    if (launch_log_on()) launch_log_add("clip_mult.lane", grid_for(a.N, 256, a.crt.k, B), dim3(256));
+    hipLaunchKernelGGL(k_clip_mult, grid_for(a.N, 256, a.crt.k, B), dim3(256), 0, st, a, x, y, mc);
 }
 void launch_rescale_hash(const Act& x, int fi, int s, const int16_t* up, int up_stride, int add_up, int64_t N, int B,
                          u128* h0, uint16_t* col0, const ModC* mc, const AesGlobals& g, hipStream_t st, int hard) {

@@ -36,6 +36,10 @@ void launch_sign_approx(const SignArgs& a, const Act& x, const ModC* mc, const A
 void launch_sign_chain(const SignArgs& a, int maxn, const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_unpack(const u128* P, int nres, const Act& out, const CrtInfo& mods, const ModC* mc, int64_t N, int B,
                    hipStream_t st);
+void launch_clip_hash(const ClipArgs& a, u128* hx, uint16_t* colx, const Act& x, int B, const ModC* mc,
+                      const AesGlobals& g, hipStream_t st);
+void launch_clip_sign_mrs(const MrsArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g, hipStream_t st);
+void launch_clip_mult(const ClipArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st);
 void launch_relu_mult(const SignArgs& a, const Act& x, const Act& y, const u128* gtab, const u128* etab,
                       const ModC* mc, hipStream_t st);
 void launch_rescale_hash(const Act& x, int fi, int s, const int16_t* up, int up_stride, int add_up, int64_t N, int B,

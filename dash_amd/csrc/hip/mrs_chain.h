@@ -58,6 +58,13 @@ __device__ __forceinline__ void store_ypads(const MrsArgs& a, u128 key, int b, i
     }
 }
 
+// A Clip's two sign chains (MODE 1 with a.ks set, a.ny = 0) keep the sign label itself: the clip multiply keys
+// its rows with the sum of the two labels (gadgets.h ClipPlan), whose pads only it can form
+template <int MODE>
+__device__ __forceinline__ void store_sign_key(const MrsArgs& a, u128 key, int b, int64_t N, int64_t e) {
+    if (MODE == 1 && a.ks) a.ks[static_cast<int64_t>(b) * N + e] = key;
+}
+
 // MODE 1 (exact sign, gadgets.h SignMrsPlan): positions convert residues
 // 1..K-1, the last position is residue 0 (mod 2): its key is the bit pack of
 // L_0 XOR the K-1 payloads aimed at it (mod-2 subtraction), i.e. the sign
@@ -139,6 +146,7 @@ __global__ __launch_bounds__(kAesBlock, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_
             if (MODE == 2)  // the sign digit's T payload row (one entry)
                 E = row0[a.dig_off[K - 1] + c] - hard_pad(key, a.gate0 ^ static_cast<uint64_t>(e), mrs_row_sub<MODE>(K - 1), 0);
             store_ypads(a, key, b, N, e);
+            store_sign_key<MODE>(a, key, b, N, e);
             a.cs[static_cast<int64_t>(b) * N + e] = static_cast<uint8_t>(c);
             if (MODE == 2) acc = add_packed(acc, E, a.hmask);
         }
@@ -338,6 +346,7 @@ __global__ __launch_bounds__(kMrsBS, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_MIN
             if (MODE == 2) E = row0[a.dig_off[K - 1] + c] - hard_pad(key, gate, mrs_row_sub<MODE>(K - 1), 0);
             if (valid) {
                 store_ypads(a, key, b, N, e);
+                store_sign_key<MODE>(a, key, b, N, e);
                 a.cs[static_cast<int64_t>(b) * N + e] = static_cast<uint8_t>(c);
             }
             if (MODE == 2) acc = add_packed(acc, E, a.hmask);
@@ -546,6 +555,7 @@ __global__ __launch_bounds__(kMrsWBS, 1) void k_mrs_chain_w(MrsArgs a, Act x, co
             if (MODE == 2) E = row0[a.dig_off[K - 1] + cb] - hard_pad(key, gate, mrs_row_sub<MODE>(K - 1), 0);
             if (valid) {
                 store_ypads(a, key, b, N, e);
+                store_sign_key<MODE>(a, key, b, N, e);
                 a.cs[static_cast<int64_t>(b) * N + e] = static_cast<uint8_t>(cb);
             }
             if (MODE == 2) acc = add_packed(acc, E, a.hmask);
@@ -962,6 +972,7 @@ __global__ __launch_bounds__(kMrsQBS, 2) void k_mrs_chain_q(MrsArgs a, Act x, co
                 }
                 if (g == 0) a.cs[static_cast<int64_t>(b) * N + e] = static_cast<uint8_t>(cb);
             }
+            if (valid && g == 0) store_sign_key<MODE>(a, key, b, N, e);
             if (MODE == 2) acc = add_packed(acc, E, a.hmask);
         }
         if (MODE == 1) continue;

@@ -697,6 +697,7 @@ class HipEvaluator {
     const int16_t* zero_rows_ = nullptr;
     const int16_t* up_rows_ = nullptr;
     u128* mrs_ps_ = nullptr;  // mixed-radix rescale chain scratch (allocated by the first such layer)
+    u128* ks_[2] = {nullptr, nullptr};  // [B][maxSignN] a Clip's two sign labels (allocated by the first Clip)
     i64 maxSignN_ = 0;
     // planner: a sign-producing rescale whose outputs the next (joint) ReLU's op writes
     bool joint_pending_ = false;
@@ -788,7 +789,7 @@ void HipEvaluator::build() {
             switch (l.kind) {
                 case K_DENSE: N = l.param("out"); break;
                 case K_CONV: N = ConvGeom(l).out_size(); break;
-                case K_RELU: case K_SIGN: case K_RESCALE: maxSignN = std::max(maxSignN, N); break;
+                case K_RELU: case K_SIGN: case K_RESCALE: case K_CLIP: maxSignN = std::max(maxSignN, N); break;
                 case K_MAXPOOL: {
                     PoolGeom G(l.p);
                     maxPoolSlots = std::max(maxPoolSlots, G.out_size() * G.kh * G.kw);
@@ -1124,6 +1125,78 @@ void HipEvaluator::build() {
                 add_op(lname + ".A", [a, x, mc, ag](hipStream_t st) { launch_sign_approx(a, x, mc, ag, st); });
                 add_op(lname + ".B", [a, maxn, mc, ag](hipStream_t st) { launch_sign_chain(a, maxn, mc, ag, st); });
                 add_op(lname + ".C", [a, x, y, gt, et, mc](hipStream_t st) { launch_relu_mult(a, x, y, gt, et, mc, st); });
+                cur = nxt;
+                break;
+            }
+            case K_CLIP: {
+                // gadgets.h ClipPlan: the half gates' keys of x, the sign evaluation once per bound on the same
+                // labels (each into its own scratch), then the multiply + cap
+                DASH_CHECK(hard_, "the Clip layer exists in the hardened encoding only");
+                for (int side = 0; side < 2; ++side)
+                    if (!ks_[side]) ks_[side] = dalloc<u128>(static_cast<size_t>(B_) * maxSignN_);
+                ClipArgs ca{};
+                ca.crt = crt;
+                ca.N = N;
+                ca.hx = hx_;
+                ca.colx = colx_;
+                ca.klo = ks_[0];
+                ca.khi = ks_[1];
+                ca.gtab = upload_tables(li, "mm.g");
+                ca.etab = upload_tables(li, "mm.e");
+                ca.cap = upload_tables(li, "cap");
+                ca.mgate0 = gate_base(li + 1, 2);
+                Act x = act_of(cur), y = act_of(nxt);
+                const ModC* mc = mc_;
+                const AesGlobals ag = aes_;
+                const int B = B_;
+                u128* hx = hx_;
+                uint16_t* colx = colx_;
+                const bool exact = g.param("smode", 0) == 1;
+                // the half gates' keys of x: the approximate sign's first phase compresses x anyway and writes them
+                // (lower bound's run, below); the mixed-radix chain does not, so they get a pass of their own
+                if (exact)
+                    add_op(lname + ".H", [ca, hx, colx, x, B, mc, ag](hipStream_t st) {
+                        launch_clip_hash(ca, hx, colx, x, B, mc, ag, st);
+                    });
+                for (int side = 0; side < 2; ++side) {
+                    const std::string pre = side ? "hi." : "lo.";
+                    const uint64_t sgate = gate_base(li + 1, side ? 3 : 1);
+                    if (exact) {  // exact mixed-radix sign (chain mode 1, label kept in ks)
+                        const SignMrsPlan P(crt_);
+                        MrsArgs a{};
+                        a.crt = crt;
+                        a.N = N;
+                        a.n_tab = g.arr(pre + "mrs").shape[1];
+                        a.tab = upload_tables(li, pre + "mrs");
+                        for (int i = 0; i + 1 < k_; ++i) a.dig_off[i] = P.dig_off[i];
+                        if (!mrs_ps_) mrs_ps_ = dalloc<u128>(static_cast<size_t>(B_) * std::max(1, k_ * (k_ - 1) / 2) * maxSignN_);
+                        a.ps = mrs_ps_;
+                        a.mode = 1;
+                        a.hs = hs_;
+                        a.cs = cs_;
+                        a.gate0 = sgate;
+                        a.rgate0 = ca.mgate0;
+                        a.ny = 0;  // no y-row pads: the multiply forms the pads of u = s_lo + s_hi itself
+                        a.ys = ys_;
+                        a.ks = ks_[side];
+                        add_op(lname + "." + pre + "mrs", [a, x, B, mc, ag](hipStream_t st) {
+                            launch_clip_sign_mrs(a, x, B, mc, ag, st);
+                        });
+                    } else {
+                        SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
+                        SignArgs a = make_sign(li, pre, sp, N, 0, sgate, 0);
+                        a.outP = ks_[side];  // nout = 1: [B][N]
+                        if (side == 0) {  // (TW_MMG, j) pads of x_j under the multiply's gate, as a ReLU's phase A
+                            a.hx = hx_;
+                            a.colx = colx_;
+                            a.mgate0 = ca.mgate0;
+                        }
+                        const int maxn = sign_maxn_;
+                        add_op(lname + "." + pre + "A", [a, x, mc, ag](hipStream_t st) { launch_sign_approx(a, x, mc, ag, st); });
+                        add_op(lname + "." + pre + "B", [a, maxn, mc, ag](hipStream_t st) { launch_sign_chain(a, maxn, mc, ag, st); });
+                    }
+                }
+                add_op(lname + ".C", [ca, x, y, B, mc](hipStream_t st) { launch_clip_mult(ca, x, y, B, mc, st); });
                 cur = nxt;
                 break;
             }

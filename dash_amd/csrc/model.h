@@ -33,6 +33,7 @@ enum Kind : int {
     K_ADD = 12,
     K_SUMPOOL = 13,
     K_CONCAT = 14,
+    K_CLIP = 15,
 };
 const char* kind_name(int kind);
 

@@ -22,7 +22,10 @@ import numpy as np
 from ..ir.bases import crt_modulus as _crt_mod
 from ..ir.bases import first_primes, get_mrs_base
 from ..ir.circuit import Circuit
+from ..ir.layers import Kind as _Kind
 from ..native import native
+
+_CLIP = _Kind.CLIP
 
 Labels = list  # list[(modulus, np.ndarray int16 [N, n_p])]
 
@@ -121,6 +124,7 @@ class GarbledCircuit:
 
         range_guard: the garbler's exact per-input range check (garbling/guard.py): "auto" (default) = on when
         the GC has the mixed-radix rescale (an input in its wrap band would decode to a valid but wrong label),
+        or a Clip layer (an input outside [-M/2 + q_hi, M/2 + q_lo) would likewise decode to a wrong value),
         "on" = always (also catches CRT overflow of the reference constructions), "off". A refused input raises
         RangeGuardError before it is encoded (host paths) or before its result is released (batched paths:
         ``guard.submit`` / ``raise_if_bad``)."""
@@ -141,6 +145,13 @@ class GarbledCircuit:
         self.rescale, self.relu = resolve_constructions(circuit, self.crt_base, rescale, relu, self.fused_sign,
                                                         hardened)
         supported = hardened_supported(circuit, self.fused_sign, self.rescale)
+        # a Clip folds its public bounds into base labels and keys several rows with one label (gadgets.h
+        # ClipPlan): it exists in the hardened encoding only
+        clips = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _CLIP]
+        if clips and not (supported if hardened is None else hardened):
+            raise ValueError("layer %d (clip): the Clip layer exists in the hardened encoding only (%s)" % (
+                clips[0], "hardened=False was asked for" if supported else
+                "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
         # the mixed-radix constructions are this framework's own (not wire-compatible with anything): they only
         # exist in the hardened encoding, whose kernels they use
         needs = self.rescale == "mrs" or self.relu in ("mrs", "joint")
@@ -165,8 +176,9 @@ class GarbledCircuit:
             range_guard = os.environ["DASH_RANGE_GUARD"]  # A/B knob (bench records say which was used)
         if range_guard not in ("auto", "on", "off"):
             raise ValueError("range_guard must be 'auto', 'on' or 'off'")
-        self.guard_enabled = range_guard == "on" or (range_guard == "auto" and self.rescale == "mrs"
-                                                      and bool(circuit._dash_rescales()))
+        # a Clip narrows the domain too: x - q_lo and x - q_hi must both be signed CRT values (docs/CLIP.md)
+        self.guard_enabled = range_guard == "on" or (range_guard == "auto" and (
+            (self.rescale == "mrs" and bool(circuit._dash_rescales())) or bool(clips)))
         self.sink = sink
         self._n = native()
         self.garbler = self._n.Garbler(self.crt_base, self.mrs_base, self.seed, int(max_modulus))

@@ -24,7 +24,8 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
 * on a GPU, ``DevRangeGuard`` (csrc/hip/guard.hip): one HIP launch per layer over chunks of the batch,
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
   evaluation; inputs whose activations exceed the int32 operand range are re-decided by the numpy model. It
-  has no Concat and no padded / ceil-mode pooling: circuits with either take the torch path on the GPU;
+  has no Concat, no Clip and no padded / ceil-mode pooling: circuits with any of them take the torch path on
+  the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
 * the per-input numpy model (``violations_np``), the exact reference of both and the path of layers without a
@@ -57,11 +58,11 @@ class RangeGuard:
         self.circuit, self.M, self.mrs = circuit, int(crt_modulus), bool(mrs)
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
-                                          L.SumPool2d, L.Add, L.Concat, L.Projection, L.BaseExtension))
+                                          L.SumPool2d, L.Add, L.Concat, L.Clip, L.Projection, L.BaseExtension))
                            for l in circuit.layers)
-        # DevRangeGuard (guard.hip) has no Concat and no padded / ceil-mode pooling: such circuits take the
-        # batched torch path
-        self.native_forms = not any(isinstance(l, L.Concat) or
+        # DevRangeGuard (guard.hip) has no Concat, no Clip and no padded / ceil-mode pooling: such circuits take
+        # the batched torch path
+        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
         self._stream = None
@@ -78,6 +79,8 @@ class RangeGuard:
             return lo, hi
         if isinstance(layer, (L.Relu, L.Sign, L.MaxPool2d, L.Max)):
             return lo, hi
+        if isinstance(layer, L.Clip):  # both sign inputs x - q_lo and x - q_hi are signed CRT values
+            return lo + layer.q_hi, hi + layer.q_lo
         return None
 
     def span_max(self) -> int:
@@ -185,6 +188,8 @@ class RangeGuard:
                 out = torch.clamp_min(inp, 0)
             elif isinstance(l, L.Sign):
                 out = torch.where(inp >= 0, 1, -1).to(torch.int64)
+            elif isinstance(l, L.Clip):
+                out = torch.clamp(inp, l.q_lo, l.q_hi)
             elif isinstance(l, L.MaxPool2d):
                 v = inp.view(B, l.C, l.H, l.W)
                 out = mn = None

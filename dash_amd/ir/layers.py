@@ -13,7 +13,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from .quant import QuantizationMethod, ceil_div, quantize_params
+from .quant import QuantizationMethod, ceil_div, quantize_params, quantize_scale
 
 Q_MAX = np.iinfo(np.int64).max
 Q_MIN = np.iinfo(np.int64).min
@@ -35,6 +35,7 @@ class Kind:
     ADD = 12
     SUMPOOL = 13
     CONCAT = 14
+    CLIP = 15
 
 
 def _size(d: Sequence[int]) -> int:
@@ -329,6 +330,68 @@ class Relu(Layer):
 
     def quantize(self, q_const):
         self.reset_ranges()
+
+
+class Clip(Layer):
+    """Clamp to [lo, hi] (ONNX Clip; PyTorch ReLU6, Hardtanh, clamp). The quantized
+    bounds are q_b = llround(b * act_scale) with the scheme's activation scale
+    (ScaleQuant: 2^l, ScaleQuantPlus: s). SimpleQuant scales biases and products
+    differently, so it has no activation scale and a Clip is refused under it.
+    Garbled as two signs of the same input, one set of mixed-modulus half gates
+    and a 2-row projection per residue (csrc/gadgets.h ClipPlan)."""
+
+    kind = Kind.CLIP
+    name = "clip"
+
+    def __init__(self, dims, lo: float, hi: float, q_parameter: int = 0,
+                 q_method: QuantizationMethod = QuantizationMethod.ScaleQuant):
+        super().__init__(dims, dims)
+        self.lo, self.hi = float(lo), float(hi)
+        if not (np.isfinite(self.lo) and np.isfinite(self.hi) and self.lo < self.hi):
+            raise ValueError(f"clip: bounds must be finite with lo < hi, got ({lo}, {hi})")
+        self.q_method, self.q_parameter = QuantizationMethod(q_method), int(q_parameter)
+        if self.q_method == QuantizationMethod.SimpleQuant:
+            raise ValueError("clip: SimpleQuant has no single activation scale to quantize the bounds with; "
+                             "use ScaleQuant or ScaleQuantPlus")
+        scale = (1 << self.q_parameter) if self.q_method == QuantizationMethod.ScaleQuant else self.q_parameter
+        q = quantize_scale(np.asarray([self.lo, self.hi]), scale)
+        self._set_q(int(q[0]), int(q[1]))
+
+    def _set_q(self, q_lo: int, q_hi: int):
+        if not int(q_lo) < int(q_hi):
+            raise ValueError(f"clip: quantized bounds must satisfy q_lo < q_hi, got ({q_lo}, {q_hi})")
+        self.q_lo, self.q_hi = int(q_lo), int(q_hi)
+
+    @classmethod
+    def from_quantized(cls, dims, q_lo: int, q_hi: int) -> "Clip":
+        if not int(q_lo) < int(q_hi):
+            raise ValueError(f"clip: quantized bounds must satisfy q_lo < q_hi, got ({q_lo}, {q_hi})")
+        c = cls(dims, float(q_lo), float(q_hi))
+        c._set_q(q_lo, q_hi)
+        return c
+
+    def plain_eval(self, x, track=True, ctx=None):
+        y = np.clip(np.asarray(x), np.float32(self.lo), np.float32(self.hi))
+        if track:
+            self._track_f(y)
+        return y
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        x = np.asarray(x, dtype=np.int64)
+        y = np.clip(x, self.q_lo, self.q_hi)
+        if track:
+            # both sign inputs must lie in [-M/2, M/2)
+            self._track_q(x, y, x - self.q_lo, x - self.q_hi)
+        return y
+
+    def quantize(self, q_const):
+        self.reset_ranges()
+
+    def garble_spec(self):
+        return self.kind, {"lo": self.q_lo, "hi": self.q_hi}
+
+    def __repr__(self) -> str:
+        return f"Clip(dims={self.in_dims}, q_lo={self.q_lo}, q_hi={self.q_hi})"
 
 
 class Sign(Layer):

@@ -20,6 +20,15 @@ factor), q_const = 0.02 for SimpleQuant. Differences (deliberate):
   branches of a fire / inception module). `Concat` along the channel axis
   becomes a `Concat` layer; `MaxPool` takes symmetric `pads` and `ceil_mode`.
 
+`Clip` (PyTorch ReLU6 / Hardtanh / clamp) becomes a `Clip` layer: at opset >= 11
+its `min` / `max` are inputs 1 and 2, given as initializers or as scalar
+`Constant` nodes that feed only Clips; at opset 6 they are attributes. `min = 0`
+without a `max` is a `Relu`; any other Clip with a missing or infinite bound is
+refused with the node's name, and so is a Clip under SimpleQuant (the bounds
+are quantized with the activation scale, which SimpleQuant does not have). A
+pending average factor f passes through with the bounds divided by f:
+clip(f x, lo, hi) = f clip(x, lo / f, hi / f).
+
 `ReduceSum` over (2, 3) is the plane `SumPool2d` itself (the exporter writes a
 global sum pool that no linear layer follows this way).
 
@@ -48,7 +57,7 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import Add, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
+from .layers import Add, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -129,6 +138,17 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
     last_conv_filters = 0
     nodes = model["nodes"]
     skip = set()
+
+    # scalar Constant nodes that feed only the min / max inputs of Clip nodes
+    clip_consts: dict[str, float] = {}
+    for node in nodes:
+        if node["op_type"] != "Constant" or "value" not in node["attrs"]:
+            continue
+        out, t = node["outputs"][0], node["attrs"]["value"]
+        uses = [(n["op_type"], pos) for n in nodes for pos, x in enumerate(n["inputs"]) if x == out]
+        vals = np.asarray(t["values"], dtype=np.float64).reshape(-1) if isinstance(t, dict) else np.zeros(0)
+        if uses and all(o == "Clip" and pos in (1, 2) for o, pos in uses) and vals.size == 1:
+            clip_consts[out] = float(vals[0])
 
     def res(name: str) -> str:
         return alias.get(name, name)
@@ -276,6 +296,44 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         elif op == "Relu":
             j, dims, fac = data_in(node, ins[0])
             emit(_Spec("relu", dims=dims), outs[0], j, dims, fac)
+        elif op == "Constant" and outs[0] in clip_consts:
+            continue
+        elif op == "Clip":
+            j, dims, fac = data_in(node, ins[0])
+            name = node.get("name") or op
+
+            def bound(pos: int, attr: str) -> Optional[float]:
+                if attr in a:  # opset 6: attributes
+                    return float(a[attr])
+                if len(ins) <= pos or not ins[pos]:
+                    return None
+                if ins[pos] in inits:
+                    v = arr(ins[pos]).reshape(-1)
+                    if v.size != 1:
+                        raise NotImplementedError(f"onnx: {name}: Clip bound {ins[pos]!r} is not a scalar")
+                    return float(v[0])
+                if ins[pos] in clip_consts:
+                    return clip_consts[ins[pos]]
+                raise NotImplementedError(f"onnx: {name}: Clip bound {ins[pos]!r} is neither an initializer nor a "
+                                          "scalar Constant")
+
+            lo, hi = bound(1, "min"), bound(2, "max")
+            # the opset-6 attribute defaults are the float limits: as good as absent
+            lo = None if lo is None or not np.isfinite(lo) or lo <= -3.4e38 else lo
+            hi = None if hi is None or not np.isfinite(hi) or hi >= 3.4e38 else hi
+            if lo == 0.0 and hi is None:
+                emit(_Spec("relu", dims=dims), outs[0], j, dims, fac)
+            elif lo is None or hi is None:
+                raise NotImplementedError(f"onnx: {name}: a Clip needs finite min and max (only min=0 without max "
+                                          "is accepted, as a Relu)")
+            else:
+                if q_method == QuantizationMethod.SimpleQuant:
+                    raise ValueError(f"onnx: {name}: a Clip layer cannot be quantized under SimpleQuant (no single "
+                                     "activation scale for its bounds); use ScaleQuant or ScaleQuantPlus")
+                if not lo < hi:
+                    raise ValueError(f"onnx: {name}: Clip needs min < max, got ({lo}, {hi})")
+                # clip(f x, lo, hi) = f clip(x, lo / f, hi / f): the pending factor passes through
+                emit(_Spec("clip", dims=dims, lo=lo / fac, hi=hi / fac), outs[0], j, dims, fac)
         elif op in ("Tanh", "SignTanh", "Sign"):
             j, dims, fac = data_in(node, ins[0])
             emit(_Spec("sign", dims=dims), outs[0], j, dims)  # the sign drops a positive factor
@@ -337,6 +395,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             layers.append(Relu(kw["dims"]))
         elif s.kind == "sign":
             layers.append(Sign(kw["dims"]))
+        elif s.kind == "clip":
+            layers.append(Clip(kw["dims"], kw["lo"], kw["hi"], q_parameter, q_method))
         elif s.kind == "add":
             layers.append(Add(kw["dims"], spec_to_layer[kw["src"]]))
         elif s.kind == "concat":
@@ -495,6 +555,11 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             scale[out] = K * l.kh * l.kw
         elif isinstance(l, Relu):
             nodes.append(_node("Relu", [cur], [out], name))
+            scale[out] = K
+        elif isinstance(l, Clip):
+            # opset-11 form: min / max are scalar inputs; on an average the bounds of the sum shrink by K
+            inits += [_tensor(f"{name}.min", np.float32(l.lo / K)), _tensor(f"{name}.max", np.float32(l.hi / K))]
+            nodes.append(_node("Clip", [cur, f"{name}.min", f"{name}.max"], [out], name))
             scale[out] = K
         elif isinstance(l, Sign):
             nodes.append(_node("Sign", [cur], [out], name))

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
+from ..ir.layers import Clip, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
 from ..ir.quant import QuantizationMethod
 from .zoo import ARCHS, canonical
 
@@ -78,6 +78,10 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             dims = [dims[0], (dims[1] + 2 * p - ks) // s + 1, (dims[2] + 2 * p - ks) // s + 1]
         elif k == "relu":
             mods.append(nn.ReLU())
+        elif k == "relu6":
+            mods.append(nn.ReLU6())
+        elif k == "clip":
+            mods.append(nn.Hardtanh(float(op[1]), float(op[2])))
         elif k == "sign":
             mods.append(nn.Tanh())  # trained as tanh, garbled as sign (onnx_modelloader.h Tanh -> Sign)
         elif k == "maxpool":
@@ -131,6 +135,8 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
             rescale(dims)
         elif isinstance(m, nn.ReLU):
             layers.append(Relu(dims))
+        elif isinstance(m, nn.Hardtanh):  # nn.ReLU6 is a Hardtanh(0, 6)
+            layers.append(Clip(dims, float(m.min_val), float(m.max_val), q_parameter, qm))
         elif isinstance(m, nn.Tanh):
             layers.append(Sign(dims))
         elif isinstance(m, nn.MaxPool2d):

@@ -12,7 +12,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import Add, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
+from ..ir.layers import Add, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
 from ..ir.quant import QuantizationMethod, quantize_input
 
 # architecture ops: ("conv", out_ch, k, stride, pad) | ("relu",) | ("sign",) | ("flatten",) | ("fc", out)
@@ -21,6 +21,8 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   | ("maxpool", k, s, pad, ceil_mode) | ("gap",) global sum pool (the average's 1/K is left to
 #                   the next linear layer) | ("fire", squeeze, e1, e3) SqueezeNet fire module: 1x1 squeeze + ReLU,
 #                   then a 1x1 and a padded 3x3 expand (each + ReLU) that both read the squeeze output, then Concat
+#                   | ("relu6",) = Clip(0, 6) | ("clip", lo, hi) clamp with float bounds (quantized with the
+#                   scheme's activation scale; refused under SimpleQuant)
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     "MODEL_B_POOL_REPL": {"input": (1, 28, 28), "ops": [
@@ -67,6 +69,13 @@ ARCHS: dict[str, dict] = {
         ("dwconv", 3, 2, 1), ("relu",), ("conv", 64, 1, 1, 0), ("relu",),
         ("dwconv", 3, 1, 1), ("relu",), ("conv", 64, 1, 1, 0), ("relu",),
         ("sumpool", 4), ("flatten",), ("fc", 10)]},
+    # MODEL_DWSEP_CIFAR's topology with the MobileNet family's ReLU6 activations and a global-average head
+    "MOBILENET_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 1, 1), ("relu6",),
+        ("dwconv", 3, 2, 1), ("relu6",), ("conv", 32, 1, 1, 0), ("relu6",),
+        ("dwconv", 3, 2, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("relu6",),
+        ("dwconv", 3, 1, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("relu6",),
+        ("gap",), ("flatten",), ("fc", 10)]},
     # SqueezeNet-style CIFAR net: a stride-2 stem (32 -> 16), ceil-mode 3x3/2 max pools whose last window is cut at
     # the edge (16 -> 8 -> 4), two fire modules, a 1x1 classifier conv and a global average over the 4x4 plane
     "SQUEEZENET_CIFAR": {"input": (3, 32, 32), "ops": [
@@ -148,6 +157,12 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             layers.append(Relu(dims))
         elif kind == "sign":
             layers.append(Sign(dims))
+        elif kind in ("relu6", "clip"):
+            lo, hi = (0.0, 6.0) if kind == "relu6" else (op[1], op[2])
+            if qm == QuantizationMethod.SimpleQuant:
+                raise ValueError(f"{name}: op {len(layers)} ({kind}): a clip layer has no quantization under "
+                                 "SimpleQuant (no single activation scale); use ScaleQuant or ScaleQuantPlus")
+            layers.append(Clip(dims, lo, hi, q_parameter, qm))
         elif kind == "maxpool":
             k, s = op[1], op[2]
             pad, ceil = (op[3], op[4]) if len(op) > 3 else (0, False)
@@ -233,6 +248,8 @@ BENCH_CONFIGS = {
                                                 crt=[32, 3, 5, 7, 11, 13, 17], mrs=[10, 9, 9, 8, 7, 7, 6]),
     "MODEL_DWSEP_CIFAR/DASH": dict(model="MODEL_DWSEP_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
                                    crt=7, mrs=100.0),
+    "MOBILENET_CIFAR/DASH": dict(model="MOBILENET_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
+                                 crt=7, mrs=100.0),
     "SQUEEZENET_CIFAR/DASH": dict(model="SQUEEZENET_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
                                   crt=7, mrs=100.0),
     "MODEL_A/SIMPLE": dict(model="MODEL_A", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8, mrs=100.0),
