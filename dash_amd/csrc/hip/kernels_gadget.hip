@@ -1196,12 +1196,11 @@ __global__ __launch_bounds__(kAesBlock, DASH_RRO_WAVES) void k_rescale_relu_out(
 
 // k_rescale_relu_out with the label staged in LDS (stage_ok, small batches): a block = (256-element tile,
 // residue j, GC b) brings x_j's rows in once as 16-byte loads, each lane rescales its column in place and
-// hashes it, the block stores the rescaled rows (x in place), then each lane rewrites its column into the
-// ReLU output, stored as rows again. The per-lane form streams the label twice with one byte per lane per
-// load, n / kChunk dependent round trips per pass. Measured at batch 1 (MiniONN): 90 us per op vs 76 for the
-// per-lane form and ~50 + ~50 for the staged output-hash and ReLU-multiply kernels, whose 2.24 ms per step
-// beat 2.30 here (64 KiB of LDS per block: two blocks per CU), so the planner only fuses unstaged shapes and
-// this form runs under DASH_JOINT_FUSE=1 (A/B).
+// hashes it (the rescaled label stays in LDS: nothing reads it after a deferred rescale), then rewrites its
+// column into the ReLU output, stored as rows. The per-lane form streams the label twice with one byte per
+// lane per load, n / kChunk dependent round trips per pass. Measured at batch 1 (MiniONN, round 4, when it
+// still stored the rescaled rows): 90 us per op vs 76 for the per-lane form and ~50 + ~50 for the staged
+// output-hash and ReLU-multiply kernels. Batches of at most 2 GCs take it; larger ones k_rescale_relu_out_t.
 constexpr int kRroBS = 256;
 __global__ __launch_bounds__(kRroBS) void k_rescale_relu_out_s(MrsArgs a, SignArgs sa, Act x, Act y, const u128* gtab,
                                                                 const u128* etab, const ModC* mc, const uint32_t* te0,
@@ -1271,9 +1270,8 @@ __global__ __launch_bounds__(kRroBS) void k_rescale_relu_out_s(MrsArgs a, SignAr
                 if (j != 0) cf.push(v, m);
             }
         }
+        // Y_j stays in LDS: the planner fuses only where nothing reads the rescaled label again (runtime.hip defer)
         const u128 key = j == 0 ? P : cf.finish();
-        __syncthreads();
-        lds_store_rows<kRroBS>(L, stg, N, e0, 0, n);  // Y_j, the rescaled label
         const u128 G = Graw - hard_pad(key, a.rgate0 ^ static_cast<uint64_t>(e), tw_sub(kTwMmg, j), 0);
         const u128 E = Eraw - HS;
         const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
@@ -1282,8 +1280,7 @@ __global__ __launch_bounds__(kRroBS) void k_rescale_relu_out_s(MrsArgs a, SignAr
         DigitStream sg, se;
         sg.init(G);
         se.init(E);
-        __syncthreads();  // the row stores have read Y_j
-        if (m.bits == 1) {
+        if (m.bits == 1) {  // each lane rereads only its own column of Y_j: no barrier between the passes
             // p = 2: (e + ypr y + 2 - g) mod 2 = e ^ g ^ (ypr & y), the digits of G and E being their bits
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
@@ -1313,6 +1310,145 @@ __global__ __launch_bounds__(kRroBS) void k_rescale_relu_out_s(MrsArgs a, SignAr
         __syncthreads();
         lds_store_rows<kRroBS>(Y, stg, N, e0, 0, n);
     }
+}
+
+// Throughput form of the joint output (batch >= 3, stage_ok): a block = (256-element tile, residue j, GC b).
+// The rescaled label Y_j lives only in LDS: nothing is stored to x, and no hx / colx round trip (the two-kernel
+// path writes and reads back n_j + 18 bytes per element and residue). Odd residues stage L_j once, rewrite it to
+// Y_j with the chunk-major walk of k_rescale_mrs_out_hash_s (key summed per chunk), hash once, rewrite it to
+// relu_j with the chunk-major walk of k_relu_mult_s and store the rows to y. Residue 0 (p = 2) needs no input
+// rows: Y_0 is the bits of the payload P and relu_0 = (G ^ E) ^ (P & -ypr) on 128-bit registers; LDS only
+// transposes the result bits into byte rows, kRrtCap rows per window. The image is kRrtCap rows (20 KiB); bases
+// with a longer odd residue, or whose residue 0 is not p = 2, take k_rescale_relu_out_s (rrt_fits).
+constexpr int kRrtBS = 256;
+constexpr int kRrtCap = 80;
+static inline bool rrt_fits(const MrsArgs& a) {
+    bool fits = a.crt.p[0] == 2 && a.crt.n[0] <= 128;
+    for (int j = 1; j < a.crt.k; ++j) fits = fits && (a.crt.p[j] & (a.crt.p[j] - 1)) != 0 && a.crt.n[j] <= kRrtCap;
+    return fits;
+}
+// lds_stage_rows<kRrtBS, 4> with the four units in named registers: the helper's uint4 v[4], filled under a
+// condition, stays an 80-byte stack object in this kernel (scratch)
+__device__ __forceinline__ void rrt_stage_rows(uint8_t* S, const act_t* L, int64_t N, int64_t e0, int cnt) {
+    constexpr int W = kRrtBS / 16;
+    const int units = cnt * W;
+    auto ld = [=](int xu) {
+        const int64_t e = e0 + 16 * (xu % W);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (xu < units && e < N) v = *reinterpret_cast<const uint4*>(L + static_cast<int64_t>(xu / W) * N + e);
+        return v;
+    };
+    auto st = [=](int xu, uint4 v) {
+        if (xu < units) *reinterpret_cast<uint4*>(S + (xu / W) * kRrtBS + 16 * (xu % W)) = v;
+    };
+    for (int x0 = threadIdx.x; x0 < units; x0 += 4 * kRrtBS) {
+        const uint4 v0 = ld(x0), v1 = ld(x0 + kRrtBS), v2 = ld(x0 + 2 * kRrtBS), v3 = ld(x0 + 3 * kRrtBS);
+        st(x0, v0);
+        st(x0 + kRrtBS, v1);
+        st(x0 + 2 * kRrtBS, v2);
+        st(x0 + 3 * kRrtBS, v3);
+    }
+}
+__global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignArgs sa, Act x, Act y, const u128* gtab,
+                                                                const u128* etab, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[kRrtCap * kRrtBS];
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int k = a.crt.k;
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int n = static_cast<int>(m.n);
+    const int tid = static_cast<int>(threadIdx.x);
+    const int64_t e0 = static_cast<int64_t>(blockIdx.x) * kRrtBS;
+    const int64_t e = min(e0 + tid, N - 1);  // spare lanes shadow a real element; the row stores skip them
+    const int64_t be = static_cast<int64_t>(b) * N + e;
+    const act_t* L = x.p[j] + static_cast<int64_t>(b) * n * N;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N;
+    // the per-element gathers first: in flight while the rows are staged
+    const u128 P = a.pf[(static_cast<int64_t>(b) * k + j) * N + e];
+    const u128 HS = a.ys[(static_cast<int64_t>(b) * a.ny + j) * N + e];
+    const u128 HM = a.ys[(static_cast<int64_t>(b) * a.ny + k + j / 8) * N + e] >> (16 * (j % 8));
+    const uint32_t cS = a.cs[be];
+    const u128* E3 = etab + (be * k + j) * 3;
+    const u128 Eraw = E3[cS];
+    const u128 mini = E3[2];
+    const u128* grow = gtab + be * sa.crt.sum + sa.crt.prefix[j];
+    const uint64_t gate = a.rgate0 ^ static_cast<uint64_t>(e);
+    if (j == 0) {
+        const u128 Graw = grow[static_cast<uint32_t>(P) & 1u];
+        const u128 G = Graw - hard_pad(P, gate, tw_sub(kTwMmg, 0), 0);  // compress(Y_0) = P
+        const u128 E = Eraw - HS;
+        const uint32_t t16 = static_cast<uint32_t>(mini >> (16 * cS)), hm = static_cast<uint32_t>(HM);
+        // (e + ypr y + 2 - g) mod 2 = e ^ g ^ (ypr & y) with ypr = (t16 - hm) mod 2
+        const u128 R = (G ^ E) ^ (((t16 ^ hm) & 1u) ? P : static_cast<u128>(0));
+        for (int q0 = 0; q0 < n; q0 += kRrtCap) {
+            const int cnt = min(kRrtCap, n - q0);
+            if (q0) __syncthreads();  // the previous window's row stores have read the image
+            const u128 Rw = R >> q0;
+#pragma unroll
+            for (int w = 0; w < (kRrtCap + 31) / 32; ++w) {
+                const uint32_t rw = static_cast<uint32_t>(Rw >> (32 * w));
+#pragma unroll 8
+                for (int u = 0; u < 32; ++u) {
+                    const int c = 32 * w + u;
+                    if (c >= cnt) break;
+                    stg[c * kRrtBS + tid] = static_cast<uint8_t>((rw >> u) & 1u);
+                }
+            }
+            __syncthreads();
+            lds_store_rows<kRrtBS>(Y, stg, N, e0, q0, cnt);
+        }
+        return;
+    }
+    const uint32_t inv = static_cast<uint32_t>(a.sinv[j]);
+    const int c = static_cast<int>(m.c);
+    rrt_stage_rows(stg, L, N, e0, n);
+    __syncthreads();
+    // digit 0 of Y_j ahead of the walk: the garbler half gate's row gather overlaps pass 1
+    u128 Graw;
+    {
+        u128 t = P;
+        uint32_t r = divmod128(t, m);
+        const uint32_t pd0 = chunk_digit(r, m);
+        Graw = grow[modq(static_cast<uint32_t>(stg[tid]) * inv + pd0, m)];
+    }
+    // pass 1: Y_j = S^-1 L_j + digits(P) in place, key = compress(Y_j) summed per chunk
+    u128 Q = P, C = 0, PW = 1;
+    for (int k0 = 0; k0 < n; k0 += c) {
+        uint32_t r = divmod128(Q, m);
+        const int kc = min(c, n - k0);
+        uint32_t acc = 0, pt = 1;
+#pragma unroll 4
+        for (int t = 0; t < kc; ++t) {
+            uint8_t& w = stg[(k0 + t) * kRrtBS + tid];
+            const uint32_t v = modq(static_cast<uint32_t>(w) * inv + chunk_digit(r, m), m);  // < p^2 + p
+            w = static_cast<uint8_t>(v);
+            acc += v * pt;
+            pt *= m.q;
+        }
+        C += PW * static_cast<u128>(acc);
+        PW *= static_cast<u128>(m.D);
+    }
+    const u128 G = Graw - hard_pad(C, gate, tw_sub(kTwMmg, j), 0);
+    const u128 E = Eraw - HS;
+    const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
+    const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
+    const uint32_t ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);  // p*2^15 > |ypr16|
+    // pass 2: relu_j = E + ypr Y_j - G in place (all terms in [0, p): the sum < p^2 + 2p)
+    u128 QG = G, QE = E;
+    for (int k0 = 0; k0 < n; k0 += c) {
+        uint32_t rg = divmod128(QG, m), re = divmod128(QE, m);
+        const int kc = min(c, n - k0);
+#pragma unroll 4
+        for (int t = 0; t < kc; ++t) {
+            const uint32_t g = chunk_digit(rg, m);
+            const uint32_t ev = chunk_digit(re, m);
+            uint8_t& v = stg[(k0 + t) * kRrtBS + tid];
+            v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g, m));
+        }
+    }
+    __syncthreads();
+    lds_store_rows<kRrtBS>(Y, stg, N, e0, 0, n);
 }
 
 // Quad form of the joint output (latency-bound launches: batch 1, small layers). Four lanes per (element,
@@ -1501,9 +1637,31 @@ __global__ __launch_bounds__(256) void k_rescale_relu_out_q(MrsArgs a, SignArgs 
             }
         }
         __syncthreads();
-        quad_store_rows(L, sL, N, e0, n);
-        quad_store_rows(Yo, sO, N, e0, n);
+        quad_store_rows(Yo, sO, N, e0, n);  // Y_j (sL) is not stored: nothing reads it again (runtime.hip defer)
     }
+}
+
+// The joint-fuse mode (launch.h): -1 auto, 0 off, 1 on; the DASH_JOINT_FUSE environment value is its initial state
+static std::atomic<int>& joint_fuse_state() {
+    static std::atomic<int> mode{[] {
+        const char* e = std::getenv("DASH_JOINT_FUSE");
+        const int v = e ? std::atoi(e) : -1;
+        return v > 0 ? 1 : (v == 0 ? 0 : -1);
+    }()};
+    return mode;
+}
+int joint_fuse_mode() { return joint_fuse_state().load(std::memory_order_relaxed); }
+void set_joint_fuse(int mode) { joint_fuse_state().store(mode > 0 ? 1 : (mode == 0 ? 0 : -1), std::memory_order_relaxed); }
+// Threshold on batch * N for batches above 2: the smallest launch measured, 24 GCs x 576 elements, where the
+// layer's rescale and ReLU ops (chain included) take 0.088 ms fused against 0.129 ms with the output-hash and
+// ReLU-multiply kernels (every larger MiniONN layer wins too, profiles/ab/joint_fused/README.md). Nothing smaller was measured at batch >= 3, so nothing smaller fuses
+// (tests/test_gpu_launch_forms.py pins the two-kernel path up to 3 x 2064 = 6192 elements).
+constexpr int64_t kJointFuseMinElems = 24 * 576;
+int64_t joint_fuse_min_elems() { return kJointFuseMinElems; }
+bool joint_fuse_pick(int64_t N, int B) { return B <= 2 || (stage_ok(N, kRrtBS) && B * N >= kJointFuseMinElems); }
+bool joint_fuse(int64_t N, int B) {
+    const int mode = joint_fuse_mode();
+    return mode >= 0 ? mode == 1 : joint_fuse_pick(N, B);
 }
 
 void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x, const Act& y, const u128* gtab,
@@ -1516,6 +1674,12 @@ void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x,
         const dim3 gq(static_cast<unsigned>((a.N + kRroQE - 1) / kRroQE), a.crt.k, B);
         if (launch_log_on()) launch_log_add("relu_out.quad", gq, dim3(256));
         hipLaunchKernelGGL(k_rescale_relu_out_q, gq, dim3(256), 0, st, a, sa, x, y, gtab, etab, mc);
+        return;
+    }
+    if (rro_stage && B >= 3 && stage_ok(a.N, kRrtBS) && rrt_fits(a)) {  // throughput batches (own log name)
+        const dim3 gt(static_cast<unsigned>((a.N + kRrtBS - 1) / kRrtBS), a.crt.k, B);
+        if (launch_log_on()) launch_log_add("relu_out.tput", gt, dim3(kRrtBS));
+        hipLaunchKernelGGL(k_rescale_relu_out_t, gt, dim3(kRrtBS), 0, st, a, sa, x, y, gtab, etab, mc);
         return;
     }
     if (rro_stage && stage_ok(a.N, kRroBS)) {

@@ -23,6 +23,19 @@ namespace dev {
 int num_cus();
 void set_planning_cus(int n);
 int planning_cus_override();  // 0: none
+// Joint rescale + ReLU: whether the planner defers the rescale's outputs to the ReLU's fused output kernel
+// (launch_rescale_relu_out) instead of the output-hash and ReLU-multiply kernels. Mode -1 (auto) follows
+// joint_fuse_pick, 0 / 1 force it off / on; the DASH_JOINT_FUSE environment value is the initial mode. Like the
+// planning count, an evaluator reads it when it plans: set it before building the evaluator. (Defined beside
+// launch_rescale_relu_out in kernels_gadget.hip: launch_plan.hip reads no environment.)
+// joint_fuse_pick is the pure host rule: batches of at most 2 GCs (latency), and staged shapes (stage_ok at 256
+// lanes) of at least joint_fuse_min_elems() elements over the batch. The threshold is an absolute element
+// count: it does not follow the planning CU count.
+int64_t joint_fuse_min_elems();
+int joint_fuse_mode();
+void set_joint_fuse(int mode);
+bool joint_fuse_pick(int64_t N, int B);
+bool joint_fuse(int64_t N, int B);  // the mode applied to the rule
 // Launch log: off by default (one relaxed load per host-side launch, nothing under graph replay, where no picker
 // runs). When on, every picker appends the form it launched as "<form> grid=(x,y,z) block=n".
 extern std::atomic<bool> g_launch_log_on;

@@ -1255,18 +1255,13 @@ void HipEvaluator::build() {
                     const AesGlobals ag = aes_;
                     const int B = B_;
                     // joint ReLU next and this output not kept for a later layer: the ReLU's op can write both
-                    // outputs in one pass (k_rescale_relu_out), here only the chain runs. Measured (MiniONN):
-                    // faster at batch 1 (2.81 vs 2.98 ms per step), slower at batch 24 (15.9 vs 15.1 ms: the
-                    // hash -> second pass dependency per lane), so only small batches take it;
-                    // DASH_JOINT_FUSE=0/1 forces it off/on.
-                    static const int fuse_env = [] {
-                        const char* e = std::getenv("DASH_JOINT_FUSE");
-                        return e ? std::atoi(e) : -1;
-                    }();
-                    // Round 4 (AES tables) had the two staged kernels ahead at batch 1 for N % 16 == 0; with the
-                    // hardened encoding the fused form wins there too (latency_b1 2.21 -> 2.14 ms) and ties at
-                    // 24 GCs (9.85 vs 9.82 ms per step, profiles/ab/r5_joint_fuse_*.json): on for batch <= 2.
-                    const bool fuse = fuse_env >= 0 ? fuse_env == 1 : B_ <= 2;
+                    // outputs in one pass (launch_rescale_relu_out), here only the chain runs. The rescaled
+                    // label is then never written: the fused kernels keep it in LDS. Which launches take it is
+                    // launch.h joint_fuse: batches of at most 2 GCs (latency_b1 2.21 -> 2.14 ms), and staged
+                    // shapes from 13,824 elements over the batch, where the throughput form wins on every MiniONN
+                    // layer (24-GC step 9.08 -> 7.55 ms, profiles/ab/joint_fused/README.md); hip_set_joint_fuse
+                    // (initially DASH_JOINT_FUSE=0/1) forces it off/on.
+                    const bool fuse = dev::joint_fuse(N, B_);
                     const bool defer = fuse && so && li + 1 < m0.layers.size() && m0.layers[li + 1].kind == K_RELU &&
                                        m0.layers[li + 1].param("smode", 0) == 2 && !keep[li + 1] &&
                                        !m0.layers[li + 1].p.count("in_src");
@@ -1954,6 +1949,19 @@ void register_hip_bindings(py::module_& m) {
     }, py::arg("n"));
     m.def("hip_planning_cus", []() { return dev::num_cus(); });
     m.def("hip_planning_override", []() { return dev::planning_cus_override(); });
+    // Joint rescale + ReLU fusion (launch.h joint_fuse): -1 auto (hip_joint_fuse_pick), 0 off, 1 on. Read when an
+    // evaluator plans, like the planning count. hip_joint_fuse_pick is the auto rule itself (host arithmetic only)
+    // and hip_joint_fuse_min_elems its threshold on batch * N for batches above 2 (INT64_MAX: none takes it).
+    m.def("hip_set_joint_fuse", [](int mode) {
+        DASH_CHECK(mode >= -1 && mode <= 1, "hip_set_joint_fuse: mode must be -1 (auto), 0 (off) or 1 (on)");
+        dev::set_joint_fuse(mode);
+    }, py::arg("mode"));
+    m.def("hip_joint_fuse", []() { return dev::joint_fuse_mode(); });
+    m.def("hip_joint_fuse_pick", [](int64_t N, int B) {
+        DASH_CHECK(N >= 1 && B >= 1, "hip_joint_fuse_pick: N and B must be positive");
+        return dev::joint_fuse_pick(N, B);
+    }, py::arg("N"), py::arg("B"));
+    m.def("hip_joint_fuse_min_elems", []() { return dev::joint_fuse_min_elems(); });
     m.def("hip_launch_log", [](bool on) { dev::launch_log_enable(on); }, py::arg("on"));
     m.def("hip_launch_log_take", []() { return dev::launch_log_take(); });
     // The conv kernel plan of a dense-conv layer, exactly as the evaluator (mfma: its switch) and the GPU garbler
