@@ -16,7 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "gadget_common.h"
+#include "gadget_walks.h"
 
 namespace dash {
 namespace dev {
@@ -370,47 +370,18 @@ __global__ __launch_bounds__(256) void k_relu_mult(SignArgs a, Act x, Act y, con
     const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
     const u128 Hx = a.hx[bke];
     const uint32_t colx = a.colx[bke];
-    const uint32_t cS = a.cs[static_cast<int64_t>(b) * N + e];
     const int64_t be = static_cast<int64_t>(b) * N + e;
-    // reference: one H(sign label) masks all k entries and minis; hardened: entry j under y-row pad j, mini j
-    // under lane j % 8 of pad k + j / 8 (MMTw, gadgets.h)
-    const u128 HS = a.hard ? a.ys[(static_cast<int64_t>(b) * a.ny + j) * N + e] : a.hs[be];
-    const u128 HM = a.hard ? (a.ys[(static_cast<int64_t>(b) * a.ny + k + j / 8) * N + e] >> (16 * (j % 8))) : HS;
+    const ReluOps o = relu_ops(a.hard ? nullptr : a.hs, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
     const u128 G = gtab[be * a.crt.sum + a.crt.prefix[j] + colx] - Hx;
-    const u128* E3 = etab + (be * k + j) * 3;
-    const u128 E = E3[cS] - HS;
-    const u128 mini = E3[2];
-    const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
-    const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
-    const uint32_t ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);  // p*2^15 > |ypr16|
-    const act_t* X = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
-    act_t* Y = y.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    const uint32_t ypr = mini_mult(o.mini, o.cS, o.HM, p, m);
     DigitStream sg, se;
     sg.init(G);
-    se.init(E);
-    const int n = static_cast<int>(m.n);
-    // the next chunk's loads go out before this chunk's stores: vmcnt retires in issue order, so a
-    // load issued after a store would also wait for that store
-    uint16_t cur[kChunk], nxt[kChunk];
-#pragma unroll
-    for (int u = 0; u < kChunk; ++u)
-        if (u < n) cur[u] = X[static_cast<int64_t>(u) * N];
-    for (int i0 = 0; i0 < n; i0 += kChunk) {
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u)
-            if (i0 + kChunk + u < n) nxt[u] = X[static_cast<int64_t>(i0 + kChunk + u) * N];
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u)
-            if (i0 + u < n) {
-                const uint32_t g = sg.next(m);
-                const uint32_t ev = se.next(m);
-                // all terms in [0, p): ev + ypr * x + (p - g) < p^2 + 2p
-                Y[static_cast<int64_t>(i0 + u) * N] =
-                    static_cast<act_t>(modq(ev + ypr * static_cast<uint32_t>(cur[u]) + static_cast<uint32_t>(p) - g, m));
-            }
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
-    }
+    se.init(o.Eraw - o.HS);
+    col_walk<kChunk>(x.p[j] + static_cast<int64_t>(b) * m.n * N + e, y.p[j] + static_cast<int64_t>(b) * m.n * N + e, N,
+                     static_cast<int>(m.n), [&](int, uint32_t xv) {
+                         const uint32_t g = sg.next(m);
+                         return mult_digit(se.next(m), ypr, xv, p, g, m);
+                     });
 }
 
 // k_relu_mult with the label staged in LDS (stage_ok): a block = (256-element tile, residue j, GC b); the
@@ -435,58 +406,12 @@ __global__ __launch_bounds__(kRmBS) void k_relu_mult_s(SignArgs a, Act x, Act y,
         const int64_t be = static_cast<int64_t>(b) * N + e;
         const u128 Hx = a.hx[bke];
         const uint32_t colx = a.colx[bke];
-        const u128 HS = a.hard ? a.ys[(static_cast<int64_t>(b) * a.ny + j) * N + e] : a.hs[be];
-        const u128 HM = a.hard ? (a.ys[(static_cast<int64_t>(b) * a.ny + k + j / 8) * N + e] >> (16 * (j % 8))) : HS;
-        const uint32_t cS = a.cs[be];
-        const u128* E3 = etab + (be * k + j) * 3;
+        const ReluOps o = relu_ops(a.hard ? nullptr : a.hs, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
         const u128 Graw = gtab[be * a.crt.sum + a.crt.prefix[j] + colx];
-        const u128 Eraw = E3[cS];
-        const u128 mini = E3[2];
         __syncthreads();  // the previous tile's stores have read the image
         lds_stage_rows<kRmBS, 4>(stg, X, N, e0, 0, n);
         __syncthreads();
-        const u128 G = Graw - Hx, E = Eraw - HS;
-        const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
-        const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
-        const uint32_t ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);
-        if (m.bits == 1) {
-            // p = 2 (the residue with the most components, 128): the digits of G and E are their bits, and
-            // (e + ypr x + 2 - g) mod 2 = e ^ g ^ (ypr & x): one bit extract and two logic ops per component
-            // instead of two 128-bit digit shifts and a reduction
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t ge = static_cast<uint32_t>(G >> (32 * w)) ^ static_cast<uint32_t>(E >> (32 * w));
-#pragma unroll 8
-                for (int u = 0; u < 32; ++u) {
-                    const int c = 32 * w + u;
-                    if (c >= n) break;
-                    uint8_t& v = stg[c * kRmBS + tid];
-                    v = static_cast<uint8_t>(((ge >> u) & 1u) ^ (static_cast<uint32_t>(v) & ypr));
-                }
-            }
-        } else if (m.bits) {
-            DigitStream sg, se;
-            sg.init(G);
-            se.init(E);
-            for (int c = 0; c < n; ++c) {
-                const uint32_t g = sg.next(m);
-                const uint32_t ev = se.next(m);
-                uint8_t& v = stg[c * kRmBS + tid];
-                v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g, m));
-            }
-        } else {  // chunk-major (chunk_digit): one divmod per stream per chunk, uniform digit loops
-            u128 QG = G, QE = E;
-            for (int c0 = 0; c0 < n; c0 += static_cast<int>(m.c)) {
-                uint32_t rg = divmod128(QG, m), re = divmod128(QE, m);
-                const int cnt = min(static_cast<int>(m.c), n - c0);
-                for (int t = 0; t < cnt; ++t) {
-                    const uint32_t g = chunk_digit(rg, m);
-                    const uint32_t ev = chunk_digit(re, m);
-                    uint8_t& v = stg[(c0 + t) * kRmBS + tid];
-                    v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g, m));
-                }
-            }
-        }
+        lds_mult_walk<kRmBS, false>(stg + tid, n, Graw - Hx, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m), p, m);
         __syncthreads();
         lds_store_rows<kRmBS>(Y, stg, N, e0, 0, n);
     }
@@ -529,9 +454,7 @@ __device__ __forceinline__ ClipLane clip_lane(const ClipArgs& a, int j, int b, i
     r.G = Graw - Hx;
     r.E = Eraw - HS;
     r.C = Craw - HC;
-    const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cU)));
-    const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
-    r.ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);  // p*2^15 > |ypr16|
+    r.ypr = mini_mult(mini, cU, HM, p, m);
     return r;
 }
 
@@ -544,36 +467,16 @@ __global__ __launch_bounds__(256) void k_clip_mult(ClipArgs a, Act x, Act y, con
     const int p = a.crt.p[j];
     const ModC m = mc[p];
     const ClipLane c = clip_lane(a, j, b, e, p, m);
-    const uint32_t ypr = c.ypr;
-    const act_t* X = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
-    act_t* Y = y.p[j] + static_cast<int64_t>(b) * m.n * N + e;
     DigitStream sg, se, sc;
     sg.init(c.G);
     se.init(c.E);
     sc.init(c.C);
-    const int n = static_cast<int>(m.n);
-    // the next chunk's loads go out before this chunk's stores (as k_relu_mult)
-    uint16_t cur[kChunk], nxt[kChunk];
-#pragma unroll
-    for (int u = 0; u < kChunk; ++u)
-        if (u < n) cur[u] = X[static_cast<int64_t>(u) * N];
-    for (int i0 = 0; i0 < n; i0 += kChunk) {
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u)
-            if (i0 + kChunk + u < n) nxt[u] = X[static_cast<int64_t>(i0 + kChunk + u) * N];
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u)
-            if (i0 + u < n) {
-                const uint32_t g = sg.next(m);
-                const uint32_t ev = se.next(m);
-                const uint32_t cv = sc.next(m);
-                // all terms in [0, p): ev + ypr * x + (p - g) + cv < p^2 + 3p
-                Y[static_cast<int64_t>(i0 + u) * N] = static_cast<act_t>(
-                    modq(ev + ypr * static_cast<uint32_t>(cur[u]) + static_cast<uint32_t>(p) - g + cv, m));
-            }
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
-    }
+    col_walk<kChunk>(x.p[j] + static_cast<int64_t>(b) * m.n * N + e, y.p[j] + static_cast<int64_t>(b) * m.n * N + e, N,
+                     static_cast<int>(m.n), [&](int, uint32_t xv) {
+                         const uint32_t g = sg.next(m);
+                         const uint32_t ev = se.next(m);
+                         return mult_digit(ev + sc.next(m), c.ypr, xv, p, g, m);
+                     });
 }
 
 // k_clip_mult with the label staged in LDS (stage_ok; as k_relu_mult_s): a block = (256-element tile, residue
@@ -592,50 +495,10 @@ __global__ __launch_bounds__(kRmBS) void k_clip_mult_s(ClipArgs a, Act x, Act y,
     for (int64_t e0 = static_cast<int64_t>(blockIdx.x) * kRmBS; e0 < N; e0 += static_cast<int64_t>(gridDim.x) * kRmBS) {
         const int64_t e = min(e0 + tid, N - 1);  // lanes past the end redo the last element (their column is not stored)
         const ClipLane c = clip_lane(a, j, b, e, p, m);
-        const uint32_t ypr = c.ypr;
         __syncthreads();  // the previous tile's stores have read the image
         lds_stage_rows<kRmBS, 4>(stg, X, N, e0, 0, n);
         __syncthreads();
-        if (m.bits == 1) {
-            // p = 2: digits are bits, (e + ypr x + 2 - g + c) mod 2 = e ^ g ^ c ^ (ypr & x)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t gec = static_cast<uint32_t>(c.G >> (32 * w)) ^ static_cast<uint32_t>(c.E >> (32 * w)) ^
-                                     static_cast<uint32_t>(c.C >> (32 * w));
-#pragma unroll 8
-                for (int u = 0; u < 32; ++u) {
-                    const int cc = 32 * w + u;
-                    if (cc >= n) break;
-                    uint8_t& v = stg[cc * kRmBS + tid];
-                    v = static_cast<uint8_t>(((gec >> u) & 1u) ^ (static_cast<uint32_t>(v) & ypr));
-                }
-            }
-        } else if (m.bits) {
-            DigitStream sg, se, sc;
-            sg.init(c.G);
-            se.init(c.E);
-            sc.init(c.C);
-            for (int cc = 0; cc < n; ++cc) {
-                const uint32_t g = sg.next(m);
-                const uint32_t ev = se.next(m);
-                const uint32_t cv = sc.next(m);
-                uint8_t& v = stg[cc * kRmBS + tid];
-                v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g + cv, m));
-            }
-        } else {  // chunk-major (chunk_digit): one divmod per stream per chunk, uniform digit loops
-            u128 QG = c.G, QE = c.E, QC = c.C;
-            for (int c0 = 0; c0 < n; c0 += static_cast<int>(m.c)) {
-                uint32_t rg = divmod128(QG, m), re = divmod128(QE, m), rc = divmod128(QC, m);
-                const int cnt = min(static_cast<int>(m.c), n - c0);
-                for (int t = 0; t < cnt; ++t) {
-                    const uint32_t g = chunk_digit(rg, m);
-                    const uint32_t ev = chunk_digit(re, m);
-                    const uint32_t cv = chunk_digit(rc, m);
-                    uint8_t& v = stg[(c0 + t) * kRmBS + tid];
-                    v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g + cv, m));
-                }
-            }
-        }
+        lds_mult_walk<kRmBS, true>(stg + tid, n, c.G, c.E, c.C, c.ypr, p, m);
         __syncthreads();
         lds_store_rows<kRmBS>(Y, stg, N, e0, 0, n);
     }
@@ -914,24 +777,9 @@ __global__ __launch_bounds__(256) void k_rescale_mrs_out(MrsArgs a, Act x, const
         return;
     }
     const uint32_t inv = static_cast<uint32_t>(a.sinv[j]);
-    // loads of group c+1 before the stores of group c (as k_relu_mult); 16-digit groups: this kernel runs one
-    // short serial walk per lane (batch-1 launches are latency-bound), so fewer, deeper round trips
-    constexpr int kG = 2 * kChunk;
-    uint16_t cur[kG], nxt[kG];
-#pragma unroll
-    for (int u = 0; u < kG; ++u)
-        if (u < n) cur[u] = L[static_cast<int64_t>(u) * N];
-    for (int c0 = 0; c0 < n; c0 += kG) {
-#pragma unroll
-        for (int u = 0; u < kG; ++u)
-            if (c0 + kG + u < n) nxt[u] = L[static_cast<int64_t>(c0 + kG + u) * N];
-#pragma unroll
-        for (int u = 0; u < kG; ++u)
-            if (c0 + u < n)
-                L[static_cast<int64_t>(c0 + u) * N] = static_cast<act_t>(modq(cur[u] * inv + s.next(m), m));  // < p^2 + p
-#pragma unroll
-        for (int u = 0; u < kG; ++u) cur[u] = nxt[u];
-    }
+    // 16-digit groups: this kernel runs one short serial walk per lane (batch-1 launches are latency-bound), so
+    // fewer, deeper round trips
+    col_walk<2 * kChunk>(L, L, N, n, [&](int, uint32_t l) { return modq(l * inv + s.next(m), m); });  // < p^2 + p
 }
 
 // Joint rescale + ReLU (MODE 2): the output kernel also produces the next ReLU's garbler half-gate keys
@@ -969,25 +817,12 @@ __global__ __launch_bounds__(kAesBlock, kAesMinBlocks) void k_rescale_mrs_out_ha
         CompressFwd cf;
         cf.init();
         uint32_t c0 = 0;
-        uint16_t cur[kChunk], nxt[kChunk];
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u)
-            if (u < n) cur[u] = L[static_cast<int64_t>(u) * N];
-        for (int q0 = 0; q0 < n; q0 += kChunk) {
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u)
-                if (q0 + kChunk + u < n) nxt[u] = L[static_cast<int64_t>(q0 + kChunk + u) * N];
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u)
-                if (q0 + u < n) {
-                    const uint32_t v = modq(cur[u] * inv + s.next(m), m);  // < p^2 + p
-                    if (q0 + u == 0) c0 = v;
-                    L[static_cast<int64_t>(q0 + u) * N] = static_cast<act_t>(v);
-                    cf.push(v, m);
-                }
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
-        }
+        col_walk<kChunk>(L, L, N, n, [&](int c, uint32_t l) {
+            const uint32_t v = modq(l * inv + s.next(m), m);  // < p^2 + p
+            if (c == 0) c0 = v;
+            cf.push(v, m);
+            return v;
+        });
         a.colx[bke] = static_cast<uint16_t>(c0);
         a.hx[bke] = hard_pad(cf.finish(), a.rgate0 ^ static_cast<uint64_t>(e), tw_sub(kTwMmg, j), 0);
     }
@@ -1019,7 +854,8 @@ __global__ __launch_bounds__(kOhBS, kAesMinBlocks) void k_rescale_mrs_out_hash_s
         s.init(P);
         CompressFwd cf;
         cf.init();
-        u128 Q = P, C = 0, PW = 1;  // chunk-major state (non-power-of-two moduli)
+        ChunkKey ck;  // chunk-major state (non-power-of-two moduli)
+        ck.init(P);
         uint32_t c0 = 0;
         // passes of whole chunks of m.c digits for the chunk-major walk
         const int pass = m.bits ? kOhCap : kOhCap / static_cast<int>(m.c) * static_cast<int>(m.c);
@@ -1057,31 +893,14 @@ __global__ __launch_bounds__(kOhBS, kAesMinBlocks) void k_rescale_mrs_out_hash_s
                     w = static_cast<uint8_t>(v);
                     if (j != 0) cf.push(v, m);
                 }
-            } else {  // chunk-major (chunk_digit): one divmod per chunk, uniform digit loops, one flush per chunk
-                // (digit loop unrolled by 4 and the first digit read back after the pass instead of a compare per
-                // digit: the loop's scalar bookkeeping was ~40 % of the kernel's instructions, r05 headline PMC)
-                for (int k0 = 0; k0 < cnt; k0 += static_cast<int>(m.c)) {
-                    uint32_t r = divmod128(Q, m);
-                    const int kc = min(static_cast<int>(m.c), cnt - k0);
-                    uint32_t acc = 0, pt = 1;
-#pragma unroll 4
-                    for (int t = 0; t < kc; ++t) {
-                        uint8_t& w = stg[(k0 + t) * kOhBS + tid];
-                        const uint32_t dd = chunk_digit(r, m);
-                        const uint32_t v = j == 0 ? dd : modq(static_cast<uint32_t>(w) * inv + dd, m);
-                        w = static_cast<uint8_t>(v);
-                        acc += v * pt;
-                        pt *= m.q;
-                    }
-                    C += PW * static_cast<u128>(acc);
-                    PW *= static_cast<u128>(m.D);
-                }
+            } else {
+                ck.walk<kOhBS>(stg + tid, cnt, inv, j == 0, m);
                 if (q0 == 0) c0 = stg[tid];  // digit 0 of the output (this lane's own LDS byte)
             }
             __syncthreads();
             lds_store_rows<kOhBS>(L, stg, N, e0, q0, cnt);
         }
-        const u128 H = hard_pad(j == 0 ? P : (m.bits ? cf.finish() : C),
+        const u128 H = hard_pad(j == 0 ? P : (m.bits ? cf.finish() : ck.C),
                                 a.rgate0 ^ static_cast<uint64_t>(valid ? e0 + tid : N - 1), tw_sub(kTwMmg, j), 0);
         if (valid) {
             a.colx[bke] = static_cast<uint16_t>(c0);
@@ -1116,13 +935,7 @@ __global__ __launch_bounds__(kAesBlock, DASH_RRO_WAVES) void k_rescale_relu_out(
         const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
         act_t* L = x.p[j] + static_cast<int64_t>(b) * n * N + e;
         act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N + e;
-        // hardened y-row pads (chain MODE 2 store_ypads): entry j, mini lane j % 8 of slot k + j / 8
-        const u128 HS = a.ys[(static_cast<int64_t>(b) * a.ny + j) * N + e];
-        const u128 HM = a.ys[(static_cast<int64_t>(b) * a.ny + k + j / 8) * N + e] >> (16 * (j % 8));
-        const uint32_t cS = a.cs[be];
-        const u128* E3 = etab + (be * k + j) * 3;
-        const u128 Eraw = E3[cS];
-        const u128 mini = E3[2];
+        const ReluOps o = relu_ops(nullptr, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
         const u128* grow = gtab + be * sa.crt.sum + sa.crt.prefix[j];
         const u128 P = a.pf[bke];
         DigitStream s;
@@ -1143,35 +956,22 @@ __global__ __launch_bounds__(kAesBlock, DASH_RRO_WAVES) void k_rescale_relu_out(
         } else {
             CompressFwd cf;
             cf.init();
-            uint16_t cur[kChunk], nxt[kChunk];
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u)
-                if (u < n) cur[u] = L[static_cast<int64_t>(u) * N];
-            for (int q0 = 0; q0 < n; q0 += kChunk) {
-#pragma unroll
-                for (int u = 0; u < kChunk; ++u)
-                    if (q0 + kChunk + u < n) nxt[u] = L[static_cast<int64_t>(q0 + kChunk + u) * N];
-#pragma unroll
-                for (int u = 0; u < kChunk; ++u)
-                    if (q0 + u < n) {
-                        const uint32_t v = modq(cur[u] * inv + s.next(m), m);  // < p^2 + p
-                        if (q0 + u == 0) Graw = grow[v];
-                        L[static_cast<int64_t>(q0 + u) * N] = static_cast<act_t>(v);
-                        cf.push(v, m);
-                    }
-#pragma unroll
-                for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
-            }
+            col_walk<kChunk>(L, L, N, n, [&](int c, uint32_t l) {
+                const uint32_t v = modq(l * inv + s.next(m), m);  // < p^2 + p
+                if (c == 0) Graw = grow[v];
+                cf.push(v, m);
+                return v;
+            });
             key = cf.finish();
         }
         const u128 G = Graw - hard_pad(key, a.rgate0 ^ static_cast<uint64_t>(e), tw_sub(kTwMmg, j), 0);
-        const u128 E = Eraw - HS;
-        const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
-        const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
-        const uint32_t ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);
+        const uint32_t ypr = mini_mult(o.mini, o.cS, o.HM, p, m);
         DigitStream sg, se;
         sg.init(G);
-        se.init(E);
+        se.init(o.Eraw - o.HS);
+        // col_walk<kChunk>(L, Y, ...) written out: through the helper this second walk is allocated 74 registers
+        // for the parent's 87 and the kernel's occupancy moves from 5 to 6 waves per SIMD
+        // (profiles/ab/gadget_walks/README.md)
         uint16_t cur[kChunk], nxt[kChunk];
 #pragma unroll
         for (int u = 0; u < kChunk; ++u)
@@ -1185,8 +985,7 @@ __global__ __launch_bounds__(kAesBlock, DASH_RRO_WAVES) void k_rescale_relu_out(
                 if (i0 + u < n) {
                     const uint32_t g = sg.next(m);
                     const uint32_t ev = se.next(m);
-                    Y[static_cast<int64_t>(i0 + u) * N] =
-                        static_cast<act_t>(modq(ev + ypr * static_cast<uint32_t>(cur[u]) + static_cast<uint32_t>(p) - g, m));
+                    Y[static_cast<int64_t>(i0 + u) * N] = static_cast<act_t>(mult_digit(ev, ypr, cur[u], p, g, m));
                 }
 #pragma unroll
             for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
@@ -1222,91 +1021,47 @@ __global__ __launch_bounds__(kRroBS) void k_rescale_relu_out_s(MrsArgs a, SignAr
         const int64_t e = min(e0 + tid, N - 1);  // spare lanes shadow a real element; the row stores skip them
         const int64_t be = static_cast<int64_t>(b) * N + e;
         const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
-        const u128 HS = a.ys[(static_cast<int64_t>(b) * a.ny + j) * N + e];
-        const u128 HM = a.ys[(static_cast<int64_t>(b) * a.ny + k + j / 8) * N + e] >> (16 * (j % 8));
-        const uint32_t cS = a.cs[be];
-        const u128* E3 = etab + (be * k + j) * 3;
-        const u128 Eraw = E3[cS];
-        const u128 mini = E3[2];
+        const ReluOps o = relu_ops(nullptr, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
         const u128* grow = gtab + be * sa.crt.sum + sa.crt.prefix[j];
         const u128 P = a.pf[bke];
         __syncthreads();  // the previous tile's row stores have read the image
         if (j != 0) lds_stage_rows<kRroBS, 4>(stg, L, N, e0, 0, n);
         __syncthreads();
+        uint8_t* col = stg + tid;
         DigitStream s;
         s.init(P);
         CompressFwd cf;
         cf.init();
         u128 Graw = 0;
-        // groups of kRroG digits: the group's LDS reads are issued together (one exposed latency per group instead
-        // of per digit: a digit's write-back may alias the next digit's read, so the compiler cannot hoist it)
-        constexpr int kRroG = 8;
-        if (j == 0 && m.bits == 1) {
-            // p = 2: Y_0's digits are the bits of P. Its 128 components are the longest label, so the residue-0
-            // blocks were the launch's tail when each digit took a 128-bit stream shift
+        constexpr int kRroG = 8;  // digits per grouped LDS read (lds_group_walk)
+        // p = 2: Y_0's digits are the bits of P. Its 128 components are the longest label, so the residue-0 blocks
+        // were the launch's tail when each digit took a 128-bit stream shift. (The walks below get a row count of
+        // 0 instead of sitting in an else: as an if / else the kernel takes 115 registers for 85.)
+        const bool bits0 = j == 0 && m.bits == 1;
+        if (bits0) {
             Graw = grow[static_cast<uint32_t>(P) & 1u];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t pw = static_cast<uint32_t>(P >> (32 * w));
-#pragma unroll 8
-                for (int u = 0; u < 32; ++u) {
-                    const int c = 32 * w + u;
-                    if (c >= n) break;
-                    stg[c * kRroBS + tid] = static_cast<uint8_t>((pw >> u) & 1u);
-                }
-            }
+            lds_bit_rows<kRroBS>(col, n, P, [](uint32_t bit, uint32_t) { return bit; });
         }
-        for (int c0 = 0; c0 < ((j == 0 && m.bits == 1) ? 0 : n); c0 += kRroG) {
-            uint32_t w8[kRroG];
-#pragma unroll
-            for (int u = 0; u < kRroG; ++u) w8[u] = (j != 0 && c0 + u < n) ? stg[(c0 + u) * kRroBS + tid] : 0u;
-#pragma unroll
-            for (int u = 0; u < kRroG; ++u) {
-                const int c = c0 + u;
-                if (c >= n) break;
-                const uint32_t v = j == 0 ? s.next(m) : modq(w8[u] * inv + s.next(m), m);
-                if (c == 0) Graw = grow[v];
-                stg[c * kRroBS + tid] = static_cast<uint8_t>(v);
-                if (j != 0) cf.push(v, m);
-            }
-        }
+        lds_group_walk<kRroBS, kRroG>(col, bits0 ? 0 : n, j != 0, [&](int c, uint32_t l) {
+            const uint32_t v = j == 0 ? s.next(m) : modq(l * inv + s.next(m), m);
+            if (c == 0) Graw = grow[v];
+            if (j != 0) cf.push(v, m);
+            return v;
+        });
         // Y_j stays in LDS: the planner fuses only where nothing reads the rescaled label again (runtime.hip defer)
         const u128 key = j == 0 ? P : cf.finish();
         const u128 G = Graw - hard_pad(key, a.rgate0 ^ static_cast<uint64_t>(e), tw_sub(kTwMmg, j), 0);
-        const u128 E = Eraw - HS;
-        const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
-        const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
-        const uint32_t ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);
+        const u128 E = o.Eraw - o.HS;
+        const uint32_t ypr = mini_mult(o.mini, o.cS, o.HM, p, m);
+        // each lane rereads only its own column of Y_j: no barrier between the passes
         DigitStream sg, se;
         sg.init(G);
         se.init(E);
-        if (m.bits == 1) {  // each lane rereads only its own column of Y_j: no barrier between the passes
-            // p = 2: (e + ypr y + 2 - g) mod 2 = e ^ g ^ (ypr & y), the digits of G and E being their bits
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t ge = static_cast<uint32_t>(G >> (32 * w)) ^ static_cast<uint32_t>(E >> (32 * w));
-#pragma unroll 8
-                for (int u = 0; u < 32; ++u) {
-                    const int c = 32 * w + u;
-                    if (c >= n) break;
-                    uint8_t& v = stg[c * kRroBS + tid];
-                    v = static_cast<uint8_t>(((ge >> u) & 1u) ^ (static_cast<uint32_t>(v) & ypr));
-                }
-            }
-        }
-        for (int c0 = 0; c0 < (m.bits == 1 ? 0 : n); c0 += kRroG) {
-            uint32_t w8[kRroG];
-#pragma unroll
-            for (int u = 0; u < kRroG; ++u) w8[u] = c0 + u < n ? stg[(c0 + u) * kRroBS + tid] : 0u;
-#pragma unroll
-            for (int u = 0; u < kRroG; ++u) {
-                const int c = c0 + u;
-                if (c >= n) break;
-                const uint32_t g = sg.next(m);
-                const uint32_t ev = se.next(m);
-                stg[c * kRroBS + tid] = static_cast<uint8_t>(modq(ev + ypr * w8[u] + static_cast<uint32_t>(p) - g, m));
-            }
-        }
+        if (m.bits == 1) lds_bit_rows<kRroBS>(col, n, G ^ E, [=](uint32_t bit, uint32_t yv) { return bit ^ (yv & ypr); });
+        lds_group_walk<kRroBS, kRroG>(col, m.bits == 1 ? 0 : n, true, [&](int, uint32_t yv) {
+            const uint32_t g = sg.next(m);
+            return mult_digit(se.next(m), ypr, yv, p, g, m);
+        });
         __syncthreads();
         lds_store_rows<kRroBS>(Y, stg, N, e0, 0, n);
     }
@@ -1366,24 +1121,22 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignAr
     act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N;
     // the per-element gathers first: in flight while the rows are staged
     const u128 P = a.pf[(static_cast<int64_t>(b) * k + j) * N + e];
-    const u128 HS = a.ys[(static_cast<int64_t>(b) * a.ny + j) * N + e];
-    const u128 HM = a.ys[(static_cast<int64_t>(b) * a.ny + k + j / 8) * N + e] >> (16 * (j % 8));
-    const uint32_t cS = a.cs[be];
-    const u128* E3 = etab + (be * k + j) * 3;
-    const u128 Eraw = E3[cS];
-    const u128 mini = E3[2];
+    const ReluOps o = relu_ops(nullptr, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
     const u128* grow = gtab + be * sa.crt.sum + sa.crt.prefix[j];
     const uint64_t gate = a.rgate0 ^ static_cast<uint64_t>(e);
+    uint8_t* col = stg + tid;
     if (j == 0) {
         const u128 Graw = grow[static_cast<uint32_t>(P) & 1u];
         const u128 G = Graw - hard_pad(P, gate, tw_sub(kTwMmg, 0), 0);  // compress(Y_0) = P
-        const u128 E = Eraw - HS;
-        const uint32_t t16 = static_cast<uint32_t>(mini >> (16 * cS)), hm = static_cast<uint32_t>(HM);
+        const u128 E = o.Eraw - o.HS;
+        const uint32_t t16 = static_cast<uint32_t>(o.mini >> (16 * o.cS)), hm = static_cast<uint32_t>(o.HM);
         // (e + ypr y + 2 - g) mod 2 = e ^ g ^ (ypr & y) with ypr = (t16 - hm) mod 2
         const u128 R = (G ^ E) ^ (((t16 ^ hm) & 1u) ? P : static_cast<u128>(0));
         for (int q0 = 0; q0 < n; q0 += kRrtCap) {
             const int cnt = min(kRrtCap, n - q0);
             if (q0) __syncthreads();  // the previous window's row stores have read the image
+            // lds_bit_rows written out (over kRrtCap rows): through the helper the residue-0 blocks, the longest
+            // label of the headline's kernel, gain 68 instructions (profiles/ab/gadget_walks/README.md)
             const u128 Rw = R >> q0;
 #pragma unroll
             for (int w = 0; w < (kRrtCap + 31) / 32; ++w) {
@@ -1401,7 +1154,6 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignAr
         return;
     }
     const uint32_t inv = static_cast<uint32_t>(a.sinv[j]);
-    const int c = static_cast<int>(m.c);
     rrt_stage_rows(stg, L, N, e0, n);
     __syncthreads();
     // digit 0 of Y_j ahead of the walk: the garbler half gate's row gather overlaps pass 1
@@ -1413,40 +1165,12 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignAr
         Graw = grow[modq(static_cast<uint32_t>(stg[tid]) * inv + pd0, m)];
     }
     // pass 1: Y_j = S^-1 L_j + digits(P) in place, key = compress(Y_j) summed per chunk
-    u128 Q = P, C = 0, PW = 1;
-    for (int k0 = 0; k0 < n; k0 += c) {
-        uint32_t r = divmod128(Q, m);
-        const int kc = min(c, n - k0);
-        uint32_t acc = 0, pt = 1;
-#pragma unroll 4
-        for (int t = 0; t < kc; ++t) {
-            uint8_t& w = stg[(k0 + t) * kRrtBS + tid];
-            const uint32_t v = modq(static_cast<uint32_t>(w) * inv + chunk_digit(r, m), m);  // < p^2 + p
-            w = static_cast<uint8_t>(v);
-            acc += v * pt;
-            pt *= m.q;
-        }
-        C += PW * static_cast<u128>(acc);
-        PW *= static_cast<u128>(m.D);
-    }
-    const u128 G = Graw - hard_pad(C, gate, tw_sub(kTwMmg, j), 0);
-    const u128 E = Eraw - HS;
-    const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
-    const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
-    const uint32_t ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);  // p*2^15 > |ypr16|
-    // pass 2: relu_j = E + ypr Y_j - G in place (all terms in [0, p): the sum < p^2 + 2p)
-    u128 QG = G, QE = E;
-    for (int k0 = 0; k0 < n; k0 += c) {
-        uint32_t rg = divmod128(QG, m), re = divmod128(QE, m);
-        const int kc = min(c, n - k0);
-#pragma unroll 4
-        for (int t = 0; t < kc; ++t) {
-            const uint32_t g = chunk_digit(rg, m);
-            const uint32_t ev = chunk_digit(re, m);
-            uint8_t& v = stg[(k0 + t) * kRrtBS + tid];
-            v = static_cast<uint8_t>(modq(ev + ypr * static_cast<uint32_t>(v) + static_cast<uint32_t>(p) - g, m));
-        }
-    }
+    ChunkKey ck;
+    ck.init(P);
+    ck.walk<kRrtBS>(col, n, inv, false, m);
+    const u128 G = Graw - hard_pad(ck.C, gate, tw_sub(kTwMmg, j), 0);
+    // pass 2: relu_j = E + ypr Y_j - G in place
+    lds_mult_chunks<kRrtBS, false>(col, n, G, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m), p, m);
     __syncthreads();
     lds_store_rows<kRrtBS>(Y, stg, N, e0, 0, n);
 }
@@ -1509,7 +1233,6 @@ __global__ __launch_bounds__(256) void k_rescale_relu_out_q(MrsArgs a, SignArgs 
     const int p = a.crt.p[j];
     const ModC m = mc[p];
     const int n = static_cast<int>(m.n);
-    const uint32_t q = m.q;
     const int tid = static_cast<int>(threadIdx.x);
     const int el = tid >> 2, g = tid & 3;
     const uint32_t inv = static_cast<uint32_t>(a.sinv[j]);
@@ -1519,14 +1242,9 @@ __global__ __launch_bounds__(256) void k_rescale_relu_out_q(MrsArgs a, SignArgs 
         const int64_t e = min(e0 + el, N - 1);  // spare quads shadow a real element; the row stores skip them
         const int64_t be = static_cast<int64_t>(b) * N + e;
         const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
-        const u128 HS = a.ys[(static_cast<int64_t>(b) * a.ny + j) * N + e];
-        const u128 HM = a.ys[(static_cast<int64_t>(b) * a.ny + k + j / 8) * N + e] >> (16 * (j % 8));
-        const uint32_t cS = a.cs[be];
-        const u128* E3 = etab + (be * k + j) * 3;
-        const u128 mini = E3[2];
+        const ReluOps o = relu_ops(nullptr, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
         const u128* grow = gtab + be * sa.crt.sum + sa.crt.prefix[j];
         const u128 P = a.pf[bke];
-        const u128 Eraw = E3[cS];
         __syncthreads();  // the previous tile's row stores have read the images
         if (j != 0) quad_stage_rows(sL, L, N, e0, n);
         __syncthreads();
@@ -1535,7 +1253,7 @@ __global__ __launch_bounds__(256) void k_rescale_relu_out_q(MrsArgs a, SignArgs 
         {
             uint32_t pd0;
             if (m.bits) {
-                pd0 = static_cast<uint32_t>(P) & (q - 1);
+                pd0 = static_cast<uint32_t>(P) & (m.q - 1);
             } else {
                 u128 t = P;
                 uint32_t r = divmod128(t, m);
@@ -1545,49 +1263,7 @@ __global__ __launch_bounds__(256) void k_rescale_relu_out_q(MrsArgs a, SignArgs 
             Graw = grow[v0];
         }
         // Y_j = S^-1 L_j + P (mod p), residue 0: Y_0 = decompress(P); the lane's digits and its partial key
-        u128 part = 0;
-        const int bb = static_cast<int>(m.bits), cpl = (n + 3) >> 2;
-        QPow pw;
-        if (m.bits) {
-            // the lane's digits g cpl .. g cpl + cpl - 1 fit one 64-bit window (bb cpl <= 32 + bb): one 128-bit
-            // shift per lane instead of one per digit
-            const uint64_t Pw = static_cast<uint64_t>(P >> (bb * g * cpl));
-            for (int t = 0; t < cpl; ++t) {
-                const int idx = g * cpl + t;
-                if (idx >= n) break;
-                const uint32_t pd = static_cast<uint32_t>(Pw >> (bb * t)) & (q - 1);
-                const uint32_t v = j == 0 ? pd : modq(static_cast<uint32_t>(sL[idx * kRroQE + el]) * inv + pd, m);
-                sL[idx * kRroQE + el] = static_cast<uint8_t>(v);
-                part |= static_cast<u128>(v) << (bb * idx);
-            }
-        } else {
-            pw.init(m);
-            const int c = static_cast<int>(m.c), nch = (n + c - 1) / c;
-            u128 Q = P, PW = pw.first(g);
-            for (int jj = 0; 4 * jj < nch; ++jj) {
-                uint32_t mine = 0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (4 * jj + u >= nch) break;
-                    const uint32_t r = divmod128(Q, m);
-                    mine = u == g ? r : mine;
-                }
-                const int i = 4 * jj + g;
-                uint32_t cv = 0, pt = 1;
-                for (int t = 0; t < c; ++t) {
-                    const int idx = i * c + t;
-                    const uint32_t pd = chunk_digit(mine, m);
-                    if (idx < n) {
-                        const uint32_t v = j == 0 ? pd : modq(static_cast<uint32_t>(sL[idx * kRroQE + el]) * inv + pd, m);
-                        sL[idx * kRroQE + el] = static_cast<uint8_t>(v);
-                        cv += v * pt;
-                    }
-                    pt *= q;
-                }
-                part += PW * static_cast<u128>(cv);
-                PW *= pw.d4;
-            }
-        }
+        const u128 part = quad_rescale_walk<kRroQE, true>(sL + el, n, g, P, inv, j == 0, m);
         const u128 key = j == 0 ? P : quad_sum128(part);
         u128 G;
         if constexpr (kQCoop) {  // the quad runs the pad block together (every lane holds the same key)
@@ -1597,45 +1273,8 @@ __global__ __launch_bounds__(256) void k_rescale_relu_out_q(MrsArgs a, SignArgs 
         } else {
             G = Graw - hard_pad(key, a.rgate0 ^ static_cast<uint64_t>(e), tw_sub(kTwMmg, j), 0);
         }
-        const u128 E = Eraw - HS;
-        const int16_t t16 = static_cast<int16_t>(static_cast<uint16_t>(mini >> (16 * cS)));
-        const int16_t ypr16 = static_cast<int16_t>(t16 - static_cast<int16_t>(static_cast<uint16_t>(HM)));
-        const uint32_t ypr = modq(static_cast<uint32_t>(static_cast<int32_t>(ypr16) + (p << 15)), m);
-        // relu_j = E + ypr Y_j - G, the lane's own digits (k_relu_mult's arithmetic)
-        if (m.bits) {
-            const uint64_t Gw = static_cast<uint64_t>(G >> (bb * g * cpl)), Ew = static_cast<uint64_t>(E >> (bb * g * cpl));
-            for (int t = 0; t < cpl; ++t) {
-                const int idx = g * cpl + t;
-                if (idx >= n) break;
-                const uint32_t gd = static_cast<uint32_t>(Gw >> (bb * t)) & (q - 1);
-                const uint32_t ed = static_cast<uint32_t>(Ew >> (bb * t)) & (q - 1);
-                sO[idx * kRroQE + el] =
-                    static_cast<uint8_t>(modq(ed + ypr * static_cast<uint32_t>(sL[idx * kRroQE + el]) + static_cast<uint32_t>(p) - gd, m));
-            }
-        } else {
-            const int c = static_cast<int>(m.c), nch = (n + c - 1) / c;
-            u128 QG = G, QE = E;
-            for (int jj = 0; 4 * jj < nch; ++jj) {
-                uint32_t mg = 0, me = 0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (4 * jj + u >= nch) break;
-                    const uint32_t rg = divmod128(QG, m);
-                    const uint32_t re = divmod128(QE, m);
-                    mg = u == g ? rg : mg;
-                    me = u == g ? re : me;
-                }
-                const int i = 4 * jj + g;
-                for (int t = 0; t < c; ++t) {
-                    const int idx = i * c + t;
-                    const uint32_t gd = chunk_digit(mg, m);
-                    const uint32_t ed = chunk_digit(me, m);
-                    if (idx < n)
-                        sO[idx * kRroQE + el] = static_cast<uint8_t>(
-                            modq(ed + ypr * static_cast<uint32_t>(sL[idx * kRroQE + el]) + static_cast<uint32_t>(p) - gd, m));
-                }
-            }
-        }
+        // relu_j = E + ypr Y_j - G, the lane's own digits
+        quad_mult_walk<kRroQE>(sL + el, sO + el, n, g, G, o.Eraw - o.HS, mini_mult(o.mini, o.cS, o.HM, p, m), p, m);
         __syncthreads();
         quad_store_rows(Yo, sO, N, e0, n);  // Y_j (sL) is not stored: nothing reads it again (runtime.hip defer)
     }
@@ -1757,7 +1396,6 @@ __global__ __launch_bounds__(256) void k_rescale_mrs_out_q(MrsArgs a, Act x, con
     const int k = a.crt.k;
     const ModC m = mc[a.crt.p[j]];
     const int n = static_cast<int>(m.n);
-    const uint32_t q = m.q;
     const int tid = static_cast<int>(threadIdx.x);
     const int el = tid >> 2, g = tid & 3;
     const uint32_t inv = static_cast<uint32_t>(a.sinv[j]);
@@ -1768,37 +1406,7 @@ __global__ __launch_bounds__(256) void k_rescale_mrs_out_q(MrsArgs a, Act x, con
         __syncthreads();
         if (j != 0) quad_stage_rows(sL, L, N, e0, n);
         __syncthreads();
-        if (m.bits) {
-            const int bb = static_cast<int>(m.bits), cpl = (n + 3) >> 2;
-            const uint64_t Pw = static_cast<uint64_t>(P >> (bb * g * cpl));  // (as k_rescale_relu_out_q)
-            for (int t = 0; t < cpl; ++t) {
-                const int idx = g * cpl + t;
-                if (idx >= n) break;
-                const uint32_t pd = static_cast<uint32_t>(Pw >> (bb * t)) & (q - 1);
-                sL[idx * kRroQE + el] =
-                    static_cast<uint8_t>(j == 0 ? pd : modq(static_cast<uint32_t>(sL[idx * kRroQE + el]) * inv + pd, m));
-            }
-        } else {
-            const int c = static_cast<int>(m.c), nch = (n + c - 1) / c;
-            u128 Q = P;
-            for (int jj = 0; 4 * jj < nch; ++jj) {
-                uint32_t mine = 0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (4 * jj + u >= nch) break;
-                    const uint32_t r = divmod128(Q, m);
-                    mine = u == g ? r : mine;
-                }
-                const int i = 4 * jj + g;
-                for (int t = 0; t < c; ++t) {
-                    const int idx = i * c + t;
-                    const uint32_t pd = chunk_digit(mine, m);
-                    if (idx < n)
-                        sL[idx * kRroQE + el] = static_cast<uint8_t>(
-                            j == 0 ? pd : modq(static_cast<uint32_t>(sL[idx * kRroQE + el]) * inv + pd, m));  // < p^2 + p
-                }
-            }
-        }
+        quad_rescale_walk<kRroQE, false>(sL + el, n, g, P, inv, j == 0, m);
         __syncthreads();
         quad_store_rows(L, sL, N, e0, n);
     }
@@ -2020,20 +1628,26 @@ void launch_unpack(const u128* P, int nres, const Act& out, const CrtInfo& mods,
                    hipStream_t st) {
     hipLaunchKernelGGL(k_unpack, grid_for(N, 256, nres, B), dim3(256), 0, st, P, nres, out, mods, mc, N);
 }
+// The multiply's picker: the staged form (256-element tiles, kRmBS threads) where the shape allows and the
+// output is apart from the input, a block striding over the tiles at 16 blocks per CU over the launch; else a
+// lane per element (256 threads). Logs "<op>.staged" / "<op>.lane"; true for the staged form.
+static bool mult_grid(const char* op, int64_t N, int k, int B, const Act& x, const Act& y, dim3& grid) {
+    const bool staged = stage_ok(N, kRmBS) && x.p[0] != y.p[0];
+    grid = grid_for(N, 256, k, B);
+    if (staged) grid.x = static_cast<unsigned>(std::min<int64_t>((N + kRmBS - 1) / kRmBS, std::max(1, 16 * num_cus() / (k * B))));
+    if (launch_log_on()) launch_log_add(std::string(op) + (staged ? ".staged" : ".lane"), grid, dim3(staged ? kRmBS : 256));
+    return staged;
+}
 void launch_relu_mult(const SignArgs& a, const Act& x, const Act& y, const u128* gtab, const u128* etab,
                       const ModC* mc, hipStream_t st) {
-    if (stage_ok(a.N, kRmBS) && x.p[0] != y.p[0]) {
-        const unsigned nx = static_cast<unsigned>(std::min<int64_t>((a.N + kRmBS - 1) / kRmBS,
-                                                                   std::max(1, 16 * num_cus() / (a.crt.k * a.B))));
-        if (launch_log_on()) launch_log_add("relu_mult.staged", dim3(nx, a.crt.k, a.B), dim3(kRmBS));
-        hipLaunchKernelGGL(k_relu_mult_s, dim3(nx, a.crt.k, a.B), dim3(kRmBS), 0, st, a, x, y, gtab, etab, mc);
-        return;
-    }
-    if (launch_log_on()) launch_log_add("relu_mult.lane", grid_for(a.N, 256, a.crt.k, a.B), dim3(256));
-    hipLaunchKernelGGL(k_relu_mult, grid_for(a.N, 256, a.crt.k, a.B), dim3(256), 0, st, a, x, y, gtab, etab, mc);
+    dim3 grid;
+    if (mult_grid("relu_mult", a.N, a.crt.k, a.B, x, y, grid))
+        hipLaunchKernelGGL(k_relu_mult_s, grid, dim3(kRmBS), 0, st, a, x, y, gtab, etab, mc);
+    else
+        hipLaunchKernelGGL(k_relu_mult, grid, dim3(256), 0, st, a, x, y, gtab, etab, mc);
 }
 // Clip: the half gates' keys of x (as launch_relu_mrs), then one sign per bound into its own scratch, then the
-// multiply. The multiply's picker is launch_relu_mult's.
+// multiply. The multiply's picker is launch_relu_mult's (mult_grid).
 void launch_clip_hash(const ClipArgs& a, u128* hx, uint16_t* colx, const Act& x, int B, const ModC* mc,
                       const AesGlobals& g, hipStream_t st) {
     AES_LAUNCH_GGL(k_label_hash, a.N, a.crt.k, B, kAesLds, st, x, a.crt, a.N, hx, colx, mc, g.te0, g.rk, 1, a.mgate0);
@@ -2042,15 +1656,11 @@ void launch_clip_sign_mrs(const MrsArgs& a, const Act& x, int B, const ModC* mc,
     dispatch_mrs_chain(a, x, B, mc, g, st);
 }
 void launch_clip_mult(const ClipArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st) {
-    if (stage_ok(a.N, kRmBS) && x.p[0] != y.p[0]) {
-        const unsigned nx = static_cast<unsigned>(std::min<int64_t>((a.N + kRmBS - 1) / kRmBS,
-                                                                   std::max(1, 16 * num_cus() / (a.crt.k * B))));
-        if (launch_log_on()) launch_log_add("clip_mult.staged", dim3(nx, a.crt.k, B), dim3(kRmBS));
-        hipLaunchKernelGGL(k_clip_mult_s, dim3(nx, a.crt.k, B), dim3(kRmBS), 0, st, a, x, y, mc);
-        return;
-    }
-    if (launch_log_on()) launch_log_add("clip_mult.lane", grid_for(a.N, 256, a.crt.k, B), dim3(256));
-    hipLaunchKernelGGL(k_clip_mult, grid_for(a.N, 256, a.crt.k, B), dim3(256), 0, st, a, x, y, mc);
+    dim3 grid;
+    if (mult_grid("clip_mult", a.N, a.crt.k, B, x, y, grid))
+        hipLaunchKernelGGL(k_clip_mult_s, grid, dim3(kRmBS), 0, st, a, x, y, mc);
+    else
+        hipLaunchKernelGGL(k_clip_mult, grid, dim3(256), 0, st, a, x, y, mc);
 }
 void launch_rescale_hash(const Act& x, int fi, int s, const int16_t* up, int up_stride, int add_up, int64_t N, int B,
                          u128* h0, uint16_t* col0, const ModC* mc, const AesGlobals& g, hipStream_t st, int hard) {

@@ -308,6 +308,67 @@ def test_staged_forms_every_k(native, kind, k):
     _run(native, kind, k, 528, 2, 1)
 
 
+_POW2_BASE, _POW2_MRS = [32, 97, 107], [22, 19, 15, 13]  # M = 332128: residue 32 of the ReDash optimized bases
+
+
+def _pow2_circuit(N):
+    """Relu over a base whose first residue is a power of two above 2 (the multiply walks' digit-stream branch,
+    ModC bits = 5; the first-k-primes bases of the cases above have only p = 2 and odd residues): the hardened
+    default with the approximate sign, 2 GCs, a permuted input per GC."""
+    key = ("pow2", N)
+    if key not in _BUILT:
+        c = d.Circuit([d.Relu((N,))])
+        gcs = [GarbledCircuit(c, _POW2_BASE, _POW2_MRS, seed=bytes([32, i + 1]) * 8) for i in range(2)]
+        M = gcs[0].crt_modulus
+        assert M == 332128 and all(g.hardened for g in gcs)
+        # uniform over [-M/8, M/8): there the approximate sign is exact for every element (the host evaluator
+        # equals max(x, 0) below, no element excluded)
+        x = np.random.default_rng(32 + N).integers(-(M // 8), M // 8, N).astype(np.int64)
+        small = [0, 1, -1, 2, -2]
+        x[70:75] = small
+        for n, i in enumerate(EDGE_AT):
+            if -N <= i < N:
+                x[i] = small[n % len(small)]
+        xs = [x, x[::-1].copy()]
+        enc = [g.garble_inputs(v) for g, v in zip(gcs, xs)]
+        cpu = [g.cpu_evaluate(e) for g, e in zip(gcs, enc)]
+        closed = [np.maximum(v, 0) for v in xs]
+        for g, v, o, ref in zip(gcs, xs, cpu, closed):
+            np.testing.assert_array_equal(g.plain_q_eval(v), ref)
+            np.testing.assert_array_equal(g.decode_outputs(o), ref)
+        _BUILT[key] = dict(gcs=gcs, enc=enc, cpu=cpu, closed=closed)
+    return _BUILT[key]
+
+
+@pytest.mark.parametrize("N,form", [(528, "relu_mult.staged"), (1031, "relu_mult.lane")])
+def test_relu_mult_power_of_two_residue(native, N, form):
+    from dash_amd.runtime import HipEvaluator
+
+    c = _pow2_circuit(N)
+    native.hip_launch_log_take()
+    native.hip_set_planning_cus(1)
+    try:
+        ev = HipEvaluator([g.model for g in c["gcs"]])
+        native.hip_launch_log(True)
+        try:
+            gpu = ev.evaluate(c["enc"])
+        finally:
+            native.hip_launch_log(False)
+        log = native.hip_launch_log_take()
+    finally:
+        native.hip_set_planning_cus(0)
+    print("\n".join(log))
+    want_line = _relu_mult(len(_POW2_BASE), N, 2, 1)
+    assert want_line.startswith(form) and want_line in log
+    for want, got in zip(c["cpu"], gpu):
+        assert len(want) == len(got)
+        for (pw, aw), (pg, ag) in zip(want, got):
+            assert pw == pg
+            np.testing.assert_array_equal(aw, ag)
+    for g, o, ref in zip(c["gcs"], gpu, c["closed"]):
+        np.testing.assert_array_equal(g.decode_outputs(o), ref)  # == plain_q_eval == max(x, 0) (_pow2_circuit)
+
+
 def test_planning_count_restores(native):
     dev = native.hip_planning_cus()
     assert native.hip_planning_override() == 0 and dev >= 1
