@@ -49,6 +49,7 @@ class DashConfig:
     max_modulus: int = 0
     rescale: str = "auto"                     # DASH rescale construction: auto (mrs where the base and ranges allow) | mrs (one mixed-radix gadget) | legacy
     relu: str = "auto"                        # ReLU sign: auto (joint with the mrs rescale, else approx) | approx (reference gadget) | mrs (exact mixed radix) | joint (from the preceding mixed-radix rescale)
+    clip: Optional[str] = None                # Clip(0, q_hi) behind a mixed-radix rescale: separate (two signs of its own input) | joint (lower sign from the rescale, upper sign on the rescale's input); None: separate, or the DASH_CLIP environment value
     sign: str = "fused"                       # approximate sign gadget: fused casts | reference
     encoding: str = "auto"                    # offline-message encoding: auto (hardened where the constructions allow; the serving engine then refuses the reference one) | hardened | reference (wire-compatible, R_p recoverable: docs/SECURITY.md §1.1)
     seed: Optional[str] = None                # hex seed for reproducible garbling (tests only)
@@ -84,8 +85,13 @@ class DashConfig:
             raise ValueError(f"bad gadget construction: rescale={self.rescale} relu={self.relu} sign={self.sign}")
         if self.encoding not in ("auto", "hardened", "reference"):
             raise ValueError(f"bad encoding {self.encoding!r}: auto | hardened | reference")
+        if self.clip not in (None, "separate", "joint"):
+            raise ValueError(f"bad clip construction {self.clip!r}: separate | joint")
         hardened = {"auto": None, "hardened": True, "reference": False}[self.encoding]
-        return dict(rescale=self.rescale, relu=self.relu, fused_sign=self.sign == "fused", hardened=hardened)
+        kw = dict(rescale=self.rescale, relu=self.relu, fused_sign=self.sign == "fused", hardened=hardened)
+        if self.clip is not None:  # only when chosen: callers that predate the option keep their keywords
+            kw["clip"] = self.clip
+        return kw
 
     def resolved(self):
         """(q_method, q_parameter, crt, mrs, max_modulus) after applying the scheme."""

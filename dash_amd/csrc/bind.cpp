@@ -210,6 +210,11 @@ PYBIND11_MODULE(_dash_native, m) {
         return out;
     });
     m.def("kind_name", &kind_name);
+    // joint Clip (gadgets.h ClipPlan): the upper sign's threshold on the input of a mixed-radix Rescale(l), the
+    // smallest x that rescale maps to q_hi, from the plan's own arithmetic
+    m.def("clip_joint_threshold", [](const std::vector<int>& crt, int l, i64 q_hi) {
+        return ClipPlan(crt, q_hi, RescaleMrsPlan(crt, l, true)).t_hi;
+    });
 
     // Single gates of the native garbler with caller-chosen labels (wire-compatibility vectors: the tests
     // rebuild the reference's formulas in a pure-Python oracle and compare table bytes). Tables come back as
@@ -381,7 +386,7 @@ PYBIND11_MODULE(_dash_native, m) {
              py::arg("crt"), py::arg("mrs"), py::arg("seed"), py::arg("max_mod") = 0)
         .def("garble", [](Garbler& g, std::shared_ptr<GarbleSpecs> specs, std::vector<i64> in_dims, int nthreads,
                           int device, bool fused_sign, bool rescale_mrs, bool relu_mrs, bool relu_joint,
-                          std::shared_ptr<TableSink> sink, bool hardened) {
+                          std::shared_ptr<TableSink> sink, bool hardened, bool clip_joint) {
             GarbleOptions o;
             o.hardened = hardened;
             o.sink = std::move(sink);
@@ -391,6 +396,7 @@ PYBIND11_MODULE(_dash_native, m) {
             o.rescale_mrs = rescale_mrs;
             o.relu_mrs = relu_mrs;
             o.relu_joint = relu_joint;
+            o.clip_joint = clip_joint;
             o.cache = specs.get();
             GarbledModel gm;
             {
@@ -401,10 +407,10 @@ PYBIND11_MODULE(_dash_native, m) {
         }, py::arg("layers"), py::arg("in_dims"), py::arg("nthreads") = 0, py::arg("device") = -1,
            py::arg("fused_sign") = true, py::arg("rescale_mrs") = false,
            py::arg("relu_mrs") = false, py::arg("relu_joint") = false, py::arg("sink") = nullptr,
-           py::arg("hardened") = false)
+           py::arg("hardened") = false, py::arg("clip_joint") = false)
         .def("garble", [](Garbler& g, const py::list& layers, std::vector<i64> in_dims, int nthreads, int device,
                           bool fused_sign, bool rescale_mrs, bool relu_mrs, bool relu_joint,
-                          std::shared_ptr<TableSink> sink, bool hardened) {
+                          std::shared_ptr<TableSink> sink, bool hardened, bool clip_joint) {
             auto specs = specs_from_py(layers);
             GarbleOptions o;
             o.hardened = hardened;
@@ -415,6 +421,7 @@ PYBIND11_MODULE(_dash_native, m) {
             o.rescale_mrs = rescale_mrs;
             o.relu_mrs = relu_mrs;
             o.relu_joint = relu_joint;
+            o.clip_joint = clip_joint;
             GarbledModel gm;
             {
                 py::gil_scoped_release rel;
@@ -424,7 +431,7 @@ PYBIND11_MODULE(_dash_native, m) {
         }, py::arg("layers"), py::arg("in_dims"), py::arg("nthreads") = 0, py::arg("device") = -1,
            py::arg("fused_sign") = true, py::arg("rescale_mrs") = false,
            py::arg("relu_mrs") = false, py::arg("relu_joint") = false, py::arg("sink") = nullptr,
-           py::arg("hardened") = false)
+           py::arg("hardened") = false, py::arg("clip_joint") = false)
         .def("layer_ms", [](const Garbler& g) { return g.layer_ms(); })
         .def("encode", [](const Garbler& g, py::array_t<i64, py::array::c_style | py::array::forcecast> x) {
             std::vector<i64> v(x.data(), x.data() + x.size());

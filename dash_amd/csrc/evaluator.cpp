@@ -152,7 +152,8 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
     };
 
     if (layer_ms) layer_ms->assign(m.layers.size(), 0.0);
-    Labels sig_joint;  // sign labels a mixed-radix rescale with sign_out leaves for the next ReLU
+    Labels sig_joint;  // sign labels a mixed-radix rescale with sign_out leaves for the next ReLU / joint Clip
+    Labels shi_joint;  // a joint Clip's upper sign labels, evaluated at that rescale on its input labels
     for (size_t li = 0; li < m.layers.size(); ++li) {
         const auto t_layer = std::chrono::steady_clock::now();
         const GLayer& g = m.layers[li];
@@ -323,6 +324,36 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
             case K_CLIP: {
                 DASH_CHECK(hard, "clip: the Clip layer exists in the hardened encoding only");
                 const ClipPlan cp(crt, g.vec("lo").at(0), g.vec("hi").at(0));
+                if (g.param("smode", 0) == 2) {  // joint variant: both signs were left by the preceding rescale
+                    DASH_CHECK(li > 0 && m.layers[li - 1].kind == K_RESCALE &&
+                                   m.layers[li - 1].param("sign_out", 0) == 1 && !g.p.count("in_src") &&
+                                   cp.lo == 0 && sig_joint.N == Nin && shi_joint.N == Nin,
+                               "joint Clip without a preceding sign-producing rescale");
+                    const Array& tg = g.arr("mm.g");
+                    const Array& te = g.arr("mm.e");
+                    const Array& tc = g.arr("cap");
+                    DASH_CHECK(tg.shape[0] == Nin && tg.shape[1] == cp.sum_crt && te.shape[0] == Nin &&
+                                   tc.shape[0] == Nin, "joint Clip table shape");
+                    CrtLabels nxt;
+                    for (int j = 0; j < k; ++j) nxt.emplace_back(crt[j], Nin);
+                    parallel_for(Nin, [&](i64 b0, i64 b1) {
+                        std::vector<const comp_t*> x(k);
+                        std::vector<comp_t*> y(k);
+                        for (i64 e = b0; e < b1; ++e) {
+                            for (int j = 0; j < k; ++j) {
+                                x[j] = cur[j].at(e);
+                                y[j] = nxt[j].at(e);
+                            }
+                            clip_mult_eval(cp, x.data(), sig_joint.at(e), shi_joint.at(e),
+                                           tg.ptr<u128>() + e * cp.sum_crt, te.ptr<u128>() + e * k * 3,
+                                           tc.ptr<u128>() + e * k * 2, y.data(), stream_id(L, 2, e));
+                        }
+                    }, nt);
+                    cur = std::move(nxt);
+                    sig_joint = Labels();
+                    shi_joint = Labels();
+                    break;
+                }
                 const bool exact = g.param("smode", 0) == 1;
                 SignPlan sp_a;
                 SignMrsPlan sp_m;
@@ -379,6 +410,23 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                     const Array& tab = g.arr("mrs");
                     DASH_CHECK(tab.shape[1] == P.n_tab, "mixed-radix rescale table shape");
                     if (so) sig_joint = Labels(2, Nin);
+                    if (so && li + 1 < m.layers.size() && m.layers[li + 1].kind == K_CLIP &&
+                        m.layers[li + 1].param("smode", 0) == 2) {
+                        // the joint Clip's upper sign, on this layer's input labels (tables and gate of the Clip)
+                        const SignMrsPlan sp(crt);
+                        const Array& ht = m.layers[li + 1].arr("hi.mrs");
+                        DASH_CHECK(ht.shape.size() == 2 && ht.shape[0] == Nin && ht.shape[1] == std::max<i64>(sp.n_tab, 1),
+                                   "joint Clip upper sign table shape");
+                        shi_joint = Labels(2, Nin);
+                        parallel_for(Nin, [&](i64 b0, i64 b1) {
+                            std::vector<const comp_t*> x(k);
+                            for (i64 e = b0; e < b1; ++e) {
+                                for (int j = 0; j < k; ++j) x[j] = cur[j].at(e);
+                                sign_mrs_eval_elem(sp, x.data(), ht.ptr<u128>() + e * ht.shape[1], shi_joint.at(e), true,
+                                                   stream_id(L + 1, 3, e));
+                            }
+                        }, nt);
+                    }
                     parallel_for(Nin, [&](i64 b0, i64 b1) {
                         std::vector<comp_t*> Lp(k);
                         for (i64 e = b0; e < b1; ++e) {

@@ -337,6 +337,8 @@ struct RescaleMrsPlan {
     i64 digit_fn(int i, int t, i64 v) const;
     // payload value of final target j for key value v = x_u mod T
     i64 final_fn(int j, i64 v) const;
+    // the smallest input x with output floor((x + U) / S) - q >= y
+    i64 min_input(i64 y) const { return (y + q) * S - U; }
 };
 // L[j] (one element's labels mod crt[j]) are replaced by the rescaled labels;
 // with sign_last, sig (nullable) receives the mod-2 label of a_{k-1}.
@@ -410,11 +412,23 @@ void sign_mrs_eval_elem(const SignMrsPlan& P, const comp_t* const* x, const u128
 // (k = 7, first primes: exact 294 + 58 + 35 = 387 against 452.)
 // PRG streams: sign lo = slot 1, multiply and cap = slot 2 (the cap's base
 // label is drawn after the k half gates' draws), sign hi = slot 3.
+//
+// Joint variant (a Clip(0, q_hi) directly behind a mixed-radix rescale with
+// sign_last, input x, output y = ceil(x / S)): s_lo is the rescale's own sign
+// label a_{k-1} = [x >= M/2 - U] (it differs from [y >= 0] only where y = 0,
+// where u y = 0 either way, as for the joint ReLU), and s_hi = [y >= q_hi] =
+// [x >= t_hi] is one exact SignMrsPlan sign of the wire x - t_hi on the
+// rescale's INPUT labels, t_hi = the smallest x the rescale maps to q_hi
+// (RescaleMrsPlan::min_input). t_hi >= 1 > M/2 - U, so s_hi = 1 still implies
+// s_lo = 1. The multiply and the cap run on y_j unchanged. Tables: hi.mrs,
+// mm.g, mm.e, cap; n_sign + P + 5 k entries. Domain: x - t_hi >= -M/2.
 struct ClipPlan {
     std::vector<int> crt;
     i64 lo = 0, hi = 1;
     i64 sum_crt = 0;
     std::vector<i64> prefix;  // mm.g offset of residue j
+    bool joint = false;
+    i64 t_hi = 0;  // joint: threshold of the upper sign on the rescale's input
     ClipPlan() = default;
     ClipPlan(const std::vector<int>& crt_, i64 lo_, i64 hi_) : crt(crt_), lo(lo_), hi(hi_) {
         DASH_CHECK(lo < hi, "clip needs lo < hi");
@@ -423,9 +437,15 @@ struct ClipPlan {
             sum_crt += p;
         }
     }
+    // the joint variant behind the rescale `rs`
+    ClipPlan(const std::vector<int>& crt_, i64 hi_, const RescaleMrsPlan& rs) : ClipPlan(crt_, 0, hi_) {
+        DASH_CHECK(rs.sign_last, "joint clip needs a sign-producing rescale");
+        joint = true;
+        t_hi = rs.min_input(hi);
+    }
     int k() const { return static_cast<int>(crt.size()); }
     // table entries per element given the sign gadget's entry count
-    i64 entries(i64 n_sign) const { return 2 * n_sign + sum_crt + 3 * k() + 2 * k(); }
+    i64 entries(i64 n_sign) const { return (joint ? 1 : 2) * n_sign + sum_crt + 3 * k() + 2 * k(); }
     static i64 two_relu_entries(i64 n_sign, i64 sum_crt, int k) { return 2 * n_sign + 2 * sum_crt + 6 * k; }
 };
 // Tables of one element: the multiply's g [sum_crt] and e [k][3] and the cap [k][2]. slo0 / shi0 (garbler) and

@@ -605,6 +605,9 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
     // joint rescale + ReLU sign: the rescale leaves the sign base labels here (host) or in the GPU garbler
     bool sig_next = false;
     Labels sig_host;
+    // joint Clip: its upper sign's base labels and table, garbled at the rescale on that layer's input labels
+    Labels shi_host;
+    Array clip_hi_tab;
     for (size_t li = 0; li < layers.size(); ++li) {
         const auto t_layer = std::chrono::steady_clock::now();
         const LayerSpec& spec = layers[li];
@@ -645,8 +648,14 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         // legacy rescale as one mixed-radix gadget (RescaleMrsPlan)
         const bool mrs_rescale = opt.rescale_mrs && spec.kind == K_RESCALE && param1(spec.p, "mode", 0) == 0;
         const bool relu_mrs = opt.relu_mrs && spec.kind == K_RELU;
-        const bool joint_out = mrs_rescale && opt.relu_joint && li + 1 < layers.size() &&
+        const bool relu_next = mrs_rescale && opt.relu_joint && li + 1 < layers.size() &&
                                layers[li + 1].kind == K_RELU && param1(layers[li + 1].p, "in_src", -2) == -2;
+        // a Clip(0, q_hi) directly behind this rescale takes its lower sign from the conversion too, and its
+        // upper sign is garbled here, on the rescale's input labels (gadgets.h ClipPlan, joint variant)
+        const bool clip_next = mrs_rescale && opt.clip_joint && hard && li + 1 < layers.size() &&
+                               layers[li + 1].kind == K_CLIP && param1(layers[li + 1].p, "in_src", -2) == -2 &&
+                               paramv(layers[li + 1].p, "lo").at(0) == 0;
+        const bool joint_out = relu_next || clip_next;
         // every layer kind but the test-only projection / mult layers garbles on the device when a GPU garbler
         // is present (the legacy rescale's sign base extension needs residue 0 = 2)
         const bool lin_kind = spec.kind == K_CONV || spec.kind == K_DENSE || spec.kind == K_SUMPOOL ||
@@ -902,6 +911,49 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
             case K_CLIP: {
                 DASH_CHECK(is_crt(), "clip needs CRT-base labels");
                 DASH_CHECK(hard, "clip: the Clip layer exists in the hardened encoding only");
+                if (sig_in) {
+                    // joint variant: s_lo from the preceding rescale's conversion, s_hi garbled at that rescale
+                    // (above); the multiply and the cap on the rescaled labels
+                    const ClipPlan cp(crt_, paramv(spec.p, "hi").at(0),
+                                      RescaleMrsPlan(crt_, static_cast<int>(param1(layers[li - 1].p, "l")), true));
+                    DASH_CHECK(clip_hi_tab.shape.size() == 2 && clip_hi_tab.shape[0] == Nin,
+                               "joint clip: upper sign tables missing");
+                    Array tg(DType::u128, {Nin, sum_crt}), te(DType::u128, {Nin, static_cast<i64>(k), 3}),
+                        tc(DType::u128, {Nin, static_cast<i64>(k), 2});
+                    if (on_gpu) {
+                        sinkify(tg, "mm.g");
+                        sinkify(te, "mm.e");
+                        sinkify(tc, "cap");
+                        gpu->clip_joint(L, cp.hi, cur, &prefix, tg, te, tc);
+                    } else {
+                        DASH_CHECK(sig_host.N == Nin && shi_host.N == Nin, "joint clip: sign labels missing");
+                        CrtLabels nxt;
+                        for (int j = 0; j < k; ++j) nxt.emplace_back(crt_[j], Nin);
+                        parallel_for(Nin, [&](i64 b0, i64 b1) {
+                            std::vector<const comp_t*> x(k);
+                            std::vector<comp_t*> y(k);
+                            for (i64 e = b0; e < b1; ++e) {
+                                for (int j = 0; j < k; ++j) {
+                                    x[j] = cur[j].at(e);
+                                    y[j] = nxt[j].at(e);
+                                }
+                                clip_mult_garble(cp, R_, prg_, stream_id(L, 2, e), x.data(), sig_host.at(e),
+                                                 shi_host.at(e), tg.ptr<u128>() + e * cp.sum_crt,
+                                                 te.ptr<u128>() + e * k * 3, tc.ptr<u128>() + e * k * 2, y.data());
+                            }
+                        }, nt);
+                        cur = std::move(nxt);
+                        shi_host = Labels();
+                    }
+                    g.a["hi.mrs"] = clip_hi_tab;
+                    clip_hi_tab = Array();
+                    g.a["mm.g"] = tg;
+                    g.a["mm.e"] = te;
+                    g.a["cap"] = tc;
+                    g.p["smode"] = {2};
+                    g.p["t_hi"] = {cp.t_hi};
+                    break;
+                }
                 const ClipPlan cp(crt_, paramv(spec.p, "lo").at(0), paramv(spec.p, "hi").at(0));
                 // the sign construction follows the ReLU's: exact with relu_mrs / relu_joint, else approximate
                 const bool exact = opt.relu_mrs || opt.relu_joint;
@@ -1024,6 +1076,33 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                     const RescaleMrsPlan P(crt_, static_cast<int>(param1(spec.p, "l")), joint_out);
                     Array tab(DType::u128, {Nin, P.n_tab});
                     if (joint_out && !on_gpu) sig_host = Labels(2, Nin);
+                    if (clip_next) {
+                        // the Clip's upper sign s_hi = [x >= t_hi], on this layer's input labels with the Clip
+                        // layer's stream slot 3 (the tables come out as if garbled at the Clip)
+                        const ClipPlan cp(crt_, paramv(layers[li + 1].p, "hi").at(0), P);
+                        const SignMrsPlan sp(crt_);
+                        clip_hi_tab = Array(DType::u128, {Nin, std::max<i64>(sp.n_tab, 1)});
+                        if (on_gpu) {
+                            cur_layer = li + 1;
+                            sinkify(clip_hi_tab, "hi.mrs");
+                            cur_layer = li;
+                            gpu->clip_hi_sign(L + 1, sp, cp.t_hi, cur, clip_hi_tab);
+                        } else {
+                            shi_host = Labels(2, Nin);
+                            parallel_for(Nin, [&](i64 b0, i64 b1) {
+                                std::vector<const comp_t*> x(k), xp(k);
+                                std::vector<comp_t> xs(static_cast<size_t>(128) * k);
+                                for (int j = 0; j < k; ++j) xp[j] = xs.data() + static_cast<size_t>(128) * j;
+                                for (i64 e = b0; e < b1; ++e) {
+                                    for (int j = 0; j < k; ++j) x[j] = cur[j].at(e);
+                                    clip_shift_base(cp, R_, x.data(), cp.t_hi, xs.data());
+                                    sign_mrs_garble_elem(sp, R_, prg_, stream_id(L + 1, 3, e), xp.data(),
+                                                         clip_hi_tab.ptr<u128>() + e * clip_hi_tab.shape[1],
+                                                         shi_host.at(e), true);
+                                }
+                            }, nt);
+                        }
+                    }
                     if (on_gpu) {
                         sinkify(tab, "mrs");
                         gpu->rescale_mrs(L, P, cur, tab);

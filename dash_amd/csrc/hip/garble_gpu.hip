@@ -2936,6 +2936,11 @@ struct GpuGarbler::Impl {
     int sig_slot = -1;
     int64_t sig_N = 0;
     const int16_t* sig_S = nullptr;
+    // joint Clip: slot-sized copies of the two mod-2 base labels kept for clip_joint ([0] the rescale's sign
+    // label, [1] the upper sign garbled by clip_hi_sign); clip_pending: the next rescale_mrs keeps its label
+    DevBlock clip_sig[2];
+    int64_t clip_sig_N = 0;
+    bool clip_pending = false;
     // device copies of layer outputs that a later residual add or in_src layer reads (index = layer + 1)
     struct Saved {
         std::vector<DevBlock> L;
@@ -2980,6 +2985,8 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     : impl_(new Impl(device)) {
     concat_hook() = &GpuGarbler::concat_saved_dev;
     clip_hook() = &GpuGarbler::clip_dev;
+    clip_hi_hook() = &GpuGarbler::clip_hi_dev;
+    clip_joint_hook() = &GpuGarbler::clip_joint_dev;
     Impl& I = *impl_;
     I.enter();
     I.c.hard = hardened ? 1 : 0;
@@ -3638,31 +3645,38 @@ void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, 
 // or the approximate fused one (pa; st[side] = approx, cast2, sign). Scratch slots: the two sign labels, u, the
 // 2k half-gate labels, the k cap labels; the exact sign's own slots come first (both sides side by side), the
 // approximate sign runs in sign_core's scratch and leaves a copy of its label.
-void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
-                          CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,
-                          Array& cap) {
-    Impl& I = *self.impl_;
+// the device cur shifted by a public constant: cur_j += (q mod p_j) R_pj
+static void fold_cur(GpuGarbler::Impl& I, i64 q) {
+    const int64_t N = I.cur_N;
+    const int k = I.k;
+    gg::FoldArgs a{};
+    a.N = N;
+    a.group = N;
+    int ncmax = 1;
+    for (int j = 0; j < k; ++j) {
+        const int p = I.crt[j];
+        const int32_t cj = static_cast<int32_t>(pmod(q, p));
+        a.j[j] = gg::FoldJob{I.cur[j].as<int16_t>(), gg::dconst(&cj, 1), p, static_cast<int>(gg::chunks_of(nr_comps(p)))};
+        ncmax = std::max(ncmax, a.j[j].nc);
+    }
+    const int blocks = static_cast<int>(std::min<int64_t>((N * ncmax + 255) / 256, 4096));
+    hipLaunchKernelGGL(gg::k_fold, dim3(blocks, k), dim3(256), 0, gg::tl_st, I.c, a);
+}
+
+// kept (joint variant, lo = 0): the two sign labels were garbled earlier (clip_hi_dev, rescale_mrs) and are
+// copied into the sign slots; no sign gadget and no fold runs here.
+static void clip_core(GpuGarbler::Impl& I, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
+                      CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,
+                      Array& cap, const DevBlock* kept) {
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_("clip");
     const int64_t N = I.cur_N;
     const int k = I.k;
-    DASH_CHECK((pm != nullptr) != (pa != nullptr), "gpu garbler: clip needs exactly one sign plan");
+    DASH_CHECK(kept ? (!pm && !pa && lo == 0) : ((pm != nullptr) != (pa != nullptr)),
+               "gpu garbler: clip needs exactly one sign plan, or the kept labels of the joint variant");
     DASH_CHECK(!pm || pm->k() == k, "gpu garbler: mixed-radix sign plan mismatch");
-    auto fold = [&](i64 q) {  // cur_j += (q mod p_j) R_pj
-        gg::FoldArgs a{};
-        a.N = N;
-        a.group = N;
-        int ncmax = 1;
-        for (int j = 0; j < k; ++j) {
-            const int p = I.crt[j];
-            const int32_t cj = static_cast<int32_t>(pmod(q, p));
-            a.j[j] = gg::FoldJob{I.cur[j].as<int16_t>(), gg::dconst(&cj, 1), p, static_cast<int>(gg::chunks_of(nr_comps(p)))};
-            ncmax = std::max(ncmax, a.j[j].nc);
-        }
-        const int blocks = static_cast<int>(std::min<int64_t>((N * ncmax + 255) / 256, 4096));
-        hipLaunchKernelGGL(gg::k_fold, dim3(blocks, k), dim3(256), 0, gg::tl_st, I.c, a);
-    };
+    auto fold = [&](i64 q) { fold_cur(I, q); };
     const gg::In in = labels_in(I.cur, I.crt, N);
     std::vector<void*> tmp;
     int sig[2] = {0, 1};
@@ -3678,7 +3692,7 @@ void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* p
                                        *st[side][2], nullptr, nullptr, nullptr, omods);
             DASH_CHECK(omods.size() == 1 && omods[0] == 2, "gpu garbler: clip sign plan must output one mod-2 label");
         }
-    } else {
+    } else if (pm) {
         base = 2 * mrs_sign_desc(*pm, 0).end_slot;
     }
     const int u_slot = base, sk0 = u_slot + 1, cap0 = sk0 + 2 * k, nslots = cap0 + k;
@@ -3689,11 +3703,11 @@ void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* p
     g.N = N;
     g.nslots = nslots;
     DevTable tT[2], tG, tE, tC;
-    if (pa) {
+    if (pa || kept) {
         const size_t bytes = static_cast<size_t>(gg::chunks_of(nr_comps(2))) * gg::kCh * N * sizeof(int16_t);
         for (int side = 0; side < 2; ++side)
-            HIPCHECK(hipMemcpyAsync(gg::slot_base(g, sig[side]), sig_copy[side][0].p, bytes, hipMemcpyDeviceToDevice,
-                                    gg::tl_st));
+            HIPCHECK(hipMemcpyAsync(gg::slot_base(g, sig[side]), kept ? kept[side].p : sig_copy[side][0].p, bytes,
+                                    hipMemcpyDeviceToDevice, gg::tl_st));
     } else {
         for (int side = 0; side < 2; ++side) {
             fold(side ? hi - lo : lo);
@@ -3718,7 +3732,7 @@ void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* p
             project(I.c, gs, in, tb, D.pr, ProjFns{&D.flut, &D.fan});
         }
     }
-    fold(lo - hi);  // back to x0 + q_lo R: the wire x - q_lo
+    if (!kept) fold(lo - hi);  // back to x0 + q_lo R: the wire x - q_lo
     tG.alloc(I.device, N, mmg.shape[1], mmg);
     tE.alloc(I.device, N, static_cast<int64_t>(k) * 3, mme, true);
     tC.alloc(I.device, N, static_cast<int64_t>(k) * 2, cap);
@@ -3796,6 +3810,76 @@ void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* p
     tC.to_array(cap, I.device);
     I.cur = std::move(out);
     set_stale(cur, I.crt, N);
+}
+
+void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
+                          CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,
+                          Array& cap) {
+    clip_core(*self.impl_, layer, pm, pa, lo, hi, cur, st, prefix, mmg, mme, cap, nullptr);
+}
+
+// Joint Clip, first half (gpu_garbler.h clip_hi_sign): the exact sign of x - t_hi on the device cur, which the
+// rescale_mrs that follows still reads: + t_hi R, the mixed-radix sign's draw / derive / fan-out passes on the
+// Clip layer's stream 3, - t_hi R. The sign label leaves the garbling scratch (the rescale reuses it) for a
+// block of its own.
+void GpuGarbler::clip_hi_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan& pm, i64 t_hi, CrtLabels& cur,
+                             Array& tab) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("clip_hi");
+    const int64_t N = I.cur_N;
+    const int k = I.k;
+    DASH_CHECK(pm.k() == k, "gpu garbler: mixed-radix sign plan mismatch");
+    const MrsSignDesc D = mrs_sign_desc(pm, 0);
+    fold_cur(I, t_hi);
+    const gg::In in = labels_in(I.cur, I.crt, N);
+    DevTable tT;
+    tT.alloc(I.device, N, tab.shape[1], tab);
+    gg::Tables tb{};
+    tb.t[0] = tT.p(); tb.row[0] = tT.row;
+    gg::Gadget g{};
+    g.layer = layer;
+    g.sslot = 3;
+    g.mask = 0;
+    g.S = I.scratch(static_cast<size_t>(N) * D.end_slot * gg::kW * sizeof(int16_t));
+    g.PB = I.pbank(2, N);
+    g.N = N;
+    g.nslots = D.end_slot;
+    g.draws = gg::dconst(D.dr.data(), D.dr.size());
+    g.ndraws = static_cast<int>(D.dr.size());
+    g.projs = gg::dconst(D.pr.data(), D.pr.size());
+    g.nprojs = static_cast<int>(D.pr.size());
+    g.entries = D.entries;
+    g.nblk = draw_blocks(D.dr);
+    check_desc(g);
+    std::vector<void*> tmp;
+    hipLaunchKernelGGL(gg::draw_kernel(), dim3(draw_grid(g)), dim3(gg::kGB), 0, gg::tl_st, I.c, g);
+    hipLaunchKernelGGL(gg::k_mrs_sign_derive, dim3(blocks_for(N, 256), k), dim3(256), 0, gg::tl_st, I.c, g, in, D.a);
+    project(I.c, g, in, tb, D.pr, ProjFns{&D.flut, &D.fan});
+    const size_t bytes = static_cast<size_t>(gg::chunks_of(nr_comps(2))) * gg::kCh * N * sizeof(int16_t);
+    for (DevBlock& b : I.clip_sig) b.alloc(I.device, bytes);
+    HIPCHECK(hipMemcpyAsync(I.clip_sig[1].p, gg::slot_base(g, D.sig_slot), bytes, hipMemcpyDeviceToDevice, gg::tl_st));
+    fold_cur(I, -t_hi);
+    HIPCHECK(hipGetLastError());
+    gg::end_layer(tmp);
+    tr_.mark("kernels");
+    tT.to_array(tab, I.device);
+    I.clip_sig_N = N;
+    I.clip_pending = true;
+}
+
+// Joint Clip, second half: the kept labels into the sign slots, then clip_dev's multiply, cap and finish.
+void GpuGarbler::clip_joint_dev(GpuGarbler& self, uint64_t layer, i64 hi, CrtLabels& cur, const std::vector<i64>* prefix,
+                                Array& mmg, Array& mme, Array& cap) {
+    Impl& I = *self.impl_;
+    DASH_CHECK(I.clip_sig_N == I.cur_N && !I.clip_pending && I.clip_sig[0].p && I.clip_sig[1].p,
+               "gpu garbler: joint Clip without its kept sign labels");
+    clip_core(I, layer, nullptr, nullptr, 0, hi, cur, nullptr, prefix, mmg, mme, cap, I.clip_sig);
+    I.clip_sig_N = 0;
+    I.sig_slot = -1;
+    I.sig_N = 0;
+    I.sig_S = nullptr;
 }
 
 // Mixed-radix rescale: draw (digit-target labels, then the k final labels, in
@@ -3915,6 +3999,12 @@ void GpuGarbler::rescale_mrs(uint64_t layer, const RescaleMrsPlan& P, CrtLabels&
         I.sig_slot = a.key0;
         I.sig_N = N;
         I.sig_S = g.S;
+        if (I.clip_pending) {  // a joint Clip follows: its lower sign label, kept beside the upper one
+            const size_t bytes = static_cast<size_t>(gg::chunks_of(nr_comps(2))) * gg::kCh * N * sizeof(int16_t);
+            HIPCHECK(hipMemcpyAsync(I.clip_sig[0].p, gg::slot_base(g, a.key0), bytes, hipMemcpyDeviceToDevice,
+                                    gg::tl_st));
+            I.clip_pending = false;
+        }
     }
     HIPCHECK(hipGetLastError());
     gg::end_layer(tmp);

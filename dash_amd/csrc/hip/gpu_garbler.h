@@ -60,6 +60,33 @@ class GpuGarbler {
         clip_hook()(*this, layer, pm, pa, lo, hi, cur, st, prefix, mmg, mme, cap);
     }
 
+    // Joint Clip (gadgets.h ClipPlan, joint variant), two calls around the rescale_mrs of the layer before it.
+    // clip_hi_sign, before that rescale: the exact sign of x - t_hi on the device cur (the rescale's input; the
+    // shift folded in and out again), PRG stream and gate of the Clip layer's slot 3, tables -> tab; its mod-2
+    // base labels are kept on the device, and the rescale_mrs that follows keeps a copy of its own sign label
+    // beside them. clip_joint, at the Clip: u = the two kept labels' sum, the half gates, the cap rows keyed by
+    // the kept upper sign, and the output base labels; device cur -> next. Hooks as for clip.
+    using ClipHiFn = void (*)(GpuGarbler&, uint64_t, const SignMrsPlan&, i64, CrtLabels&, Array&);
+    using ClipJointFn = void (*)(GpuGarbler&, uint64_t, i64, CrtLabels&, const std::vector<i64>*, Array&, Array&,
+                                 Array&);
+    static ClipHiFn& clip_hi_hook() {
+        static ClipHiFn f = nullptr;
+        return f;
+    }
+    static ClipJointFn& clip_joint_hook() {
+        static ClipJointFn f = nullptr;
+        return f;
+    }
+    void clip_hi_sign(uint64_t layer, const SignMrsPlan& pm, i64 t_hi, CrtLabels& cur, Array& tab) {
+        DASH_CHECK(clip_hi_hook() != nullptr, "gpu garbler: clip is not linked in");
+        clip_hi_hook()(*this, layer, pm, t_hi, cur, tab);
+    }
+    void clip_joint(uint64_t layer, i64 hi, CrtLabels& cur, const std::vector<i64>* prefix, Array& mmg, Array& mme,
+                    Array& cap) {
+        DASH_CHECK(clip_joint_hook() != nullptr, "gpu garbler: clip is not linked in");
+        clip_joint_hook()(*this, layer, hi, cur, prefix, mmg, mme, cap);
+    }
+
     // ReLU whose sign labels the preceding rescale_mrs (P.sign_last) left on the device: mixed-modulus half
     // gates only; device cur -> next
     void relu_mult(uint64_t layer, CrtLabels& cur, const std::vector<i64>* prefix, Array& mmg, Array& mme);
@@ -108,6 +135,10 @@ class GpuGarbler {
     static void clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
                          CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,
                          Array& cap);
+    static void clip_hi_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan& pm, i64 t_hi, CrtLabels& cur,
+                            Array& tab);
+    static void clip_joint_dev(GpuGarbler& self, uint64_t layer, i64 hi, CrtLabels& cur, const std::vector<i64>* prefix,
+                               Array& mmg, Array& mme, Array& cap);
     std::unique_ptr<Impl> impl_;
 };
 

@@ -426,19 +426,17 @@ struct ClipLane {
     u128 G, E, C;
     uint32_t ypr;
 };
-__device__ __forceinline__ ClipLane clip_lane(const ClipArgs& a, int j, int b, int64_t e, int p, const ModC& m) {
+// The rows keyed by the two sign labels (everything of a lane but the garbler half gate G, which hangs on the
+// multiplied label's own key): shared by the clip multiply kernels and the fused rescale + clip output.
+__device__ __forceinline__ ClipLane clip_keyed(const ClipArgs& a, int j, int b, int64_t e, int p, const ModC& m) {
     const int k = a.crt.k;
     const int64_t N = a.N;
-    const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
     const int64_t be = static_cast<int64_t>(b) * N + e;
     // the gathers go out before the pads are computed
-    const u128 Hx = a.hx[bke];
-    const uint32_t colx = a.colx[bke];
     const u128 Khi = a.khi[be];
     const u128 U = a.klo[be] ^ Khi;
     const uint32_t cU = static_cast<uint32_t>(U) & 1u, cH = static_cast<uint32_t>(Khi) & 1u;
     const u128* E3 = a.etab + (be * k + j) * 3;
-    const u128 Graw = a.gtab[be * a.crt.sum + a.crt.prefix[j] + colx];
     const u128 Eraw = E3[cU];
     const u128 mini = E3[2];
     const u128 Craw = a.cap[(be * k + j) * 2 + cH];
@@ -451,10 +449,19 @@ __device__ __forceinline__ ClipLane clip_lane(const ClipArgs& a, int j, int b, i
     const u128 HM = pd[sM & 3] >> (16 * (j % 8));
     const u128 HC = hard_pad(Khi, mg, tw_sub(kTwCap, 0), j);
     ClipLane r;
-    r.G = Graw - Hx;
+    r.G = 0;
     r.E = Eraw - HS;
     r.C = Craw - HC;
     r.ypr = mini_mult(mini, cU, HM, p, m);
+    return r;
+}
+__device__ __forceinline__ ClipLane clip_lane(const ClipArgs& a, int j, int b, int64_t e, int p, const ModC& m) {
+    const int64_t bke = (static_cast<int64_t>(b) * a.crt.k + j) * a.N + e;
+    const u128 Hx = a.hx[bke];
+    const uint32_t colx = a.colx[bke];
+    const u128 Graw = a.gtab[(static_cast<int64_t>(b) * a.N + e) * a.crt.sum + a.crt.prefix[j] + colx];
+    ClipLane r = clip_keyed(a, j, b, e, p, m);
+    r.G = Graw - Hx;
     return r;
 }
 
@@ -1175,6 +1182,78 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignAr
     lds_store_rows<kRrtBS>(Y, stg, N, e0, 0, n);
 }
 
+// k_rescale_relu_out_t for a joint Clip (gadgets.h ClipPlan, joint variant): the same block, image and two
+// passes, with the clip multiply's rows instead of the ReLU's. The two sign labels come from the rescale chain
+// (mode 2, ca.klo) and the Clip's upper sign chain (mode 1, ca.khi), which both ran on the rescale's input; the
+// lane derives the pads of u and of s_hi (clip_keyed) while the rows are staged. Pass 2 adds the cap stream;
+// residue 0 is (G ^ E ^ C) ^ (ypr ? P : 0) on 128-bit registers. The rescaled label is never written.
+__global__ __launch_bounds__(kRrtBS) void k_rescale_clip_out_t(MrsArgs a, ClipArgs ca, Act x, Act y, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[kRrtCap * kRrtBS];
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int k = a.crt.k;
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int n = static_cast<int>(m.n);
+    const int tid = static_cast<int>(threadIdx.x);
+    const int64_t e0 = static_cast<int64_t>(blockIdx.x) * kRrtBS;
+    const int64_t e = min(e0 + tid, N - 1);  // spare lanes shadow a real element; the row stores skip them
+    const int64_t be = static_cast<int64_t>(b) * N + e;
+    const act_t* L = x.p[j] + static_cast<int64_t>(b) * n * N;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N;
+    // the per-element gathers first: in flight while the rows are staged
+    const u128 P = a.pf[(static_cast<int64_t>(b) * k + j) * N + e];
+    const u128* grow = ca.gtab + be * ca.crt.sum + ca.crt.prefix[j];
+    const uint64_t gate = ca.mgate0 ^ static_cast<uint64_t>(e);
+    uint8_t* col = stg + tid;
+    if (j == 0) {
+        const u128 Graw = grow[static_cast<uint32_t>(P) & 1u];
+        const ClipLane c = clip_keyed(ca, j, b, e, p, m);
+        const u128 G = Graw - hard_pad(P, gate, tw_sub(kTwMmg, 0), 0);  // compress(Y_0) = P
+        // (e + c + ypr y + 2 - g) mod 2 = e ^ c ^ g ^ (ypr & y)
+        const u128 R = (G ^ c.E ^ c.C) ^ ((c.ypr & 1u) ? P : static_cast<u128>(0));
+        for (int q0 = 0; q0 < n; q0 += kRrtCap) {
+            const int cnt = min(kRrtCap, n - q0);
+            if (q0) __syncthreads();  // the previous window's row stores have read the image
+            const u128 Rw = R >> q0;
+#pragma unroll
+            for (int w = 0; w < (kRrtCap + 31) / 32; ++w) {
+                const uint32_t rw = static_cast<uint32_t>(Rw >> (32 * w));
+#pragma unroll 8
+                for (int u = 0; u < 32; ++u) {
+                    const int cc = 32 * w + u;
+                    if (cc >= cnt) break;
+                    stg[cc * kRrtBS + tid] = static_cast<uint8_t>((rw >> u) & 1u);
+                }
+            }
+            __syncthreads();
+            lds_store_rows<kRrtBS>(Y, stg, N, e0, q0, cnt);
+        }
+        return;
+    }
+    const uint32_t inv = static_cast<uint32_t>(a.sinv[j]);
+    rrt_stage_rows(stg, L, N, e0, n);
+    __syncthreads();
+    // digit 0 of Y_j ahead of the walk: the garbler half gate's row gather overlaps the pads and pass 1
+    u128 Graw;
+    {
+        u128 t = P;
+        uint32_t r = divmod128(t, m);
+        const uint32_t pd0 = chunk_digit(r, m);
+        Graw = grow[modq(static_cast<uint32_t>(stg[tid]) * inv + pd0, m)];
+    }
+    const ClipLane c = clip_keyed(ca, j, b, e, p, m);
+    // pass 1: Y_j = S^-1 L_j + digits(P) in place, key = compress(Y_j) summed per chunk
+    ChunkKey ck;
+    ck.init(P);
+    ck.walk<kRrtBS>(col, n, inv, false, m);
+    const u128 G = Graw - hard_pad(ck.C, gate, tw_sub(kTwMmg, j), 0);
+    // pass 2: clip_j = E + C + ypr Y_j - G in place
+    lds_mult_chunks<kRrtBS, true>(col, n, G, c.E, c.C, c.ypr, p, m);
+    __syncthreads();
+    lds_store_rows<kRrtBS>(Y, stg, N, e0, 0, n);
+}
+
 // Quad form of the joint output (latency-bound launches: batch 1, small layers). Four lanes per (element,
 // residue): the label's base-q chunks are dealt over the quad (lane g takes chunks 4j + g, power-of-two moduli
 // a quarter of the digits each), every lane runs the payload's chunk divisions and keeps its own chunk, the
@@ -1331,6 +1410,34 @@ void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x,
     hipLaunchKernelGGL(k_rescale_relu_out, d.grid, d.block, kAesLds, st, a, sa, x, y, gtab, etab, mc, g.te0, g.rk);
 }
 
+// Joint Clip: whether the planner defers the rescale's outputs to launch_rescale_clip_out. The joint-fuse mode
+// forces it on (1) or off (0); in auto mode (-1) clip_fuse_pick decides: the launches that take the throughput
+// kernel (batches of at least 3 GCs, staged shapes) from 2048 elements per GC, the smallest layer measured. The
+// fused form won every alternation at N = 2048 .. 16384 and B = 3, 8, 24, 85 (profiles/ab/clip_joint/README.md:
+// 10 - 22 % of the pair); nothing smaller was measured, so nothing smaller fuses. This is the Clip's own
+// threshold, not kJointFuseMinElems.
+constexpr int64_t kClipFuseMinN = 2048;
+bool clip_fuse_pick(int64_t N, int B) { return B >= 3 && stage_ok(N, kRrtBS) && N >= kClipFuseMinN; }
+bool clip_fuse(int64_t N, int B) {
+    const int mode = joint_fuse_mode();
+    return mode >= 0 ? mode == 1 : clip_fuse_pick(N, B);
+}
+
+// The deferred outputs of a rescale with a joint Clip behind it: the throughput form (k_rescale_clip_out_t) for
+// batches of at least 3 GCs on staged shapes whose base fits its image; every other launch runs the rescale's
+// output-hash kernel and the clip multiply, as the planner does without the fusion.
+void launch_rescale_clip_out(const MrsArgs& a, const ClipArgs& ca, const Act& x, const Act& y, int B, const ModC* mc,
+                             const AesGlobals& g, hipStream_t st) {
+    if (B >= 3 && stage_ok(a.N, kRrtBS) && rrt_fits(a)) {
+        const dim3 gt(static_cast<unsigned>((a.N + kRrtBS - 1) / kRrtBS), a.crt.k, B);
+        if (launch_log_on()) launch_log_add("clip_out.tput", gt, dim3(kRrtBS));
+        hipLaunchKernelGGL(k_rescale_clip_out_t, gt, dim3(kRrtBS), 0, st, a, ca, x, y, mc);
+        return;
+    }
+    launch_rescale_mrs_out(a, x, B, mc, g, st);
+    launch_clip_mult(ca, x, y, B, mc, st);
+}
+
 // hx[b][j][e] = H(compress(x_j)), colx = color: the ReLU multiply's garbler half gates (exact-sign path;
 // the approximate path gets them from k_sign_approx). grid (x, k, B)
 __global__ __launch_bounds__(kAesBlock, kAesMinBlocks) void k_label_hash(Act x, CrtInfo crt, int64_t N, u128* hx,
@@ -1416,6 +1523,13 @@ void launch_rescale_mrs(const MrsArgs& a, const Act& x, int B, const ModC* mc, c
                         bool chain_only) {
     dispatch_mrs_chain(a, x, B, mc, g, st);
     if (chain_only) return;  // the joint ReLU's k_rescale_relu_out writes the outputs
+    launch_rescale_mrs_out(a, x, B, mc, g, st);
+}
+
+// The output kernels of a mixed-radix rescale whose chain has run (a.pf): split from the chain for a joint Clip,
+// whose upper sign chain reads the rescale's input labels between the two.
+void launch_rescale_mrs_out(const MrsArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g,
+                            hipStream_t st) {
     if (a.mode == 2 && stage_ok(a.N, kOhBS)) {
         const dim3 gs = grid_aes(a.N, kOhBS, a.crt.k, B);
         if (launch_log_on()) launch_log_add("out_hash.staged", gs, dim3(kOhBS));

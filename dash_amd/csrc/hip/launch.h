@@ -36,6 +36,10 @@ int joint_fuse_mode();
 void set_joint_fuse(int mode);
 bool joint_fuse_pick(int64_t N, int B);
 bool joint_fuse(int64_t N, int B);  // the mode applied to the rule
+// The same for a joint Clip behind the rescale (launch_rescale_clip_out): the mode forces it, the auto rule
+// clip_fuse_pick is the Clip's own (not joint_fuse_pick's threshold).
+bool clip_fuse_pick(int64_t N, int B);
+bool clip_fuse(int64_t N, int B);
 // Launch log: off by default (one relaxed load per host-side launch, nothing under graph replay, where no picker
 // runs). When on, every picker appends the form it launched as "<form> grid=(x,y,z) block=n".
 extern std::atomic<bool> g_launch_log_on;
@@ -66,11 +70,15 @@ void launch_rescale_update_approx(const RescaleArgs& r, const SignArgs& a, const
                                   const u128* zh, int B, const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_rescale_mrs(const MrsArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g, hipStream_t st,
                         bool chain_only = false);
+void launch_rescale_mrs_out(const MrsArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g,
+                            hipStream_t st);
 // mixed-radix chain of K residues (mrs_chain.h; instantiated per K in kernels_mrs_*.hip)
 template <int K>
 void launch_mrs_chain_k(const MrsArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x, const Act& y, const u128* gtab,
                              const u128* etab, int B, const ModC* mc, const AesGlobals& g, hipStream_t st);
+void launch_rescale_clip_out(const MrsArgs& a, const ClipArgs& ca, const Act& x, const Act& y, int B, const ModC* mc,
+                             const AesGlobals& g, hipStream_t st);
 void launch_relu_joint(const SignArgs& sa, const Act& x, const Act& y, const u128* gtab, const u128* etab, int B,
                        const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_relu_mrs(const MrsArgs& a, const SignArgs& sa, const Act& x, const Act& y, const u128* gtab,

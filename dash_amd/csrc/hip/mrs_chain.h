@@ -59,10 +59,11 @@ __device__ __forceinline__ void store_ypads(const MrsArgs& a, u128 key, int b, i
 }
 
 // A Clip's two sign chains (MODE 1 with a.ks set, a.ny = 0) keep the sign label itself: the clip multiply keys
-// its rows with the sum of the two labels (gadgets.h ClipPlan), whose pads only it can form
+// its rows with the sum of the two labels (gadgets.h ClipPlan), whose pads only it can form. A joint Clip's
+// lower sign is the rescale's (MODE 2 with a.ks set, a.ny = 0).
 template <int MODE>
 __device__ __forceinline__ void store_sign_key(const MrsArgs& a, u128 key, int b, int64_t N, int64_t e) {
-    if (MODE == 1 && a.ks) a.ks[static_cast<int64_t>(b) * N + e] = key;
+    if (MODE >= 1 && a.ks) a.ks[static_cast<int64_t>(b) * N + e] = key;
 }
 
 // MODE 1 (exact sign, gadgets.h SignMrsPlan): positions convert residues

@@ -702,6 +702,9 @@ class HipEvaluator {
     // planner: a sign-producing rescale whose outputs the next (joint) ReLU's op writes
     bool joint_pending_ = false;
     MrsArgs joint_a_{};
+    // the same for a joint Clip (launch_rescale_clip_out)
+    bool clip_pending_ = false;
+    MrsArgs clip_a_{};
     const u128* zc_ = nullptr;
     const u128* zh_ = nullptr;
     const uint16_t* zcol_ = nullptr;
@@ -1151,6 +1154,25 @@ void HipEvaluator::build() {
                 const int B = B_;
                 u128* hx = hx_;
                 uint16_t* colx = colx_;
+                if (g.param("smode", 0) == 2) {
+                    // joint variant: the rescale before it left both sign labels (ks_) and the half-gate keys of
+                    // its output (hx_ / colx_); only the multiply + cap is left
+                    DASH_CHECK(li > 0 && m0.layers[li - 1].kind == K_RESCALE &&
+                                   m0.layers[li - 1].param("sign_out", 0) == 1 && !g.p.count("in_src") &&
+                                   g.vec("lo").at(0) == 0,
+                               "joint Clip must follow a sign-producing rescale");
+                    if (clip_pending_) {
+                        const MrsArgs ma = clip_a_;
+                        clip_pending_ = false;
+                        add_op(lname + ".C", [ma, ca, x, y, B, mc, ag](hipStream_t st) {
+                            launch_rescale_clip_out(ma, ca, x, y, B, mc, ag, st);
+                        });
+                    } else {
+                        add_op(lname + ".C", [ca, x, y, B, mc](hipStream_t st) { launch_clip_mult(ca, x, y, B, mc, st); });
+                    }
+                    cur = nxt;
+                    break;
+                }
                 const bool exact = g.param("smode", 0) == 1;
                 // the half gates' keys of x: the approximate sign's first phase compresses x anyway and writes them
                 // (lower bound's run, below); the mixed-radix chain does not, so they get a pass of their own
@@ -1261,6 +1283,63 @@ void HipEvaluator::build() {
                     // shapes from 13,824 elements over the batch, where the throughput form wins on every MiniONN
                     // layer (24-GC step 9.08 -> 7.55 ms, profiles/ab/joint_fused/README.md); hip_set_joint_fuse
                     // (initially DASH_JOINT_FUSE=0/1) forces it off/on.
+                    // A joint Clip next (gadgets.h ClipPlan, joint variant): the chain keeps its mod-2 key as the
+                    // Clip's lower sign label (ks_[0], no y-row pads), the Clip's upper sign chain (mode 1, the
+                    // Clip layer's tables and slot-3 gate) runs on the same input labels into ks_[1], and only
+                    // then the output kernel rewrites x in place, leaving y's half-gate keys under the Clip's
+                    // multiply gate in hx_ / colx_. Both chains share mrs_ps_; the mode-1 chain writes neither
+                    // a.pf nor outP_, so the rescale's final payloads wait there.
+                    const bool clip_next = so && li + 1 < m0.layers.size() && m0.layers[li + 1].kind == K_CLIP &&
+                                           m0.layers[li + 1].param("smode", 0) == 2;
+                    if (clip_next) {
+                        const GLayer& gc = m0.layers[li + 1];
+                        DASH_CHECK(!gc.p.count("in_src"), "joint Clip must read the rescale before it");
+                        for (int side = 0; side < 2; ++side)
+                            if (!ks_[side]) ks_[side] = dalloc<u128>(static_cast<size_t>(B_) * maxSignN_);
+                        a.ks = ks_[0];
+                        a.ny = 0;
+                        const SignMrsPlan SP(crt_);
+                        MrsArgs h{};
+                        h.crt = crt;
+                        h.N = N;
+                        h.n_tab = gc.arr("hi.mrs").shape[1];
+                        DASH_CHECK(gc.arr("hi.mrs").shape[0] == N && h.n_tab == std::max<i64>(SP.n_tab, 1),
+                                   "joint Clip upper sign table shape");
+                        h.tab = upload_tables(li + 1, "hi.mrs");
+                        for (int i = 0; i + 1 < k_; ++i) h.dig_off[i] = SP.dig_off[i];
+                        h.ps = mrs_ps_;
+                        h.mode = 1;
+                        h.hs = hs_;
+                        h.cs = cs_;
+                        h.gate0 = gate_base(li + 2, 3);
+                        h.rgate0 = a.rgate0;
+                        h.ny = 0;
+                        h.ys = ys_;
+                        h.ks = ks_[1];
+                        add_op(lname + ".mrs", [a, x, B, mc, ag](hipStream_t st) {
+                            launch_rescale_mrs(a, x, B, mc, ag, st, true);
+                        });
+                        // streamed tables: the Clip layer's window was issued by this layer's stage op
+                        if (stream_)
+                            add_op(lname + ".wait", [this, li](hipStream_t st) {
+                                HIPCHECK(hipStreamWaitEvent(st, ready_[li + 1], 0));
+                            });
+                        add_op(lname + ".clip_hi", [h, x, B, mc, ag](hipStream_t st) {
+                            launch_clip_sign_mrs(h, x, B, mc, ag, st);
+                        });
+                        // output not kept for a later layer and the fusion on (launch.h clip_fuse): the Clip's op
+                        // writes both outputs in one pass (launch_rescale_clip_out), the rescaled label stays
+                        // in LDS
+                        if (dev::clip_fuse(N, B_) && !keep[li + 1]) {
+                            clip_a_ = a;
+                            clip_pending_ = true;
+                        } else {
+                            add_op(lname + ".out", [a, x, B, mc, ag](hipStream_t st) {
+                                launch_rescale_mrs_out(a, x, B, mc, ag, st);
+                            });
+                        }
+                        break;
+                    }
                     const bool fuse = dev::joint_fuse(N, B_);
                     const bool defer = fuse && so && li + 1 < m0.layers.size() && m0.layers[li + 1].kind == K_RELU &&
                                        m0.layers[li + 1].param("smode", 0) == 2 && !keep[li + 1] &&
@@ -1962,6 +2041,10 @@ void register_hip_bindings(py::module_& m) {
         return dev::joint_fuse_pick(N, B);
     }, py::arg("N"), py::arg("B"));
     m.def("hip_joint_fuse_min_elems", []() { return dev::joint_fuse_min_elems(); });
+    m.def("hip_clip_fuse_pick", [](int64_t N, int B) {
+        DASH_CHECK(N >= 1 && B >= 1, "hip_clip_fuse_pick: N and B must be positive");
+        return dev::clip_fuse_pick(N, B);
+    });
     m.def("hip_launch_log", [](bool on) { dev::launch_log_enable(on); }, py::arg("on"));
     m.def("hip_launch_log_take", []() { return dev::launch_log_take(); });
     // The conv kernel plan of a dense-conv layer, exactly as the evaluator (mfma: its switch) and the GPU garbler

@@ -140,6 +140,10 @@ struct GarbleOptions {
     // A ReLU right after a mixed-radix rescale takes its sign from that rescale's conversion
     // (gadgets.h RescaleMrsPlan::sign_last); other ReLUs use relu_mrs / the approximate gadget.
     bool relu_joint = false;
+    // A Clip(0, q_hi) right after a mixed-radix rescale takes its lower sign from that rescale's conversion and
+    // its upper sign from one exact sign of the rescale's input (gadgets.h ClipPlan, joint variant); other
+    // Clips keep the two-sign construction. Hardened encoding only.
+    bool clip_joint = false;
     bool hardened = false;  // ModelHeader::hardened
     std::shared_ptr<TableSink> sink;  // GPU-garbled tables go straight to these buffers (device >= 0 only)
     GarbleSpecs* cache = nullptr;     // reduced-weight cache of the specs being garbled (optional)

@@ -79,6 +79,34 @@ def resolve_constructions(circuit: Circuit, crt_base: Sequence[int], rescale: st
     return rescale, relu
 
 
+def joint_clip_layers(circuit: Circuit, crt_base: Sequence[int]) -> dict:
+    """{layer index: t_hi} of the Clips that meet the joint construction's structural conditions (gadgets.h
+    ClipPlan, joint variant): quantized q_lo == 0, directly behind a DASH Rescale(l), no in_src. t_hi is the
+    upper sign's threshold on that rescale's input, the smallest x it maps to q_hi (from the native plan)."""
+    out = {}
+    if not mrs_capable(crt_base):
+        return out
+    dash = circuit._dash_rescales()
+    for i, l in enumerate(circuit.layers):
+        if (getattr(l, "kind", -1) == _CLIP and i > 0 and l.q_lo == 0 and getattr(l, "in_src", None) is None
+                and any(circuit.layers[i - 1] is r for r in dash)):
+            out[i] = int(native().clip_joint_threshold([int(p) for p in crt_base], int(circuit.layers[i - 1].l),
+                                                       int(l.q_hi)))
+    return out
+
+
+def joint_clip_violations(circuit: Circuit, crt_modulus: int, joint: dict) -> list:
+    """Joint Clips whose rescale's tracked input goes below -M/2 + t_hi, where x - t_hi is no signed CRT value:
+    (clip layer index, tracked min, bound). Empty for rescales evaluated without range tracking."""
+    bad = []
+    for i, t_hi in sorted(joint.items()):
+        r = circuit.layers[i - 1]
+        lim = -(int(crt_modulus) // 2) + t_hi
+        if r.input_tracked and r.in_min_q < lim:
+            bad.append((i, int(r.in_min_q), int(lim)))
+    return bad
+
+
 def hardened_supported(circuit: Circuit, fused_sign: bool, rescale: str) -> bool:
     """The hardened encoding keys no projection with a public label: the reference sign construction's zero
     carry and the legacy rescale's zero residue 0 (fed to a sign gadget) do, so it needs the fused sign and,
@@ -90,7 +118,8 @@ class GarbledCircuit:
     def __init__(self, circuit: Circuit, crt: Union[int, Sequence[int]], mrs: Union[None, float, Sequence[int]] = None,
                  max_modulus: int = 0, seed: Optional[bytes] = None, garble_me: bool = True, nthreads: int = 0,
                  device: Optional[int] = None, fused_sign: bool = True, rescale: str = "auto",
-                 relu: str = "auto", sink=None, hardened: Optional[bool] = None, range_guard: str = "auto"):
+                 relu: str = "auto", sink=None, hardened: Optional[bool] = None, range_guard: str = "auto",
+                 clip: Optional[str] = None):
         """fused_sign: sign-gadget construction. True (default): the MRS casts are folded into the approx and
         carry projections (same function, 3.7x fewer gates per sign; gadgets.h SignPlan::fused). False: the
         reference construction with explicit identity casts (sign_gadget.h:456-546).
@@ -121,6 +150,16 @@ class GarbledCircuit:
         Z_p / bias labels and its shared-hash leaks (mixed half gate mini tables, repeated MRS digit moduli).
         Needs the fused sign and no legacy rescale. False: the reference's wire-compatible encoding. None
         (default): hardened whenever the resolved constructions allow it.
+
+        clip: construction of a Clip(0, q_hi) (ReLU6) directly behind a mixed-radix Rescale(l) without in_src.
+        "separate": two exact or approximate signs of the Clip's own input (docs/CLIP.md). "joint": the lower
+        sign is the rescale's own conversion digit (as for a joint ReLU) and the upper sign one exact sign of the
+        rescale's input against the public threshold t_hi (gadgets.h ClipPlan, joint variant): n_sign + P + 5k
+        table entries instead of 2 n_sign + P + 5k, and the rescale's input must stay at or above -M/2 + t_hi.
+        Needs rescale="mrs" and the hardened encoding, else ValueError, as for a tracked rescale input below the
+        bound. Clips that do not meet the structural conditions keep the separate construction. None (default):
+        "separate", or the DASH_CLIP=joint|separate environment value (an A/B knob that never raises: "joint
+        where the resolved constructions allow").
 
         range_guard: the garbler's exact per-input range check (garbling/guard.py): "auto" (default) = on when
         the GC has the mixed-radix rescale (an input in its wrap band would decode to a valid but wrong label),
@@ -172,6 +211,32 @@ class GarbledCircuit:
             raise ValueError("the mixed-radix constructions (rescale='mrs', relu='mrs' / 'joint') use the hardened "
                              "encoding only (fused sign; hardened=None or True)")
         self.hardened = bool(hardened)
+        explicit = clip is not None
+        if clip is None:
+            clip = os.environ.get("DASH_CLIP") if os.environ.get("DASH_CLIP") in ("joint", "separate") else "separate"
+        if clip not in ("separate", "joint"):
+            raise ValueError(f"clip construction must be 'separate' or 'joint', got {clip!r}")
+        # {layer: t_hi} of the Clips garbled with the joint construction
+        self.joint_clips: dict = {}
+        if clip == "joint":
+            cand = joint_clip_layers(circuit, self.crt_base)
+            why = None
+            if self.rescale != "mrs":
+                why = "needs the mixed-radix rescale (rescale='mrs', resolved: %r)" % self.rescale
+            elif not self.hardened:
+                why = "exists in the hardened encoding only"
+            else:
+                bad = joint_clip_violations(circuit, self.crt_modulus, cand)
+                if bad:
+                    i, mn, lim = bad[0]
+                    why = ("layer %d's tracked input reaches %d < %d = -M/2 + t_hi, where the upper sign's input "
+                           "x - t_hi is no signed CRT value; use clip='separate' or a larger CRT base" % (i - 1, mn, lim))
+            if why is None:
+                self.joint_clips = cand
+            elif explicit and clips:  # a circuit without a Clip has nothing to refuse
+                raise ValueError("clip='joint': layer %d (clip): the joint construction %s" % (
+                    min(cand) if cand else clips[0], why))
+        self.clip = "joint" if self.joint_clips else "separate"
         if range_guard == "auto" and os.environ.get("DASH_RANGE_GUARD") in ("on", "off"):
             range_guard = os.environ["DASH_RANGE_GUARD"]  # A/B knob (bench records say which was used)
         if range_guard not in ("auto", "on", "off"):
@@ -195,7 +260,7 @@ class GarbledCircuit:
         self.model = self.garbler.garble(specs, list(self.circuit.input_dims), self.nthreads, self.device,
                                          self.fused_sign, self.rescale == "mrs", self.relu == "mrs",
                                          self.relu == "joint", self.sink if self.device >= 0 else None,
-                                         self.hardened)
+                                         self.hardened, bool(self.joint_clips))
         self.sink = None  # single use: the slot now holds this GC
         self.garbling_time_s = time.perf_counter() - t
         self.decoder = self.garbler.decoder()
@@ -208,7 +273,7 @@ class GarbledCircuit:
         from .guard import guard_for
 
         return guard_for(self.circuit, self.crt_modulus, self.rescale == "mrs",
-                         self.device if self.device >= 0 else None)
+                         self.device if self.device >= 0 else None, self.joint_clips)
 
     def check_inputs(self, xs) -> None:
         """Raise RangeGuardError if a garbled evaluation of any of xs would leave an exact gadget range."""
@@ -297,8 +362,13 @@ class GarbledCircuit:
             relu = f"joint({len(joint)})+{other}({len(relus) - len(joint)})"
         else:
             relu = other
-        return dict(sign="fused" if self.fused_sign else "reference", rescale=rescale, relu=relu,
-                    encoding="hardened" if self.hardened else "reference")
+        out = dict(sign="fused" if self.fused_sign else "reference", rescale=rescale, relu=relu,
+                   encoding="hardened" if self.hardened else "reference")
+        nclip = sum(1 for k, _ in specs if k == Kind.CLIP)
+        nj = len(self.joint_clips)
+        if nj:  # only when a Clip is joint: every other record keeps its keys
+            out["clip"] = "joint" if nj == nclip else f"joint({nj})+separate({nclip - nj})"
+        return out
 
     @property
     def table_bytes(self) -> int:

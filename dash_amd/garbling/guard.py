@@ -54,8 +54,13 @@ class RangeGuard:
 
     CHUNK = 16  # inputs per GPU pass (im2col working set ~60 MB on the MiniONN CNN)
 
-    def __init__(self, circuit, crt_modulus: int, mrs: bool = True, device: Optional[int] = None):
+    def __init__(self, circuit, crt_modulus: int, mrs: bool = True, device: Optional[int] = None,
+                 joint_clips: Optional[dict] = None):
+        """joint_clips: {layer index: t_hi} of the Clips garbled with the joint construction (gadgets.h ClipPlan):
+        their upper sign reads the input x of the rescale before them, so that rescale needs x >= -M/2 + t_hi,
+        and the Clip's own input only has to be a signed CRT value."""
         self.circuit, self.M, self.mrs = circuit, int(crt_modulus), bool(mrs)
+        self.joint_clips = {int(i): int(t) for i, t in (joint_clips or {}).items()}
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.Projection, L.BaseExtension))
@@ -73,13 +78,19 @@ class RangeGuard:
         """(lo, hi_exclusive) the layer's input must satisfy, or None (linear / free layers)."""
         h = _half(self.M)
         lo, hi = -h, self.M - h
+        idx = next((i for i, l in enumerate(self.circuit.layers) if l is layer), -1) if self.joint_clips else -1
         if isinstance(layer, L.Rescale):
             if self.mrs and layer.use_sign_base_extension and layer.l >= 1:
                 hi = min(hi, layer.mrs_limit(self.M))
+            if idx + 1 in self.joint_clips:  # the joint Clip's upper sign input x - t_hi is a signed CRT value
+                lo = lo + self.joint_clips[idx + 1]
             return lo, hi
         if isinstance(layer, (L.Relu, L.Sign, L.MaxPool2d, L.Max)):
             return lo, hi
-        if isinstance(layer, L.Clip):  # both sign inputs x - q_lo and x - q_hi are signed CRT values
+        if isinstance(layer, L.Clip):
+            if idx in self.joint_clips:  # its signs were taken at the rescale before it
+                return lo, hi
+            # both sign inputs x - q_lo and x - q_hi are signed CRT values
             return lo + layer.q_hi, hi + layer.q_lo
         return None
 
@@ -441,11 +452,12 @@ def _i32(a) -> np.ndarray:
     return a.astype(np.int32)
 
 
-def guard_for(circuit, crt_modulus: int, mrs: bool, device: Optional[int] = None) -> RangeGuard:
+def guard_for(circuit, crt_modulus: int, mrs: bool, device: Optional[int] = None,
+              joint_clips: Optional[dict] = None) -> RangeGuard:
     """The circuit's cached guard (weights staged once per device)."""
     cache = circuit.__dict__.setdefault("_range_guards", {})
-    key = (int(crt_modulus), bool(mrs), device)
+    key = (int(crt_modulus), bool(mrs), device, tuple(sorted((joint_clips or {}).items())))
     g = cache.get(key)
     if g is None:
-        g = cache[key] = RangeGuard(circuit, crt_modulus, mrs, device)
+        g = cache[key] = RangeGuard(circuit, crt_modulus, mrs, device, joint_clips)
     return g

@@ -197,7 +197,7 @@ class InferenceService:
                  fault_hook: Optional[Callable[[int, int], bool]] = None, nthreads: int = 0,
                  rescale: str = "auto", relu: str = "auto", fused_sign: bool = True,
                  insecure_fixed_seed: bool = False, garble_workers: Optional[int] = None,
-                 input_encoding: Optional[str] = None, hardened: Optional[bool] = None):
+                 input_encoding: Optional[str] = None, hardened: Optional[bool] = None, clip: Optional[str] = None):
         if backend not in ("hip", "cpu"):
             raise ValueError("backend must be 'hip' or 'cpu'")
         if seed is not None and not insecure_fixed_seed:
@@ -232,6 +232,8 @@ class InferenceService:
                                  "reference encoding, whose constant labels reveal R_p (docs/SECURITY.md §1.1); pass "
                                  "hardened=False to serve it anyway" % (fused_sign, r))
         self.gc_kw = dict(rescale=rescale, relu=relu, fused_sign=fused_sign, hardened=hardened)
+        if clip is not None:  # GarbledCircuit(clip=...): the Clip construction behind a mixed-radix rescale
+            self.gc_kw["clip"] = clip
         self._seed = seed if seed is not None else os.urandom(16)
         self._ctr = 0
         self.stats = ServiceStats()
