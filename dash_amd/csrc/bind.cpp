@@ -215,6 +215,15 @@ PYBIND11_MODULE(_dash_native, m) {
     m.def("clip_joint_threshold", [](const std::vector<int>& crt, int l, i64 q_hi) {
         return ClipPlan(crt, q_hi, RescaleMrsPlan(crt, l, true)).t_hi;
     });
+    // ArgMax (gadgets.h ArgMaxPlan): table entries per output position over K candidates, and per pair
+    // operation of every level
+    m.def("argmax_entries", [](const std::vector<int>& crt, i64 K) { return ArgMaxPlan::entries(crt, K); });
+    m.def("argmax_op_entries", [](const std::vector<int>& crt, i64 K) {
+        const ArgMaxPlan P(crt, K);
+        std::vector<std::pair<i64, i64>> out;  // (operations, entries each) per level
+        for (int lv = 0; lv < P.levels(); ++lv) out.emplace_back(P.ops[lv], P.op_entries(lv));
+        return out;
+    });
 
     // Single gates of the native garbler with caller-chosen labels (wire-compatibility vectors: the tests
     // rebuild the reference's formulas in a pure-Python oracle and compare table bytes). Tables come back as

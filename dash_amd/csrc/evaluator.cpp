@@ -548,6 +548,63 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 cur = std::move(nxt);
                 break;
             }
+            case K_ARGMAX: {
+                // gadgets.h ArgMaxPlan (the garbler's element order)
+                DASH_CHECK(hard, "argmax: the ArgMax layer exists in the hardened encoding only");
+                const i64 K = g.param("K"), P = g.param("P");
+                DASH_CHECK(K >= 2 && K * P == Nin, "argmax input size mismatch");
+                const ArgMaxPlan ap(crt, K);
+                const i64 nsig = std::max<i64>(ap.sign.n_tab, 1);
+                CrtLabels vals = std::move(cur), idxl;
+                for (int lv = 0; lv < ap.levels(); ++lv) {
+                    const i64 ops = ap.ops[lv], cnt = ap.cnt[lv], cnt1 = ap.cnt[lv + 1], Nops = ops * P;
+                    const bool root = ap.root(lv);
+                    const std::string pre = arr_name("lv", lv, ".");
+                    const u128* mrs = g.arr(pre + "mrs").ptr<u128>();
+                    const u128* tg = root ? nullptr : g.arr(pre + "mm.g").ptr<u128>();
+                    const u128* te = root ? nullptr : g.arr(pre + "mm.e").ptr<u128>();
+                    const u128* ti = lv == 0 ? g.arr(pre + "idx").ptr<u128>() : nullptr;
+                    const u128* tig = lv == 0 ? nullptr : g.arr(pre + "im.g").ptr<u128>();
+                    const u128* tie = lv == 0 ? nullptr : g.arr(pre + "im.e").ptr<u128>();
+                    CrtLabels nv, ni;
+                    for (int j = 0; j < k; ++j) {
+                        if (!root) nv.emplace_back(crt[j], cnt1 * P);
+                        ni.emplace_back(crt[j], cnt1 * P);
+                    }
+                    const std::vector<i64>& pub = ap.pub[lv];
+                    parallel_for(Nops, [&](i64 b0, i64 b1) {
+                        std::vector<const comp_t*> va(k), vb(k), ia(k, nullptr), ib(k, nullptr);
+                        std::vector<comp_t*> vo(k), io(k);
+                        for (i64 e = b0; e < b1; ++e) {
+                            const i64 q = e / P, o = e % P, sa = 2 * q * P + o, sb = sa + P;
+                            for (int j = 0; j < k; ++j) {
+                                va[j] = vals[j].at(sa);
+                                vb[j] = vals[j].at(sb);
+                                if (pub[2 * q] < 0) ia[j] = idxl[j].at(sa);
+                                if (pub[2 * q + 1] < 0) ib[j] = idxl[j].at(sb);
+                                if (!root) vo[j] = nv[j].at(e);
+                                io[j] = ni[j].at(e);
+                            }
+                            argmax_pair_eval(ap, lv, stream_id(L, 20 + 3 * lv, e), stream_id(L, 21 + 3 * lv, e),
+                                             stream_id(L, 22 + 3 * lv, e), va.data(), vb.data(), ia.data(), ib.data(),
+                                             pub[2 * q + 1] >= 0, mrs + e * nsig, root ? nullptr : tg + e * ap.sum_crt,
+                                             root ? nullptr : te + e * k * 3, lv == 0 ? ti + e * k * 2 : nullptr,
+                                             lv == 0 ? nullptr : tig + e * ap.sum_crt, lv == 0 ? nullptr : tie + e * k * 3,
+                                             root ? nullptr : vo.data(), io.data());
+                        }
+                    }, nt);
+                    if (cnt % 2)
+                        for (int j = 0; j < k; ++j) {
+                            const size_t row = sizeof(comp_t) * vals[j].n * P;
+                            std::memcpy(nv[j].at(ops * P), vals[j].at((cnt - 1) * P), row);
+                            if (pub[cnt - 1] < 0) std::memcpy(ni[j].at(ops * P), idxl[j].at((cnt - 1) * P), row);
+                        }
+                    vals = std::move(nv);
+                    idxl = std::move(ni);
+                }
+                cur = std::move(idxl);
+                break;
+            }
             case K_SUMPOOL: {
                 PoolGeom G(g.p);
                 CrtLabels nxt;

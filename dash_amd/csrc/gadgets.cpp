@@ -903,4 +903,119 @@ void clip_mult_eval(const ClipPlan& P, const comp_t* const* x, const comp_t* slo
     }
 }
 
+// ---------------------------------------------------------------------------
+// ArgMax (gadgets.h ArgMaxPlan)
+ArgMaxPlan::ArgMaxPlan(const std::vector<int>& crt_, i64 K_) : crt(crt_), K(K_), sign(crt_) {
+    DASH_CHECK(K >= 2, "argmax needs at least 2 candidates");
+    DASH_CHECK(k() <= 16, "argmax: at most 16 residues");
+    for (int p : crt) {
+        prefix.push_back(sum_crt);
+        sum_crt += p;
+    }
+    int c = static_cast<int>(K);
+    cnt.push_back(c);
+    pub.emplace_back(c);
+    for (int s = 0; s < c; ++s) pub[0][s] = s;
+    while (c > 1) {
+        const int o = c / 2, c1 = o + (c % 2);
+        std::vector<i64> nx(c1, -1);
+        if (c % 2) nx[o] = pub.back()[c - 1];  // the carried slot keeps what it was
+        ops.push_back(o);
+        cnt.push_back(c1);
+        pub.push_back(std::move(nx));
+        c = c1;
+    }
+}
+
+void argmax_pair_garble(const ArgMaxPlan& P, int lv, const LabelBank& R, const Prg& prg, u64 s_stream, u64 v_stream,
+                        u64 i_stream, const comp_t* const* va0, const comp_t* const* vb0, const comp_t* const* ia0,
+                        i64 ia_pub, const comp_t* const* ib0, i64 ib_pub, u128* mrs, u128* g, u128* e, u128* idx,
+                        u128* ig, u128* ie, comp_t* const* vout0, comp_t* const* iout0) {
+    const int k = P.k();
+    const ModInfo& m2 = mod_info(2);
+    comp_t d0[16 * 128], s0[128], e0[128], c0[128];
+    const comp_t* dp[16];
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        comp_t* d = d0 + static_cast<size_t>(128) * j;
+        std::memcpy(d, va0[j], sizeof(comp_t) * mp.n);
+        lab_sub(d, vb0[j], mp.n, mp.p);
+        dp[j] = d;
+    }
+    sign_mrs_garble_elem(P.sign, R, prg, s_stream, dp, mrs, s0, true);
+    if (vout0) {
+        u64 ctr = 0;
+        for (int j = 0; j < k; ++j) {
+            const ModInfo& mp = mod_info(P.crt[j]);
+            mixed_mult_garble(dp[j], mp, s0, m2, R, prg, v_stream, ctr, g + P.prefix[j], e + 3 * j, vout0[j],
+                              MMTw{true, v_stream, j, k, true});
+            lab_add(vout0[j], vb0[j], mp.n, mp.p);
+        }
+    }
+    u64 ctr = 0;
+    if (lv == 0) {
+        DASH_CHECK(ia_pub >= 0 && ib_pub >= 0, "argmax: level 0 indices are public");
+        ProjKeys& Ks = proj_keys_scratch();
+        proj_keys(s0, R.get(2), m2, Ks, true);
+        for (int j = 0; j < k; ++j) {
+            const ModInfo& mp = mod_info(P.crt[j]);
+            draw(prg, i_stream, ctr, mp.p, iout0[j]);
+            const i64 df = pmod(ia_pub - ib_pub, mp.p);
+            garble_proj_keys(Ks, iout0[j], R.get(mp.p), mp, [df](int v) { return v * df; }, idx + 2 * j, 1,
+                             Mask{true, i_stream, tw_sub(TW_CAP, 0), j});
+            lab_axpy(iout0[j], pmod(-ib_pub, mp.p), R.get(mp.p), mp.n, mp.p);  // + i_b: base - i_b R
+        }
+        return;
+    }
+    DASH_CHECK(ia_pub < 0, "argmax: only a carried last slot has a public index after level 0");
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        if (ib_pub >= 0) {  // the wire i_a - c on the labels of i_a
+            lab_affine(e0, ia0[j], pmod(ib_pub, mp.p), R.get(mp.p), mp.n, mp.p);
+        } else {
+            std::memcpy(e0, ia0[j], sizeof(comp_t) * mp.n);
+            lab_sub(e0, ib0[j], mp.n, mp.p);
+        }
+        mixed_mult_garble(e0, mp, s0, m2, R, prg, i_stream, ctr, ig + P.prefix[j], ie + 3 * j, c0,
+                          MMTw{true, i_stream, j, k, true});
+        std::memcpy(iout0[j], c0, sizeof(comp_t) * mp.n);
+        if (ib_pub >= 0) lab_axpy(iout0[j], pmod(-ib_pub, mp.p), R.get(mp.p), mp.n, mp.p);  // + c: base - c R
+        else lab_add(iout0[j], ib0[j], mp.n, mp.p);
+    }
+}
+
+void argmax_pair_eval(const ArgMaxPlan& P, int lv, u64 s_gate, u64 v_gate, u64 i_gate, const comp_t* const* va,
+                      const comp_t* const* vb, const comp_t* const* ia, const comp_t* const* ib, bool ib_pub,
+                      const u128* mrs, const u128* g, const u128* e, const u128* idx, const u128* ig, const u128* ie,
+                      comp_t* const* vout, comp_t* const* iout) {
+    const int k = P.k();
+    const ModInfo& m2 = mod_info(2);
+    comp_t d0[16 * 128], s[128], ed[128], c[128];
+    const comp_t* dp[16];
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        comp_t* d = d0 + static_cast<size_t>(128) * j;
+        std::memcpy(d, va[j], sizeof(comp_t) * mp.n);
+        lab_sub(d, vb[j], mp.n, mp.p);
+        dp[j] = d;
+    }
+    sign_mrs_eval_elem(P.sign, dp, mrs, s, true, s_gate);
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        if (vout) {
+            mixed_mult_eval(dp[j], mp, s, m2, g + P.prefix[j], e + 3 * j, vout[j], MMTw{true, v_gate, j, k, true});
+            lab_add(vout[j], vb[j], mp.n, mp.p);
+        }
+        if (lv == 0) {
+            eval_proj(s, m2, idx + 2 * j, mp, iout[j], 1, Mask{true, i_gate, tw_sub(TW_CAP, 0), j});
+            continue;
+        }
+        std::memcpy(ed, ia[j], sizeof(comp_t) * mp.n);
+        if (!ib_pub) lab_sub(ed, ib[j], mp.n, mp.p);
+        mixed_mult_eval(ed, mp, s, m2, ig + P.prefix[j], ie + 3 * j, c, MMTw{true, i_gate, j, k, true});
+        std::memcpy(iout[j], c, sizeof(comp_t) * mp.n);
+        if (!ib_pub) lab_add(iout[j], ib[j], mp.n, mp.p);
+    }
+}
+
 }  // namespace dash

@@ -457,4 +457,80 @@ void clip_mult_eval(const ClipPlan& P, const comp_t* const* x, const comp_t* slo
 // base labels of the wire x - q on the labels of x: x0_j + (q mod p_j) R_j (dst: k rows of 128 components)
 void clip_shift_base(const ClipPlan& P, const LabelBank& R, const comp_t* const* x0, i64 q, comp_t* dst);
 
+// ---------------------------------------------------------------------------
+// ArgMax (index of the largest of K candidates; ties to the lowest index) per
+// output position
+//
+// The max tournament (layers.h MaxTree: level l pairs slots 2q / 2q + 1, an odd
+// last slot is carried) over candidates (v, i) = (value, index). Slot order is
+// index order, so in a pair (a, b) the candidate a holds the lower indices.
+//   d_j = v_a,j - v_b,j (free), s = [d >= 0]  (mod-2 label)
+// from one exact SignMrsPlan sign of d; an approximate sign errs exactly where
+// two values are close, which is where an argmax is decided, so only the exact
+// sign is offered. s = 1 keeps a, also on a tie: the lowest index wins.
+//   value  v_j = v_b,j + s d_j     the ReLU's mixed-modulus half gates keyed by
+//          the label of s (mm.g [P], mm.e [k][3]); omitted at the root level,
+//          whose value nobody reads;
+//   index  level 0: both indices are public, i_j = i_b + s (i_a - i_b) mod p_j
+//          is a 2-row projection Z_2 -> Z_{p_j} of s per residue (idx [k][2],
+//          row = colour of s; the Clip cap's gate form, rows (TW_CAP, 0) slot j)
+//          with i_b folded into the output base label;
+//          later levels: e_j = i_a,j - i_b,j, i_j = i_b,j + s e_j, a second set
+//          of half gates keyed by s (im.g [P], im.e [k][3]). A carried candidate
+//          that has not played yet has a public index c: it is folded into the
+//          base labels, e = i_a - c on the labels of i_a and c into the output
+//          base, as the Clip folds its bounds.
+// Hardened encoding only (the folds, and one sign label keying up to 2 k + 2
+// rows). The sign, the value gates and the index gates (or the projection) of
+// level l draw from PRG stream slots 20 + 3 l, 21 + 3 l, 22 + 3 l and mask with
+// these streams as gates, so the two half-gate sets share no pad although both
+// use rows (TW_MMG, j) / (TW_MMY, 0) (docs/SECURITY.md 2.2).
+// Pair operation q of output position o at a level with `ops` operations over P
+// positions is element e = q P + o; candidate slot s of position o is element
+// s P + o, the layout of the (K, P) input itself. Tables under "lv<l>.": mrs
+// [n_sign], mm.g, mm.e (not at the root), idx (level 0) or im.g, im.e (later).
+// Entries per pair operation, n_sign = SignMrsPlan::n_tab, P = sum_j p_j:
+//   level 0, not the root      n_sign + P + 3 k + 2 k
+//   later level, not the root  n_sign + 2 (P + 3 k)
+//   root, later level          n_sign + P + 3 k
+//   root at level 0 (K = 2)    n_sign + 2 k
+// (k = 7, first primes: 240, 305, 226, 161; K = 10: 2341 per output.)
+struct ArgMaxPlan {
+    std::vector<int> crt;
+    i64 K = 2;
+    i64 sum_crt = 0;
+    std::vector<i64> prefix;  // mm.g / im.g offset of residue j
+    SignMrsPlan sign;
+    std::vector<int> ops, cnt;          // the MaxTree(K) schedule
+    std::vector<std::vector<i64>> pub;  // [level][slot]: the slot's public index, -1 once it has played
+    ArgMaxPlan() = default;
+    ArgMaxPlan(const std::vector<int>& crt_, i64 K_);
+    int k() const { return static_cast<int>(crt.size()); }
+    int levels() const { return static_cast<int>(ops.size()); }
+    bool root(int lv) const { return lv + 1 == levels(); }
+    // table entries of one pair operation of level lv
+    i64 op_entries(int lv) const {
+        const i64 half = sum_crt + 3 * k();
+        return sign.n_tab + (root(lv) ? 0 : half) + (lv == 0 ? 2 * k() : half);
+    }
+    // table entries per output position
+    i64 entries() const {
+        i64 n = 0;
+        for (int lv = 0; lv < levels(); ++lv) n += ops[lv] * op_entries(lv);
+        return n;
+    }
+    static i64 entries(const std::vector<int>& crt, i64 K) { return ArgMaxPlan(crt, K).entries(); }
+};
+// One pair operation of level lv. va / vb: the candidates' value labels; ia / ib: their index labels, unused
+// (may be null) where the index is public (ia_pub / ib_pub >= 0). Tables of this operation: mrs [n_sign]; g, e
+// (null at the root); idx (level 0) or ig, ie (later levels). vout is null at the root. Garbler: base labels.
+void argmax_pair_garble(const ArgMaxPlan& P, int lv, const LabelBank& R, const Prg& prg, u64 s_stream, u64 v_stream,
+                        u64 i_stream, const comp_t* const* va0, const comp_t* const* vb0, const comp_t* const* ia0,
+                        i64 ia_pub, const comp_t* const* ib0, i64 ib_pub, u128* mrs, u128* g, u128* e, u128* idx,
+                        u128* ig, u128* ie, comp_t* const* vout0, comp_t* const* iout0);
+void argmax_pair_eval(const ArgMaxPlan& P, int lv, u64 s_gate, u64 v_gate, u64 i_gate, const comp_t* const* va,
+                      const comp_t* const* vb, const comp_t* const* ia, const comp_t* const* ib, bool ib_pub,
+                      const u128* mrs, const u128* g, const u128* e, const u128* idx, const u128* ig, const u128* ie,
+                      comp_t* const* vout, comp_t* const* iout);
+
 }  // namespace dash

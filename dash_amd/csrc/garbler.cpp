@@ -35,6 +35,7 @@ const char* kind_name(int kind) {
         case K_SUMPOOL: return "sum_pool";
         case K_CONCAT: return "concat";
         case K_CLIP: return "clip";
+        case K_ARGMAX: return "argmax";
     }
     return "unknown";
 }
@@ -663,7 +664,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
                                     (spec.kind == K_RELU || spec.kind == K_SIGN ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
-                                    spec.kind == K_CLIP ||
+                                    spec.kind == K_CLIP || spec.kind == K_ARGMAX ||
                                     (spec.kind == K_RESCALE && (param1(spec.p, "mode", 0) != 0 || crt_[0] == 2)))));
         const bool passthru = spec.kind == K_FLATTEN;
         if (on_gpu && !dev_ok) {
@@ -1288,6 +1289,97 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 }
                 g.p["levels"] = {static_cast<i64>(T.ops.size())};
                 cur = std::move(nxt);
+                break;
+            }
+            case K_ARGMAX: {
+                // gadgets.h ArgMaxPlan: candidate slot s of position o is element s P + o (the input's own layout),
+                // pair operation q of position o is element q P + o
+                DASH_CHECK(is_crt(), "argmax needs CRT-base labels");
+                DASH_CHECK(hard, "argmax: the ArgMax layer exists in the hardened encoding only");
+                const i64 K = param1(spec.p, "K"), P = param1(spec.p, "P");
+                DASH_CHECK(K >= 2 && P >= 1 && K * P == Nin, "argmax input size mismatch");
+                const ArgMaxPlan ap(crt_, K);
+                const i64 nsig = std::max<i64>(ap.sign.n_tab, 1);
+                CrtLabels vals, idxl;
+                if (!on_gpu) vals = std::move(cur);
+                for (int lv = 0; lv < ap.levels(); ++lv) {
+                    const i64 ops = ap.ops[lv], cnt = ap.cnt[lv], cnt1 = ap.cnt[lv + 1], Nops = ops * P;
+                    const bool root = ap.root(lv);
+                    const std::string pre = arr_name("lv", lv, ".");
+                    Array mrs(DType::u128, {Nops, nsig}), tg, te, ti, tig, tie;
+                    if (!root) {
+                        tg = Array(DType::u128, {Nops, sum_crt});
+                        te = Array(DType::u128, {Nops, static_cast<i64>(k), 3});
+                    }
+                    if (lv == 0) {
+                        ti = Array(DType::u128, {Nops, static_cast<i64>(k), 2});
+                    } else {
+                        tig = Array(DType::u128, {Nops, sum_crt});
+                        tie = Array(DType::u128, {Nops, static_cast<i64>(k), 3});
+                    }
+                    if (on_gpu) {
+                        sinkify(mrs, pre + "mrs");
+                        sinkify(tg, pre + "mm.g");
+                        sinkify(te, pre + "mm.e");
+                        sinkify(ti, pre + "idx");
+                        sinkify(tig, pre + "im.g");
+                        sinkify(tie, pre + "im.e");
+                        gpu->argmax_level(L, lv, ap, P, prefix, cur, mrs, tg, te, ti, tig, tie);
+                    } else {
+                        CrtLabels nv, ni;
+                        for (int j = 0; j < k; ++j) {
+                            if (!root) nv.emplace_back(crt_[j], cnt1 * P);
+                            ni.emplace_back(crt_[j], cnt1 * P);
+                        }
+                        const std::vector<i64>& pub = ap.pub[lv];
+                        parallel_for(Nops, [&](i64 b0, i64 b1) {
+                            std::vector<const comp_t*> va(k), vb(k), ia(k, nullptr), ib(k, nullptr);
+                            std::vector<comp_t*> vo(k), io(k);
+                            for (i64 e = b0; e < b1; ++e) {
+                                const i64 q = e / P, o = e % P, sa = 2 * q * P + o, sb = sa + P;
+                                for (int j = 0; j < k; ++j) {
+                                    va[j] = vals[j].at(sa);
+                                    vb[j] = vals[j].at(sb);
+                                    if (pub[2 * q] < 0) ia[j] = idxl[j].at(sa);
+                                    if (pub[2 * q + 1] < 0) ib[j] = idxl[j].at(sb);
+                                    if (!root) vo[j] = nv[j].at(e);
+                                    io[j] = ni[j].at(e);
+                                }
+                                argmax_pair_garble(ap, lv, R_, prg_, stream_id(L, 20 + 3 * lv, e),
+                                                   stream_id(L, 21 + 3 * lv, e), stream_id(L, 22 + 3 * lv, e), va.data(),
+                                                   vb.data(), ia.data(), pub[2 * q], ib.data(), pub[2 * q + 1],
+                                                   mrs.ptr<u128>() + e * nsig, root ? nullptr : tg.ptr<u128>() + e * sum_crt,
+                                                   root ? nullptr : te.ptr<u128>() + e * k * 3,
+                                                   lv == 0 ? ti.ptr<u128>() + e * k * 2 : nullptr,
+                                                   lv == 0 ? nullptr : tig.ptr<u128>() + e * sum_crt,
+                                                   lv == 0 ? nullptr : tie.ptr<u128>() + e * k * 3,
+                                                   root ? nullptr : vo.data(), io.data());
+                            }
+                        }, nt);
+                        if (cnt % 2)  // the carried slot: its value, and its index labels once it has played
+                            for (int j = 0; j < k; ++j) {
+                                const size_t row = sizeof(comp_t) * vals[j].n * P;
+                                std::memcpy(nv[j].at(ops * P), vals[j].at((cnt - 1) * P), row);
+                                if (pub[cnt - 1] < 0) std::memcpy(ni[j].at(ops * P), idxl[j].at((cnt - 1) * P), row);
+                            }
+                        vals = std::move(nv);
+                        idxl = std::move(ni);
+                    }
+                    g.a[pre + "mrs"] = mrs;
+                    if (!root) {
+                        g.a[pre + "mm.g"] = tg;
+                        g.a[pre + "mm.e"] = te;
+                    }
+                    if (lv == 0) {
+                        g.a[pre + "idx"] = ti;
+                    } else {
+                        g.a[pre + "im.g"] = tig;
+                        g.a[pre + "im.e"] = tie;
+                    }
+                }
+                g.p["levels"] = {static_cast<i64>(ap.levels())};
+                if (!on_gpu) cur = std::move(idxl);
+                dims = dims.size() == 3 ? std::vector<i64>{1, dims[1], dims[2]} : std::vector<i64>{1};
                 break;
             }
             case K_SUMPOOL: {

@@ -42,6 +42,29 @@ __device__ __forceinline__ ReluOps relu_ops(const u128* hs, const u128* ys, int 
     return o;
 }
 
+// The same operands from the compressed mod-2 label Y itself (a Clip's u, an ArgMax's s), which keys residue
+// j's evaluator half gate E3 = [k][3] under `gate`: the lane derives Y's y-row pads (TW_MMY, 0: entry slot j,
+// mini lane j % 8 of slot k + j / 8). j is uniform per block, so is the choice of one or two pad blocks.
+struct KeyedOps {
+    u128 E;        // the entry of Y's colour minus its pad
+    uint32_t ypr;  // the half gate's multiplier
+};
+__device__ __forceinline__ KeyedOps keyed_ops(u128 Y, uint64_t gate, const u128* E3, int j, int k, int p, const ModC& m) {
+    const uint32_t cY = static_cast<uint32_t>(Y) & 1u;
+    const u128 Eraw = E3[cY];
+    const u128 mini = E3[2];
+    const int sS = j, sM = k + j / 8;
+    u128 pd[4];
+    hard_block(Y, gate, tw_sub(kTwMmy, 0), static_cast<uint32_t>(sS) >> 2, pd);
+    const u128 HS = pd[sS & 3];
+    if ((sM >> 2) != (sS >> 2)) hard_block(Y, gate, tw_sub(kTwMmy, 0), static_cast<uint32_t>(sM) >> 2, pd);
+    const u128 HM = pd[sM & 3] >> (16 * (j % 8));
+    KeyedOps r;
+    r.E = Eraw - HS;
+    r.ypr = mini_mult(mini, cY, HM, p, m);
+    return r;
+}
+
 // One digit of the multiply; all terms in [0, p): ev + ypr x + (p - g) (+ cv) < p^2 + 3p
 __device__ __forceinline__ uint32_t mult_digit(uint32_t ev, uint32_t ypr, uint32_t x, int p, uint32_t g, const ModC& m) {
     return modq(ev + ypr * x + static_cast<uint32_t>(p) - g, m);
@@ -66,6 +89,37 @@ __device__ __forceinline__ void col_walk(const act_t* src, act_t* dst, int64_t N
             if (c0 + u < n) dst[static_cast<int64_t>(c0 + u) * N] = static_cast<act_t>(f(c0 + u, static_cast<uint32_t>(cur[u])));
 #pragma unroll
         for (int u = 0; u < G; ++u) cur[u] = nxt[u];
+    }
+}
+
+// The same walk over NS source columns with a stride each (an ArgMax's pair operands live in buffers of
+// different slot counts): f(c, v) gets component c of every source and does its own stores.
+template <int G, int NS, class F>
+__device__ __forceinline__ void col_walk_n(const act_t* const (&src)[NS], const int64_t (&ld)[NS], int n, F&& f) {
+    uint16_t cur[NS][G], nxt[NS][G];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int u = 0; u < G; ++u)
+            if (u < n) cur[s][u] = src[s][static_cast<int64_t>(u) * ld[s]];
+    for (int c0 = 0; c0 < n; c0 += G) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int u = 0; u < G; ++u)
+                if (c0 + G + u < n) nxt[s][u] = src[s][static_cast<int64_t>(c0 + G + u) * ld[s]];
+#pragma unroll
+        for (int u = 0; u < G; ++u)
+            if (c0 + u < n) {
+                uint32_t v[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) v[s] = cur[s][u];
+                f(c0 + u, v);
+            }
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int u = 0; u < G; ++u) cur[s][u] = nxt[s][u];
     }
 }
 

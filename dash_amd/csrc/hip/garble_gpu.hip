@@ -2951,6 +2951,8 @@ struct GpuGarbler::Impl {
     // max pool in progress: value slots [Nout][cnt] (output-major) of the current tree level
     std::vector<DevBlock> mp_V;
     int64_t mp_Nout = 0, mp_cnt = 0;
+    // argmax in progress: the candidates' value and index labels [cnt][P] (slot-major) of the current level
+    std::vector<DevBlock> am_V, am_I;
     explicit Impl(int dev) : lock(acquire_ctx(dev, dcp)), dc(*dcp), device(dev) {}
     template <class T>
     const T* stage(const T* h, size_t n) { return dc.stage(h, n); }
@@ -2987,6 +2989,7 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     clip_hook() = &GpuGarbler::clip_dev;
     clip_hi_hook() = &GpuGarbler::clip_hi_dev;
     clip_joint_hook() = &GpuGarbler::clip_joint_dev;
+    argmax_hook() = &GpuGarbler::argmax_level_dev;
     Impl& I = *impl_;
     I.enter();
     I.c.hard = hardened ? 1 : 0;
@@ -3458,10 +3461,12 @@ void GpuGarbler::rescale_legacy_iter(uint64_t layer, int it, const RescalePlan& 
 }
 
 // ReLU mixed-modulus half gates out_j = x_j * sig (relu_garble_elem's mixed_mult_garble order): draws of the
-// sk03/sk04 labels (slots sk0 + 2j, + 1) on PRG stream 2 of g.layer, the g (F_MULR) and e (F_NEGR) projections
-// into tables 4 / 5, the mini payloads and output base labels. g.S holds the sign label at sig_slot.
+// sk03/sk04 labels (slots sk0 + 2j, + 1) on PRG stream `sslot` of g.layer (2 but for an ArgMax's gate sets), the
+// g (F_MULR) and e (F_NEGR) projections into tables 4 / 5, the mini payloads and output base labels. g.S holds
+// the sign label at sig_slot.
 static std::vector<DevBlock> relu_mult_gates(GpuGarbler::Impl& I, const gg::Gadget& g, const gg::In& in,
-                                             gg::Tables& tb, int sig_slot, int sk0, const std::vector<i64>& prefix) {
+                                             gg::Tables& tb, int sig_slot, int sk0, const std::vector<i64>& prefix,
+                                             int sslot = 2) {
     const int64_t N = g.N;
     const int k = I.k;
     std::vector<DevBlock> out = I.alloc_labels(I.crt, N);
@@ -3493,7 +3498,7 @@ static std::vector<DevBlock> relu_mult_gates(GpuGarbler::Impl& I, const gg::Gadg
         pm.push_back(q);
     }
     gg::Gadget gm = g;
-    gm.sslot = 2;
+    gm.sslot = sslot;
     gm.PB = I.pbank(2, N);
     gm.draws = gg::dconst(dm.data(), dm.size());
     gm.ndraws = static_cast<int>(dm.size());
@@ -4493,6 +4498,214 @@ void GpuGarbler::maxpool_end(CrtLabels& cur) {
     I.cur_mod = I.crt;
     I.mp_Nout = I.mp_cnt = 0;
     set_stale(cur, I.cur_mod, I.cur_N);
+}
+
+// ArgMax (garbler.cpp K_ARGMAX, argmax_pair_garble's order), one tournament level over P positions. Candidate
+// slot s of position o is element s P + o, pair operation q is element q P + o (gadgets.h ArgMaxPlan). The
+// pair differences d = v_a - v_b; the exact sign of d (mrs_sign_desc, stream 20 + 3 lv); the value half gates
+// keyed by the sign label on d (stream 21 + 3 lv), + v_b; the index on stream 22 + 3 lv: level 0 one two-row
+// projection of the sign label per residue (i_a - i_b = -1 for every pair; the cap's gate form) with the public
+// i_b folded into the output base per operation, later levels the half gates on e = i_a - i_b, + i_b. A carried
+// candidate that has not played has no index labels: its public index c is folded into e (+ c R) and into the
+// output (- c R). Scratch slots: the sign's, then 2k half-gate labels per gate set (level 0: k projection labels).
+void GpuGarbler::argmax_level_dev(GpuGarbler& self, uint64_t layer, int lv, const ArgMaxPlan& ap, i64 P,
+                                  const std::vector<i64>& prefix, CrtLabels& cur, Array& mrs, Array& mmg, Array& mme,
+                                  Array& idx, Array& img, Array& ime) {
+    Impl& I = *self.impl_;
+    I.enter();
+    PhaseTrace tr_("argmax_level");
+    const int k = I.k;
+    const bool root = ap.root(lv), l0 = lv == 0;
+    DASH_CHECK(ap.k() == k && lv >= 0 && lv < ap.levels(), "gpu garbler: argmax plan mismatch");
+    if (l0) {
+        I.check_cur(cur);
+        DASH_CHECK(I.cur_mod == I.crt && I.cur_N == ap.K * P, "gpu garbler: argmax input mismatch");
+        I.am_V = std::move(I.cur);
+        I.am_I.clear();
+    }
+    const int64_t ops = ap.ops[lv], cnt = ap.cnt[lv], cnt1 = ap.cnt[lv + 1], N = ops * P, Nc = cnt * P, Nn = cnt1 * P;
+    const std::vector<i64>& pub = ap.pub[lv];
+    // gather maps: differences (a, b), the b candidate of every next slot (the carried slot: itself), the
+    // operation's output of every next slot
+    std::vector<int32_t> dm(static_cast<size_t>(N) * 2), em(static_cast<size_t>(N) * 2), bm(static_cast<size_t>(Nn)),
+        ibm(static_cast<size_t>(Nn)), ym(static_cast<size_t>(Nn));
+    std::vector<int32_t> efold(static_cast<size_t>(ops) * k, 0), ofold(static_cast<size_t>(cnt1) * k, 0);
+    bool any_efold = false;
+    for (int64_t q = 0; q < ops; ++q) {
+        const bool bpub = pub[2 * q + 1] >= 0;
+        for (int64_t o = 0; o < P; ++o) {
+            const int64_t e = q * P + o;
+            dm[static_cast<size_t>(2 * e)] = em[static_cast<size_t>(2 * e)] = static_cast<int32_t>(2 * q * P + o);
+            dm[static_cast<size_t>(2 * e + 1)] = static_cast<int32_t>((2 * q + 1) * P + o);
+            em[static_cast<size_t>(2 * e + 1)] = bpub ? -1 : static_cast<int32_t>((2 * q + 1) * P + o);
+            bm[static_cast<size_t>(e)] = static_cast<int32_t>((2 * q + 1) * P + o);
+            ibm[static_cast<size_t>(e)] = bpub ? -1 : static_cast<int32_t>((2 * q + 1) * P + o);
+            ym[static_cast<size_t>(e)] = static_cast<int32_t>(e);
+        }
+        if (bpub)
+            for (int j = 0; j < k; ++j) {
+                efold[static_cast<size_t>(j) * ops + q] = static_cast<int32_t>(pmod(pub[2 * q + 1], I.crt[j]));
+                ofold[static_cast<size_t>(j) * cnt1 + q] = static_cast<int32_t>(pmod(-pub[2 * q + 1], I.crt[j]));
+                any_efold = any_efold || !l0;
+            }
+    }
+    if (cnt % 2)
+        for (int64_t o = 0; o < P; ++o) {
+            bm[static_cast<size_t>(ops * P + o)] = static_cast<int32_t>((cnt - 1) * P + o);
+            ibm[static_cast<size_t>(ops * P + o)] = pub[cnt - 1] >= 0 ? -1 : static_cast<int32_t>((cnt - 1) * P + o);
+            ym[static_cast<size_t>(ops * P + o)] = -1;
+        }
+    // y_e += c_{e / P} R per residue (k_fold; consts[j]: one constant per group of P elements)
+    auto fold = [&](std::vector<DevBlock>& L, int64_t n, const std::vector<int32_t>& consts, int64_t groups) {
+        gg::FoldArgs a{};
+        a.N = n;
+        a.group = P;
+        int ncmax = 1;
+        for (int j = 0; j < k; ++j) {
+            a.j[j] = gg::FoldJob{L[j].as<int16_t>(), gg::dconst(consts.data() + static_cast<size_t>(j) * groups, groups),
+                                 I.crt[j], static_cast<int>(gg::chunks_of(nr_comps(I.crt[j])))};
+            ncmax = std::max(ncmax, a.j[j].nc);
+        }
+        const int blocks = static_cast<int>(std::min<int64_t>((n * ncmax + 255) / 256, 4096));
+        hipLaunchKernelGGL(gg::k_fold, dim3(blocks, k), dim3(256), 0, gg::tl_st, I.c, a);
+    };
+    std::vector<DevBlock> D = I.alloc_labels(I.crt, N), E;
+    launch_gsum(I.c, D, I.am_V, I.crt, N, Nc, gg::dconst(dm.data(), dm.size()), 2, false,
+                [](int p, int t) { return t == 0 ? 1 : p - 1; });
+    if (!l0) {
+        E = I.alloc_labels(I.crt, N);
+        launch_gsum(I.c, E, I.am_I, I.crt, N, Nc, gg::dconst(em.data(), em.size()), 2, false,
+                    [](int p, int t) { return t == 0 ? 1 : p - 1; });
+        if (any_efold) fold(E, N, efold, ops);
+    }
+    const gg::In in = labels_in(D, I.crt, N);
+    const MrsSignDesc S = mrs_sign_desc(ap.sign, 0);
+    const int sig = S.sig_slot, sk0 = S.end_slot, sk1 = sk0 + 2 * k, nslots = sk1 + 2 * k;
+    gg::Gadget g{};
+    g.layer = layer;
+    g.mask = 0;
+    g.S = I.scratch(static_cast<size_t>(N) * nslots * gg::kW * sizeof(int16_t));
+    g.N = N;
+    g.nslots = nslots;
+    DevTable tT, tG, tE, tX, tIG, tIE;
+    std::vector<void*> tmp;
+    {  // the sign of d
+        tT.alloc(I.device, N, mrs.shape[1], mrs);
+        gg::Tables tb{};
+        tb.t[0] = tT.p(); tb.row[0] = tT.row;
+        gg::Gadget gs = g;
+        gs.sslot = 20 + 3 * lv;
+        gs.PB = I.pbank(2, N);
+        gs.draws = gg::dconst(S.dr.data(), S.dr.size());
+        gs.ndraws = static_cast<int>(S.dr.size());
+        gs.projs = gg::dconst(S.pr.data(), S.pr.size());
+        gs.nprojs = static_cast<int>(S.pr.size());
+        gs.entries = S.entries;
+        gs.nblk = draw_blocks(S.dr);
+        check_desc(gs);
+        hipLaunchKernelGGL(gg::draw_kernel(), dim3(draw_grid(gs)), dim3(gg::kGB), 0, gg::tl_st, I.c, gs);
+        hipLaunchKernelGGL(gg::k_mrs_sign_derive, dim3(blocks_for(N, 256), k), dim3(256), 0, gg::tl_st, I.c, gs, in, S.a);
+        project(I.c, gs, in, tb, S.pr, ProjFns{&S.flut, &S.fan});
+    }
+    std::vector<DevBlock> nv, ni = I.alloc_labels(I.crt, Nn);
+    if (!root) {  // v = v_b + s d, the carried value
+        tG.alloc(I.device, N, mmg.shape[1], mmg);
+        tE.alloc(I.device, N, static_cast<int64_t>(k) * 3, mme, true);
+        gg::Tables tb{};
+        tb.t[4] = tG.p(); tb.row[4] = tG.row;
+        tb.t[5] = tE.p(); tb.row[5] = tE.row;
+        std::vector<DevBlock> Y = relu_mult_gates(I, g, in, tb, sig, sk0, prefix, 21 + 3 * lv);
+        nv = I.alloc_labels(I.crt, Nn);
+        launch_gsum(I.c, nv, I.am_V, I.crt, Nn, Nc, gg::dconst(bm.data(), bm.size()), 1, false,
+                    [](int, int) { return 1; });
+        launch_gsum(I.c, nv, Y, I.crt, Nn, N, gg::dconst(ym.data(), ym.size()), 1, true, [](int, int) { return 1; });
+    }
+    if (l0) {
+        // i = i_b + s (i_a - i_b): base labels c0_j drawn on the index stream, one 2-row projection of s per
+        // residue (table row [k][2], pad slot j of row (TW_CAP, 0)), then - i_b R
+        tX.alloc(I.device, N, static_cast<int64_t>(k) * 2, idx);
+        std::vector<gg::Draw> dc;
+        std::vector<gg::Proj> pc;
+        std::vector<int> fan;
+        std::vector<int16_t> flut;
+        int ctr = 0;
+        int64_t first = 0;
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            dc.push_back({sk1 + j, p, ctr});
+            ctr += prg_blocks(p);
+            const int a0 = static_cast<int>(flut.size()), a1 = static_cast<int>(fan.size());
+            flut.push_back(0);
+            flut.push_back(static_cast<int16_t>(p - 1));
+            fan.push_back(p);
+            gg::Proj q{};
+            q.in_kind = gg::S_SLOT; q.in_idx = sig; q.pin = 2;
+            q.out_slot = sk1 + j; q.pout = p; q.fn = gg::F_FAN; q.a0 = a0; q.a1 = a1;
+            q.outr_kind = gg::R_BANK; q.table = 6; q.stride = 1; q.off = 2 * j; q.first = first;
+            q.hsub = tw_sub(kTwCap, 0);
+            q.hslot = j;
+            first += 2;
+            pc.push_back(q);
+        }
+        gg::Tables tb{};
+        tb.t[6] = tX.p(); tb.row[6] = tX.row;
+        gg::Gadget gc = g;
+        gc.sslot = 22 + 3 * lv;
+        gc.PB = I.pbank(2, N);
+        gc.draws = gg::dconst(dc.data(), dc.size());
+        gc.ndraws = static_cast<int>(dc.size());
+        gc.projs = gg::dconst(pc.data(), pc.size());
+        gc.nprojs = static_cast<int>(pc.size());
+        gc.entries = first;
+        gc.nblk = draw_blocks(dc);
+        check_desc(gc);
+        hipLaunchKernelGGL(gg::draw_kernel(), dim3(draw_grid(gc)), dim3(gg::kGB), 0, gg::tl_st, I.c, gc);
+        project(I.c, gc, in, tb, pc, ProjFns{&flut, &fan});
+        std::vector<DevBlock> Yi = I.alloc_labels(I.crt, N);
+        std::vector<gg::LinJob> jobs;
+        for (int j = 0; j < k; ++j) {
+            gg::LinJob J = lin_job(Yi[j].as<int16_t>(), I.crt[j]);
+            lin_b(J, gg::slot_base(gc, sk1 + j), N, 1);
+            jobs.push_back(J);
+        }
+        launch_lin(I.c, jobs, N);
+        launch_gsum(I.c, ni, Yi, I.crt, Nn, N, gg::dconst(ym.data(), ym.size()), 1, false, [](int, int) { return 1; });
+    } else {  // i = i_b + s e
+        tIG.alloc(I.device, N, img.shape[1], img);
+        tIE.alloc(I.device, N, static_cast<int64_t>(k) * 3, ime, true);
+        gg::Tables tb{};
+        tb.t[4] = tIG.p(); tb.row[4] = tIG.row;
+        tb.t[5] = tIE.p(); tb.row[5] = tIE.row;
+        std::vector<DevBlock> Yi = relu_mult_gates(I, g, labels_in(E, I.crt, N), tb, sig, sk1, prefix, 22 + 3 * lv);
+        launch_gsum(I.c, ni, Yi, I.crt, Nn, N, gg::dconst(ym.data(), ym.size()), 1, false, [](int, int) { return 1; });
+        launch_gsum(I.c, ni, I.am_I, I.crt, Nn, Nc, gg::dconst(ibm.data(), ibm.size()), 1, true,
+                    [](int, int) { return 1; });
+    }
+    fold(ni, Nn, ofold, cnt1);  // + the public i_b of an operation: base - i_b R
+    HIPCHECK(hipGetLastError());
+    gg::end_layer(tmp);
+    tr_.mark("kernels");
+    tT.to_array(mrs, I.device);
+    if (!root) {
+        tG.to_array(mmg, I.device);
+        tE.to_array(mme, I.device);
+    }
+    if (l0) {
+        tX.to_array(idx, I.device);
+    } else {
+        tIG.to_array(img, I.device);
+        tIE.to_array(ime, I.device);
+    }
+    I.am_V = std::move(nv);
+    I.am_I = std::move(ni);
+    if (root) {
+        I.cur = std::move(I.am_I);
+        I.am_I.clear();
+        I.am_V.clear();
+        I.cur_N = P;
+        I.cur_mod = I.crt;
+        set_stale(cur, I.cur_mod, P);
+    }
 }
 
 // ReDash rescale iteration (rescale_garble_elem with a base-extension plan): L += up; per factor the identity

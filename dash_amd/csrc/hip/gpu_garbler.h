@@ -121,6 +121,21 @@ class GpuGarbler {
     void maxpool_level(uint64_t layer, int lv, i64 ops, const SignPlan& sp, const std::vector<i64>& prefix, Array& ap,
                        Array& c1, Array& c2, Array& sg, Array& mmg, Array& mme);
     void maxpool_end(CrtLabels& cur);
+    // ArgMax (gadgets.h ArgMaxPlan), one tournament level over P positions: level 0 takes the device cur as the
+    // candidates' values, the root leaves the index labels as the device cur. Tables of the level: mrs; mmg, mme
+    // (empty at the root); idx (level 0) or img, ime (later levels). A hook as for clip, so host-only links need
+    // no definition.
+    using ArgMaxFn = void (*)(GpuGarbler&, uint64_t, int, const ArgMaxPlan&, i64, const std::vector<i64>&, CrtLabels&,
+                              Array&, Array&, Array&, Array&, Array&, Array&);
+    static ArgMaxFn& argmax_hook() {
+        static ArgMaxFn f = nullptr;
+        return f;
+    }
+    void argmax_level(uint64_t layer, int lv, const ArgMaxPlan& ap, i64 P, const std::vector<i64>& prefix,
+                      CrtLabels& cur, Array& mrs, Array& mmg, Array& mme, Array& idx, Array& img, Array& ime) {
+        DASH_CHECK(argmax_hook() != nullptr, "gpu garbler: argmax is not linked in");
+        argmax_hook()(*this, layer, lv, ap, P, prefix, cur, mrs, mmg, mme, idx, img, ime);
+    }
     // ReDash rescale iteration (base-extension plan) on the device cur, in place
     void rescale_redash(uint64_t layer, int it, const RescalePlan& P, CrtLabels& cur,
                         const std::vector<std::vector<comp_t>>& up, const std::vector<std::vector<comp_t>>& down,
@@ -139,6 +154,9 @@ class GpuGarbler {
                             Array& tab);
     static void clip_joint_dev(GpuGarbler& self, uint64_t layer, i64 hi, CrtLabels& cur, const std::vector<i64>* prefix,
                                Array& mmg, Array& mme, Array& cap);
+    static void argmax_level_dev(GpuGarbler& self, uint64_t layer, int lv, const ArgMaxPlan& ap, i64 P,
+                                 const std::vector<i64>& prefix, CrtLabels& cur, Array& mrs, Array& mmg, Array& mme,
+                                 Array& idx, Array& img, Array& ime);
     std::unique_ptr<Impl> impl_;
 };
 

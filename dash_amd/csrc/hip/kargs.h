@@ -147,6 +147,28 @@ struct ClipArgs {
     uint64_t mgate0;       // gate base of the multiply (stream slot 2): rows (TW_MMY, 0) of u, (TW_CAP, 0) of s_hi
 };
 
+// One level of an ArgMax (gadgets.h ArgMaxPlan): `ops` pair operations over `cnt` candidate slots at each of P
+// positions. Slot s of position o is element s P + o of the candidate buffers, pair operation q is element
+// e = q P + o of the per-operation arrays (N = ops P) and of the next level's slot q.
+struct ArgMaxArgs {
+    CrtInfo crt;
+    int64_t P;
+    int ops, cnt, cnt1;    // cnt1 = slots of the next level (ops, + 1 with a carried slot)
+    int pubq;              // the pair operation whose b candidate has a public index (the last one), else -1
+    int carry_idx;         // the carried slot (cnt odd) has index labels to copy (it has played)
+    const u128* ks;        // [B][N] compressed sign labels s = [v_a >= v_b]
+    const u128* hx;        // [B][k][N] value gates: pads of d_j's garbler half gate row (TW_MMG, j), gate vgate0
+    const uint16_t* colx;  // [B][k][N]
+    const u128* hi;        // the same of the index difference e_j under igate0 (levels >= 1)
+    const uint16_t* coli;
+    const u128* gtab;      // mm.g [B][N][sum]     (not at the root)
+    const u128* etab;      // mm.e [B][N][k][3]
+    const u128* itab;      // idx  [B][N][k][2]    (level 0)
+    const u128* igtab;     // im.g [B][N][sum]     (levels >= 1)
+    const u128* ietab;     // im.e [B][N][k][3]
+    uint64_t vgate0, igate0;  // gate bases of the value gates and of the index gates / projection
+};
+
 struct BEArgs {
     int E, nonext;
     int swapped[kMaxRes];    // moduli in MRS order

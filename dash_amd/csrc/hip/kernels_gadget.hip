@@ -435,24 +435,16 @@ __device__ __forceinline__ ClipLane clip_keyed(const ClipArgs& a, int j, int b, 
     // the gathers go out before the pads are computed
     const u128 Khi = a.khi[be];
     const u128 U = a.klo[be] ^ Khi;
-    const uint32_t cU = static_cast<uint32_t>(U) & 1u, cH = static_cast<uint32_t>(Khi) & 1u;
-    const u128* E3 = a.etab + (be * k + j) * 3;
-    const u128 Eraw = E3[cU];
-    const u128 mini = E3[2];
+    const uint32_t cH = static_cast<uint32_t>(Khi) & 1u;
     const u128 Craw = a.cap[(be * k + j) * 2 + cH];
     const uint64_t mg = a.mgate0 ^ static_cast<uint64_t>(e);
-    const int sS = j, sM = k + j / 8;  // j is uniform per block: so is the choice of one or two pad blocks
-    u128 pd[4];
-    hard_block(U, mg, tw_sub(kTwMmy, 0), static_cast<uint32_t>(sS) >> 2, pd);
-    const u128 HS = pd[sS & 3];
-    if ((sM >> 2) != (sS >> 2)) hard_block(U, mg, tw_sub(kTwMmy, 0), static_cast<uint32_t>(sM) >> 2, pd);
-    const u128 HM = pd[sM & 3] >> (16 * (j % 8));
+    const KeyedOps o = keyed_ops(U, mg, a.etab + (be * k + j) * 3, j, k, p, m);
     const u128 HC = hard_pad(Khi, mg, tw_sub(kTwCap, 0), j);
     ClipLane r;
     r.G = 0;
-    r.E = Eraw - HS;
+    r.E = o.E;
     r.C = Craw - HC;
-    r.ypr = mini_mult(mini, cU, HM, p, m);
+    r.ypr = o.ypr;
     return r;
 }
 __device__ __forceinline__ ClipLane clip_lane(const ClipArgs& a, int j, int b, int64_t e, int p, const ModC& m) {
@@ -508,6 +500,129 @@ __global__ __launch_bounds__(kRmBS) void k_clip_mult_s(ClipArgs a, Act x, Act y,
         lds_mult_walk<kRmBS, true>(stg + tid, n, c.G, c.E, c.C, c.ypr, p, m);
         __syncthreads();
         lds_store_rows<kRmBS>(Y, stg, N, e0, 0, n);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// ArgMax (gadgets.h ArgMaxPlan; kargs.h ArgMaxArgs for the element layout).
+// Pair differences of one level: d[e] = v[slot 2q] - v[slot 2q + 1], e = q P + o; the operation pubq has no b
+// labels (a public index folded into the garbler's bases), its difference is a's label. grid (x, k, B)
+__global__ __launch_bounds__(256) void k_argmax_diff(Act v, Act d, int64_t P, int ops, int cnt, int pubq, CrtInfo crt) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int n = crt.n[j], p = crt.p[j];
+    const int64_t Nd = P * ops, Nv = P * cnt;
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= Nd * n) return;
+    const int64_t c = t / Nd, e = t - c * Nd, q = e / P;
+    const act_t* V = v.p[j] + (static_cast<int64_t>(b) * n + c) * Nv + e + q * P;  // slot 2q of position o
+    const int32_t x = static_cast<int32_t>(V[0]) - (q == pubq ? 0 : static_cast<int32_t>(V[P]));
+    d.p[j][(static_cast<int64_t>(b) * n + c) * Nd + e] = static_cast<act_t>(x < 0 ? x + p : x);
+}
+
+// One half gate keyed by the sign label S: the garbler half's row of the multiplied label (its pad and colour
+// from the hash pass) and the evaluator half's operands
+struct ArgMaxGate {
+    u128 G, E;
+    uint32_t ypr;
+};
+__device__ __forceinline__ ArgMaxGate argmax_gate(const ArgMaxArgs& a, u128 S, uint64_t gate, const u128* hx,
+                                                  const uint16_t* colx, const u128* gtab, const u128* etab, int j,
+                                                  int64_t be, int64_t bke, int p, const ModC& m) {
+    const u128 Hx = hx[bke];
+    const uint32_t col = colx[bke];
+    const u128 Graw = gtab[be * a.crt.sum + a.crt.prefix[j] + col];
+    const KeyedOps o = keyed_ops(S, gate, etab + (be * a.crt.k + j) * 3, j, a.crt.k, p, m);
+    ArgMaxGate r;
+    r.G = Graw - Hx;
+    r.E = o.E;
+    r.ypr = o.ypr;
+    return r;
+}
+
+// The multiply of one level, grid (ceil(N / 256), k, B), N = ops P: lane e fetches the sign label once, derives
+// the pads of both gate sets, and writes v_b + s d and i_b + s e (level 0: the projection row of s) into slot q
+// of the next level; the lanes of q = 0 also copy the carried slot. VAL: the level has value gates (not the
+// root); L0: level 0 (public indices). d / ed: the pair differences; v / i: this level's candidates.
+template <bool VAL, bool L0>
+__global__ __launch_bounds__(256) void k_argmax_mult(ArgMaxArgs a, Act v, Act d, Act i, Act ed, Act nv, Act ni,
+                                                     const ModC* mc) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t P = a.P, N = P * a.ops, Nc = P * a.cnt, Nn = P * a.cnt1;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const int k = a.crt.k, p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int n = static_cast<int>(m.n);
+    const int64_t q = e / P;
+    const int64_t sb = e + (q + 1) * P;  // slot 2q + 1 of position o
+    const int64_t be = static_cast<int64_t>(b) * N + e, bke = (static_cast<int64_t>(b) * k + j) * N + e;
+    const int64_t gb = static_cast<int64_t>(b) * n;
+    const u128 S = a.ks[be];
+    ArgMaxGate gv{}, gi{};
+    u128 C = 0;
+    if (VAL) gv = argmax_gate(a, S, a.vgate0 ^ static_cast<uint64_t>(e), a.hx, a.colx, a.gtab, a.etab, j, be, bke, p, m);
+    if (L0) {
+        const u128 Craw = a.itab[(be * k + j) * 2 + (static_cast<uint32_t>(S) & 1u)];
+        C = Craw - hard_pad(S, a.igate0 ^ static_cast<uint64_t>(e), tw_sub(kTwCap, 0), j);
+    } else {
+        gi = argmax_gate(a, S, a.igate0 ^ static_cast<uint64_t>(e), a.hi, a.coli, a.igtab, a.ietab, j, be, bke, p, m);
+    }
+    DigitStream svg, sve, sig, sie, sc;
+    svg.init(gv.G);
+    sve.init(gv.E);
+    sig.init(gi.G);
+    sie.init(gi.E);
+    sc.init(C);
+    const uint32_t up = static_cast<uint32_t>(p);
+    const bool ib_secret = q != a.pubq;
+    act_t* NV = nv.p[j] + gb * Nn + e;
+    act_t* NI = ni.p[j] + gb * Nn + e;
+    const act_t* Dj = d.p[j] + gb * N + e;
+    const act_t* Vb = v.p[j] + gb * Nc + sb;
+    // one digit of a gate's output plus the b candidate's digit, both in [0, p)
+    auto gate_digit = [&](DigitStream& se, DigitStream& sg, uint32_t ypr, uint32_t x, uint32_t add) {
+        const uint32_t g = sg.next(m);
+        const uint32_t r = mult_digit(se.next(m), ypr, x, p, g, m) + add;
+        return static_cast<act_t>(r >= up ? r - up : r);
+    };
+    if (L0 && VAL) {
+        const act_t* const src[2] = {Dj, Vb};
+        const int64_t ld[2] = {N, Nc};
+        col_walk_n<kChunk, 2>(src, ld, n, [&](int c, const uint32_t (&x)[2]) {
+            NV[static_cast<int64_t>(c) * Nn] = gate_digit(sve, svg, gv.ypr, x[0], x[1]);
+            NI[static_cast<int64_t>(c) * Nn] = static_cast<act_t>(sc.next(m));
+        });
+    } else if (L0) {
+        for (int c = 0; c < n; ++c) NI[static_cast<int64_t>(c) * Nn] = static_cast<act_t>(sc.next(m));
+    } else {
+        const act_t* Ej = ed.p[j] + gb * N + e;
+        const act_t* Ib = i.p[j] + gb * Nc + sb;  // unread labels of a public b: inside the buffer, masked below
+        if (VAL) {
+            const act_t* const src[4] = {Dj, Vb, Ej, Ib};
+            const int64_t ld[4] = {N, Nc, N, Nc};
+            col_walk_n<kChunk, 4>(src, ld, n, [&](int c, const uint32_t (&x)[4]) {
+                NV[static_cast<int64_t>(c) * Nn] = gate_digit(sve, svg, gv.ypr, x[0], x[1]);
+                NI[static_cast<int64_t>(c) * Nn] = gate_digit(sie, sig, gi.ypr, x[2], ib_secret ? x[3] : 0u);
+            });
+        } else {
+            const act_t* const src[2] = {Ej, Ib};
+            const int64_t ld[2] = {N, Nc};
+            col_walk_n<kChunk, 2>(src, ld, n, [&](int c, const uint32_t (&x)[2]) {
+                NI[static_cast<int64_t>(c) * Nn] = gate_digit(sie, sig, gi.ypr, x[0], ib_secret ? x[1] : 0u);
+            });
+        }
+    }
+    // the carried slot cnt - 1 -> slot ops of the next level (cnt odd, never at the root), by the lanes of q = 0
+    if (VAL && (a.cnt & 1) && e < P) {
+        const int64_t from = static_cast<int64_t>(a.cnt - 1) * P + e, to = static_cast<int64_t>(a.ops) * P + e;
+        const act_t* Vs = v.p[j] + gb * Nc + from;
+        act_t* Vd = nv.p[j] + gb * Nn + to;
+        for (int c = 0; c < n; ++c) Vd[static_cast<int64_t>(c) * Nn] = Vs[static_cast<int64_t>(c) * Nc];
+        if (!L0 && a.carry_idx) {
+            const act_t* Is = i.p[j] + gb * Nc + from;
+            act_t* Id = ni.p[j] + gb * Nn + to;
+            for (int c = 0; c < n; ++c) Id[static_cast<int64_t>(c) * Nn] = Is[static_cast<int64_t>(c) * Nc];
+        }
     }
 }
 
@@ -1775,6 +1890,29 @@ void launch_clip_mult(const ClipArgs& a, const Act& x, const Act& y, int B, cons
         hipLaunchKernelGGL(k_clip_mult_s, grid, dim3(kRmBS), 0, st, a, x, y, mc);
     else
         hipLaunchKernelGGL(k_clip_mult, grid, dim3(256), 0, st, a, x, y, mc);
+}
+// ArgMax (gadgets.h ArgMaxPlan), per level: the pair differences, the half gates' keys of a difference under one
+// gate set's gate, the sign chain (launch_clip_sign_mrs) and the multiply, whose form is the level's shape.
+void launch_argmax_diff(const Act& v, const Act& d, int64_t P, int ops, int cnt, int pubq, const CrtInfo& crt, int B,
+                        hipStream_t st) {
+    int nmax = 1;
+    for (int j = 0; j < crt.k; ++j) nmax = std::max(nmax, crt.n[j]);
+    hipLaunchKernelGGL(k_argmax_diff, grid_for(P * ops * nmax, 256, crt.k, B), dim3(256), 0, st, v, d, P, ops, cnt, pubq,
+                       crt);
+}
+void launch_argmax_hash(const Act& d, const CrtInfo& crt, int64_t N, u128* hx, uint16_t* colx, uint64_t gate0, int B,
+                        const ModC* mc, const AesGlobals& g, hipStream_t st) {
+    AES_LAUNCH_GGL(k_label_hash, N, crt.k, B, kAesLds, st, d, crt, N, hx, colx, mc, g.te0, g.rk, 1, gate0);
+}
+void launch_argmax_mult(const ArgMaxArgs& a, bool val, bool l0, const Act& v, const Act& d, const Act& i, const Act& ed,
+                        const Act& nv, const Act& ni, int B, const ModC* mc, hipStream_t st) {
+    const dim3 grid = grid_for(a.P * a.ops, 256, a.crt.k, B);
+    if (launch_log_on())
+        launch_log_add(std::string("argmax_mult.") + (l0 ? (val ? "l0" : "root0") : (val ? "mid" : "root")), grid, dim3(256));
+    if (val && l0) hipLaunchKernelGGL((k_argmax_mult<true, true>), grid, dim3(256), 0, st, a, v, d, i, ed, nv, ni, mc);
+    else if (val) hipLaunchKernelGGL((k_argmax_mult<true, false>), grid, dim3(256), 0, st, a, v, d, i, ed, nv, ni, mc);
+    else if (l0) hipLaunchKernelGGL((k_argmax_mult<false, true>), grid, dim3(256), 0, st, a, v, d, i, ed, nv, ni, mc);
+    else hipLaunchKernelGGL((k_argmax_mult<false, false>), grid, dim3(256), 0, st, a, v, d, i, ed, nv, ni, mc);
 }
 void launch_rescale_hash(const Act& x, int fi, int s, const int16_t* up, int up_stride, int add_up, int64_t N, int B,
                          u128* h0, uint16_t* col0, const ModC* mc, const AesGlobals& g, hipStream_t st, int hard) {

@@ -57,6 +57,12 @@ void launch_clip_hash(const ClipArgs& a, u128* hx, uint16_t* colx, const Act& x,
                       const AesGlobals& g, hipStream_t st);
 void launch_clip_sign_mrs(const MrsArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_clip_mult(const ClipArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st);
+void launch_argmax_diff(const Act& v, const Act& d, int64_t P, int ops, int cnt, int pubq, const CrtInfo& crt, int B,
+                        hipStream_t st);
+void launch_argmax_hash(const Act& d, const CrtInfo& crt, int64_t N, u128* hx, uint16_t* colx, uint64_t gate0, int B,
+                        const ModC* mc, const AesGlobals& g, hipStream_t st);
+void launch_argmax_mult(const ArgMaxArgs& a, bool val, bool l0, const Act& v, const Act& d, const Act& i, const Act& ed,
+                        const Act& nv, const Act& ni, int B, const ModC* mc, hipStream_t st);
 void launch_relu_mult(const SignArgs& a, const Act& x, const Act& y, const u128* gtab, const u128* etab,
                       const ModC* mc, hipStream_t st);
 void launch_rescale_hash(const Act& x, int fi, int s, const int16_t* up, int up_stride, int add_up, int64_t N, int B,

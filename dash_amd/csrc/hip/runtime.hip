@@ -698,6 +698,11 @@ class HipEvaluator {
     const int16_t* up_rows_ = nullptr;
     u128* mrs_ps_ = nullptr;  // mixed-radix rescale chain scratch (allocated by the first such layer)
     u128* ks_[2] = {nullptr, nullptr};  // [B][maxSignN] a Clip's two sign labels (allocated by the first Clip)
+    // ArgMax scratch (allocated by the first ArgMax): candidate values / index labels of the odd levels, the value
+    // and index differences; the index gates' garbler-half pads and colours
+    Act amb_[4] = {};
+    u128* am_hi_ = nullptr;
+    uint16_t* am_coli_ = nullptr;
     i64 maxSignN_ = 0;
     // planner: a sign-producing rescale whose outputs the next (joint) ReLU's op writes
     bool joint_pending_ = false;
@@ -780,7 +785,7 @@ void HipEvaluator::build() {
     // ---- shape pass: buffer capacities
     N0_ = 1;
     for (auto d : m0.h.in_dims) N0_ *= d;
-    i64 maxN = N0_, maxSignN = 1, maxPoolSlots = 1;
+    i64 maxN = N0_, maxSignN = 1, maxPoolSlots = 1, maxArgSlots = 0;
     std::vector<int> widest(k_, 0), mods = crt_;
     for (int j = 0; j < k_; ++j) widest[j] = nr_comps(crt_[j]);
     {
@@ -805,6 +810,13 @@ void HipEvaluator::build() {
                     maxSignN = std::max(maxSignN, N);
                     N = 1;
                     break;
+                case K_ARGMAX: {  // the widest level: floor(K / 2) pair operations, ceil(K / 2) slots behind it
+                    const i64 K = l.param("K"), P = l.param("P");
+                    maxSignN = std::max(maxSignN, (K / 2) * P);
+                    maxArgSlots = std::max(maxArgSlots, ((K + 1) / 2) * P);
+                    N = P;
+                    break;
+                }
                 case K_SUMPOOL: N = PoolGeom(l.p).out_size(); break;
                 case K_CONCAT:
                     N = 0;
@@ -1519,6 +1531,116 @@ void HipEvaluator::build() {
                     launch_copy_gather(vres, Nout, y, Nout, did, crt, B, st);
                 });
                 N = Nout;
+                cur = nxt;
+                break;
+            }
+            case K_ARGMAX: {
+                // gadgets.h ArgMaxPlan. The (K, P) input is level 0's candidate buffer as it stands; later levels
+                // ping-pong between bufs 2 / 3 (values / index labels) and the ArgMax scratch; the root writes
+                // its index labels into the layer's output buffer.
+                DASH_CHECK(hard_, "the ArgMax layer exists in the hardened encoding only");
+                const i64 K = g.param("K"), P = g.param("P");
+                DASH_CHECK(K >= 2 && K * P == N, "argmax input size mismatch");
+                const ArgMaxPlan ap(crt_, K);
+                if (!amb_[0].p[0]) {
+                    for (auto& ab : amb_)
+                        for (int j = 0; j < k_; ++j) {
+                            const size_t count = static_cast<size_t>(B_) * widest[j] * maxArgSlots + 64;
+                            ab.p[j] = dalloc<act_t>(count);
+                            HIPCHECK(hipMemset(ab.p[j], 0, count * sizeof(act_t)));
+                        }
+                    am_hi_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * maxSignN_);
+                    am_coli_ = dalloc<uint16_t>(static_cast<size_t>(B_) * k_ * maxSignN_);
+                }
+                if (!ks_[0]) ks_[0] = dalloc<u128>(static_cast<size_t>(B_) * maxSignN_);
+                if (!mrs_ps_) mrs_ps_ = dalloc<u128>(static_cast<size_t>(B_) * std::max(1, k_ * (k_ - 1) / 2) * maxSignN_);
+                const ModC* mc = mc_;
+                const AesGlobals ag = aes_;
+                const int B = B_;
+                Act V = act_of(cur), I = act_of(3);
+                const Act D = amb_[2], E = amb_[3];
+                for (int lv = 0; lv < ap.levels(); ++lv) {
+                    const bool root = ap.root(lv), l0 = lv == 0;
+                    const int ops = ap.ops[lv], cnt = ap.cnt[lv];
+                    const i64 Nops = P * ops;
+                    const std::string pre = arr_name("lv", lv, ".");
+                    const std::string op = lname + ".lv" + std::to_string(lv);
+                    // outputs: values into buf 2 / scratch 0, index labels into buf 3 / scratch 1, alternating
+                    const Act NV = (lv % 2 == 0) ? act_of(2) : amb_[0];
+                    const Act NI = root ? act_of(nxt) : ((lv % 2 == 0) ? act_of(3) : amb_[1]);
+                    ArgMaxArgs a{};
+                    a.crt = crt;
+                    a.P = P;
+                    a.ops = ops;
+                    a.cnt = cnt;
+                    a.cnt1 = ap.cnt[lv + 1];
+                    a.pubq = ap.pub[lv][cnt - 1] >= 0 && cnt % 2 == 0 ? ops - 1 : -1;
+                    a.carry_idx = cnt % 2 == 1 && ap.pub[lv][cnt - 1] < 0;
+                    a.ks = ks_[0];
+                    a.hx = hx_;
+                    a.colx = colx_;
+                    a.hi = am_hi_;
+                    a.coli = am_coli_;
+                    a.vgate0 = gate_base(li + 1, 21 + 3 * lv);
+                    a.igate0 = gate_base(li + 1, 22 + 3 * lv);
+                    if (!root) {
+                        a.gtab = upload_tables(li, pre + "mm.g");
+                        a.etab = upload_tables(li, pre + "mm.e");
+                    }
+                    if (l0) {
+                        a.itab = upload_tables(li, pre + "idx");
+                    } else {
+                        a.igtab = upload_tables(li, pre + "im.g");
+                        a.ietab = upload_tables(li, pre + "im.e");
+                    }
+                    MrsArgs s{};
+                    s.crt = crt;
+                    s.N = Nops;
+                    s.n_tab = g.arr(pre + "mrs").shape[1];
+                    s.tab = upload_tables(li, pre + "mrs");
+                    for (int i = 0; i + 1 < k_; ++i) s.dig_off[i] = ap.sign.dig_off[i];
+                    s.ps = mrs_ps_;
+                    s.mode = 1;
+                    s.hs = hs_;
+                    s.cs = cs_;
+                    s.gate0 = gate_base(li + 1, 20 + 3 * lv);
+                    s.rgate0 = a.vgate0;
+                    s.ny = 0;  // no y-row pads: the multiply derives the pads of both gate sets from the label
+                    s.ys = ys_;
+                    s.ks = ks_[0];
+                    add_op(op + ".diff", [V, D, P, ops, cnt, crt, B](hipStream_t st) {
+                        launch_argmax_diff(V, D, P, ops, cnt, -1, crt, B, st);
+                    });
+                    if (!l0) {
+                        const int pubq = a.pubq;
+                        add_op(op + ".idiff", [I, E, P, ops, cnt, pubq, crt, B](hipStream_t st) {
+                            launch_argmax_diff(I, E, P, ops, cnt, pubq, crt, B, st);
+                        });
+                    }
+                    if (!root) {
+                        u128* hx = hx_;
+                        uint16_t* colx = colx_;
+                        const uint64_t vg = a.vgate0;
+                        add_op(op + ".H", [D, crt, Nops, hx, colx, vg, B, mc, ag](hipStream_t st) {
+                            launch_argmax_hash(D, crt, Nops, hx, colx, vg, B, mc, ag, st);
+                        });
+                    }
+                    if (!l0) {
+                        u128* hi = am_hi_;
+                        uint16_t* coli = am_coli_;
+                        const uint64_t ig = a.igate0;
+                        add_op(op + ".iH", [E, crt, Nops, hi, coli, ig, B, mc, ag](hipStream_t st) {
+                            launch_argmax_hash(E, crt, Nops, hi, coli, ig, B, mc, ag, st);
+                        });
+                    }
+                    add_op(op + ".mrs", [s, D, B, mc, ag](hipStream_t st) { launch_clip_sign_mrs(s, D, B, mc, ag, st); });
+                    add_op(op + ".C", [a, root, l0, V, D, I, E, NV, NI, B, mc](hipStream_t st) {
+                        launch_argmax_mult(a, !root, l0, V, D, I, E, NV, NI, B, mc, st);
+                    });
+                    V = NV;
+                    I = NI;
+                }
+                N = P;
                 cur = nxt;
                 break;
             }

@@ -34,6 +34,7 @@ enum Kind : int {
     K_SUMPOOL = 13,
     K_CONCAT = 14,
     K_CLIP = 15,
+    K_ARGMAX = 16,
 };
 const char* kind_name(int kind);
 

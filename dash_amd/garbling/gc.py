@@ -26,6 +26,7 @@ from ..ir.layers import Kind as _Kind
 from ..native import native
 
 _CLIP = _Kind.CLIP
+_ARGMAX = _Kind.ARGMAX
 
 Labels = list  # list[(modulus, np.ndarray int16 [N, n_p])]
 
@@ -191,9 +192,19 @@ class GarbledCircuit:
             raise ValueError("layer %d (clip): the Clip layer exists in the hardened encoding only (%s)" % (
                 clips[0], "hardened=False was asked for" if supported else
                 "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
+        # an ArgMax folds public indices into base labels, keys several rows with one sign label and uses the
+        # exact mixed-radix sign only (gadgets.h ArgMaxPlan): hardened encoding, residue 0 = 2, odd other residues
+        argmaxes = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _ARGMAX]
+        if argmaxes and not (supported if hardened is None else hardened):
+            raise ValueError("layer %d (argmax): the ArgMax layer exists in the hardened encoding only (%s)" % (
+                argmaxes[0], "hardened=False was asked for" if supported else
+                "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
+        if argmaxes and not mrs_capable(self.crt_base):
+            raise ValueError("layer %d (argmax): the ArgMax layer's exact sign needs a CRT base with residue 0 = 2 "
+                             "and odd other residues, got %s" % (argmaxes[0], self.crt_base))
         # the mixed-radix constructions are this framework's own (not wire-compatible with anything): they only
         # exist in the hardened encoding, whose kernels they use
-        needs = self.rescale == "mrs" or self.relu in ("mrs", "joint")
+        needs =self.rescale == "mrs" or self.relu in ("mrs", "joint")
         if hardened is None:
             hardened = supported
             if not supported:

@@ -24,8 +24,8 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
 * on a GPU, ``DevRangeGuard`` (csrc/hip/guard.hip): one HIP launch per layer over chunks of the batch,
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
   evaluation; inputs whose activations exceed the int32 operand range are re-decided by the numpy model. It
-  has no Concat, no Clip and no padded / ceil-mode pooling: circuits with any of them take the torch path on
-  the GPU;
+  has no Concat, no Clip, no ArgMax and no padded / ceil-mode pooling: circuits with any of them take the
+  torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
 * the per-input numpy model (``violations_np``), the exact reference of both and the path of layers without a
@@ -63,11 +63,12 @@ class RangeGuard:
         self.joint_clips = {int(i): int(t) for i, t in (joint_clips or {}).items()}
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
-                                          L.SumPool2d, L.Add, L.Concat, L.Clip, L.Projection, L.BaseExtension))
+                                          L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Projection,
+                                          L.BaseExtension))
                            for l in circuit.layers)
-        # DevRangeGuard (guard.hip) has no Concat, no Clip and no padded / ceil-mode pooling: such circuits take
-        # the batched torch path
-        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip)) or
+        # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax and no padded / ceil-mode pooling: such
+        # circuits take the batched torch path
+        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
         self._stream = None
@@ -85,7 +86,7 @@ class RangeGuard:
             if idx + 1 in self.joint_clips:  # the joint Clip's upper sign input x - t_hi is a signed CRT value
                 lo = lo + self.joint_clips[idx + 1]
             return lo, hi
-        if isinstance(layer, (L.Relu, L.Sign, L.MaxPool2d, L.Max)):
+        if isinstance(layer, (L.Relu, L.Sign, L.MaxPool2d, L.Max, L.ArgMax)):
             return lo, hi
         if isinstance(layer, L.Clip):
             if idx in self.joint_clips:  # its signs were taken at the rescale before it
@@ -95,7 +96,8 @@ class RangeGuard:
         return None
 
     def span_max(self) -> int:
-        """Largest max - min of a max-pooling window whose pairwise differences are all signed CRT values."""
+        """Largest max - min of a max-pooling window (or of an ArgMax's candidates) whose pairwise differences
+        are all signed CRT values."""
         h = _half(self.M)
         return min(h, self.M - h - 1)
 
@@ -116,6 +118,11 @@ class RangeGuard:
             if isinstance(l, L.MaxPool2d) and inp.size:
                 w = np.stack(l._windows(inp))
                 span = int((w.max(axis=0) - w.min(axis=0)).max())
+                if span > self.span_max():
+                    bad.append((i, "span", span, 0, self.span_max()))
+            if isinstance(l, L.ArgMax) and inp.size:
+                v = inp.reshape(l.K, l.P)
+                span = int((v.max(axis=0) - v.min(axis=0)).max())
                 if span > self.span_max():
                     bad.append((i, "span", span, 0, self.span_max()))
             cur = l.plain_q_eval(inp, False, ctx, M)
@@ -201,6 +208,10 @@ class RangeGuard:
                 out = torch.where(inp >= 0, 1, -1).to(torch.int64)
             elif isinstance(l, L.Clip):
                 out = torch.clamp(inp, l.q_lo, l.q_hi)
+            elif isinstance(l, L.ArgMax):
+                v = inp.view(B, l.K, l.P)
+                bad |= ((v.amax(dim=1) - v.amin(dim=1)) > self.span_max()).any(dim=1)
+                out = torch.argmax(v, dim=1)  # the first of equal maxima, as np.argmax
             elif isinstance(l, L.MaxPool2d):
                 v = inp.view(B, l.C, l.H, l.W)
                 out = mn = None

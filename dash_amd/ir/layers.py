@@ -36,6 +36,7 @@ class Kind:
     SUMPOOL = 13
     CONCAT = 14
     CLIP = 15
+    ARGMAX = 16
 
 
 def _size(d: Sequence[int]) -> int:
@@ -758,6 +759,46 @@ class Max(Layer):
 
     def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
         return np.asarray([np.max(np.asarray(x, dtype=np.int64))])
+
+
+class ArgMax(Layer):
+    """Index of the largest value along the first axis: (K,) -> (1,) or
+    (C, H, W) -> (1, H, W). Ties go to the lowest index (np.argmax; ONNX ArgMax
+    with select_last_index = 0). Scale-free, so it works under every
+    quantization scheme. Garbled as the max tournament over (value, index)
+    candidates with one exact sign per pair (csrc/gadgets.h ArgMaxPlan); the
+    output is an ordinary CRT label tensor."""
+
+    kind = Kind.ARGMAX
+    name = "argmax"
+
+    def __init__(self, dims):
+        dims = tuple(int(d) for d in dims)
+        if len(dims) not in (1, 3):
+            raise ValueError(f"argmax: the input is (K,) or (C, H, W), got {dims}")
+        self.K = dims[0]
+        if self.K < 2:
+            raise ValueError(f"argmax: needs at least 2 candidates along the first axis, got {self.K}")
+        self.P = _size(dims[1:])  # output positions
+        super().__init__(dims, (1,) + dims[1:])
+
+    def plain_eval(self, x, track=True, ctx=None):
+        y = np.argmax(np.asarray(x).reshape(self.K, self.P), axis=0).astype(np.float32)
+        if track:
+            self._track_f(y)
+        return y
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        v = np.asarray(x, dtype=np.int64).reshape(self.K, self.P)
+        y = np.argmax(v, axis=0).astype(np.int64)
+        if track:
+            # every difference of two candidates of a position may feed a sign: the extreme ones bound them all
+            span = v.max(axis=0) - v.min(axis=0)
+            self._track_q(y, span, -span)
+        return y
+
+    def garble_spec(self):
+        return self.kind, {"K": self.K, "P": self.P}
 
 
 class BaseExtension(Layer):

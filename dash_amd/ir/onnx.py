@@ -29,6 +29,12 @@ are quantized with the activation scale, which SimpleQuant does not have). A
 pending average factor f passes through with the bounds divided by f:
 clip(f x, lo, hi) = f clip(x, lo / f, hi / f).
 
+`ArgMax` along axis 1 (the classes of an [N, K] tensor, the channels of NCHW;
+or the equivalent negative axis) becomes an `ArgMax` layer. Either `keepdims`
+is accepted, since the batch-free dims (1,) / (1, H, W) are the same; any
+other axis and `select_last_index = 1` are refused with the node's name. The
+index drops a pending (positive) average factor, as a Sign does.
+
 `ReduceSum` over (2, 3) is the plane `SumPool2d` itself (the exporter writes a
 global sum pool that no linear layer follows this way).
 
@@ -57,7 +63,7 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import Add, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
+from .layers import Add, ArgMax, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -334,6 +340,18 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                     raise ValueError(f"onnx: {name}: Clip needs min < max, got ({lo}, {hi})")
                 # clip(f x, lo, hi) = f clip(x, lo / f, hi / f): the pending factor passes through
                 emit(_Spec("clip", dims=dims, lo=lo / fac, hi=hi / fac), outs[0], j, dims, fac)
+        elif op == "ArgMax":
+            j, dims, fac = data_in(node, ins[0])
+            name = node.get("name") or op
+            axis, nd = int(a.get("axis", 0)), len(dims) + 1  # dims leave the batch axis out
+            if tf or len(dims) not in (1, 3) or axis not in (1, 1 - nd):
+                raise NotImplementedError(f"onnx: {name}: ArgMax is supported along axis 1 (the classes of an [N, K] "
+                                          f"tensor, the channels of NCHW) only, got axis {axis} of a rank-{nd} tensor")
+            if int(a.get("select_last_index", 0)):
+                raise NotImplementedError(f"onnx: {name}: ArgMax with select_last_index=1 is not supported (ties go "
+                                          "to the lowest index)")
+            # keepdims only shapes the output; the index drops a pending positive factor
+            emit(_Spec("argmax", dims=dims, keepdims=int(a.get("keepdims", 1))), outs[0], j, (1,) + tuple(dims[1:]))
         elif op in ("Tanh", "SignTanh", "Sign"):
             j, dims, fac = data_in(node, ins[0])
             emit(_Spec("sign", dims=dims), outs[0], j, dims)  # the sign drops a positive factor
@@ -397,6 +415,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             layers.append(Sign(kw["dims"]))
         elif s.kind == "clip":
             layers.append(Clip(kw["dims"], kw["lo"], kw["hi"], q_parameter, q_method))
+        elif s.kind == "argmax":
+            layers.append(ArgMax(kw["dims"]))
         elif s.kind == "add":
             layers.append(Add(kw["dims"], spec_to_layer[kw["src"]]))
         elif s.kind == "concat":
@@ -563,6 +583,8 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             scale[out] = K
         elif isinstance(l, Sign):
             nodes.append(_node("Sign", [cur], [out], name))
+        elif isinstance(l, ArgMax):  # scale-free: a pending average ratio ends here
+            nodes.append(_node("ArgMax", [cur], [out], name, _attr_int("axis", 1) + _attr_int("keepdims", 1)))
         elif isinstance(l, Add):
             nodes.append(_node("Add", [cur, names[l.src]], [out], name))
         elif isinstance(l, Concat):

@@ -91,6 +91,11 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
         elif k == "sumpool":
             mods.append(nn.AvgPool2d(op[1]))
             dims = [dims[0], dims[1] // op[1], dims[2] // op[1]]
+        elif k == "argmax":
+            # to_circuit maps modules to layers one to one and the loss needs the logits: no module stands for an
+            # index, so the model is refused instead of silently training something else
+            raise NotImplementedError(f"training: {name} ends in an argmax, which has no gradient; train the model "
+                                      "without the op (MODEL_A for MODEL_A_ARGMAX) and append ArgMax to its circuit")
         else:
             raise NotImplementedError(f"training: op {k} (residual blocks, fire modules, global pooling) not supported "
                                       "by the sequential trainer")

@@ -12,7 +12,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import Add, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
+from ..ir.layers import Add, ArgMax, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
 from ..ir.quant import QuantizationMethod, quantize_input
 
 # architecture ops: ("conv", out_ch, k, stride, pad) | ("relu",) | ("sign",) | ("flatten",) | ("fc", out)
@@ -23,8 +23,13 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   then a 1x1 and a padded 3x3 expand (each + ReLU) that both read the squeeze output, then Concat
 #                   | ("relu6",) = Clip(0, 6) | ("clip", lo, hi) clamp with float bounds (quantized with the
 #                   scheme's activation scale; refused under SimpleQuant)
+#                   | ("argmax",) index of the largest value along the first axis (the class of a logit vector,
+#                   the per-pixel class of a (C, H, W) score map); scale-free
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
+    # MODEL_A whose decoded output is the class alone, not the ten logits
+    "MODEL_A_ARGMAX": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10),
+                                                     ("argmax",)]},
     "MODEL_B_POOL_REPL": {"input": (1, 28, 28), "ops": [
         ("conv", 5, 5, 1, 0), ("relu",), ("conv", 5, 3, 3, 0), ("relu",), ("conv", 10, 3, 1, 0), ("relu",),
         ("conv", 10, 3, 3, 0), ("flatten",), ("fc", 100), ("relu",), ("fc", 10)]},
@@ -163,6 +168,10 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
                 raise ValueError(f"{name}: op {len(layers)} ({kind}): a clip layer has no quantization under "
                                  "SimpleQuant (no single activation scale); use ScaleQuant or ScaleQuantPlus")
             layers.append(Clip(dims, lo, hi, q_parameter, qm))
+        elif kind == "argmax":
+            am = ArgMax(dims)
+            layers.append(am)
+            dims = am.out_dims
         elif kind == "maxpool":
             k, s = op[1], op[2]
             pad, ceil = (op[3], op[4]) if len(op) > 3 else (0, False)
@@ -252,5 +261,7 @@ BENCH_CONFIGS = {
                                  crt=7, mrs=100.0),
     "SQUEEZENET_CIFAR/DASH": dict(model="SQUEEZENET_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
                                   crt=7, mrs=100.0),
+    "MODEL_A_ARGMAX/SIMPLE": dict(model="MODEL_A_ARGMAX", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8,
+                                  mrs=100.0),
     "MODEL_A/SIMPLE": dict(model="MODEL_A", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8, mrs=100.0),
 }
