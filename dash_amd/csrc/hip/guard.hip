@@ -17,6 +17,19 @@
 //   k_g_out    the outputs' signed range
 // Flags per input (int32): bit 0 = a range violation, bit 1 = an activation beyond the int32 operand range of
 // the linear layers (the exact int64 host model decides those, guard.py).
+// Operand and accumulator bounds (pinned at their edges by tests/guard_cases.py, tests/test_gpu_range_guard.py):
+//   24-bit conv form  weights |w| <= 2^23 - 1 and operands |x| <= asafe = min(2^23 - 1, (2^31 - 1) / max_f sum|w_f|):
+//                     every partial sum stays inside int32 (the worst case, every operand +-asafe with its weight's
+//                     sign, is exact); the first operand beyond +-asafe marks its input uncertain
+//   64-bit forms      (conv with a weight >= 2^23 or DASH_GUARD_I24=0, dense) operands in [-2^31, 2^31 - 1] are exact,
+//                     2^31 and -2^31 - 1 mark the input uncertain. The int64 accumulator holds sum|w| * 2^31 + |bias|
+//                     only while sum_k |w_fk| < 2^32 per row: the quantized model-zoo rows are below 2^10
+//                     (tests/test_guard_cases.py test_zoo_rows_fit_the_int64_accumulator), so no layer is refused
+//   an uncertain input's activations are not exact from that layer on: its bit 0 means nothing, the host model
+//   decides it (guard.py PendingCheck.bad_indices)
+// Test hook: peek_output(rows) copies the first rows of the final layer's activations of the last chunk that ran
+// to the host, synchronously, after wait(). It adds nothing to submit(), enqueue() or the captured graphs; tests
+// reach an intermediate layer by truncating a small circuit there.
 // Reference semantics: rescale_gadget.h:115-242 (exact on the whole signed range), circuit.h:159-265 (range
 // tracking); the reference has no run-time guard.
 #include <hip/hip_runtime.h>
@@ -506,6 +519,26 @@ class DevRangeGuard {
         t->busy = false;
         return out;
     }
+    // test hook (see the header): the first `rows` rows of the final layer's activations of the last chunk that
+    // ran, read after wait(). Off the checked path: nothing here is launched, captured or stored by submit().
+    // rows must not exceed the inputs of that last chunk (rows beyond them hold an earlier chunk's values)
+    std::vector<int64_t> peek_output(int64_t rows) {
+        std::lock_guard<std::mutex> lk(mu_);
+        DASH_CHECK(rows >= 0 && rows <= chunk_, "DevRangeGuard::peek_output: more rows than a chunk holds");
+        hostutil::bind_device(dev_, st_, "DevRangeGuard::peek_output");
+        const Layer& last = layers_.back();
+        std::vector<int64_t> out(static_cast<size_t>(rows * last.out_size));
+        if (out.empty()) return out;
+        const int64_t stride = buf_elems_[last.buf];  // rows <= chunk_: inside the buffer's chunk_ * stride
+        std::vector<int64_t> raw(static_cast<size_t>((rows - 1) * stride + last.out_size));
+        HIPCHECK(hipStreamSynchronize(st_));
+        HIPCHECK(hipMemcpy(raw.data(), bufs_[last.buf], sizeof(int64_t) * raw.size(), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < rows; ++r)
+            std::copy_n(raw.data() + r * stride, last.out_size, out.data() + r * last.out_size);
+        return out;
+    }
+    int64_t output_size() const { return layers_.back().out_size; }
+    int chunk() const { return chunk_; }
     int64_t input_size() const { return N_; }
     size_t device_bytes() const {
         size_t s = 0;
@@ -646,6 +679,17 @@ void register_guard_bindings(py::module_& m) {
             return g.submit(p, B);
         })
         .def("wait", &DevRangeGuard::wait, py::call_guard<py::gil_scoped_release>())
+        .def("peek_output", [](DevRangeGuard& g, int64_t rows) {
+            std::vector<int64_t> v;
+            {
+                py::gil_scoped_release rel;
+                v = g.peek_output(rows);
+            }
+            py::array_t<int64_t> a({static_cast<py::ssize_t>(rows), static_cast<py::ssize_t>(g.output_size())});
+            std::copy(v.begin(), v.end(), a.mutable_data());
+            return a;
+        }, py::arg("rows"))
+        .def("chunk", &DevRangeGuard::chunk)
         .def("device_bytes", &DevRangeGuard::device_bytes)
         .def("input_size", &DevRangeGuard::input_size);
 }

@@ -23,7 +23,8 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
 
 * on a GPU, ``DevRangeGuard`` (csrc/hip/guard.hip): one HIP launch per layer over chunks of the batch,
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
-  evaluation; inputs whose activations exceed the int32 operand range are re-decided by the numpy model. It
+  evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
+  bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
   has no Concat, no Clip, no ArgMax and no padded / ceil-mode pooling: circuits with any of them take the
   torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
@@ -435,8 +436,10 @@ class PendingCheck:
             g, ticket = self.native
             f = np.asarray(g.wait(ticket))
             self.native = None
-            self._bad = [int(i) for i in np.nonzero(f & 1)[0]]
-            self._bad += [int(i) for i in np.nonzero(f == 2)[0] if self.guard.violations_np(self.xs[i])]
+            # an uncertain input's device activations are not exact from the layer that marked it on, so its
+            # bit 0 means nothing either way (a wrapped 24-bit sum can look like a violation): the host decides
+            self._bad = [int(i) for i in np.nonzero(f == 1)[0]]
+            self._bad += [int(i) for i in np.nonzero(f & 2)[0] if self.guard.violations_np(self.xs[i])]
             self._bad.sort()
             return self._bad
         if self.flags is None:  # per-input numpy path

@@ -14,6 +14,7 @@ import pytest
 import dash_amd as d
 from dash_amd.garbling import GarbledCircuit, RangeGuard, RangeGuardError
 from dash_amd.ir.bases import crt_modulus, first_primes
+from tests.guard_cases import simulate_spec as _simulate_spec
 
 K = 6
 M = crt_modulus(first_primes(K))
@@ -144,74 +145,6 @@ def test_batched_outputs_equal_plain_q_eval():
 
 
 # ---------------------------------------------------------------- the native (DevRangeGuard) description
-def _simulate_spec(spec, xs):
-    """Numpy interpreter of RangeGuard.native_spec with the kernels' semantics (csrc/hip/guard.hip), buffers
-    shared exactly as the spec assigns them: a CPU check of the description the GPU guard runs."""
-    X = np.asarray(xs, dtype=np.int64)
-    B = X.shape[0]
-    bufs = [np.full((B, e), 7777777, dtype=np.int64) for e in spec["buf_elems"]]
-    flags = np.zeros(B, dtype=bool)
-
-    def ctx(i):
-        return X if i == 0 else bufs[spec["ctx_buf"][i]]
-
-    def post(ops, y):
-        nonlocal flags
-        for o in ops:
-            if o.get("check"):
-                flags |= ((y < o["lo"]) | (y >= o["hi"])).any(axis=1)
-            k = o["kind"]
-            if k == 2:
-                for _ in range(o["l"]):
-                    y = (y + o["c"]) >> 1
-            elif k == 3:
-                y = (y + o["c"]) // o["S"]
-            elif k == 4:
-                y = np.maximum(y, 0)
-            elif k == 5:
-                y = np.where(y >= 0, 1, -1)
-        return y
-
-    for d in spec["layers"]:
-        x = ctx(d["src"])[:, :d["in_size"]].copy()
-        k = d["kind"]
-        if k == 0:
-            C, H, W = d["C"], d["H"], d["W"]
-            xp = np.pad(x.reshape(B, C, H, W), ((0, 0), (0, 0), (d["ph"], d["ph"]), (d["pw"], d["pw"])))
-            w = d["w"].astype(np.int64).reshape(d["F"], C, d["kh"], d["kw"])
-            y = np.zeros((B, d["F"], d["OH"], d["OW"]), np.int64)
-            for dy in range(d["kh"]):
-                for dx in range(d["kw"]):
-                    win = xp[:, :, dy:dy + d["sh"] * (d["OH"] - 1) + 1:d["sh"], dx:dx + d["sw"] * (d["OW"] - 1) + 1:d["sw"]]
-                    y += np.einsum("bchw,fc->bfhw", win, w[:, :, dy, dx])
-            y = (y + d["b"][None, :, None, None]).reshape(B, -1)
-        elif k == 1:
-            xin = x if d.get("perm") is None else x[:, d["perm"]]
-            y = xin @ d["w"].astype(np.int64).T + d["b"]
-        elif k in (6, 7):
-            v = x.reshape(B, d["C"], d["H"], d["W"])
-            ws = [v[:, :, dy:dy + d["sh"] * (d["OH"] - 1) + 1:d["sh"], dx:dx + d["sw"] * (d["OW"] - 1) + 1:d["sw"]]
-                  for dy in range(d["kh"]) for dx in range(d["kw"])]
-            st = np.stack(ws)
-            if d.get("check"):
-                flags |= ((x < d["lo"]) | (x >= d["hi"])).any(axis=1)
-            if k == 6:
-                y = st.max(axis=0)
-                if d.get("check"):
-                    flags |= ((st.max(axis=0) - st.min(axis=0)).reshape(B, -1) > d["span_max"]).any(axis=1)
-            else:
-                y = st.sum(axis=0)
-            y = y.reshape(B, -1)
-        elif k == 8:
-            y = x + ctx(d["add_src"])[:, :d["in_size"]]
-        else:
-            y = x
-        bufs[d["buf"]][:, :d["out_size"]] = post(d.get("post", []), y)
-    out = bufs[spec["layers"][-1]["buf"]][:, :spec["layers"][-1]["out_size"]]
-    flags |= ((out < spec["out_lo"]) | (out >= spec["out_hi"])).any(axis=1)
-    return [int(i) for i in np.nonzero(flags)[0]], out
-
-
 def _residual_circuit():
     """conv -> rescale -> relu -> conv -> add(residual of the relu) -> maxpool -> flatten -> dense: a live
     value held across layers (buffer sharing) and a max-pooling span check."""
