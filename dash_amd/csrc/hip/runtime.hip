@@ -568,8 +568,12 @@ class HipEvaluator {
     }
 
     // sign gadget phases over `x` (N elements); results in sign scratch
-    SignArgs make_sign(size_t li, const std::string& pre, const SignPlan& sp, i64 N, int relu, uint64_t sgate0 = 0,
-                       uint64_t mgate0 = 0) {
+    struct Sign {
+        SignArgs a;
+        int maxn;  // widest label of the carry chain (launch_sign_chain's template pick)
+    };
+    Sign make_sign(size_t li, const std::string& pre, const SignPlan& sp, i64 N, int relu, uint64_t sgate0 = 0,
+                   uint64_t mgate0 = 0) {
         SignArgs a{};
         a.hard = hard_ ? 1 : 0;
         a.sgate0 = sgate0;
@@ -617,12 +621,186 @@ class HipEvaluator {
         for (size_t d = 1; d < sp.mrs.size(); ++d) maxn = std::max(maxn, nr_comps((k + 1) * sp.mrs[d]));
         maxn = std::max(maxn, nr_comps(sp.mrs[0]));
         DASH_CHECK(maxn <= 64, "MRS moduli too small for the GPU sign chain (label width > 64)");
-        sign_maxn_ = maxn;
+        return {a, maxn};
+    }
+
+    // ------------------------------------------------------------ planner
+    // build() is the driver: constants, shape pass, buffers, one plan_<kind> per layer, output staging. What the
+    // walk over the layers knows lives in a Walk on build()'s stack; nothing of it outlives build().
+    struct Env {  // what almost every op needs besides its own arguments; captured by value
+        const ModC* mc;
+        AesGlobals ag;
+        int B;
+    };
+    struct Caps {  // shape pass: buffer capacities in elements per GC, label widths, every layer's output size
+        i64 maxN, maxSignN, maxPoolSlots, maxArgSlots;
+        std::vector<int> widest;  // [j] widest label of residue j's buffer (projections change the moduli)
+        std::vector<i64> outN;    // [slot] slot 0: the circuit input, slot li + 1: layer li's output
+    };
+    struct Walk {
+        Env env;
+        Caps caps;
+        CrtInfo crt;            // of crt_
+        int cur = 0;            // buffer index holding the current activation
+        i64 N = 0;              // its elements per GC
+        std::vector<int> mods;  // its moduli
+        std::vector<int> keep;  // [slot] a later layer reads this output (Add, Concat, in_src): save_if_needed
+        std::vector<i64> saved_n;  // [slot] elements and moduli of the copies in saved_
+        std::vector<std::vector<int>> saved_mods;
+        // a sign-producing rescale whose outputs the next layer's op writes in its own pass: a joint ReLU's
+        // launch_rescale_relu_out or a joint Clip's launch_rescale_clip_out. At most one is pending.
+        enum class Pending { none, relu, clip } pending = Pending::none;
+        MrsArgs pending_a{};
+        int nxt() const { return (cur + 1) % 2; }
+    };
+    // The one statement of a layer's output element count: the shape pass sizes the buffers with it and every
+    // planner checks the N it leaves against it (set_out).
+    static i64 out_elems(const GLayer& l, i64 N_in, const std::vector<i64>& outN) {
+        switch (l.kind) {
+            case K_DENSE: return l.param("out");
+            case K_CONV: return ConvGeom(l).out_size();
+            case K_MAXPOOL: case K_SUMPOOL: return PoolGeom(l.p).out_size();
+            case K_MAX: return 1;
+            case K_ARGMAX: return l.param("P");
+            case K_CONCAT: {
+                i64 N = 0;
+                for (i64 s : l.vec("srcs")) {
+                    DASH_CHECK(s >= -1 && s + 1 < static_cast<i64>(outN.size()), "concat: bad source layer");
+                    N += outN[s + 1];
+                }
+                return N;
+            }
+            case K_MULT: case K_MMULT: return N_in / 2;
+            default: return N_in;
+        }
+    }
+    // a planner's last step: its output, N elements, is in buffer `buf` (w.nxt(), or w.cur for an in-place layer)
+    void set_out(Walk& w, const GLayer& g, i64 N, int buf) const {
+        DASH_CHECK(N == out_elems(g, w.N, w.caps.outN),
+                   std::string("planner and shape pass disagree on the output size of ") + kind_name(g.kind));
+        w.N = N;
+        w.cur = buf;
+    }
+    template <typename A>
+    void set_label_rows(A& a) const {  // DenseArgs, ConvArgs, RescaleArgs: the zero-label rows and their layout
+        a.zero = zero_rows_;
+        a.lab_stride = lab_stride_;
+        for (int j = 0; j < k_; ++j) a.lab_off[j] = lab_off_[j];
+    }
+    // factor f of a RescalePlan: the residues it updates, their trans rows and the factor residue's hashes
+    void set_active(RescaleArgs& ra, const RescalePlan& P, size_t f, const u128* trans) const {
+        for (size_t q = 0; q < P.active[f].size(); ++q) {
+            const int jj = P.active[f][q];
+            ra.active[jj] = 1;
+            ra.aidx[jj] = static_cast<int>(q);
+            ra.inv[jj] = static_cast<int>(P.inv[f][q]);
+        }
+        ra.n_trans = P.n_trans;
+        ra.trans = trans;
+        ra.h0 = h0_;
+        ra.col0 = col0_;
+    }
+    // scratch that only some layer kinds need, allocated by the first layer that does
+    void ensure_mrs_ps(const Walk& w) {
+        if (!mrs_ps_) mrs_ps_ = dalloc<u128>(static_cast<size_t>(B_) * std::max(1, k_ * (k_ - 1) / 2) * w.caps.maxSignN);
+    }
+    void ensure_ks(const Walk& w, int sides) {
+        for (int side = 0; side < sides; ++side)
+            if (!ks_[side]) ks_[side] = dalloc<u128>(static_cast<size_t>(B_) * w.caps.maxSignN);
+    }
+    // The exact mixed-radix sign's chain (mode 1, gadgets.h SignMrsPlan) over N elements with layer li's table
+    // `table`: a ReLU's (ny = ny_: the sign label's y-row pads), or with the label itself kept in `ks` and ny = 0
+    // for a Clip's two signs, a joint Clip's upper sign and an ArgMax level.
+    MrsArgs mrs_sign_args(const Walk& w, size_t li, const std::string& table, i64 N, uint64_t gate0, uint64_t rgate0,
+                          int ny, u128* ks) {
+        const SignMrsPlan P(crt_);
+        MrsArgs a{};
+        a.crt = w.crt;
+        a.N = N;
+        a.n_tab = tmpl_->layers[li].arr(table).shape[1];
+        a.tab = upload_tables(li, table);
+        for (int i = 0; i + 1 < k_; ++i) a.dig_off[i] = P.dig_off[i];
+        ensure_mrs_ps(w);
+        a.ps = mrs_ps_;
+        a.mode = 1;
+        a.hs = hs_;
+        a.cs = cs_;
+        a.gate0 = gate0;
+        a.rgate0 = rgate0;
+        a.ny = ny;
+        a.ys = ys_;
+        a.ks = ks;
         return a;
+    }
+    // the multiply of a ReLU whose sign label is already in hs_ / cs_ (joint and mixed-radix-sign ReLUs)
+    SignArgs joint_sign_args(const Walk& w, size_t li, i64 N) const {
+        SignArgs sa{};
+        sa.crt = w.crt;
+        sa.N = N;
+        sa.B = B_;
+        sa.hx = hx_;
+        sa.colx = colx_;
+        sa.hs = hs_;
+        sa.cs = cs_;
+        sa.hard = hard_ ? 1 : 0;
+        sa.mgate0 = gate_base(li + 1, 2);
+        sa.ny = ny_;
+        sa.ys = ys_;
+        return sa;
+    }
+    BEArgs be_args(const Walk& w, const BEPlan& be, size_t li, const std::string& table, i64 N, uint64_t gate0) {
+        BEArgs ba{};
+        ba.E = static_cast<int>(be.moduli.size());
+        ba.nonext = be.nonext;
+        std::vector<int> idx(ba.E);
+        for (int i = 0; i < ba.E; ++i) idx[be.pos_of[i]] = i;
+        for (int i = 0; i < ba.E; ++i) {
+            ba.swapped[i] = be.swapped[i];
+            ba.src[i] = idx[i];
+        }
+        for (int i = 0; i + 1 < ba.E; ++i)
+            for (size_t jj = 0; jj < be.inv_partial[i].size(); ++jj) ba.inv[i][jj] = static_cast<int>(be.inv_partial[i][jj]);
+        ba.nextra = static_cast<int>(be.extra.size());
+        for (int xi = 0; xi < ba.nextra; ++xi) {
+            ba.extra_res[xi] = be.extra_idx[xi];
+            ba.extra_pos[xi] = be.pos_of[be.extra_idx[xi]];
+            ba.invv[xi] = static_cast<int>(pmod(-be.invv[xi], be.moduli[be.extra_idx[xi]]));
+        }
+        ba.N = N;
+        ba.n_tab = be.n_tab;
+        ba.tab = upload_tables(li, table);
+        if (!be_work_) be_work_ = dalloc<int16_t>(static_cast<size_t>(B_) * k_ * 128 * w.caps.maxN);
+        ba.work = be_work_;
+        ba.hard = hard_ ? 1 : 0;
+        ba.gate0 = gate0;
+        return ba;
     }
 
     void build();
-    void plan_rescale_legacy(size_t li, i64 iters, i64 N, const CrtInfo& crt, const std::string& lname);
+    void upload_constants();
+    Caps shape_pass() const;
+    void alloc_buffers(const Caps& c);
+    void save_if_needed(Walk& w, size_t slot);
+    void restore_in_src(Walk& w, const GLayer& g);
+    void alloc_output_staging(const Walk& w);
+    void plan_dense(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_conv(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_relu(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_clip(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_sign(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_rescale(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_rescale_mrs(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_rescale_clip(Walk& w, size_t li, MrsArgs a, const std::string& lname);
+    void plan_rescale_legacy(Walk& w, size_t li, i64 iters, Act x, const std::string& lname);
+    void plan_rescale_redash(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_max(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_argmax(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_sumpool(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_add(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_concat(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_proj(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_mult(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname);
 
     std::shared_ptr<GarbledModel> tmpl_;  // build() only
     ModelHeader tmpl_h_;
@@ -673,7 +851,6 @@ class HipEvaluator {
     std::vector<hipEvent_t> ev_;
     Act bufs_[4]{};  // ping-pong activation buffers (+ scratch)
     Act final_{};
-    Act cur_act_{};
     std::vector<int16_t*> in_stage_;
     std::vector<act_t*> out_stage_;
     std::vector<void*> out_stage_dev_;  // device addresses of the mapped out_stage_ buffers
@@ -703,13 +880,6 @@ class HipEvaluator {
     Act amb_[4] = {};
     u128* am_hi_ = nullptr;
     uint16_t* am_coli_ = nullptr;
-    i64 maxSignN_ = 0;
-    // planner: a sign-producing rescale whose outputs the next (joint) ReLU's op writes
-    bool joint_pending_ = false;
-    MrsArgs joint_a_{};
-    // the same for a joint Clip (launch_rescale_clip_out)
-    bool clip_pending_ = false;
-    MrsArgs clip_a_{};
     const u128* zc_ = nullptr;
     const u128* zh_ = nullptr;
     const uint16_t* zcol_ = nullptr;
@@ -720,15 +890,72 @@ class HipEvaluator {
     uint8_t* cs_ = nullptr;
     int16_t* csum_ = nullptr;
     int16_t* be_work_ = nullptr;
-    int sign_maxn_ = 32;
     std::vector<std::vector<act_t*>> saved_;  // residual-add sources
 };
 
 void HipEvaluator::build() {
     const GarbledModel& m0 = *tmpl_;
+    const size_t L = m0.layers.size();
     hard_ = m0.h.hardened != 0;
     ny_ = k_ + (k_ + 7) / 8;
-    // ---- global constants
+    upload_constants();
+    N0_ = 1;
+    for (auto d : m0.h.in_dims) N0_ *= d;
+    Walk w{Env{mc_, aes_, B_}, shape_pass(), crt_info(crt_)};
+    alloc_buffers(w.caps);
+
+    w.N = N0_;
+    w.mods = crt_;
+    w.keep.assign(L + 1, 0);
+    for (auto& l : m0.layers) {
+        if (l.kind == K_ADD) w.keep[l.param("src") + 1] = 1;
+        if (l.kind == K_CONCAT)
+            for (i64 s : l.vec("srcs")) w.keep[s + 1] = 1;
+        if (l.p.count("in_src")) w.keep[l.param("in_src") + 1] = 1;
+    }
+    saved_.assign(L + 1, {});
+    w.saved_n.assign(L + 1, 0);
+    w.saved_mods.assign(L + 1, {});
+    save_if_needed(w, 0);
+    if (stream_) init_streaming(m0);
+
+    for (size_t li = 0; li < L; ++li) {
+        const GLayer& g = m0.layers[li];
+        if (stream_) add_op("stage", [this, li](hipStream_t st) { stage_layer(li, st); });
+        const std::string lname = std::string(kind_name(g.kind)) + "#" + std::to_string(li);
+        if (g.p.count("in_src")) restore_in_src(w, g);
+        switch (g.kind) {
+            case K_FLATTEN: break;
+            case K_DENSE: plan_dense(w, li, g, lname); break;
+            case K_CONV: plan_conv(w, li, g, lname); break;
+            case K_RELU: plan_relu(w, li, g, lname); break;
+            case K_CLIP: plan_clip(w, li, g, lname); break;
+            case K_SIGN: plan_sign(w, li, g, lname); break;
+            case K_RESCALE: plan_rescale(w, li, g, lname); break;
+            case K_MAXPOOL: case K_MAX: plan_max(w, li, g, lname); break;
+            case K_ARGMAX: plan_argmax(w, li, g, lname); break;
+            case K_SUMPOOL: plan_sumpool(w, li, g, lname); break;
+            case K_ADD: plan_add(w, li, g, lname); break;
+            case K_CONCAT: plan_concat(w, li, g, lname); break;
+            case K_PROJ: plan_proj(w, li, g, lname); break;
+            case K_MULT: case K_MMULT: plan_mult(w, li, g, lname); break;
+            case K_BASEEXT: plan_base_ext(w, li, g, lname); break;
+            default:
+                throw std::runtime_error(std::string("dash: HIP evaluator cannot run layer kind ") + kind_name(g.kind));
+        }
+        save_if_needed(w, li + 1);
+    }
+    // a deferred rescale's output kernel is the next layer's op: left pending, it would never run
+    DASH_CHECK(w.pending == Walk::Pending::none, "planner: a deferred rescale output was never planned");
+    if (stream_) add_op("stage_end", [this](hipStream_t st) { stage_end(st); });
+    alloc_output_staging(w);
+    finish_small();
+    HIPCHECK(hipDeviceSynchronize());
+}
+
+// ---- global constants
+void HipEvaluator::upload_constants() {
+    const GarbledModel& m0 = *tmpl_;
     const int maxmod = m0.h.max_mod;
     std::vector<ModC> mc(maxmod + 1);
     for (int q = 2; q <= maxmod; ++q) mc[q] = make_modc(q);
@@ -781,1039 +1008,119 @@ void HipEvaluator::build() {
     bool any_rescale = false;
     for (auto& l : m0.layers) any_rescale |= (l.kind == K_RESCALE && l.param("mode", 0) != 2);  // mode 2: no shift labels
     if (any_rescale) up_rows_ = upload_const_rows([&](int j) { return "up." + std::to_string(j); });
+}
 
-    // ---- shape pass: buffer capacities
-    N0_ = 1;
-    for (auto d : m0.h.in_dims) N0_ *= d;
-    i64 maxN = N0_, maxSignN = 1, maxPoolSlots = 1, maxArgSlots = 0;
-    std::vector<int> widest(k_, 0), mods = crt_;
-    for (int j = 0; j < k_; ++j) widest[j] = nr_comps(crt_[j]);
-    {
-        i64 N = N0_;
-        std::vector<i64> outN(m0.layers.size() + 1, N0_);
-        size_t li0 = 0;
-        for (auto& l : m0.layers) {
-            if (l.p.count("in_src")) N = outN[l.param("in_src") + 1];
-            switch (l.kind) {
-                case K_DENSE: N = l.param("out"); break;
-                case K_CONV: N = ConvGeom(l).out_size(); break;
-                case K_RELU: case K_SIGN: case K_RESCALE: case K_CLIP: maxSignN = std::max(maxSignN, N); break;
-                case K_MAXPOOL: {
-                    PoolGeom G(l.p);
-                    maxPoolSlots = std::max(maxPoolSlots, G.out_size() * G.kh * G.kw);
-                    maxSignN = std::max(maxSignN, G.out_size() * G.kh * G.kw);
-                    N = G.out_size();
-                    break;
-                }
-                case K_MAX:
-                    maxPoolSlots = std::max(maxPoolSlots, N);
-                    maxSignN = std::max(maxSignN, N);
-                    N = 1;
-                    break;
-                case K_ARGMAX: {  // the widest level: floor(K / 2) pair operations, ceil(K / 2) slots behind it
-                    const i64 K = l.param("K"), P = l.param("P");
-                    maxSignN = std::max(maxSignN, (K / 2) * P);
-                    maxArgSlots = std::max(maxArgSlots, ((K + 1) / 2) * P);
-                    N = P;
-                    break;
-                }
-                case K_SUMPOOL: N = PoolGeom(l.p).out_size(); break;
-                case K_CONCAT:
-                    N = 0;
-                    for (i64 s : l.vec("srcs")) {
-                        DASH_CHECK(s >= -1 && s < static_cast<i64>(li0), "concat: bad source layer");
-                        N += outN[s + 1];
-                    }
-                    break;
-                case K_MULT: case K_MMULT: N /= 2; break;
-                case K_PROJ: {
-                    const auto& om = l.vec("out_mod");
-                    for (int j = 0; j < k_; ++j) widest[j] = std::max(widest[j], nr_comps(static_cast<int>(om[j])));
-                    break;
-                }
-                default: break;
+// ---- shape pass: buffer capacities. Output sizes come from out_elems; the scratch capacities are this pass's own.
+HipEvaluator::Caps HipEvaluator::shape_pass() const {
+    Caps c{N0_, 1, 1, 0, std::vector<int>(k_, 0), {N0_}};
+    for (int j = 0; j < k_; ++j) c.widest[j] = nr_comps(crt_[j]);
+    i64 N = N0_;
+    for (auto& l : tmpl_->layers) {
+        if (l.p.count("in_src")) N = c.outN.at(l.param("in_src") + 1);
+        const i64 No = out_elems(l, N, c.outN);
+        switch (l.kind) {
+            case K_RELU: case K_SIGN: case K_RESCALE: case K_CLIP: c.maxSignN = std::max(c.maxSignN, N); break;
+            case K_MAXPOOL: {
+                PoolGeom G(l.p);
+                c.maxPoolSlots = std::max(c.maxPoolSlots, No * G.kh * G.kw);
+                c.maxSignN = std::max(c.maxSignN, No * G.kh * G.kw);
+                break;
             }
-            maxN = std::max(maxN, N);
-            outN[++li0] = N;
+            case K_MAX:
+                c.maxPoolSlots = std::max(c.maxPoolSlots, N);
+                c.maxSignN = std::max(c.maxSignN, N);
+                break;
+            case K_ARGMAX: {  // the widest level: floor(K / 2) pair operations, ceil(K / 2) slots behind it
+                const i64 K = l.param("K");
+                c.maxSignN = std::max(c.maxSignN, (K / 2) * No);
+                c.maxArgSlots = std::max(c.maxArgSlots, ((K + 1) / 2) * No);
+                break;
+            }
+            case K_PROJ: {
+                const auto& om = l.vec("out_mod");
+                for (int j = 0; j < k_; ++j) c.widest[j] = std::max(c.widest[j], nr_comps(static_cast<int>(om[j])));
+                break;
+            }
+            default: break;
         }
+        N = No;
+        c.maxN = std::max(c.maxN, N);
+        c.outN.push_back(N);
     }
-    const i64 cap = std::max(maxN, maxPoolSlots);
+    return c;
+}
+
+void HipEvaluator::alloc_buffers(const Caps& c) {
+    const i64 cap = std::max(c.maxN, c.maxPoolSlots), maxSignN = c.maxSignN;
     for (int bi = 0; bi < 4; ++bi) {
         bufs_[bi].N = 0;
         for (int j = 0; j < k_; ++j) {
             // + 64 B: the MFMA dense kernel reads whole 16-byte k slices past the last column's end
-            const size_t count = static_cast<size_t>(B_) * widest[j] * cap + 64;
+            const size_t count = static_cast<size_t>(B_) * c.widest[j] * cap + 64;
             bufs_[bi].p[j] = dalloc<act_t>(count);
             // defined contents before any input is staged (serving primes the hipGraph with an unencoded run)
             HIPCHECK(hipMemset(bufs_[bi].p[j], 0, count * sizeof(act_t)));
         }
     }
-    int tmax = std::max<int>(1, static_cast<int>(m0.h.mrs.size()));
+    int tmax = std::max<int>(1, static_cast<int>(tmpl_->h.mrs.size()));
     mrsP_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * tmax * maxSignN);
     hx_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * maxSignN);
     csum_ = dalloc<int16_t>(static_cast<size_t>(B_) * tmax * kCsumComps * maxSignN);
     colx_ = dalloc<uint16_t>(static_cast<size_t>(B_) * k_ * maxSignN);
     outP_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * maxSignN);
-    maxSignN_ = maxSignN;
     hs_ = dalloc<u128>(static_cast<size_t>(B_) * maxSignN);
     if (hard_) ys_ = dalloc<u128>(static_cast<size_t>(B_) * ny_ * maxSignN);
     cs_ = dalloc<uint8_t>(static_cast<size_t>(B_) * maxSignN);
-    h0_ = dalloc<u128>(static_cast<size_t>(B_) * maxN);
-    col0_ = dalloc<uint16_t>(static_cast<size_t>(B_) * maxN);
+    h0_ = dalloc<u128>(static_cast<size_t>(B_) * c.maxN);
+    col0_ = dalloc<uint16_t>(static_cast<size_t>(B_) * c.maxN);
     for (int j = 0; j < k_; ++j) {
         int16_t* p = nullptr;
         HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(int16_t) * B_ * nr_comps(crt_[j]) * N0_));
         host_allocs_.push_back(p);
         in_stage_.push_back(p);
     }
+}
 
-    // ---- plan
-    std::vector<int> keep(m0.layers.size() + 1, 0);
-    for (auto& l : m0.layers) {
-        if (l.kind == K_ADD) keep[l.param("src") + 1] = 1;
-        if (l.kind == K_CONCAT)
-            for (i64 s : l.vec("srcs")) keep[s + 1] = 1;
-        if (l.p.count("in_src")) keep[l.param("in_src") + 1] = 1;
+// a copy of the current activation for the later layers that read output `slot` (w.keep)
+void HipEvaluator::save_if_needed(Walk& w, size_t slot) {
+    if (!w.keep[slot]) return;
+    std::vector<act_t*> s;
+    for (int j = 0; j < k_; ++j) {
+        const size_t bytes = sizeof(act_t) * B_ * nr_comps(w.mods[j]) * w.N;
+        act_t* d = dalloc<act_t>(bytes / sizeof(act_t));
+        act_t* src = bufs_[w.cur].p[j];
+        add_op("save", [d, src, bytes](hipStream_t st) { HIPCHECK(hipMemcpyAsync(d, src, bytes, hipMemcpyDeviceToDevice, st)); });
+        s.push_back(d);
     }
-    saved_.assign(m0.layers.size() + 1, {});
-    std::vector<i64> saved_n(m0.layers.size() + 1, 0);
-    std::vector<std::vector<int>> saved_mods(m0.layers.size() + 1);
-    int cur = 0;  // buffer index holding the current activation
-    i64 N = N0_;
-    const CrtInfo crt = crt_info(crt_);
-    auto save_if_needed = [&](size_t slot, int buf, i64 n_el, const std::vector<int>& md) {
-        if (!keep[slot]) return;
-        std::vector<act_t*> s;
-        for (int j = 0; j < k_; ++j) {
-            const size_t bytes = sizeof(act_t) * B_ * nr_comps(md[j]) * n_el;
-            act_t* d = dalloc<act_t>(bytes / sizeof(act_t));
-            act_t* src = bufs_[buf].p[j];
-            add_op("save", [d, src, bytes](hipStream_t st) { HIPCHECK(hipMemcpyAsync(d, src, bytes, hipMemcpyDeviceToDevice, st)); });
-            s.push_back(d);
-        }
-        saved_[slot] = s;
-        saved_n[slot] = n_el;
-        saved_mods[slot] = md;
-    };
-    save_if_needed(0, cur, N, mods);
-    if (stream_) init_streaming(m0);
+    saved_[slot] = s;
+    w.saved_n[slot] = w.N;
+    w.saved_mods[slot] = w.mods;
+}
 
-    for (size_t li = 0; li < m0.layers.size(); ++li) {
-        const GLayer& g = m0.layers[li];
-        if (stream_) add_op("stage", [this, li](hipStream_t st) { stage_layer(li, st); });
-        const int nxt = (cur + 1) % 2;
-        const std::string lname = std::string(kind_name(g.kind)) + "#" + std::to_string(li);
-        if (g.p.count("in_src")) {
-            // layer reads an earlier output (projection shortcut): restore it into the current buffer
-            const i64 src = g.param("in_src");
-            const auto& sv = saved_[src + 1];
-            DASH_CHECK(!sv.empty(), "in_src source not saved");
-            N = saved_n[src + 1];
-            mods = saved_mods[src + 1];
-            for (int j = 0; j < k_; ++j) {
-                const size_t bytes = sizeof(act_t) * B_ * nr_comps(mods[j]) * N;
-                act_t* d = bufs_[cur].p[j];
-                const act_t* sp = sv[j];
-                add_op("restore", [d, sp, bytes](hipStream_t st) {
-                    HIPCHECK(hipMemcpyAsync(d, sp, bytes, hipMemcpyDeviceToDevice, st));
-                });
-            }
-        }
-        cur_act_ = act_of(cur);
-        switch (g.kind) {
-            case K_FLATTEN:
-                break;
-            case K_DENSE: {
-                DenseArgs a{};
-                a.crt = crt;
-                a.K = g.param("in");
-                a.O = g.param("out");
-                const i64 ch = g.param("channel_tf", 0);
-                const Array& w = g.arr("w");
-                for (int j = 0; j < k_; ++j) {
-                    const int p = crt_[j];
-                    std::vector<int16_t> wt(static_cast<size_t>(a.K * a.O));
-                    std::vector<int32_t> zc(a.O, 0);
-                    for (i64 o = 0; o < a.O; ++o)
-                        for (i64 i = 0; i < a.K; ++i) {
-                            const int v = static_cast<int>(w.ptr<i64>()[o * a.K + i] % p);
-                            wt[i * a.O + o] = static_cast<int16_t>(v);
-                            if (v == 0) ++zc[o];
-                        }
-                    a.w[j] = upload(wt.data(), wt.size());
-                    a.zc[j] = upload(zc.data(), zc.size());
-                    a.bias[j] = hard_ ? zero_i16(static_cast<size_t>(B_) * a.O * nr_comps(p))
-                                      : upload_i16_rows(li, arr_name("bias.", j, ""));
-                }
-                // MFMA path: centered int8 weights [O][Kpad], channel_tf folded into the column order
-                a.Kpad = static_cast<int>((a.K + 63) / 64 * 64);
-                bool mfma_ok = mfma_ && a.K < (1 << 17);  // 127 * 127 * K fits the int32 accumulator
-                for (int j = 0; j < k_; ++j) mfma_ok = mfma_ok && crt_[j] <= 255;
-                for (int j = 0; j < k_; ++j) {
-                    a.w8[j] = nullptr;
-                    if (!mfma_ok) continue;
-                    const int p = crt_[j];
-                    std::vector<int8_t> w8(static_cast<size_t>(a.O) * a.Kpad, 0);
-                    for (i64 o = 0; o < a.O; ++o)
-                        for (i64 i = 0; i < a.K; ++i) {
-                            const int v = static_cast<int>(w.ptr<i64>()[o * a.K + i] % p);
-                            const i64 s = ch > 0 ? dense_src(i, a.K, ch) : i;
-                            w8[static_cast<size_t>(o) * a.Kpad + s] = static_cast<int8_t>(v > p / 2 ? v - p : v);
-                        }
-                    a.w8[j] = upload(w8.data(), w8.size());
-                }
-                a.zero = zero_rows_;
-                a.lab_stride = lab_stride_;
-                for (int j = 0; j < k_; ++j) a.lab_off[j] = lab_off_[j];
-                if (ch > 0) {
-                    std::vector<int32_t> src(a.K);
-                    for (i64 i = 0; i < a.K; ++i) src[i] = static_cast<int32_t>(dense_src(i, a.K, ch));
-                    a.src = upload(src.data(), src.size());
-                }
-                Act x = act_of(cur), y = act_of(nxt);
-                x.N = N;
-                y.N = a.O;
-                const int B = B_;
-                add_op(lname, [a, x, y, B](hipStream_t st) { launch_dense(a, x, y, B, st); });
-                N = a.O;
-                cur = nxt;
-                break;
-            }
-            case K_CONV: {
-                ConvGeom G(g);
-                ConvArgs a{};
-                a.crt = crt;
-                a.C = static_cast<int>(G.C); a.H = static_cast<int>(G.H); a.W = static_cast<int>(G.W);
-                a.F = static_cast<int>(G.F); a.kh = static_cast<int>(G.kh); a.kw = static_cast<int>(G.kw);
-                a.sh = static_cast<int>(G.sh); a.sw = static_cast<int>(G.sw);
-                a.ph = static_cast<int>(G.ph); a.pw = static_cast<int>(G.pw);
-                a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
-                const i64 K = G.K();
-                a.use_mfma = mfma_ ? 1 : 0;
-                a.groups = static_cast<int>(G.g);
-                if (G.g > 1) {
-                    // grouped conv: the byte-stencil kernel, no MFMA plan
-                    a.use_mfma = 0;
-                    for (int j = 0; j < k_; ++j) {
-                        const u64 pm = static_cast<u64>(crt_[j] - 1);
-                        DASH_CHECK(crt_[j] <= kActMaxModulus, "grouped conv: residue modulus above 255");
-                        DASH_CHECK(static_cast<u64>(K) * pm * pm < (1ull << 32),
-                                   "grouped conv: (C/g)*kh*kw*(p-1)^2 must stay below 2^32 (32-bit accumulator)");
-                    }
-                    DASH_CHECK(conv_grp_geometry(a) > 0, "grouped conv: one output row of a group exceeds 64 KiB of LDS");
-                } else {
-                    // LDS-image kernel geometry: 64-channel chunks, row bands that fit the LDS budget
-                    conv_layer_plan(a, mfma_ && conv_img_enabled());
-                }
-                a.img_off[0] = 0;
-                for (int j = 0; j < k_; ++j) a.img_off[j + 1] = a.img_off[j] + static_cast<i64>(B_) * crt.n[j];
-                const Array& w = g.arr("w");
-                for (int j = 0; j < k_; ++j) {
-                    const int p = crt_[j];
-                    const bool grp = G.g > 1;  // k_conv_grp reads its own image (wg) only
-                    std::vector<int16_t> wm(grp ? 0 : static_cast<size_t>(G.F * K));
-                    std::vector<int8_t> w8(grp ? 0 : static_cast<size_t>(G.F) * a.Kpad, 0);
-                    std::vector<int32_t> zc(G.F, 0);
-                    for (i64 f = 0; f < G.F; ++f)
-                        for (i64 q = 0; q < K; ++q) {
-                            const int v = static_cast<int>(w.ptr<i64>()[f * K + q] % p);
-                            if (v == 0) ++zc[f];
-                            if (grp) continue;
-                            wm[f * K + q] = static_cast<int16_t>(v);
-                            w8[f * a.Kpad + q] = static_cast<int8_t>(v > p / 2 ? v - p : v);
-                        }
-                    a.w[j] = grp ? nullptr : upload(wm.data(), wm.size());
-                    a.w8[j] = (mfma_ && p <= 255 && !grp) ? upload(w8.data(), w8.size()) : nullptr;
-                    a.wg[j] = nullptr;
-                    if (grp) {
-                        const std::vector<uint32_t> wg = conv_grp_weights(w.ptr<i64>(), G.F, G.Cg(), a.kh, a.kw, p);
-                        a.wg[j] = upload(wg.data(), wg.size());
-                    }
-                    if (a.nbands > 0 && p <= 255) {
-                        // [F16][kh][kw][Cpad] centered int8 (im2col order ci*kh*kw + dy*kw + dx -> (dy, dx, ci))
-                        const std::vector<int8_t> w8r = conv_w8r(a, w8, static_cast<int>(G.F));
-                        a.w8r[j] = upload(w8r.data(), w8r.size());
-                    } else {
-                        a.w8r[j] = nullptr;
-                    }
-                    a.zc[j] = upload(zc.data(), zc.size());
-                    a.bias[j] = hard_ ? zero_i16(static_cast<size_t>(B_) * G.F * nr_comps(p))
-                                      : upload_i16_rows(li, arr_name("bias.", j, ""));
-                }
-                a.zero = zero_rows_;
-                a.lab_stride = lab_stride_;
-                for (int j = 0; j < k_; ++j) a.lab_off[j] = lab_off_[j];
-                Act x = act_of(cur), y = act_of(nxt);
-                const int B = B_;
-                add_op(lname, [a, x, y, B](hipStream_t st) { launch_conv(a, x, y, B, st); });
-                N = G.out_size();
-                cur = nxt;
-                break;
-            }
-            case K_RELU: {
-                if (g.param("smode", 0) == 2) {  // sign from the preceding rescale (RescaleMrsPlan::sign_last)
-                    DASH_CHECK(li > 0 && m0.layers[li - 1].kind == K_RESCALE &&
-                                   m0.layers[li - 1].param("sign_out", 0) == 1,
-                               "joint ReLU must follow a sign-producing rescale");
-                    SignArgs sa{};
-                    sa.crt = crt;
-                    sa.N = N;
-                    sa.B = B_;
-                    sa.hx = hx_;
-                    sa.colx = colx_;
-                    sa.hs = hs_;
-                    sa.cs = cs_;
-                    sa.hard = hard_ ? 1 : 0;
-                    sa.mgate0 = gate_base(li + 1, 2);
-                    sa.ny = ny_;
-                    sa.ys = ys_;
-                    const u128* gt = upload_tables(li, "mm.g");
-                    const u128* et = upload_tables(li, "mm.e");
-                    Act x = act_of(cur), y = act_of(nxt);
-                    const ModC* mc = mc_;
-                    const AesGlobals ag = aes_;
-                    const int B = B_;
-                    if (joint_pending_) {
-                        const MrsArgs ma = joint_a_;
-                        joint_pending_ = false;
-                        add_op(lname + ".C", [ma, sa, x, y, gt, et, B, mc, ag](hipStream_t st) {
-                            launch_rescale_relu_out(ma, sa, x, y, gt, et, B, mc, ag, st);
-                        });
-                    } else {
-                        add_op(lname + ".C", [sa, x, y, gt, et, B, mc, ag](hipStream_t st) {
-                            launch_relu_joint(sa, x, y, gt, et, B, mc, ag, st);
-                        });
-                    }
-                    cur = nxt;
-                    break;
-                }
-                if (g.param("smode", 0) == 1) {  // exact mixed-radix sign (gadgets.h SignMrsPlan)
-                    const SignMrsPlan P(crt_);
-                    MrsArgs a{};
-                    a.crt = crt;
-                    a.N = N;
-                    a.n_tab = g.arr("mrs").shape[1];
-                    a.tab = upload_tables(li, "mrs");
-                    for (int i = 0; i + 1 < k_; ++i) a.dig_off[i] = P.dig_off[i];
-                    if (!mrs_ps_) mrs_ps_ = dalloc<u128>(static_cast<size_t>(B_) * std::max(1, k_ * (k_ - 1) / 2) * maxSignN_);
-                    a.ps = mrs_ps_;
-                    a.mode = 1;
-                    a.hs = hs_;
-                    a.cs = cs_;
-                    DASH_CHECK(hard_, "the mixed-radix sign exists in the hardened encoding only");
-                    a.gate0 = gate_base(li + 1, 1);
-                    a.rgate0 = gate_base(li + 1, 2);
-                    a.ny = ny_;
-                    a.ys = ys_;
-                    SignArgs sa{};
-                    sa.crt = crt;
-                    sa.N = N;
-                    sa.B = B_;
-                    sa.hx = hx_;
-                    sa.colx = colx_;
-                    sa.hs = hs_;
-                    sa.cs = cs_;
-                    sa.hard = 1;
-                    sa.mgate0 = gate_base(li + 1, 2);
-                    sa.ny = ny_;
-                    sa.ys = ys_;
-                    const u128* gt = upload_tables(li, "mm.g");
-                    const u128* et = upload_tables(li, "mm.e");
-                    Act x = act_of(cur), y = act_of(nxt);
-                    const ModC* mc = mc_;
-                    const AesGlobals ag = aes_;
-                    const int B = B_;
-                    add_op(lname + ".mrs", [a, sa, x, y, gt, et, B, mc, ag](hipStream_t st) {
-                        launch_relu_mrs(a, sa, x, y, gt, et, B, mc, ag, st);
-                    });
-                    cur = nxt;
-                    break;
-                }
-                SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
-                SignArgs a = make_sign(li, "", sp, N, 1, gate_base(li + 1, 1), gate_base(li + 1, 2));
-                const u128* gt = upload_tables(li, "mm.g");
-                const u128* et = upload_tables(li, "mm.e");
-                Act x = act_of(cur), y = act_of(nxt);
-                const ModC* mc = mc_;
-                const AesGlobals ag = aes_;
-                const int maxn = sign_maxn_;
-                add_op(lname + ".A", [a, x, mc, ag](hipStream_t st) { launch_sign_approx(a, x, mc, ag, st); });
-                add_op(lname + ".B", [a, maxn, mc, ag](hipStream_t st) { launch_sign_chain(a, maxn, mc, ag, st); });
-                add_op(lname + ".C", [a, x, y, gt, et, mc](hipStream_t st) { launch_relu_mult(a, x, y, gt, et, mc, st); });
-                cur = nxt;
-                break;
-            }
-            case K_CLIP: {
-                // gadgets.h ClipPlan: the half gates' keys of x, the sign evaluation once per bound on the same
-                // labels (each into its own scratch), then the multiply + cap
-                DASH_CHECK(hard_, "the Clip layer exists in the hardened encoding only");
-                for (int side = 0; side < 2; ++side)
-                    if (!ks_[side]) ks_[side] = dalloc<u128>(static_cast<size_t>(B_) * maxSignN_);
-                ClipArgs ca{};
-                ca.crt = crt;
-                ca.N = N;
-                ca.hx = hx_;
-                ca.colx = colx_;
-                ca.klo = ks_[0];
-                ca.khi = ks_[1];
-                ca.gtab = upload_tables(li, "mm.g");
-                ca.etab = upload_tables(li, "mm.e");
-                ca.cap = upload_tables(li, "cap");
-                ca.mgate0 = gate_base(li + 1, 2);
-                Act x = act_of(cur), y = act_of(nxt);
-                const ModC* mc = mc_;
-                const AesGlobals ag = aes_;
-                const int B = B_;
-                u128* hx = hx_;
-                uint16_t* colx = colx_;
-                if (g.param("smode", 0) == 2) {
-                    // joint variant: the rescale before it left both sign labels (ks_) and the half-gate keys of
-                    // its output (hx_ / colx_); only the multiply + cap is left
-                    DASH_CHECK(li > 0 && m0.layers[li - 1].kind == K_RESCALE &&
-                                   m0.layers[li - 1].param("sign_out", 0) == 1 && !g.p.count("in_src") &&
-                                   g.vec("lo").at(0) == 0,
-                               "joint Clip must follow a sign-producing rescale");
-                    if (clip_pending_) {
-                        const MrsArgs ma = clip_a_;
-                        clip_pending_ = false;
-                        add_op(lname + ".C", [ma, ca, x, y, B, mc, ag](hipStream_t st) {
-                            launch_rescale_clip_out(ma, ca, x, y, B, mc, ag, st);
-                        });
-                    } else {
-                        add_op(lname + ".C", [ca, x, y, B, mc](hipStream_t st) { launch_clip_mult(ca, x, y, B, mc, st); });
-                    }
-                    cur = nxt;
-                    break;
-                }
-                const bool exact = g.param("smode", 0) == 1;
-                // the half gates' keys of x: the approximate sign's first phase compresses x anyway and writes them
-                // (lower bound's run, below); the mixed-radix chain does not, so they get a pass of their own
-                if (exact)
-                    add_op(lname + ".H", [ca, hx, colx, x, B, mc, ag](hipStream_t st) {
-                        launch_clip_hash(ca, hx, colx, x, B, mc, ag, st);
-                    });
-                for (int side = 0; side < 2; ++side) {
-                    const std::string pre = side ? "hi." : "lo.";
-                    const uint64_t sgate = gate_base(li + 1, side ? 3 : 1);
-                    if (exact) {  // exact mixed-radix sign (chain mode 1, label kept in ks)
-                        const SignMrsPlan P(crt_);
-                        MrsArgs a{};
-                        a.crt = crt;
-                        a.N = N;
-                        a.n_tab = g.arr(pre + "mrs").shape[1];
-                        a.tab = upload_tables(li, pre + "mrs");
-                        for (int i = 0; i + 1 < k_; ++i) a.dig_off[i] = P.dig_off[i];
-                        if (!mrs_ps_) mrs_ps_ = dalloc<u128>(static_cast<size_t>(B_) * std::max(1, k_ * (k_ - 1) / 2) * maxSignN_);
-                        a.ps = mrs_ps_;
-                        a.mode = 1;
-                        a.hs = hs_;
-                        a.cs = cs_;
-                        a.gate0 = sgate;
-                        a.rgate0 = ca.mgate0;
-                        a.ny = 0;  // no y-row pads: the multiply forms the pads of u = s_lo + s_hi itself
-                        a.ys = ys_;
-                        a.ks = ks_[side];
-                        add_op(lname + "." + pre + "mrs", [a, x, B, mc, ag](hipStream_t st) {
-                            launch_clip_sign_mrs(a, x, B, mc, ag, st);
-                        });
-                    } else {
-                        SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
-                        SignArgs a = make_sign(li, pre, sp, N, 0, sgate, 0);
-                        a.outP = ks_[side];  // nout = 1: [B][N]
-                        if (side == 0) {  // (TW_MMG, j) pads of x_j under the multiply's gate, as a ReLU's phase A
-                            a.hx = hx_;
-                            a.colx = colx_;
-                            a.mgate0 = ca.mgate0;
-                        }
-                        const int maxn = sign_maxn_;
-                        add_op(lname + "." + pre + "A", [a, x, mc, ag](hipStream_t st) { launch_sign_approx(a, x, mc, ag, st); });
-                        add_op(lname + "." + pre + "B", [a, maxn, mc, ag](hipStream_t st) { launch_sign_chain(a, maxn, mc, ag, st); });
-                    }
-                }
-                add_op(lname + ".C", [ca, x, y, B, mc](hipStream_t st) { launch_clip_mult(ca, x, y, B, mc, st); });
-                cur = nxt;
-                break;
-            }
-            case K_SIGN: {
-                SignPlan sp(crt_, m0.h.mrs, crt_, -1, 1, m0.h.sign_fused != 0);
-                SignArgs a = make_sign(li, "", sp, N, 0, gate_base(li + 1, 1), 0);
-                Act x = act_of(cur), y = act_of(nxt);
-                const ModC* mc = mc_;
-                const AesGlobals ag = aes_;
-                const int maxn = sign_maxn_;
-                const int B = B_;
-                const u128* outP = outP_;
-                const i64 NN = N;
-                add_op(lname + ".A", [a, x, mc, ag](hipStream_t st) { launch_sign_approx(a, x, mc, ag, st); });
-                add_op(lname + ".B", [a, maxn, mc, ag](hipStream_t st) { launch_sign_chain(a, maxn, mc, ag, st); });
-                add_op(lname + ".unpack", [outP, y, crt, mc, NN, B](hipStream_t st) { launch_unpack(outP, crt.k, y, crt, mc, NN, B, st); });
-                cur = nxt;
-                break;
-            }
-            case K_RESCALE: {
-                const i64 mode = g.param("mode", 0);
-                const i64 iters = g.param("iters");
-                if (mode == 2) {  // mixed-radix construction of the legacy function (gadgets.h RescaleMrsPlan)
-                    const bool so = g.param("sign_out", 0) == 1;  // joint: the next ReLU's sign -> hs_, cs_
-                    const RescaleMrsPlan P(crt_, static_cast<int>(g.param("l")), so);
-                    DASH_CHECK(P.T <= m0.h.max_mod, "model lacks the mod-2^(l+1) label constants");
-                    MrsArgs a{};
-                    a.crt = crt;
-                    a.T = static_cast<int>(P.T);
-                    a.N = N;
-                    a.n_tab = P.n_tab;
-                    a.tab = upload_tables(li, "mrs");
-                    for (int i = 0; i < k_; ++i) {
-                        a.dig_off[i] = P.dig_off[i];
-                        a.sinv[i] = static_cast<int>(P.Sinv[i]);
-                    }
-                    a.fin_off = P.fin_off;
-                    const int bits = P.l + 1, nf = nr_comps(static_cast<int>(P.T));
-                    a.hmask = 0;
-                    for (int f = 0; f < nf; ++f) a.hmask |= static_cast<u128>(1) << (bits * f + bits - 1);
-                    a.pf = outP_;  // [B][k][N] <= the sign outputs' scratch
-                    if (!mrs_ps_) mrs_ps_ = dalloc<u128>(static_cast<size_t>(B_) * std::max(1, k_ * (k_ - 1) / 2) * maxSignN_);
-                    a.ps = mrs_ps_;
-                    a.mode = so ? 2 : 0;
-                    a.hs = hs_;
-                    a.cs = cs_;
-                    a.hx = hx_;
-                    a.colx = colx_;
-                    DASH_CHECK(hard_, "the mixed-radix rescale exists in the hardened encoding only");
-                    a.gate0 = gate_base(li + 1, 30);
-                    a.rgate0 = so ? gate_base(li + 2, 2) : 0;  // the joint ReLU (next layer)'s half gates
-                    a.ny = ny_;
-                    a.ys = ys_;
-                    Act x = act_of(cur);
-                    const ModC* mc = mc_;
-                    const AesGlobals ag = aes_;
-                    const int B = B_;
-                    // joint ReLU next and this output not kept for a later layer: the ReLU's op can write both
-                    // outputs in one pass (launch_rescale_relu_out), here only the chain runs. The rescaled
-                    // label is then never written: the fused kernels keep it in LDS. Which launches take it is
-                    // launch.h joint_fuse: batches of at most 2 GCs (latency_b1 2.21 -> 2.14 ms), and staged
-                    // shapes from 13,824 elements over the batch, where the throughput form wins on every MiniONN
-                    // layer (24-GC step 9.08 -> 7.55 ms, profiles/ab/joint_fused/README.md); hip_set_joint_fuse
-                    // (initially DASH_JOINT_FUSE=0/1) forces it off/on.
-                    // A joint Clip next (gadgets.h ClipPlan, joint variant): the chain keeps its mod-2 key as the
-                    // Clip's lower sign label (ks_[0], no y-row pads), the Clip's upper sign chain (mode 1, the
-                    // Clip layer's tables and slot-3 gate) runs on the same input labels into ks_[1], and only
-                    // then the output kernel rewrites x in place, leaving y's half-gate keys under the Clip's
-                    // multiply gate in hx_ / colx_. Both chains share mrs_ps_; the mode-1 chain writes neither
-                    // a.pf nor outP_, so the rescale's final payloads wait there.
-                    const bool clip_next = so && li + 1 < m0.layers.size() && m0.layers[li + 1].kind == K_CLIP &&
-                                           m0.layers[li + 1].param("smode", 0) == 2;
-                    if (clip_next) {
-                        const GLayer& gc = m0.layers[li + 1];
-                        DASH_CHECK(!gc.p.count("in_src"), "joint Clip must read the rescale before it");
-                        for (int side = 0; side < 2; ++side)
-                            if (!ks_[side]) ks_[side] = dalloc<u128>(static_cast<size_t>(B_) * maxSignN_);
-                        a.ks = ks_[0];
-                        a.ny = 0;
-                        const SignMrsPlan SP(crt_);
-                        MrsArgs h{};
-                        h.crt = crt;
-                        h.N = N;
-                        h.n_tab = gc.arr("hi.mrs").shape[1];
-                        DASH_CHECK(gc.arr("hi.mrs").shape[0] == N && h.n_tab == std::max<i64>(SP.n_tab, 1),
-                                   "joint Clip upper sign table shape");
-                        h.tab = upload_tables(li + 1, "hi.mrs");
-                        for (int i = 0; i + 1 < k_; ++i) h.dig_off[i] = SP.dig_off[i];
-                        h.ps = mrs_ps_;
-                        h.mode = 1;
-                        h.hs = hs_;
-                        h.cs = cs_;
-                        h.gate0 = gate_base(li + 2, 3);
-                        h.rgate0 = a.rgate0;
-                        h.ny = 0;
-                        h.ys = ys_;
-                        h.ks = ks_[1];
-                        add_op(lname + ".mrs", [a, x, B, mc, ag](hipStream_t st) {
-                            launch_rescale_mrs(a, x, B, mc, ag, st, true);
-                        });
-                        // streamed tables: the Clip layer's window was issued by this layer's stage op
-                        if (stream_)
-                            add_op(lname + ".wait", [this, li](hipStream_t st) {
-                                HIPCHECK(hipStreamWaitEvent(st, ready_[li + 1], 0));
-                            });
-                        add_op(lname + ".clip_hi", [h, x, B, mc, ag](hipStream_t st) {
-                            launch_clip_sign_mrs(h, x, B, mc, ag, st);
-                        });
-                        // output not kept for a later layer and the fusion on (launch.h clip_fuse): the Clip's op
-                        // writes both outputs in one pass (launch_rescale_clip_out), the rescaled label stays
-                        // in LDS
-                        if (dev::clip_fuse(N, B_) && !keep[li + 1]) {
-                            clip_a_ = a;
-                            clip_pending_ = true;
-                        } else {
-                            add_op(lname + ".out", [a, x, B, mc, ag](hipStream_t st) {
-                                launch_rescale_mrs_out(a, x, B, mc, ag, st);
-                            });
-                        }
-                        break;
-                    }
-                    const bool fuse = dev::joint_fuse(N, B_);
-                    const bool defer = fuse && so && li + 1 < m0.layers.size() && m0.layers[li + 1].kind == K_RELU &&
-                                       m0.layers[li + 1].param("smode", 0) == 2 && !keep[li + 1] &&
-                                       !m0.layers[li + 1].p.count("in_src");
-                    if (defer) {
-                        joint_a_ = a;
-                        joint_pending_ = true;
-                    }
-                    add_op(lname + ".mrs", [a, x, B, mc, ag, defer](hipStream_t st) {
-                        launch_rescale_mrs(a, x, B, mc, ag, st, defer);
-                    });
-                    break;
-                }
-                if (mode == 0) {
-                    plan_rescale_legacy(li, iters, N, crt, lname);
-                    break;
-                }
-                for (i64 it = 0; it < iters; ++it) {
-                    std::vector<int> factors;
-                    if (mode == 0)
-                        factors = {2};
-                    else
-                        for (auto v : g.vec("s")) factors.push_back(static_cast<int>(v));
-                    RescalePlan P(crt_, m0.h.mrs, factors, mode == 0, m0.h.sign_fused != 0);
-                    const std::string pre = arr_name("it", static_cast<int>(it), ".");
-                    const u128* trans = upload_tables(li, pre + "trans");
-                    Act x = act_of(cur);
-                    const ModC* mc = mc_;
-                    const AesGlobals ag = aes_;
-                    const int B = B_;
-                    const i64 NN = N;
-                    i64 off = 0;
-                    for (size_t f = 0; f < P.factors.size(); ++f) {
-                        const int fi = P.factor_idx[f], s = P.factors[f];
-                        const int add_up = f == 0 ? 1 : 0;
-                        const int16_t* up = up_rows_ + lab_off_[fi];
-                        u128* h0 = h0_;
-                        uint16_t* col0 = col0_;
-                        const int ls = lab_stride_;
-                        const int hd = hard_ ? 1 : 0;
-                        add_op(lname + ".hash", [x, fi, s, up, ls, add_up, NN, B, h0, col0, mc, ag, hd](hipStream_t st) {
-                            launch_rescale_hash(x, fi, s, up, ls, add_up, NN, B, h0, col0, mc, ag, st, hd);
-                        });
-                        RescaleArgs ra{};
-                        ra.crt = crt;
-                        ra.N = N;
-                        ra.fi = fi;
-                        ra.s = s;
-                        ra.add_up = add_up;
-                        for (size_t q = 0; q < P.active[f].size(); ++q) {
-                            const int jj = P.active[f][q];
-                            ra.active[jj] = 1;
-                            ra.aidx[jj] = static_cast<int>(q);
-                            ra.inv[jj] = static_cast<int>(P.inv[f][q]);
-                        }
-                        ra.n_trans = P.n_trans;
-                        ra.off = off;
-                        off += static_cast<i64>(P.active[f].size()) * s;
-                        ra.trans = trans;
-                        ra.h0 = h0_;
-                        ra.col0 = col0_;
-                        ra.up = up_rows_;
-                        ra.zero = zero_rows_;
-                        ra.lab_stride = lab_stride_;
-                        for (int j = 0; j < k_; ++j) ra.lab_off[j] = lab_off_[j];
-                        ra.hard = hard_ ? 1 : 0;
-                        ra.gate0 = gate_base(li + 1, 10 + it);
-                        ra.factor = static_cast<int>(f);
-                        add_op(lname + ".update", [ra, x, B, mc](hipStream_t st) { launch_rescale_update(ra, x, B, mc, st); });
-                    }
-                    const u128* signP = nullptr;
-                    if (P.sign_be) {
-                        SignArgs a = make_sign(li, pre, P.sign, N, 0);
-                        const int maxn = sign_maxn_;
-                        add_op(lname + ".sA", [a, x, mc, ag](hipStream_t st) { launch_sign_approx(a, x, mc, ag, st); });
-                        add_op(lname + ".sB", [a, maxn, mc, ag](hipStream_t st) { launch_sign_chain(a, maxn, mc, ag, st); });
-                        signP = outP_;
-                    } else {
-                        const BEPlan& be = P.be;
-                        BEArgs ba{};
-                        ba.E = static_cast<int>(be.moduli.size());
-                        ba.nonext = be.nonext;
-                        std::vector<int> idx(ba.E);
-                        for (int i = 0; i < ba.E; ++i) idx[be.pos_of[i]] = i;
-                        for (int i = 0; i < ba.E; ++i) {
-                            ba.swapped[i] = be.swapped[i];
-                            ba.src[i] = idx[i];
-                        }
-                        for (int i = 0; i + 1 < ba.E; ++i)
-                            for (size_t jj = 0; jj < be.inv_partial[i].size(); ++jj)
-                                ba.inv[i][jj] = static_cast<int>(be.inv_partial[i][jj]);
-                        ba.nextra = static_cast<int>(be.extra.size());
-                        for (int xi = 0; xi < ba.nextra; ++xi) {
-                            ba.extra_res[xi] = be.extra_idx[xi];
-                            ba.extra_pos[xi] = be.pos_of[be.extra_idx[xi]];
-                            const int q = be.moduli[be.extra_idx[xi]];
-                            ba.invv[xi] = static_cast<int>(pmod(-be.invv[xi], q));
-                        }
-                        ba.N = N;
-                        ba.n_tab = be.n_tab;
-                        ba.tab = upload_tables(li, pre + "be");
-                        if (!be_work_) be_work_ = dalloc<int16_t>(static_cast<size_t>(B_) * k_ * 128 * maxN);
-                        ba.work = be_work_;
-                        ba.hard = hard_ ? 1 : 0;
-                        ba.gate0 = gate_base(li + 1, 10 + it);
-                        add_op(lname + ".be", [ba, x, B, mc, ag](hipStream_t st) { launch_base_ext(ba, x, B, mc, ag, st); });
-                    }
-                    const int16_t* down = upload_const_rows(
-                        [&](int j) { return "down." + std::to_string(P.sprod) + "." + std::to_string(j); });
-                    const int ls = lab_stride_;
-                    const int* loff = d_lab_off_;
-                    add_op(lname + ".post", [x, crt, NN, B, signP, down, ls, loff, mc](hipStream_t st) {
-                        launch_rescale_post(x, crt, NN, B, signP, down, ls, loff, mc, st);
-                    });
-                }
-                break;
-            }
-            case K_MAXPOOL:
-            case K_MAX: {
-                i64 Nout, K;
-                std::vector<i64> idx;
-                if (g.kind == K_MAXPOOL) {
-                    PoolGeom G(g.p);
-                    Nout = G.out_size();
-                    K = G.kh * G.kw;
-                    std::vector<i64> w;
-                    for (i64 o = 0; o < Nout; ++o) {
-                        G.window(o, w);
-                        idx.insert(idx.end(), w.begin(), w.end());
-                    }
-                } else {
-                    Nout = 1;
-                    K = N;
-                    for (i64 i = 0; i < N; ++i) idx.push_back(i);
-                }
-                const int64_t* didx = upload(idx.data(), idx.size());
-                MaxTree T(K);
-                SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
-                // buffers: vals in 2/3 ping-pong, diff in nxt-other... use bufs 2,3 for vals; relu out in buf nxt
-                int va = 2, vb = 3;
-                Act xin = act_of(cur), v0 = act_of(va);
-                const int B = B_;
-                const i64 NN = N;
-                add_op(lname + ".gather", [xin, NN, v0, Nout, K, didx, crt, B](hipStream_t st) {
-                    launch_copy_gather(xin, NN, v0, Nout * K, didx, crt, B, st);
-                });
-                // scratch for diffs: reuse buffer `cur` (its content is no longer needed) and relu out in `nxt`
-                for (size_t lv = 0; lv < T.ops.size(); ++lv) {
-                    const int ops = T.ops[lv], cnt = T.cnt[lv], cnt1 = T.cnt[lv + 1];
-                    const std::string pre = arr_name("lv", static_cast<int>(lv), ".");
-                    SignArgs a = make_sign(li, pre, sp, Nout * ops, 1, gate_base(li + 1, 20 + 2 * lv),
-                                           gate_base(li + 1, 21 + 2 * lv));
-                    const u128* gt = upload_tables(li, pre + "mm.g");
-                    const u128* et = upload_tables(li, pre + "mm.e");
-                    Act V = act_of(va), D = act_of(cur), Rr = act_of(nxt), NV = act_of(vb);
-                    const ModC* mc = mc_;
-                    const AesGlobals ag = aes_;
-                    const int maxn = sign_maxn_;
-                    const i64 Nv = Nout * cnt;
-                    add_op(lname + ".diff", [V, Nv, D, Nout, ops, cnt, crt, B](hipStream_t st) {
-                        launch_pair_diff(V, Nv, D, Nout, ops, cnt, crt, B, st);
-                    });
-                    add_op(lname + ".A", [a, D, mc, ag](hipStream_t st) { launch_sign_approx(a, D, mc, ag, st); });
-                    add_op(lname + ".B", [a, maxn, mc, ag](hipStream_t st) { launch_sign_chain(a, maxn, mc, ag, st); });
-                    add_op(lname + ".C", [a, D, Rr, gt, et, mc](hipStream_t st) { launch_relu_mult(a, D, Rr, gt, et, mc, st); });
-                    add_op(lname + ".add", [V, Nv, Rr, NV, Nout, ops, cnt, cnt1, crt, B](hipStream_t st) {
-                        launch_pair_add(V, Nv, Rr, NV, Nout, ops, cnt, cnt1, crt, B, st);
-                    });
-                    std::swap(va, vb);
-                }
-                // result (cnt == 1) lives in buffer va: copy into nxt
-                std::vector<i64> ident(Nout);
-                for (i64 o = 0; o < Nout; ++o) ident[o] = o;
-                const int64_t* did = upload(ident.data(), ident.size());
-                Act vres = act_of(va), y = act_of(nxt);
-                add_op(lname + ".out", [vres, Nout, y, did, crt, B](hipStream_t st) {
-                    launch_copy_gather(vres, Nout, y, Nout, did, crt, B, st);
-                });
-                N = Nout;
-                cur = nxt;
-                break;
-            }
-            case K_ARGMAX: {
-                // gadgets.h ArgMaxPlan. The (K, P) input is level 0's candidate buffer as it stands; later levels
-                // ping-pong between bufs 2 / 3 (values / index labels) and the ArgMax scratch; the root writes
-                // its index labels into the layer's output buffer.
-                DASH_CHECK(hard_, "the ArgMax layer exists in the hardened encoding only");
-                const i64 K = g.param("K"), P = g.param("P");
-                DASH_CHECK(K >= 2 && K * P == N, "argmax input size mismatch");
-                const ArgMaxPlan ap(crt_, K);
-                if (!amb_[0].p[0]) {
-                    for (auto& ab : amb_)
-                        for (int j = 0; j < k_; ++j) {
-                            const size_t count = static_cast<size_t>(B_) * widest[j] * maxArgSlots + 64;
-                            ab.p[j] = dalloc<act_t>(count);
-                            HIPCHECK(hipMemset(ab.p[j], 0, count * sizeof(act_t)));
-                        }
-                    am_hi_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * maxSignN_);
-                    am_coli_ = dalloc<uint16_t>(static_cast<size_t>(B_) * k_ * maxSignN_);
-                }
-                if (!ks_[0]) ks_[0] = dalloc<u128>(static_cast<size_t>(B_) * maxSignN_);
-                if (!mrs_ps_) mrs_ps_ = dalloc<u128>(static_cast<size_t>(B_) * std::max(1, k_ * (k_ - 1) / 2) * maxSignN_);
-                const ModC* mc = mc_;
-                const AesGlobals ag = aes_;
-                const int B = B_;
-                Act V = act_of(cur), I = act_of(3);
-                const Act D = amb_[2], E = amb_[3];
-                for (int lv = 0; lv < ap.levels(); ++lv) {
-                    const bool root = ap.root(lv), l0 = lv == 0;
-                    const int ops = ap.ops[lv], cnt = ap.cnt[lv];
-                    const i64 Nops = P * ops;
-                    const std::string pre = arr_name("lv", lv, ".");
-                    const std::string op = lname + ".lv" + std::to_string(lv);
-                    // outputs: values into buf 2 / scratch 0, index labels into buf 3 / scratch 1, alternating
-                    const Act NV = (lv % 2 == 0) ? act_of(2) : amb_[0];
-                    const Act NI = root ? act_of(nxt) : ((lv % 2 == 0) ? act_of(3) : amb_[1]);
-                    ArgMaxArgs a{};
-                    a.crt = crt;
-                    a.P = P;
-                    a.ops = ops;
-                    a.cnt = cnt;
-                    a.cnt1 = ap.cnt[lv + 1];
-                    a.pubq = ap.pub[lv][cnt - 1] >= 0 && cnt % 2 == 0 ? ops - 1 : -1;
-                    a.carry_idx = cnt % 2 == 1 && ap.pub[lv][cnt - 1] < 0;
-                    a.ks = ks_[0];
-                    a.hx = hx_;
-                    a.colx = colx_;
-                    a.hi = am_hi_;
-                    a.coli = am_coli_;
-                    a.vgate0 = gate_base(li + 1, 21 + 3 * lv);
-                    a.igate0 = gate_base(li + 1, 22 + 3 * lv);
-                    if (!root) {
-                        a.gtab = upload_tables(li, pre + "mm.g");
-                        a.etab = upload_tables(li, pre + "mm.e");
-                    }
-                    if (l0) {
-                        a.itab = upload_tables(li, pre + "idx");
-                    } else {
-                        a.igtab = upload_tables(li, pre + "im.g");
-                        a.ietab = upload_tables(li, pre + "im.e");
-                    }
-                    MrsArgs s{};
-                    s.crt = crt;
-                    s.N = Nops;
-                    s.n_tab = g.arr(pre + "mrs").shape[1];
-                    s.tab = upload_tables(li, pre + "mrs");
-                    for (int i = 0; i + 1 < k_; ++i) s.dig_off[i] = ap.sign.dig_off[i];
-                    s.ps = mrs_ps_;
-                    s.mode = 1;
-                    s.hs = hs_;
-                    s.cs = cs_;
-                    s.gate0 = gate_base(li + 1, 20 + 3 * lv);
-                    s.rgate0 = a.vgate0;
-                    s.ny = 0;  // no y-row pads: the multiply derives the pads of both gate sets from the label
-                    s.ys = ys_;
-                    s.ks = ks_[0];
-                    add_op(op + ".diff", [V, D, P, ops, cnt, crt, B](hipStream_t st) {
-                        launch_argmax_diff(V, D, P, ops, cnt, -1, crt, B, st);
-                    });
-                    if (!l0) {
-                        const int pubq = a.pubq;
-                        add_op(op + ".idiff", [I, E, P, ops, cnt, pubq, crt, B](hipStream_t st) {
-                            launch_argmax_diff(I, E, P, ops, cnt, pubq, crt, B, st);
-                        });
-                    }
-                    if (!root) {
-                        u128* hx = hx_;
-                        uint16_t* colx = colx_;
-                        const uint64_t vg = a.vgate0;
-                        add_op(op + ".H", [D, crt, Nops, hx, colx, vg, B, mc, ag](hipStream_t st) {
-                            launch_argmax_hash(D, crt, Nops, hx, colx, vg, B, mc, ag, st);
-                        });
-                    }
-                    if (!l0) {
-                        u128* hi = am_hi_;
-                        uint16_t* coli = am_coli_;
-                        const uint64_t ig = a.igate0;
-                        add_op(op + ".iH", [E, crt, Nops, hi, coli, ig, B, mc, ag](hipStream_t st) {
-                            launch_argmax_hash(E, crt, Nops, hi, coli, ig, B, mc, ag, st);
-                        });
-                    }
-                    add_op(op + ".mrs", [s, D, B, mc, ag](hipStream_t st) { launch_clip_sign_mrs(s, D, B, mc, ag, st); });
-                    add_op(op + ".C", [a, root, l0, V, D, I, E, NV, NI, B, mc](hipStream_t st) {
-                        launch_argmax_mult(a, !root, l0, V, D, I, E, NV, NI, B, mc, st);
-                    });
-                    V = NV;
-                    I = NI;
-                }
-                N = P;
-                cur = nxt;
-                break;
-            }
-            case K_SUMPOOL: {
-                PoolGeom G(g.p);
-                if (G.padded()) {
-                    // ragged windows: the geometry-direct kernel skips the taps outside the image
-                    const PoolArgs pa{static_cast<int>(G.C),  static_cast<int>(G.H),  static_cast<int>(G.W),
-                                      static_cast<int>(G.kh), static_cast<int>(G.kw), static_cast<int>(G.sh),
-                                      static_cast<int>(G.sw), static_cast<int>(G.ph), static_cast<int>(G.pw),
-                                      static_cast<int>(G.OH), static_cast<int>(G.OW)};
-                    DASH_CHECK(G.C * G.H * G.W == N, "sumpool input size mismatch");
-                    Act x = act_of(cur), y = act_of(nxt);
-                    const int B = B_;
-                    add_op(lname + ".geom", [x, y, pa, crt, B](hipStream_t st) { launch_pool_sum(x, y, pa, crt, B, st); });
-                    N = G.out_size();
-                    cur = nxt;
-                    break;
-                }
-                std::vector<i64> idx, w;
-                for (i64 o = 0; o < G.out_size(); ++o) {
-                    G.window(o, w);
-                    idx.insert(idx.end(), w.begin(), w.end());
-                }
-                const int64_t* didx = upload(idx.data(), idx.size());
-                Act x = act_of(cur), y = act_of(nxt);
-                const i64 NN = N, No = G.out_size();
-                const int K = static_cast<int>(G.kh * G.kw);
-                const int B = B_;
-                add_op(lname, [x, NN, y, No, didx, K, crt, B](hipStream_t st) { launch_window_sum(x, NN, y, No, didx, K, crt, B, st); });
-                N = No;
-                cur = nxt;
-                break;
-            }
-            case K_ADD: {
-                const i64 src = g.param("src");
-                const auto& s = saved_[src + 1];
-                DASH_CHECK(!s.empty(), "residual source not saved");
-                Act x = act_of(cur), y{};
-                for (int j = 0; j < k_; ++j) y.p[j] = s[j];
-                const i64 NN = N;
-                const int B = B_;
-                add_op(lname, [x, y, NN, crt, B](hipStream_t st) { launch_add(x, y, NN, crt, B, st); });
-                break;
-            }
-            case K_CONCAT: {
-                // operands are saved copies (also the previous layer's output); each goes to its element offset
-                const auto& srcs = g.vec("srcs");
-                DASH_CHECK(!srcs.empty(), "concat: no operands");
-                i64 Ntot = 0;
-                for (i64 s : srcs) {
-                    DASH_CHECK(s >= -1 && s < static_cast<i64>(li) && !saved_[s + 1].empty(), "concat source not saved");
-                    DASH_CHECK(saved_mods[s + 1] == saved_mods[srcs[0] + 1], "concat: operands on different moduli");
-                    Ntot += saved_n[s + 1];
-                }
-                mods = saved_mods[srcs[0] + 1];
-                const CrtInfo ci = crt_info(mods);
-                Act y = act_of(nxt);
-                const int B = B_;
-                i64 off = 0;
-                for (i64 s : srcs) {
-                    Act x{};
-                    for (int j = 0; j < k_; ++j) x.p[j] = saved_[s + 1][j];
-                    const i64 Ns = saved_n[s + 1], o = off;
-                    add_op(lname, [x, Ns, y, Ntot, o, ci, B](hipStream_t st) {
-                        launch_concat_copy(x, Ns, y, Ntot, o, ci, B, st);
-                    });
-                    off += Ns;
-                }
-                N = Ntot;
-                cur = nxt;
-                break;
-            }
-            case K_PROJ: {
-                const auto& inm = g.vec("in_mod");
-                const auto& outm = g.vec("out_mod");
-                ProjArgs a{};
-                a.k = k_;
-                a.N = N;
-                a.hard = hard_ ? 1 : 0;
-                a.gate0 = gate_base(li + 1, 1);
-                for (int j = 0; j < k_; ++j) {
-                    a.pin[j] = static_cast<int>(inm[j]);
-                    a.pout[j] = static_cast<int>(outm[j]);
-                    a.tab[j] = upload_tables(li, arr_name("t.", j, ""));
-                    mods[j] = a.pout[j];
-                }
-                Act x = act_of(cur), y = act_of(nxt);
-                const ModC* mc = mc_;
-                const AesGlobals ag = aes_;
-                const int B = B_;
-                add_op(lname, [a, x, y, B, mc, ag](hipStream_t st) { launch_proj(a, x, y, B, mc, ag, st); });
-                cur = nxt;
-                break;
-            }
-            case K_MULT:
-            case K_MMULT: {
-                MultArgs a{};
-                a.crt = crt;
-                a.No = N / 2;
-                a.hard = hard_ ? 1 : 0;
-                a.gate0 = gate_base(li + 1, 1);
-                a.q = g.kind == K_MMULT ? static_cast<int>(g.param("q")) : 0;
-                if (a.q) a.t = upload_tables(li, "t");
-                a.g = upload_tables(li, "g");
-                a.e = upload_tables(li, "e");
-                Act x = act_of(cur), y = act_of(nxt);
-                const ModC* mc = mc_;
-                const AesGlobals ag = aes_;
-                const int B = B_;
-                add_op(lname, [a, x, y, B, mc, ag](hipStream_t st) { launch_mult(a, x, y, B, mc, ag, st); });
-                N = a.No;
-                cur = nxt;
-                break;
-            }
-            case K_BASEEXT: {
-                std::vector<int> ext;
-                for (auto v : g.vec("extra")) ext.push_back(static_cast<int>(v));
-                BEPlan be(crt_, ext);
-                Act x = act_of(cur);
-                const ModC* mc = mc_;
-                const AesGlobals ag = aes_;
-                const int B = B_;
-                for (int xi : be.extra_idx) {
-                    RescaleArgs ra{};
-                    ra.crt = crt;
-                    ra.N = N;
-                    ra.fi = xi;
-                    ra.zero = zero_rows_;
-                    ra.up = zero_rows_;
-                    ra.lab_stride = lab_stride_;
-                    for (int j = 0; j < k_; ++j) ra.lab_off[j] = lab_off_[j];
-                    add_op(lname + ".zero", [ra, x, B, mc](hipStream_t st) { launch_rescale_update(ra, x, B, mc, st); });
-                }
-                BEArgs ba{};
-                ba.E = static_cast<int>(be.moduli.size());
-                ba.nonext = be.nonext;
-                std::vector<int> idx(ba.E);
-                for (int i = 0; i < ba.E; ++i) idx[be.pos_of[i]] = i;
-                for (int i = 0; i < ba.E; ++i) {
-                    ba.swapped[i] = be.swapped[i];
-                    ba.src[i] = idx[i];
-                }
-                for (int i = 0; i + 1 < ba.E; ++i)
-                    for (size_t jj = 0; jj < be.inv_partial[i].size(); ++jj) ba.inv[i][jj] = static_cast<int>(be.inv_partial[i][jj]);
-                ba.nextra = static_cast<int>(be.extra.size());
-                for (int xi = 0; xi < ba.nextra; ++xi) {
-                    ba.extra_res[xi] = be.extra_idx[xi];
-                    ba.extra_pos[xi] = be.pos_of[be.extra_idx[xi]];
-                    ba.invv[xi] = static_cast<int>(pmod(-be.invv[xi], be.moduli[be.extra_idx[xi]]));
-                }
-                ba.N = N;
-                ba.n_tab = be.n_tab;
-                ba.tab = upload_tables(li, "be");
-                if (!be_work_) be_work_ = dalloc<int16_t>(static_cast<size_t>(B_) * k_ * 128 * maxN);
-                ba.work = be_work_;
-                ba.hard = hard_ ? 1 : 0;
-                ba.gate0 = gate_base(li + 1, 1);
-                add_op(lname, [ba, x, B, mc, ag](hipStream_t st) { launch_base_ext(ba, x, B, mc, ag, st); });
-                break;
-            }
-            default:
-                throw std::runtime_error(std::string("dash: HIP evaluator cannot run layer kind ") + kind_name(g.kind));
-        }
-        save_if_needed(li + 1, cur, N, mods);
+// layer reads an earlier output (projection shortcut): restore it into the current buffer
+void HipEvaluator::restore_in_src(Walk& w, const GLayer& g) {
+    const i64 src = g.param("in_src");
+    const auto& sv = saved_[src + 1];
+    DASH_CHECK(!sv.empty(), "in_src source not saved");
+    w.N = w.saved_n[src + 1];
+    w.mods = w.saved_mods[src + 1];
+    for (int j = 0; j < k_; ++j) {
+        const size_t bytes = sizeof(act_t) * B_ * nr_comps(w.mods[j]) * w.N;
+        act_t* d = bufs_[w.cur].p[j];
+        const act_t* sp = sv[j];
+        add_op("restore", [d, sp, bytes](hipStream_t st) {
+            HIPCHECK(hipMemcpyAsync(d, sp, bytes, hipMemcpyDeviceToDevice, st));
+        });
     }
-    if (stream_) add_op("stage_end", [this](hipStream_t st) { stage_end(st); });
-    final_ = act_of(cur);
-    Nout_ = N;
-    out_mod_ = mods;
+}
+
+void HipEvaluator::alloc_output_staging(const Walk& w) {
+    final_ = act_of(w.cur);
+    Nout_ = w.N;
+    out_mod_ = w.mods;
     for (int j = 0; j < k_; ++j) {
         act_t* p = nullptr;
-        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(act_t) * B_ * nr_comps(mods[j]) * std::max<i64>(Nout_, 1)));
+        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(act_t) * B_ * nr_comps(w.mods[j]) * std::max<i64>(Nout_, 1)));
         host_allocs_.push_back(p);
         out_stage_.push_back(p);
         void* dp = nullptr;
@@ -1823,19 +1130,432 @@ void HipEvaluator::build() {
         }
         out_stage_dev_.push_back(dp);
     }
-    finish_small();
-    HIPCHECK(hipDeviceSynchronize());
 }
 
-void HipEvaluator::plan_rescale_legacy(size_t li, i64 iters, i64 N, const CrtInfo& crt, const std::string& lname) {
-    const GarbledModel& m0 = *tmpl_;
-    Act x = act_of(0);
-    // the current activation buffer is whatever `cur` is; callers keep the
-    // in-place convention: rescale always operates on the current buffer
-    x = cur_act_;
-    const ModC* mc = mc_;
-    const AesGlobals ag = aes_;
+void HipEvaluator::plan_dense(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    DenseArgs a{};
+    a.crt = w.crt;
+    a.K = g.param("in");
+    a.O = g.param("out");
+    const i64 ch = g.param("channel_tf", 0);
+    const Array& wt_src = g.arr("w");
+    for (int j = 0; j < k_; ++j) {
+        const int p = crt_[j];
+        std::vector<int16_t> wt(static_cast<size_t>(a.K * a.O));
+        std::vector<int32_t> zc(a.O, 0);
+        for (i64 o = 0; o < a.O; ++o)
+            for (i64 i = 0; i < a.K; ++i) {
+                const int v = static_cast<int>(wt_src.ptr<i64>()[o * a.K + i] % p);
+                wt[i * a.O + o] = static_cast<int16_t>(v);
+                if (v == 0) ++zc[o];
+            }
+        a.w[j] = upload(wt.data(), wt.size());
+        a.zc[j] = upload(zc.data(), zc.size());
+        a.bias[j] = hard_ ? zero_i16(static_cast<size_t>(B_) * a.O * nr_comps(p))
+                          : upload_i16_rows(li, arr_name("bias.", j, ""));
+    }
+    // MFMA path: centered int8 weights [O][Kpad], channel_tf folded into the column order
+    a.Kpad = static_cast<int>((a.K + 63) / 64 * 64);
+    bool mfma_ok = mfma_ && a.K < (1 << 17);  // 127 * 127 * K fits the int32 accumulator
+    for (int j = 0; j < k_; ++j) mfma_ok = mfma_ok && crt_[j] <= 255;
+    for (int j = 0; j < k_; ++j) {
+        a.w8[j] = nullptr;
+        if (!mfma_ok) continue;
+        const int p = crt_[j];
+        std::vector<int8_t> w8(static_cast<size_t>(a.O) * a.Kpad, 0);
+        for (i64 o = 0; o < a.O; ++o)
+            for (i64 i = 0; i < a.K; ++i) {
+                const int v = static_cast<int>(wt_src.ptr<i64>()[o * a.K + i] % p);
+                const i64 s = ch > 0 ? dense_src(i, a.K, ch) : i;
+                w8[static_cast<size_t>(o) * a.Kpad + s] = static_cast<int8_t>(v > p / 2 ? v - p : v);
+            }
+        a.w8[j] = upload(w8.data(), w8.size());
+    }
+    set_label_rows(a);
+    if (ch > 0) {
+        std::vector<int32_t> src(a.K);
+        for (i64 i = 0; i < a.K; ++i) src[i] = static_cast<int32_t>(dense_src(i, a.K, ch));
+        a.src = upload(src.data(), src.size());
+    }
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    x.N = w.N;
+    y.N = a.O;
     const int B = B_;
+    add_op(lname, [a, x, y, B](hipStream_t st) { launch_dense(a, x, y, B, st); });
+    set_out(w, g, a.O, w.nxt());
+}
+
+void HipEvaluator::plan_conv(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    ConvGeom G(g);
+    ConvArgs a{};
+    a.crt = w.crt;
+    a.C = static_cast<int>(G.C); a.H = static_cast<int>(G.H); a.W = static_cast<int>(G.W);
+    a.F = static_cast<int>(G.F); a.kh = static_cast<int>(G.kh); a.kw = static_cast<int>(G.kw);
+    a.sh = static_cast<int>(G.sh); a.sw = static_cast<int>(G.sw);
+    a.ph = static_cast<int>(G.ph); a.pw = static_cast<int>(G.pw);
+    a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
+    const i64 K = G.K();
+    a.use_mfma = mfma_ ? 1 : 0;
+    a.groups = static_cast<int>(G.g);
+    if (G.g > 1) {
+        // grouped conv: the byte-stencil kernel, no MFMA plan
+        a.use_mfma = 0;
+        for (int j = 0; j < k_; ++j) {
+            const u64 pm = static_cast<u64>(crt_[j] - 1);
+            DASH_CHECK(crt_[j] <= kActMaxModulus, "grouped conv: residue modulus above 255");
+            DASH_CHECK(static_cast<u64>(K) * pm * pm < (1ull << 32),
+                       "grouped conv: (C/g)*kh*kw*(p-1)^2 must stay below 2^32 (32-bit accumulator)");
+        }
+        DASH_CHECK(conv_grp_geometry(a) > 0, "grouped conv: one output row of a group exceeds 64 KiB of LDS");
+    } else {
+        // LDS-image kernel geometry: 64-channel chunks, row bands that fit the LDS budget
+        conv_layer_plan(a, mfma_ && conv_img_enabled());
+    }
+    a.img_off[0] = 0;
+    for (int j = 0; j < k_; ++j) a.img_off[j + 1] = a.img_off[j] + static_cast<i64>(B_) * w.crt.n[j];
+    const Array& wt = g.arr("w");
+    for (int j = 0; j < k_; ++j) {
+        const int p = crt_[j];
+        const bool grp = G.g > 1;  // k_conv_grp reads its own image (wg) only
+        std::vector<int16_t> wm(grp ? 0 : static_cast<size_t>(G.F * K));
+        std::vector<int8_t> w8(grp ? 0 : static_cast<size_t>(G.F) * a.Kpad, 0);
+        std::vector<int32_t> zc(G.F, 0);
+        for (i64 f = 0; f < G.F; ++f)
+            for (i64 q = 0; q < K; ++q) {
+                const int v = static_cast<int>(wt.ptr<i64>()[f * K + q] % p);
+                if (v == 0) ++zc[f];
+                if (grp) continue;
+                wm[f * K + q] = static_cast<int16_t>(v);
+                w8[f * a.Kpad + q] = static_cast<int8_t>(v > p / 2 ? v - p : v);
+            }
+        a.w[j] = grp ? nullptr : upload(wm.data(), wm.size());
+        a.w8[j] = (mfma_ && p <= 255 && !grp) ? upload(w8.data(), w8.size()) : nullptr;
+        a.wg[j] = nullptr;
+        if (grp) {
+            const std::vector<uint32_t> wg = conv_grp_weights(wt.ptr<i64>(), G.F, G.Cg(), a.kh, a.kw, p);
+            a.wg[j] = upload(wg.data(), wg.size());
+        }
+        if (a.nbands > 0 && p <= 255) {
+            // [F16][kh][kw][Cpad] centered int8 (im2col order ci*kh*kw + dy*kw + dx -> (dy, dx, ci))
+            const std::vector<int8_t> w8r = conv_w8r(a, w8, static_cast<int>(G.F));
+            a.w8r[j] = upload(w8r.data(), w8r.size());
+        } else {
+            a.w8r[j] = nullptr;
+        }
+        a.zc[j] = upload(zc.data(), zc.size());
+        a.bias[j] = hard_ ? zero_i16(static_cast<size_t>(B_) * G.F * nr_comps(p))
+                          : upload_i16_rows(li, arr_name("bias.", j, ""));
+    }
+    set_label_rows(a);
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const int B = B_;
+    add_op(lname, [a, x, y, B](hipStream_t st) { launch_conv(a, x, y, B, st); });
+    set_out(w, g, G.out_size(), w.nxt());
+}
+
+void HipEvaluator::plan_relu(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    const Env e = w.env;
+    const i64 smode = g.param("smode", 0);
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    if (smode == 2) {  // sign from the preceding rescale (RescaleMrsPlan::sign_last)
+        DASH_CHECK(li > 0 && m0.layers[li - 1].kind == K_RESCALE && m0.layers[li - 1].param("sign_out", 0) == 1,
+                   "joint ReLU must follow a sign-producing rescale");
+        const SignArgs sa = joint_sign_args(w, li, w.N);
+        const u128* gt = upload_tables(li, "mm.g");
+        const u128* et = upload_tables(li, "mm.e");
+        if (w.pending == Walk::Pending::relu) {
+            const MrsArgs ma = w.pending_a;
+            w.pending = Walk::Pending::none;
+            add_op(lname + ".C", [ma, sa, x, y, gt, et, e](hipStream_t st) {
+                launch_rescale_relu_out(ma, sa, x, y, gt, et, e.B, e.mc, e.ag, st);
+            });
+        } else {
+            add_op(lname + ".C", [sa, x, y, gt, et, e](hipStream_t st) {
+                launch_relu_joint(sa, x, y, gt, et, e.B, e.mc, e.ag, st);
+            });
+        }
+    } else if (smode == 1) {  // exact mixed-radix sign (gadgets.h SignMrsPlan)
+        DASH_CHECK(hard_, "the mixed-radix sign exists in the hardened encoding only");
+        const MrsArgs a = mrs_sign_args(w, li, "mrs", w.N, gate_base(li + 1, 1), gate_base(li + 1, 2), ny_, nullptr);
+        const SignArgs sa = joint_sign_args(w, li, w.N);
+        const u128* gt = upload_tables(li, "mm.g");
+        const u128* et = upload_tables(li, "mm.e");
+        add_op(lname + ".mrs", [a, sa, x, y, gt, et, e](hipStream_t st) {
+            launch_relu_mrs(a, sa, x, y, gt, et, e.B, e.mc, e.ag, st);
+        });
+    } else {
+        SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
+        const Sign s = make_sign(li, "", sp, w.N, 1, gate_base(li + 1, 1), gate_base(li + 1, 2));
+        const SignArgs a = s.a;
+        const int maxn = s.maxn;
+        const u128* gt = upload_tables(li, "mm.g");
+        const u128* et = upload_tables(li, "mm.e");
+        add_op(lname + ".A", [a, x, e](hipStream_t st) { launch_sign_approx(a, x, e.mc, e.ag, st); });
+        add_op(lname + ".B", [a, maxn, e](hipStream_t st) { launch_sign_chain(a, maxn, e.mc, e.ag, st); });
+        add_op(lname + ".C", [a, x, y, gt, et, e](hipStream_t st) { launch_relu_mult(a, x, y, gt, et, e.mc, st); });
+    }
+    set_out(w, g, w.N, w.nxt());
+}
+
+// gadgets.h ClipPlan: the half gates' keys of x, the sign evaluation once per bound on the same labels (each into
+// its own scratch), then the multiply + cap
+void HipEvaluator::plan_clip(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    DASH_CHECK(hard_, "the Clip layer exists in the hardened encoding only");
+    ensure_ks(w, 2);
+    ClipArgs ca{};
+    ca.crt = w.crt;
+    ca.N = w.N;
+    ca.hx = hx_;
+    ca.colx = colx_;
+    ca.klo = ks_[0];
+    ca.khi = ks_[1];
+    ca.gtab = upload_tables(li, "mm.g");
+    ca.etab = upload_tables(li, "mm.e");
+    ca.cap = upload_tables(li, "cap");
+    ca.mgate0 = gate_base(li + 1, 2);
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const Env e = w.env;
+    const i64 smode = g.param("smode", 0);
+    if (smode == 2) {
+        // joint variant: the rescale before it left both sign labels (ks_) and the half-gate keys of its output
+        // (hx_ / colx_); only the multiply + cap is left
+        DASH_CHECK(li > 0 && m0.layers[li - 1].kind == K_RESCALE && m0.layers[li - 1].param("sign_out", 0) == 1 &&
+                       !g.p.count("in_src") && g.vec("lo").at(0) == 0,
+                   "joint Clip must follow a sign-producing rescale");
+        if (w.pending == Walk::Pending::clip) {
+            const MrsArgs ma = w.pending_a;
+            w.pending = Walk::Pending::none;
+            add_op(lname + ".C", [ma, ca, x, y, e](hipStream_t st) {
+                launch_rescale_clip_out(ma, ca, x, y, e.B, e.mc, e.ag, st);
+            });
+        } else {
+            add_op(lname + ".C", [ca, x, y, e](hipStream_t st) { launch_clip_mult(ca, x, y, e.B, e.mc, st); });
+        }
+        set_out(w, g, w.N, w.nxt());
+        return;
+    }
+    const bool exact = smode == 1;
+    // the half gates' keys of x: the approximate sign's first phase compresses x anyway and writes them (lower
+    // bound's run, below); the mixed-radix chain does not, so they get a pass of their own
+    if (exact) {
+        u128* hx = hx_;
+        uint16_t* colx = colx_;
+        add_op(lname + ".H", [ca, hx, colx, x, e](hipStream_t st) {
+            launch_clip_hash(ca, hx, colx, x, e.B, e.mc, e.ag, st);
+        });
+    }
+    for (int side = 0; side < 2; ++side) {
+        const std::string pre = side ? "hi." : "lo.";
+        const uint64_t sgate = gate_base(li + 1, side ? 3 : 1);
+        if (exact) {  // exact mixed-radix sign, label kept in ks; no y-row pads: the multiply forms the pads of
+                      // u = s_lo + s_hi itself
+            const MrsArgs a = mrs_sign_args(w, li, pre + "mrs", w.N, sgate, ca.mgate0, 0, ks_[side]);
+            add_op(lname + "." + pre + "mrs", [a, x, e](hipStream_t st) {
+                launch_clip_sign_mrs(a, x, e.B, e.mc, e.ag, st);
+            });
+        } else {
+            SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
+            const Sign s = make_sign(li, pre, sp, w.N, 0, sgate, 0);
+            SignArgs a = s.a;
+            a.outP = ks_[side];  // nout = 1: [B][N]
+            if (side == 0) {  // (TW_MMG, j) pads of x_j under the multiply's gate, as a ReLU's phase A
+                a.hx = hx_;
+                a.colx = colx_;
+                a.mgate0 = ca.mgate0;
+            }
+            const int maxn = s.maxn;
+            add_op(lname + "." + pre + "A", [a, x, e](hipStream_t st) { launch_sign_approx(a, x, e.mc, e.ag, st); });
+            add_op(lname + "." + pre + "B", [a, maxn, e](hipStream_t st) { launch_sign_chain(a, maxn, e.mc, e.ag, st); });
+        }
+    }
+    add_op(lname + ".C", [ca, x, y, e](hipStream_t st) { launch_clip_mult(ca, x, y, e.B, e.mc, st); });
+    set_out(w, g, w.N, w.nxt());
+}
+
+void HipEvaluator::plan_sign(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    SignPlan sp(crt_, m0.h.mrs, crt_, -1, 1, m0.h.sign_fused != 0);
+    const Sign s = make_sign(li, "", sp, w.N, 0, gate_base(li + 1, 1), 0);
+    const SignArgs a = s.a;
+    const int maxn = s.maxn;
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const Env e = w.env;
+    const CrtInfo crt = w.crt;
+    const u128* outP = outP_;
+    const i64 NN = w.N;
+    add_op(lname + ".A", [a, x, e](hipStream_t st) { launch_sign_approx(a, x, e.mc, e.ag, st); });
+    add_op(lname + ".B", [a, maxn, e](hipStream_t st) { launch_sign_chain(a, maxn, e.mc, e.ag, st); });
+    add_op(lname + ".unpack", [outP, y, crt, NN, e](hipStream_t st) { launch_unpack(outP, crt.k, y, crt, e.mc, NN, e.B, st); });
+    set_out(w, g, w.N, w.nxt());
+}
+
+// every rescale works in place, on the current buffer
+void HipEvaluator::plan_rescale(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const i64 mode = g.param("mode", 0);
+    const i64 iters = g.param("iters");
+    if (mode == 2)
+        plan_rescale_mrs(w, li, g, lname);
+    else if (mode == 0)
+        plan_rescale_legacy(w, li, iters, act_of(w.cur), lname);
+    else
+        plan_rescale_redash(w, li, g, lname);
+    set_out(w, g, w.N, w.cur);
+}
+
+// mixed-radix construction of the legacy function (gadgets.h RescaleMrsPlan)
+void HipEvaluator::plan_rescale_mrs(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    const i64 N = w.N;
+    const bool so = g.param("sign_out", 0) == 1;  // joint: the next ReLU's sign -> hs_, cs_
+    const RescaleMrsPlan P(crt_, static_cast<int>(g.param("l")), so);
+    DASH_CHECK(P.T <= m0.h.max_mod, "model lacks the mod-2^(l+1) label constants");
+    MrsArgs a{};
+    a.crt = w.crt;
+    a.T = static_cast<int>(P.T);
+    a.N = N;
+    a.n_tab = P.n_tab;
+    a.tab = upload_tables(li, "mrs");
+    for (int i = 0; i < k_; ++i) {
+        a.dig_off[i] = P.dig_off[i];
+        a.sinv[i] = static_cast<int>(P.Sinv[i]);
+    }
+    a.fin_off = P.fin_off;
+    const int bits = P.l + 1, nf = nr_comps(static_cast<int>(P.T));
+    a.hmask = 0;
+    for (int f = 0; f < nf; ++f) a.hmask |= static_cast<u128>(1) << (bits * f + bits - 1);
+    a.pf = outP_;  // [B][k][N] <= the sign outputs' scratch
+    ensure_mrs_ps(w);
+    a.ps = mrs_ps_;
+    a.mode = so ? 2 : 0;
+    a.hs = hs_;
+    a.cs = cs_;
+    a.hx = hx_;
+    a.colx = colx_;
+    DASH_CHECK(hard_, "the mixed-radix rescale exists in the hardened encoding only");
+    a.gate0 = gate_base(li + 1, 30);
+    a.rgate0 = so ? gate_base(li + 2, 2) : 0;  // the joint ReLU (next layer)'s half gates
+    a.ny = ny_;
+    a.ys = ys_;
+    const bool has_next = li + 1 < m0.layers.size();
+    if (so && has_next && m0.layers[li + 1].kind == K_CLIP && m0.layers[li + 1].param("smode", 0) == 2) {
+        plan_rescale_clip(w, li, a, lname);
+        return;
+    }
+    // joint ReLU next and this output not kept for a later layer: the ReLU's op can write both outputs in one
+    // pass (launch_rescale_relu_out), here only the chain runs. The rescaled label is then never written: the
+    // fused kernels keep it in LDS. Which launches take it is launch.h joint_fuse: batches of at most 2 GCs
+    // (latency_b1 2.21 -> 2.14 ms), and staged shapes from 13,824 elements over the batch, where the throughput
+    // form wins on every MiniONN layer (24-GC step 9.08 -> 7.55 ms, profiles/ab/joint_fused/README.md);
+    // hip_set_joint_fuse (initially DASH_JOINT_FUSE=0/1) forces it off/on.
+    const bool defer = dev::joint_fuse(N, B_) && so && has_next && m0.layers[li + 1].kind == K_RELU &&
+                       m0.layers[li + 1].param("smode", 0) == 2 && !w.keep[li + 1] &&
+                       !m0.layers[li + 1].p.count("in_src");
+    if (defer) {
+        w.pending_a = a;
+        w.pending = Walk::Pending::relu;
+    }
+    Act x = act_of(w.cur);
+    const Env e = w.env;
+    add_op(lname + ".mrs", [a, x, e, defer](hipStream_t st) { launch_rescale_mrs(a, x, e.B, e.mc, e.ag, st, defer); });
+}
+
+// A joint Clip next (gadgets.h ClipPlan, joint variant): the chain keeps its mod-2 key as the Clip's lower sign
+// label (ks_[0], no y-row pads), the Clip's upper sign chain (mode 1, the Clip layer's tables and slot-3 gate) runs
+// on the same input labels into ks_[1], and only then the output kernel rewrites x in place, leaving y's half-gate
+// keys under the Clip's multiply gate in hx_ / colx_. Both chains share mrs_ps_; the mode-1 chain writes neither
+// a.pf nor outP_, so the rescale's final payloads wait there.
+void HipEvaluator::plan_rescale_clip(Walk& w, size_t li, MrsArgs a, const std::string& lname) {
+    const GLayer& gc = tmpl_->layers[li + 1];
+    const i64 N = w.N;
+    DASH_CHECK(!gc.p.count("in_src"), "joint Clip must read the rescale before it");
+    ensure_ks(w, 2);
+    a.ks = ks_[0];
+    a.ny = 0;
+    DASH_CHECK(gc.arr("hi.mrs").shape[0] == N && gc.arr("hi.mrs").shape[1] == std::max<i64>(SignMrsPlan(crt_).n_tab, 1),
+               "joint Clip upper sign table shape");
+    const MrsArgs h = mrs_sign_args(w, li + 1, "hi.mrs", N, gate_base(li + 2, 3), a.rgate0, 0, ks_[1]);
+    Act x = act_of(w.cur);
+    const Env e = w.env;
+    add_op(lname + ".mrs", [a, x, e](hipStream_t st) { launch_rescale_mrs(a, x, e.B, e.mc, e.ag, st, true); });
+    // streamed tables: the Clip layer's window was issued by this layer's stage op
+    if (stream_)
+        add_op(lname + ".wait", [this, li](hipStream_t st) {
+            HIPCHECK(hipStreamWaitEvent(st, ready_[li + 1], 0));
+        });
+    add_op(lname + ".clip_hi", [h, x, e](hipStream_t st) { launch_clip_sign_mrs(h, x, e.B, e.mc, e.ag, st); });
+    // output not kept for a later layer and the fusion on (launch.h clip_fuse): the Clip's op writes both outputs
+    // in one pass (launch_rescale_clip_out), the rescaled label stays in LDS
+    if (dev::clip_fuse(N, B_) && !w.keep[li + 1]) {
+        w.pending_a = a;
+        w.pending = Walk::Pending::clip;
+    } else {
+        add_op(lname + ".out", [a, x, e](hipStream_t st) { launch_rescale_mrs_out(a, x, e.B, e.mc, e.ag, st); });
+    }
+}
+
+// ReDash rescale: per iteration and factor the factor residue's hash and the update, then the base extension
+// that restores the factor residues and the downshift. (The sign base extension in place of the BEPlan exists in
+// the legacy mode only: plan_rescale_legacy.)
+void HipEvaluator::plan_rescale_redash(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    const i64 N = w.N, iters = g.param("iters");
+    const CrtInfo crt = w.crt;
+    const Env e = w.env;
+    Act x = act_of(w.cur);
+    std::vector<int> factors;
+    for (auto v : g.vec("s")) factors.push_back(static_cast<int>(v));
+    const RescalePlan P(crt_, m0.h.mrs, factors, false, m0.h.sign_fused != 0);
+    for (i64 it = 0; it < iters; ++it) {
+        const std::string pre = arr_name("it", static_cast<int>(it), ".");
+        const u128* trans = upload_tables(li, pre + "trans");
+        i64 off = 0;
+        for (size_t f = 0; f < P.factors.size(); ++f) {
+            const int fi = P.factor_idx[f], s = P.factors[f];
+            const int add_up = f == 0 ? 1 : 0;
+            const int16_t* up = up_rows_ + lab_off_[fi];
+            u128* h0 = h0_;
+            uint16_t* col0 = col0_;
+            const int ls = lab_stride_;
+            const int hd = hard_ ? 1 : 0;
+            add_op(lname + ".hash", [x, fi, s, up, ls, add_up, N, h0, col0, e, hd](hipStream_t st) {
+                launch_rescale_hash(x, fi, s, up, ls, add_up, N, e.B, h0, col0, e.mc, e.ag, st, hd);
+            });
+            RescaleArgs ra{};
+            ra.crt = crt;
+            ra.N = N;
+            ra.fi = fi;
+            ra.s = s;
+            ra.add_up = add_up;
+            set_active(ra, P, f, trans);
+            ra.off = off;
+            off += static_cast<i64>(P.active[f].size()) * s;
+            ra.up = up_rows_;
+            set_label_rows(ra);
+            ra.hard = hd;
+            ra.gate0 = gate_base(li + 1, 10 + it);
+            ra.factor = static_cast<int>(f);
+            add_op(lname + ".update", [ra, x, e](hipStream_t st) { launch_rescale_update(ra, x, e.B, e.mc, st); });
+        }
+        const BEArgs ba = be_args(w, P.be, li, pre + "be", N, gate_base(li + 1, 10 + it));
+        add_op(lname + ".be", [ba, x, e](hipStream_t st) { launch_base_ext(ba, x, e.B, e.mc, e.ag, st); });
+        const int16_t* down = upload_const_rows(
+            [&](int j) { return "down." + std::to_string(P.sprod) + "." + std::to_string(j); });
+        const u128* signP = nullptr;  // no sign base extension: the base extension above restored the residues
+        const int ls = lab_stride_;
+        const int* loff = d_lab_off_;
+        add_op(lname + ".post", [x, crt, N, signP, down, ls, loff, e](hipStream_t st) {
+            launch_rescale_post(x, crt, N, e.B, signP, down, ls, loff, e.mc, st);
+        });
+    }
+}
+
+void HipEvaluator::plan_rescale_legacy(Walk& w, size_t li, i64 iters, Act x, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    const i64 N = w.N;
+    const CrtInfo crt = w.crt;
+    const Env e = w.env;
     const int ls = lab_stride_;
     DASH_CHECK(crt_[0] == 2, "legacy rescale needs crt[0] == 2");
     // per-GC constants: delta = up - down (all residues), du = bits(up0) ^ bits(down0)
@@ -1869,23 +1589,24 @@ void HipEvaluator::plan_rescale_legacy(size_t li, i64 iters, i64 N, const CrtInf
         du = ddu;
     }
     const int16_t* down = upload_const_rows([&](int j) { return "down.2." + std::to_string(j); });
+    const RescalePlan P(crt_, m0.h.mrs, {2}, true, m0.h.sign_fused != 0);
     for (i64 it = 0; it < iters; ++it) {
-        RescalePlan P(crt_, m0.h.mrs, {2}, true, m0.h.sign_fused != 0);
         const std::string pre = arr_name("it", static_cast<int>(it), ".");
         const u128* trans = upload_tables(li, pre + "trans");
-        SignArgs sa = make_sign(li, pre, P.sign, N, 0);
-        const int maxn = sign_maxn_;
+        const Sign sg = make_sign(li, pre, P.sign, N, 0);
+        const SignArgs sa = sg.a;
+        const int maxn = sg.maxn;
         u128* h0 = h0_;
         uint16_t* col0 = col0_;
         if (it == 0) {
             const int16_t* up = up_rows_ + lab_off_[0];
-            add_op(lname + ".hash", [x, up, ls, N, B, h0, col0, mc, ag](hipStream_t st) {
-                launch_rescale_hash(x, 0, 2, up, ls, 1, N, B, h0, col0, mc, ag, st);
+            add_op(lname + ".hash", [x, up, ls, N, h0, col0, e](hipStream_t st) {
+                launch_rescale_hash(x, 0, 2, up, ls, 1, N, e.B, h0, col0, e.mc, e.ag, st);
             });
         } else {
             const u128* sp = outP_;
-            add_op(lname + ".hash", [sp, du, N, B, h0, col0, ag](hipStream_t st) {
-                launch_rescale_hash_sign(sp, du, N, B, h0, col0, ag, st);
+            add_op(lname + ".hash", [sp, du, N, h0, col0, e](hipStream_t st) {
+                launch_rescale_hash_sign(sp, du, N, e.B, h0, col0, e.ag, st);
             });
         }
         RescaleArgs ra{};
@@ -1894,31 +1615,307 @@ void HipEvaluator::plan_rescale_legacy(size_t li, i64 iters, i64 N, const CrtInf
         ra.fi = 0;
         ra.s = 2;
         ra.add_up = 1;
-        for (size_t q = 0; q < P.active[0].size(); ++q) {
-            const int jj = P.active[0][q];
-            ra.active[jj] = 1;
-            ra.aidx[jj] = static_cast<int>(q);
-            ra.inv[jj] = static_cast<int>(P.inv[0][q]);
-        }
-        ra.n_trans = P.n_trans;
+        set_active(ra, P, 0, trans);
         ra.off = 0;
-        ra.trans = trans;
-        ra.h0 = h0_;
-        ra.col0 = col0_;
-        ra.lab_stride = lab_stride_;
-        for (int j = 0; j < k_; ++j) ra.lab_off[j] = lab_off_[j];
+        set_label_rows(ra);
         const int16_t* dl = it == 0 ? up_rows_ : delta;
         const u128* zh = zh_;
-        add_op(lname + ".upd+A", [ra, sa, x, dl, zh, B, mc, ag](hipStream_t st) {
-            launch_rescale_update_approx(ra, sa, x, dl, zh, B, mc, ag, st);
+        add_op(lname + ".upd+A", [ra, sa, x, dl, zh, e](hipStream_t st) {
+            launch_rescale_update_approx(ra, sa, x, dl, zh, e.B, e.mc, e.ag, st);
         });
-        add_op(lname + ".B", [sa, maxn, mc, ag](hipStream_t st) { launch_sign_chain(sa, maxn, mc, ag, st); });
+        add_op(lname + ".B", [sa, maxn, e](hipStream_t st) { launch_sign_chain(sa, maxn, e.mc, e.ag, st); });
     }
     const u128* signP = outP_;
     const int* loff = d_lab_off_;
-    add_op(lname + ".post", [x, crt, N, B, signP, down, ls, loff, mc](hipStream_t st) {
-        launch_rescale_post(x, crt, N, B, signP, down, ls, loff, mc, st);
+    add_op(lname + ".post", [x, crt, N, signP, down, ls, loff, e](hipStream_t st) {
+        launch_rescale_post(x, crt, N, e.B, signP, down, ls, loff, e.mc, st);
     });
+}
+
+// K_MAXPOOL and K_MAX: a gather of the windows, then one ReLU of pairwise differences per level of the max tree
+void HipEvaluator::plan_max(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    const CrtInfo crt = w.crt;
+    const Env e = w.env;
+    const int B = B_;
+    const i64 NN = w.N;
+    const int cur = w.cur, nxt = w.nxt();
+    i64 Nout, K;
+    std::vector<i64> idx;
+    if (g.kind == K_MAXPOOL) {
+        PoolGeom G(g.p);
+        Nout = G.out_size();
+        K = G.kh * G.kw;
+        std::vector<i64> win;
+        for (i64 o = 0; o < Nout; ++o) {
+            G.window(o, win);
+            idx.insert(idx.end(), win.begin(), win.end());
+        }
+    } else {
+        Nout = 1;
+        K = NN;
+        for (i64 i = 0; i < NN; ++i) idx.push_back(i);
+    }
+    const int64_t* didx = upload(idx.data(), idx.size());
+    MaxTree T(K);
+    SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
+    // buffers: the candidate values ping-pong between bufs 2 / 3; the differences reuse buffer `cur` (its content
+    // is no longer needed) and the ReLU's output goes to `nxt`
+    int va = 2, vb = 3;
+    Act xin = act_of(cur), v0 = act_of(va);
+    add_op(lname + ".gather", [xin, NN, v0, Nout, K, didx, crt, B](hipStream_t st) {
+        launch_copy_gather(xin, NN, v0, Nout * K, didx, crt, B, st);
+    });
+    for (size_t lv = 0; lv < T.ops.size(); ++lv) {
+        const int ops = T.ops[lv], cnt = T.cnt[lv], cnt1 = T.cnt[lv + 1];
+        const std::string pre = arr_name("lv", static_cast<int>(lv), ".");
+        const Sign s = make_sign(li, pre, sp, Nout * ops, 1, gate_base(li + 1, 20 + 2 * lv), gate_base(li + 1, 21 + 2 * lv));
+        const SignArgs a = s.a;
+        const int maxn = s.maxn;
+        const u128* gt = upload_tables(li, pre + "mm.g");
+        const u128* et = upload_tables(li, pre + "mm.e");
+        Act V = act_of(va), D = act_of(cur), Rr = act_of(nxt), NV = act_of(vb);
+        const i64 Nv = Nout * cnt;
+        add_op(lname + ".diff", [V, Nv, D, Nout, ops, cnt, crt, B](hipStream_t st) {
+            launch_pair_diff(V, Nv, D, Nout, ops, cnt, crt, B, st);
+        });
+        add_op(lname + ".A", [a, D, e](hipStream_t st) { launch_sign_approx(a, D, e.mc, e.ag, st); });
+        add_op(lname + ".B", [a, maxn, e](hipStream_t st) { launch_sign_chain(a, maxn, e.mc, e.ag, st); });
+        add_op(lname + ".C", [a, D, Rr, gt, et, e](hipStream_t st) { launch_relu_mult(a, D, Rr, gt, et, e.mc, st); });
+        add_op(lname + ".add", [V, Nv, Rr, NV, Nout, ops, cnt, cnt1, crt, B](hipStream_t st) {
+            launch_pair_add(V, Nv, Rr, NV, Nout, ops, cnt, cnt1, crt, B, st);
+        });
+        std::swap(va, vb);
+    }
+    // result (cnt == 1) lives in buffer va: copy into nxt
+    std::vector<i64> ident(Nout);
+    for (i64 o = 0; o < Nout; ++o) ident[o] = o;
+    const int64_t* did = upload(ident.data(), ident.size());
+    Act vres = act_of(va), y = act_of(nxt);
+    add_op(lname + ".out", [vres, Nout, y, did, crt, B](hipStream_t st) {
+        launch_copy_gather(vres, Nout, y, Nout, did, crt, B, st);
+    });
+    set_out(w, g, Nout, nxt);
+}
+
+// gadgets.h ArgMaxPlan. The (K, P) input is level 0's candidate buffer as it stands; later levels ping-pong between
+// bufs 2 / 3 (values / index labels) and the ArgMax scratch; the root writes its index labels into the layer's
+// output buffer.
+void HipEvaluator::plan_argmax(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    DASH_CHECK(hard_, "the ArgMax layer exists in the hardened encoding only");
+    const i64 K = g.param("K"), P = g.param("P");
+    DASH_CHECK(K >= 2 && K * P == w.N, "argmax input size mismatch");
+    const ArgMaxPlan ap(crt_, K);
+    if (!amb_[0].p[0]) {
+        for (auto& ab : amb_)
+            for (int j = 0; j < k_; ++j) {
+                const size_t count = static_cast<size_t>(B_) * w.caps.widest[j] * w.caps.maxArgSlots + 64;
+                ab.p[j] = dalloc<act_t>(count);
+                HIPCHECK(hipMemset(ab.p[j], 0, count * sizeof(act_t)));
+            }
+        am_hi_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * w.caps.maxSignN);
+        am_coli_ = dalloc<uint16_t>(static_cast<size_t>(B_) * k_ * w.caps.maxSignN);
+    }
+    ensure_ks(w, 1);
+    ensure_mrs_ps(w);
+    const CrtInfo crt = w.crt;
+    const Env e = w.env;
+    const int B = B_;
+    Act V = act_of(w.cur), I = act_of(3);
+    const Act D = amb_[2], E = amb_[3];
+    for (int lv = 0; lv < ap.levels(); ++lv) {
+        const bool root = ap.root(lv), l0 = lv == 0;
+        const int ops = ap.ops[lv], cnt = ap.cnt[lv];
+        const i64 Nops = P * ops;
+        const std::string pre = arr_name("lv", lv, ".");
+        const std::string op = lname + ".lv" + std::to_string(lv);
+        // outputs: values into buf 2 / scratch 0, index labels into buf 3 / scratch 1, alternating
+        const Act NV = (lv % 2 == 0) ? act_of(2) : amb_[0];
+        const Act NI = root ? act_of(w.nxt()) : ((lv % 2 == 0) ? act_of(3) : amb_[1]);
+        ArgMaxArgs a{};
+        a.crt = crt;
+        a.P = P;
+        a.ops = ops;
+        a.cnt = cnt;
+        a.cnt1 = ap.cnt[lv + 1];
+        a.pubq = ap.pub[lv][cnt - 1] >= 0 && cnt % 2 == 0 ? ops - 1 : -1;
+        a.carry_idx = cnt % 2 == 1 && ap.pub[lv][cnt - 1] < 0;
+        a.ks = ks_[0];
+        a.hx = hx_;
+        a.colx = colx_;
+        a.hi = am_hi_;
+        a.coli = am_coli_;
+        a.vgate0 = gate_base(li + 1, 21 + 3 * lv);
+        a.igate0 = gate_base(li + 1, 22 + 3 * lv);
+        if (!root) {
+            a.gtab = upload_tables(li, pre + "mm.g");
+            a.etab = upload_tables(li, pre + "mm.e");
+        }
+        if (l0) {
+            a.itab = upload_tables(li, pre + "idx");
+        } else {
+            a.igtab = upload_tables(li, pre + "im.g");
+            a.ietab = upload_tables(li, pre + "im.e");
+        }
+        // the sign of the value difference (ArgMaxPlan::sign is the SignMrsPlan of the CRT base), label kept in ks;
+        // no y-row pads: the multiply derives the pads of both gate sets from the label
+        const MrsArgs s = mrs_sign_args(w, li, pre + "mrs", Nops, gate_base(li + 1, 20 + 3 * lv), a.vgate0, 0, ks_[0]);
+        add_op(op + ".diff", [V, D, P, ops, cnt, crt, B](hipStream_t st) {
+            launch_argmax_diff(V, D, P, ops, cnt, -1, crt, B, st);
+        });
+        if (!l0) {
+            const int pubq = a.pubq;
+            add_op(op + ".idiff", [I, E, P, ops, cnt, pubq, crt, B](hipStream_t st) {
+                launch_argmax_diff(I, E, P, ops, cnt, pubq, crt, B, st);
+            });
+        }
+        if (!root) {
+            u128* hx = hx_;
+            uint16_t* colx = colx_;
+            const uint64_t vg = a.vgate0;
+            add_op(op + ".H", [D, crt, Nops, hx, colx, vg, e](hipStream_t st) {
+                launch_argmax_hash(D, crt, Nops, hx, colx, vg, e.B, e.mc, e.ag, st);
+            });
+        }
+        if (!l0) {
+            u128* hi = am_hi_;
+            uint16_t* coli = am_coli_;
+            const uint64_t ig = a.igate0;
+            add_op(op + ".iH", [E, crt, Nops, hi, coli, ig, e](hipStream_t st) {
+                launch_argmax_hash(E, crt, Nops, hi, coli, ig, e.B, e.mc, e.ag, st);
+            });
+        }
+        add_op(op + ".mrs", [s, D, e](hipStream_t st) { launch_clip_sign_mrs(s, D, e.B, e.mc, e.ag, st); });
+        add_op(op + ".C", [a, root, l0, V, D, I, E, NV, NI, e](hipStream_t st) {
+            launch_argmax_mult(a, !root, l0, V, D, I, E, NV, NI, e.B, e.mc, st);
+        });
+        V = NV;
+        I = NI;
+    }
+    set_out(w, g, P, w.nxt());
+}
+
+void HipEvaluator::plan_sumpool(Walk& w, size_t, const GLayer& g, const std::string& lname) {
+    PoolGeom G(g.p);
+    const CrtInfo crt = w.crt;
+    const int B = B_;
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    if (G.padded()) {
+        // ragged windows: the geometry-direct kernel skips the taps outside the image
+        const PoolArgs pa{static_cast<int>(G.C),  static_cast<int>(G.H),  static_cast<int>(G.W),
+                          static_cast<int>(G.kh), static_cast<int>(G.kw), static_cast<int>(G.sh),
+                          static_cast<int>(G.sw), static_cast<int>(G.ph), static_cast<int>(G.pw),
+                          static_cast<int>(G.OH), static_cast<int>(G.OW)};
+        DASH_CHECK(G.C * G.H * G.W == w.N, "sumpool input size mismatch");
+        add_op(lname + ".geom", [x, y, pa, crt, B](hipStream_t st) { launch_pool_sum(x, y, pa, crt, B, st); });
+    } else {
+        std::vector<i64> idx, win;
+        for (i64 o = 0; o < G.out_size(); ++o) {
+            G.window(o, win);
+            idx.insert(idx.end(), win.begin(), win.end());
+        }
+        const int64_t* didx = upload(idx.data(), idx.size());
+        const i64 NN = w.N, No = G.out_size();
+        const int K = static_cast<int>(G.kh * G.kw);
+        add_op(lname, [x, NN, y, No, didx, K, crt, B](hipStream_t st) { launch_window_sum(x, NN, y, No, didx, K, crt, B, st); });
+    }
+    set_out(w, g, G.out_size(), w.nxt());
+}
+
+void HipEvaluator::plan_add(Walk& w, size_t, const GLayer& g, const std::string& lname) {
+    const i64 src = g.param("src");
+    const auto& s = saved_[src + 1];
+    DASH_CHECK(!s.empty(), "residual source not saved");
+    Act x = act_of(w.cur), y{};
+    for (int j = 0; j < k_; ++j) y.p[j] = s[j];
+    const i64 NN = w.N;
+    const CrtInfo crt = w.crt;
+    const int B = B_;
+    add_op(lname, [x, y, NN, crt, B](hipStream_t st) { launch_add(x, y, NN, crt, B, st); });
+    set_out(w, g, w.N, w.cur);
+}
+
+// operands are saved copies (also the previous layer's output); each goes to its element offset
+void HipEvaluator::plan_concat(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const auto& srcs = g.vec("srcs");
+    DASH_CHECK(!srcs.empty(), "concat: no operands");
+    i64 Ntot = 0;
+    for (i64 s : srcs) {
+        DASH_CHECK(s >= -1 && s < static_cast<i64>(li) && !saved_[s + 1].empty(), "concat source not saved");
+        DASH_CHECK(w.saved_mods[s + 1] == w.saved_mods[srcs[0] + 1], "concat: operands on different moduli");
+        Ntot += w.saved_n[s + 1];
+    }
+    w.mods = w.saved_mods[srcs[0] + 1];
+    const CrtInfo ci = crt_info(w.mods);
+    Act y = act_of(w.nxt());
+    const int B = B_;
+    i64 off = 0;
+    for (i64 s : srcs) {
+        Act x{};
+        for (int j = 0; j < k_; ++j) x.p[j] = saved_[s + 1][j];
+        const i64 Ns = w.saved_n[s + 1], o = off;
+        add_op(lname, [x, Ns, y, Ntot, o, ci, B](hipStream_t st) {
+            launch_concat_copy(x, Ns, y, Ntot, o, ci, B, st);
+        });
+        off += Ns;
+    }
+    set_out(w, g, Ntot, w.nxt());
+}
+
+void HipEvaluator::plan_proj(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const auto& inm = g.vec("in_mod");
+    const auto& outm = g.vec("out_mod");
+    ProjArgs a{};
+    a.k = k_;
+    a.N = w.N;
+    a.hard = hard_ ? 1 : 0;
+    a.gate0 = gate_base(li + 1, 1);
+    for (int j = 0; j < k_; ++j) {
+        a.pin[j] = static_cast<int>(inm[j]);
+        a.pout[j] = static_cast<int>(outm[j]);
+        a.tab[j] = upload_tables(li, arr_name("t.", j, ""));
+        w.mods[j] = a.pout[j];
+    }
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const Env e = w.env;
+    add_op(lname, [a, x, y, e](hipStream_t st) { launch_proj(a, x, y, e.B, e.mc, e.ag, st); });
+    set_out(w, g, w.N, w.nxt());
+}
+
+void HipEvaluator::plan_mult(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    MultArgs a{};
+    a.crt = w.crt;
+    a.No = w.N / 2;
+    a.hard = hard_ ? 1 : 0;
+    a.gate0 = gate_base(li + 1, 1);
+    a.q = g.kind == K_MMULT ? static_cast<int>(g.param("q")) : 0;
+    if (a.q) a.t = upload_tables(li, "t");
+    a.g = upload_tables(li, "g");
+    a.e = upload_tables(li, "e");
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const Env e = w.env;
+    add_op(lname, [a, x, y, e](hipStream_t st) { launch_mult(a, x, y, e.B, e.mc, e.ag, st); });
+    set_out(w, g, a.No, w.nxt());
+}
+
+void HipEvaluator::plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    std::vector<int> ext;
+    for (auto v : g.vec("extra")) ext.push_back(static_cast<int>(v));
+    BEPlan be(crt_, ext);
+    Act x = act_of(w.cur);
+    const Env e = w.env;
+    for (int xi : be.extra_idx) {  // the extension's target residues start from the zero label
+        RescaleArgs ra{};
+        ra.crt = w.crt;
+        ra.N = w.N;
+        ra.fi = xi;
+        ra.up = zero_rows_;
+        set_label_rows(ra);
+        add_op(lname + ".zero", [ra, x, e](hipStream_t st) { launch_rescale_update(ra, x, e.B, e.mc, st); });
+    }
+    const BEArgs ba = be_args(w, be, li, "be", w.N, gate_base(li + 1, 1));
+    add_op(lname, [ba, x, e](hipStream_t st) { launch_base_ext(ba, x, e.B, e.mc, e.ag, st); });
+    set_out(w, g, w.N, w.cur);
 }
 
 // ---------------------------------------------------------------------------
