@@ -251,6 +251,62 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 cur = std::move(nxt);
                 break;
             }
+            case K_CONVT: {
+                // hardened only (the garbler refuses the reference encoding): the bare sum over the valid taps,
+                // in the direct gather form (the bit-exact oracle of the HIP path's sub-pixel view)
+                DASH_CHECK(hard, "conv_transpose2d exists in the hardened encoding only");
+                ConvTGeom G(g);
+                DASH_CHECK(G.C * G.H * G.W == Nin, "conv_transpose2d input size mismatch");
+                const Array& wa = g.arr("w");
+                DASH_CHECK(static_cast<i64>(wa.count()) == G.F * G.K(), "conv_transpose2d weight shape");
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) {
+                    const int p = crt[j];
+                    const ModInfo& mi = mod_info(p);
+                    std::vector<int32_t> wm(static_cast<size_t>(G.F * G.K()));
+                    for (size_t q = 0; q < wm.size(); ++q) wm[q] = static_cast<int32_t>(wa.ptr<i64>()[q] % p);
+                    Labels O(p, G.out_size());
+                    const Labels& I = cur[j];
+                    parallel_for(G.out_size(), [&](i64 b0, i64 b1) {
+                        std::vector<i64> acc(mi.n);
+                        for (i64 o = b0; o < b1; ++o) {
+                            const i64 f = o / (G.OH * G.OW), r = o % (G.OH * G.OW), oy = r / G.OW, ox = r % G.OW;
+                            std::fill(acc.begin(), acc.end(), 0);
+                            for (i64 c = 0; c < G.C; ++c)
+                                for (i64 dy = 0; dy < G.kh; ++dy) {
+                                    const i64 ny = oy + G.ph - dy;
+                                    if (ny < 0 || ny % G.sh || ny / G.sh >= G.H) continue;
+                                    for (i64 dx = 0; dx < G.kw; ++dx) {
+                                        const i64 nx = ox + G.pw - dx;
+                                        if (nx < 0 || nx % G.sw || nx / G.sw >= G.W) continue;
+                                        const i64 wv = wm[((c * G.F + f) * G.kh + dy) * G.kw + dx];
+                                        if (wv == 0) continue;
+                                        const comp_t* x = I.at((c * G.H + ny / G.sh) * G.W + nx / G.sw);
+                                        for (int cc = 0; cc < mi.n; ++cc) acc[cc] += wv * x[cc];
+                                    }
+                                }
+                            comp_t* y = O.at(o);
+                            for (int cc = 0; cc < mi.n; ++cc) y[cc] = static_cast<comp_t>(acc[cc] % p);
+                        }
+                    }, nt);
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
+                break;
+            }
+            case K_UPSAMPLE: {
+                UpGeom G(g.p);
+                DASH_CHECK(G.C * G.H * G.W == Nin, "upsample input size mismatch");
+                CrtLabels nxt;
+                for (size_t j = 0; j < cur.size(); ++j) {
+                    Labels O(cur[j].p, G.out_size());
+                    for (i64 o = 0; o < G.out_size(); ++o)
+                        std::memcpy(O.at(o), cur[j].at(G.src(o)), sizeof(comp_t) * O.n);
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
+                break;
+            }
             case K_RELU: {
                 if (trace) trace->relu_in[li] = cur;
                 if (g.param("smode", 0) == 2) {  // sign from the preceding rescale (RescaleMrsPlan::sign_last)

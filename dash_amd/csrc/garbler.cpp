@@ -36,6 +36,8 @@ const char* kind_name(int kind) {
         case K_CONCAT: return "concat";
         case K_CLIP: return "clip";
         case K_ARGMAX: return "argmax";
+        case K_CONVT: return "conv_transpose2d";
+        case K_UPSAMPLE: return "upsample";
     }
     return "unknown";
 }
@@ -60,6 +62,72 @@ ConvGeom::ConvGeom(const Params& p) {
     DASH_CHECK(g > 0 && C % g == 0 && F % g == 0, "conv groups must divide both C and F");
     OH = (H + 2 * ph - kh) / sh + 1;
     OW = (W + 2 * pw - kw) / sw + 1;
+}
+
+ConvTGeom::ConvTGeom(const Params& p) {
+    C = param1(p, "C");
+    H = param1(p, "H");
+    W = param1(p, "W");
+    F = param1(p, "F");
+    kh = param1(p, "kh");
+    kw = param1(p, "kw");
+    sh = param1(p, "sh", 1);
+    sw = param1(p, "sw", 1);
+    ph = param1(p, "ph", 0);
+    pw = param1(p, "pw", 0);
+    oph = param1(p, "oph", 0);
+    opw = param1(p, "opw", 0);
+    DASH_CHECK(C > 0 && H > 0 && W > 0 && F > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0,
+               "bad transposed conv geometry");
+    Th = (kh + sh - 1) / sh;
+    Tw = (kw + sw - 1) / sw;
+    DASH_CHECK(ph >= 0 && ph <= kh - 1 && pw >= 0 && pw <= kw - 1, "transposed conv: padding outside [0, k - 1]");
+    DASH_CHECK(oph >= 0 && oph < sh && opw >= 0 && opw < sw, "transposed conv: output padding outside [0, stride)");
+    DASH_CHECK(oph <= sh * Th - kh + ph && opw <= sw * Tw - kw + pw,
+               "transposed conv: output padding leaves outputs that no tap reaches");
+    OH = (H - 1) * sh - 2 * ph + kh + oph;
+    OW = (W - 1) * sw - 2 * pw + kw + opw;
+    DASH_CHECK(OH > 0 && OW > 0, "transposed conv: empty output");
+}
+
+ConvGeom ConvTGeom::view() const {
+    Params p;
+    p["C"] = {C};
+    p["H"] = {H};
+    p["W"] = {W};
+    p["F"] = {VF()};
+    p["kh"] = {Th};
+    p["kw"] = {Tw};
+    p["ph"] = {Th - 1};
+    p["pw"] = {Tw - 1};
+    return ConvGeom(p);
+}
+
+std::vector<i64> ConvTGeom::view_weights(const i64* w) const {
+    std::vector<i64> v(static_cast<size_t>(VF() * VK()), 0);
+    for (i64 f = 0; f < F; ++f)
+        for (i64 ry = 0; ry < sh; ++ry)
+            for (i64 rx = 0; rx < sw; ++rx) {
+                const i64 fv = (f * sh + ry) * sw + rx;
+                for (i64 c = 0; c < C; ++c)
+                    for (i64 ty = 0; ty < Th; ++ty)
+                        for (i64 tx = 0; tx < Tw; ++tx) {
+                            const i64 dy = ry + sh * (Th - 1 - ty), dx = rx + sw * (Tw - 1 - tx);
+                            if (dy < kh && dx < kw)
+                                v[static_cast<size_t>(((fv * C + c) * Th + ty) * Tw + tx)] =
+                                    w[((c * F + f) * kh + dy) * kw + dx];
+                        }
+            }
+    return v;
+}
+
+UpGeom::UpGeom(const Params& p) {
+    C = param1(p, "C");
+    H = param1(p, "H");
+    W = param1(p, "W");
+    fh = param1(p, "fh");
+    fw = param1(p, "fw");
+    DASH_CHECK(C > 0 && H > 0 && W > 0 && fh >= 1 && fw >= 1 && fh * fw > 1, "bad upsample geometry");
 }
 
 PoolGeom::PoolGeom(const Params& p) {
@@ -660,7 +728,8 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         // every layer kind but the test-only projection / mult layers garbles on the device when a GPU garbler
         // is present (the legacy rescale's sign base extension needs residue 0 = 2)
         const bool lin_kind = spec.kind == K_CONV || spec.kind == K_DENSE || spec.kind == K_SUMPOOL ||
-                              spec.kind == K_ADD || spec.kind == K_CONCAT;
+                              spec.kind == K_ADD || spec.kind == K_CONCAT || spec.kind == K_CONVT ||
+                              spec.kind == K_UPSAMPLE;
         const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
                                     (spec.kind == K_RELU || spec.kind == K_SIGN ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
@@ -809,6 +878,81 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 }
                 cur = std::move(nxt);
                 dims = {G.F, G.OH, G.OW};
+                break;
+            }
+            case K_CONVT: {
+                // hardened only: zero-mod-p weights and padding reads contribute 0 and the bias is folded as
+                // -b R, so the base labels are the bare sum over the valid taps (direct gather form)
+                DASH_CHECK(hard, "conv_transpose2d exists in the hardened encoding only");
+                DASH_CHECK(is_crt(), "conv_transpose2d needs CRT-base labels");
+                ConvTGeom G(spec.p);
+                DASH_CHECK(G.C * G.H * G.W == Nin, "conv_transpose2d input size mismatch");
+                const auto& w = paramv(spec.p, "w");
+                const auto& b = paramv(spec.p, "b");
+                DASH_CHECK(static_cast<i64>(w.size()) == G.F * G.K() && static_cast<i64>(b.size()) == G.F,
+                           "conv_transpose2d weight shape");
+                const auto rw = reduced_weights(li, w, {G.C, G.F, G.kh, G.kw});
+                const Array& wa = rw.first;
+                g.a["w"] = wa;
+                dims = {G.F, G.OH, G.OW};
+                if (on_gpu) {
+                    gpu->conv_transpose(G, wa.ptr<i64>(), wa.count(), rw.second, cur);
+                    gpu->fold_constants(neg_mod(b, M_), G.OH * G.OW, cur);
+                    break;
+                }
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) {
+                    const int p = crt_[j];
+                    const ModInfo& mi = mod_info(p);
+                    Labels O(p, G.out_size());
+                    const Labels& I = cur[j];
+                    parallel_for(G.out_size(), [&](i64 b0, i64 b1) {
+                        std::vector<i64> acc(mi.n);
+                        for (i64 o = b0; o < b1; ++o) {
+                            const i64 f = o / (G.OH * G.OW), r = o % (G.OH * G.OW), oy = r / G.OW, ox = r % G.OW;
+                            std::fill(acc.begin(), acc.end(), 0);
+                            for (i64 c = 0; c < G.C; ++c)
+                                for (i64 dy = 0; dy < G.kh; ++dy) {
+                                    const i64 ny = oy + G.ph - dy;
+                                    if (ny < 0 || ny % G.sh || ny / G.sh >= G.H) continue;
+                                    for (i64 dx = 0; dx < G.kw; ++dx) {
+                                        const i64 nx = ox + G.pw - dx;
+                                        if (nx < 0 || nx % G.sw || nx / G.sw >= G.W) continue;
+                                        const i64 wv = wa.ptr<i64>()[((c * G.F + f) * G.kh + dy) * G.kw + dx] % p;
+                                        if (wv == 0) continue;
+                                        const comp_t* x = I.at((c * G.H + ny / G.sh) * G.W + nx / G.sw);
+                                        for (int cc = 0; cc < mi.n; ++cc) acc[cc] += wv * x[cc];
+                                    }
+                                }
+                            comp_t* y = O.at(o);
+                            const i64 bneg = pmod(-pmod(b[f], M_), p);
+                            const comp_t* Rp = R_.get(p);
+                            for (int cc = 0; cc < mi.n; ++cc)
+                                y[cc] = static_cast<comp_t>((acc[cc] + bneg * Rp[cc]) % p);
+                        }
+                    }, nt);
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
+                break;
+            }
+            case K_UPSAMPLE: {
+                // free in the label domain: a gather of base labels (any moduli)
+                UpGeom G(spec.p);
+                DASH_CHECK(G.C * G.H * G.W == Nin, "upsample input size mismatch");
+                dims = {G.C, G.H * G.fh, G.W * G.fw};
+                if (on_gpu) {
+                    gpu->upsample(G, cur);
+                    break;
+                }
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) {
+                    Labels O(cur[j].p, G.out_size());
+                    for (i64 o = 0; o < G.out_size(); ++o)
+                        std::memcpy(O.at(o), cur[j].at(G.src(o)), sizeof(comp_t) * O.n);
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
                 break;
             }
             case K_RELU: {

@@ -2990,6 +2990,8 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     clip_hi_hook() = &GpuGarbler::clip_hi_dev;
     clip_joint_hook() = &GpuGarbler::clip_joint_dev;
     argmax_hook() = &GpuGarbler::argmax_level_dev;
+    convt_hook() = &GpuGarbler::convt_dev;
+    upsample_hook() = &GpuGarbler::upsample_dev;
     Impl& I = *impl_;
     I.enter();
     I.c.hard = hardened ? 1 : 0;
@@ -3108,21 +3110,40 @@ std::mutex& conv_plans_mutex() {
 // (centered int8 weight images, zero counts, all-zero bias rows) is built
 // once per process and looked up by a hash of the weights.
 void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur) {
+    conv_run(G, nullptr, w, nw, wh, cur);
+}
+
+// Transposed conv (garbler.cpp K_CONVT): the same launch_conv on the layer's sub-pixel view, whose epilogue
+// scatters to the output; no zero-label terms (hardened encoding only), the caller folds the bias
+void GpuGarbler::convt_dev(GpuGarbler& self, const ConvTGeom& T, const i64* w, size_t nw, uint64_t wh,
+                           CrtLabels& cur) {
+    DASH_CHECK(self.impl_->c.hard, "gpu garbler: conv_transpose2d exists in the hardened encoding only");
+    DASH_CHECK(static_cast<i64>(nw) == T.F * T.K(), "gpu garbler: conv_transpose2d weight shape");
+    self.conv_run(T.view(), &T, w, nw, wh, cur);
+}
+
+void GpuGarbler::conv_run(const ConvGeom& G, const ConvTGeom* T, const i64* w0, size_t nw, uint64_t wh,
+                          CrtLabels& cur) {
     Impl& I = *impl_;
     I.enter();
     I.check_cur(cur);
-    PhaseTrace tr_("conv");
+    PhaseTrace tr_(T ? "conv_transpose" : "conv");
     const int K = static_cast<int>(G.K());
     const int F = static_cast<int>(G.F);
-    DASH_CHECK(static_cast<i64>(nw) == G.F * G.K(), "gpu garbler: conv weight shape");
+    DASH_CHECK(T || static_cast<i64>(nw) == G.F * G.K(), "gpu garbler: conv weight shape");
     DASH_CHECK(G.C * G.H * G.W == I.cur_N, "gpu garbler: conv input size mismatch");
     DASH_CHECK(static_cast<int>(I.cur_mod.size()) <= kMaxRes, "gpu garbler: too many residues");
     std::vector<int> mods = I.cur_mod;
-    const int64_t Nin = I.cur_N, Nout = G.out_size();
+    const int64_t Nin = I.cur_N, Nout = T ? T->out_size() : G.out_size();
     std::vector<DevBlock> out = I.alloc_labels(mods, Nout);
     dev::ConvArgs a{};
     {
         ConvPlanKey key{I.device, wh, {G.C, G.H, G.W, G.F, G.kh, G.kw, G.sh, G.sw, G.ph, G.pw, G.g}, mods};
+        // a transposed layer's view can equal a plain conv's geometry (and the weights' hash is of another
+        // layout): its own geometry goes into the key behind a marker no conv has
+        if (T) key.geom.insert(key.geom.end(), {-1, T->F, T->kh, T->kw, T->sh, T->sw, T->ph, T->pw, T->oph, T->opw});
+        std::vector<i64> wview;
+        const i64* w = w0;
         std::lock_guard<std::mutex> lk(conv_plans_mutex());
         auto it = conv_plans().find(key);
         if (it != conv_plans().end()) {
@@ -3142,6 +3163,14 @@ void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, C
             a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
             a.use_mfma = 1;
             a.groups = static_cast<int>(G.g);
+            if (T) {
+                dev::convt_view_args(a, static_cast<int>(T->C), static_cast<int>(T->H), static_cast<int>(T->W),
+                                     static_cast<int>(T->F), static_cast<int>(T->kh), static_cast<int>(T->kw),
+                                     static_cast<int>(T->sh), static_cast<int>(T->sw), static_cast<int>(T->ph),
+                                     static_cast<int>(T->pw), static_cast<int>(T->OH), static_cast<int>(T->OW));
+                wview = T->view_weights(w0);
+                w = wview.data();
+            }
             int max_p = 0;
             for (int j = 0; j < a.crt.k; ++j) max_p = std::max(max_p, mods[j]);
             if (G.g > 1) {
@@ -3165,11 +3194,11 @@ void GpuGarbler::conv(const ConvGeom& G, const i64* w, size_t nw, uint64_t wh, C
                 const bool grp = G.g > 1;  // k_conv_grp reads its own image (wg) only
                 std::vector<int16_t> wm(grp ? 0 : static_cast<size_t>(F) * K);
                 std::vector<int8_t> w8(grp ? 0 : static_cast<size_t>(F) * a.Kpad, 0);
-                std::vector<int32_t> zc(F, 1);
+                std::vector<int32_t> zc(F, T ? 0 : 1);
                 for (int f = 0; f < F; ++f)
                     for (int q = 0; q < K; ++q) {
                         const int v = static_cast<int>(w[static_cast<size_t>(f) * K + q] % p);
-                        if (v == 0) ++zc[f];
+                        if (v == 0 && !T) ++zc[f];
                         if (grp) continue;
                         wm[static_cast<size_t>(f) * K + q] = static_cast<int16_t>(v);
                         w8[static_cast<size_t>(f) * a.Kpad + q] = static_cast<int8_t>(v > p / 2 ? v - p : v);
@@ -4425,6 +4454,24 @@ void GpuGarbler::sumpool(const PoolGeom& G, CrtLabels& cur) {
         launch_gsum(I.c, y, I.cur, I.cur_mod, Nout, I.cur_N, gg::dconst(mt.data(), mt.size()), Kt, t0 > 0,
                     [](int, int) { return 1; });
     }
+    HIPCHECK(hipGetLastError());
+    I.cur = std::move(y);
+    I.cur_N = Nout;
+    set_stale(cur, I.cur_mod, Nout);
+}
+
+// Upsample (garbler.cpp K_UPSAMPLE): cur = the device cur gathered to the larger image
+void GpuGarbler::upsample_dev(GpuGarbler& self, const UpGeom& G, CrtLabels& cur) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    DASH_CHECK(G.C * G.H * G.W == I.cur_N, "gpu garbler: upsample input size");
+    const int64_t Nout = G.out_size();
+    std::vector<int32_t> map(static_cast<size_t>(Nout));
+    for (int64_t o = 0; o < Nout; ++o) map[static_cast<size_t>(o)] = static_cast<int32_t>(G.src(o));
+    std::vector<DevBlock> y = I.alloc_labels(I.cur_mod, Nout);
+    launch_gsum(I.c, y, I.cur, I.cur_mod, Nout, I.cur_N, gg::dconst(map.data(), map.size()), 1, false,
+                [](int, int) { return 1; });
     HIPCHECK(hipGetLastError());
     I.cur = std::move(y);
     I.cur_N = Nout;

@@ -115,6 +115,27 @@ class GpuGarbler {
         DASH_CHECK(concat_hook() != nullptr, "gpu garbler: concat is not linked in");
         concat_hook()(*this, idx, cur);
     }
+    // Transposed conv base labels (hardened encoding: the bare sum over the valid taps; the caller folds the bias):
+    // the evaluator's launch_conv on the layer's sub-pixel view (layers.h ConvTGeom), w [C][F][kh][kw] reduced
+    // mod M, wh their hash. Upsample: a gather of the device cur. Hooks as for concat_saved.
+    using ConvTFn = void (*)(GpuGarbler&, const ConvTGeom&, const i64*, size_t, uint64_t, CrtLabels&);
+    using UpsampleFn = void (*)(GpuGarbler&, const UpGeom&, CrtLabels&);
+    static ConvTFn& convt_hook() {
+        static ConvTFn f = nullptr;
+        return f;
+    }
+    static UpsampleFn& upsample_hook() {
+        static UpsampleFn f = nullptr;
+        return f;
+    }
+    void conv_transpose(const ConvTGeom& G, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur) {
+        DASH_CHECK(convt_hook() != nullptr, "gpu garbler: conv_transpose2d is not linked in");
+        convt_hook()(*this, G, w, nw, wh, cur);
+    }
+    void upsample(const UpGeom& G, CrtLabels& cur) {
+        DASH_CHECK(upsample_hook() != nullptr, "gpu garbler: upsample is not linked in");
+        upsample_hook()(*this, G, cur);
+    }
     // max pool / max: window values, one ReLU-gadget tree level per call (relu_garble_elem on streams
     // 20 + 2 lv / 21 + 2 lv), then the reduced values become cur
     void maxpool_begin(const std::vector<std::vector<i64>>& win, CrtLabels& cur);
@@ -146,6 +167,10 @@ class GpuGarbler {
     struct Impl;
 
    private:
+    // conv and conv_transpose: T set = G is T's sub-pixel view and w T's own weights
+    void conv_run(const ConvGeom& G, const ConvTGeom* T, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur);
+    static void convt_dev(GpuGarbler& self, const ConvTGeom& G, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur);
+    static void upsample_dev(GpuGarbler& self, const UpGeom& G, CrtLabels& cur);
     static void concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& idx, CrtLabels& cur);
     static void clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
                          CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,

@@ -57,7 +57,19 @@ __global__ __launch_bounds__(256) void k_dense(DenseArgs a, Act x, Act y, const 
     y.p[j][(static_cast<int64_t>(b) * n + c) * a.O + o] = static_cast<act_t>(mod_p(acc % p + zc * zv + bv, p));
 }
 
-// VALU conv: grid (ceil(OH*OW/256), F, B*sum_n)
+// Transposed conv scatter (ConvArgs::tsc): element offset of view output (filter fv, row qy, column qx) inside one
+// image of the tF x tOH x tOW output, or -1 when the crop drops it
+__device__ __forceinline__ int convt_dst(const ConvArgs& a, int fv, int qy, int qx) {
+    const int nph = a.tsh * a.tsw;
+    const int f = fv / nph, r = fv - f * nph, ry = r / a.tsw, rx = r - ry * a.tsw;
+    const int oy = a.tsh * qy + ry - a.tph, ox = a.tsw * qx + rx - a.tpw;
+    if (oy < 0 || oy >= a.tOH || ox < 0 || ox >= a.tOW) return -1;
+    return (f * a.tOH + oy) * a.tOW + ox;
+}
+
+// VALU conv: grid (ceil(OH*OW/256), F, B*sum_n). SC: the transposed conv's scatter epilogue (a separate
+// instantiation, as for the kernels below)
+template <bool SC>
 __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, Act x, Act y, const int* zj, const int* zcomp,
                                                    int sumn) {
     const int z = blockIdx.z;
@@ -88,6 +100,13 @@ __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, Act x, Act y, con
     }
     const int32_t zc = a.zc[j][f];
     const int16_t bv = a.bias[j][(static_cast<int64_t>(b) * a.F + f) * n + c];
+    if constexpr (SC) {
+        const int d = convt_dst(a, f, oy, ox);
+        if (d >= 0)
+            y.p[j][(static_cast<int64_t>(b) * n + c) * a.tF * a.tOH * a.tOW + d] =
+                static_cast<act_t>(mod_p(acc % p + zc * zv + bv, p));
+        return;
+    }
     y.p[j][((static_cast<int64_t>(b) * n + c) * a.F + f) * npos + pos] =
         static_cast<act_t>(mod_p(acc % p + zc * zv + bv, p));
 }
@@ -100,6 +119,7 @@ __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, Act x, Act y, con
 typedef int32_t v4i __attribute__((ext_vector_type(4)));
 typedef int64_t v2l __attribute__((ext_vector_type(2)));
 
+template <bool SC>
 __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs a, Act x, Act y, int j, int64_t ncols) {
     __shared__ __attribute__((aligned(16))) int8_t As[64 * 64];   // [f][k]
     __shared__ __attribute__((aligned(16))) int8_t Bs[64 * 64];   // [col][k]
@@ -185,6 +205,13 @@ __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs a, Act x, Act y, int
             if (f >= a.F) continue;
             const int32_t zc = a.zc[j][f];
             const int16_t bv = a.bias[j][(static_cast<int64_t>(b) * a.F + f) * n + c];
+            if constexpr (SC) {
+                const int d = convt_dst(a, f, pos / a.OW, pos % a.OW);
+                if (d >= 0)
+                    y.p[j][(static_cast<int64_t>(b) * n + c) * a.tF * a.tOH * a.tOW + d] =
+                        static_cast<act_t>(mod_p(acc[t][r] % p + zc * zvv + bv, p));
+                continue;
+            }
             y.p[j][((static_cast<int64_t>(b) * n + c) * a.F + f) * npos + pos] =
                 static_cast<act_t>(mod_p(acc[t][r] % p + zc * zvv + bv, p));
         }
@@ -355,7 +382,9 @@ static_assert(kConvFW == 16 || kConvFW == 32, "conv: 16 or 32 filters per wave")
 #endif
 // UR: tap-unrolled band (ConvArgs::ur), a separate instantiation so the channel-chunked staging keeps its
 // registers and code
-template <int KSC, bool UR>
+// SC: the transposed conv's scatter epilogue (ConvArgs::tsc), separate instantiations again: every `if constexpr
+// (SC)` below is dead in the plain conv's kernels
+template <int KSC, bool UR, bool SC = false>
 __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int B) {
     constexpr bool AREG = KSC > 0;
     extern __shared__ __attribute__((aligned(16))) int8_t img[];
@@ -634,7 +663,7 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int
     uint32_t addc[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) addc[g] = off + zq[g] * static_cast<uint32_t>(zv) + bq[g];
-    act_t* Y = y.p[j] + (static_cast<int64_t>(b) * n + c) * a.F * npos;
+    act_t* Y = y.p[j] + (static_cast<int64_t>(b) * n + c) * (SC ? a.tF * a.tOH * a.tOW : a.F * npos);
     // dword stores need 4-byte aligned filter rows and band starts, the transposed 16-byte stores 16-byte ones
     const bool dw = (npos & 3) == 0 && ((oy0 * a.OW) & 3) == 0;
     const bool dw16 = (npos & 15) == 0 && ((oy0 * a.OW) & 15) == 0 &&
@@ -721,6 +750,67 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int
     #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 const int fl = fw + 16 * g + (lane & 15);
+                if constexpr (SC) {
+                    // view filter fl = (f tsh + ry) tsw + rx; the lane's rows r = 0..3 are view positions cb + r
+                    const bool fin = fl < a.F;
+                    const int nph = a.tsh * a.tsw;
+                    const int fo = fl / nph, rr = fl - fo * nph, ry = rr / a.tsw, rx = rr - ry * a.tsw;
+                    act_t* yf = Y + static_cast<int64_t>(fo) * (a.tOH * a.tOW);
+    #pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        const int cb = colw + t * 16 + (lane >> 4) * 4;
+                        uint32_t o[4];
+    #pragma unroll
+                        for (int r = 0; r < 4; ++r) o[r] = red(u24, acc[g][t][r], addc[g]);
+                        const int qyl = a.OW > 1 ? static_cast<int>(__umulhi(static_cast<uint32_t>(cb), owm)) : cb;
+                        const int qx0 = cb - qyl * a.OW;
+                        if (a.tsc == 2) {  // (uniform) tsw = 2
+                            // Lanes l and l ^ 1 hold rx = 0 / 1 of the same (f, ry) (the wave's first filter is a
+                            // multiple of 16) at the same four view columns qx0 .. qx0 + 3: output columns
+                            // 2 qx0 - tpw + 0 .. 7, the even ones in lane l, the odd ones in l ^ 1. The even lane
+                            // gives away its upper two values and takes the odd lane's lower two (one 16-bit
+                            // exchange), and then owns output bytes 0..3, the odd lane bytes 4..7. Every lane of the
+                            // wave takes part in the exchange: the conditions below are the same in both lanes.
+                            const bool odd = (lane & 1) != 0;
+                            const uint32_t snd = odd ? (o[0] | (o[1] << 8)) : (o[2] | (o[3] << 8));
+                            const uint32_t rcv = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(
+                                0, static_cast<int>(snd), 0xB1 /* quad_perm [1, 0, 3, 2] */, 0xf, 0xf, true));
+                            if (cb + 3 < ncol && qx0 + 3 < a.OW) {  // four columns of one view row
+                                const int oy = a.tsh * (oy0 + qyl) + ry - a.tph;
+                                if (!fin || oy < 0 || oy >= a.tOH) continue;
+                                const uint32_t r0 = rcv & 0xffu, r1 = (rcv >> 8) & 0xffu;
+                                const uint32_t wv = odd ? (r0 | (o[2] << 8) | (r1 << 16) | (o[3] << 24))
+                                                        : (o[0] | (r0 << 8) | (o[1] << 16) | (r1 << 24));
+                                const int ox0 = 2 * qx0 - a.tpw + (odd ? 4 : 0);
+                                act_t* yr = yf + oy * a.tOW + ox0;
+                                if (ox0 >= 0 && ox0 + 3 < a.tOW && (reinterpret_cast<uintptr_t>(yr) & 3) == 0) {
+                                    *reinterpret_cast<uint32_t*>(yr) = wv;
+                                } else {
+    #pragma unroll
+                                    for (int u = 0; u < 4; ++u)
+                                        if (ox0 + u >= 0 && ox0 + u < a.tOW) yr[u] = static_cast<act_t>(wv >> (8 * u));
+                                }
+                                continue;
+                            }
+                        }
+                        if (!fin) continue;
+                        // four byte stores (also the wide form's row ends: positions that wrap to the next view row)
+                        int qy = oy0 + qyl, qx = qx0;
+    #pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (cb + r < ncol) {
+                                const int oy = a.tsh * qy + ry - a.tph, ox = a.tsw * qx + rx - a.tpw;
+                                if (oy >= 0 && oy < a.tOH && ox >= 0 && ox < a.tOW)
+                                    yf[oy * a.tOW + ox] = static_cast<act_t>(o[r]);
+                            }
+                            if (++qx == a.OW) {
+                                qx = 0;
+                                ++qy;
+                            }
+                        }
+                    }
+                    continue;
+                }
                 if (NT == 4 && dw16 && colw + 64 <= ncol) {
                     // whole 64-column chunk: lane (f, h) holds positions 16 t + 4 h + 0..3 of tile t as one dword; a
                     // 4x4 transpose over (t, h) with v_permlane32_swap / v_permlane16_swap gives it positions
@@ -1154,7 +1244,22 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
         }();
         const int KS = a.kh * a.kw * (a.Cpad / 64);
         const char* form;  // the kernel and its real template arguments, for the launch log
-        if (ver == 1 && a.ldsS == a.Cpad + 16 && a.ldsR == (a.W + 2 * a.pw) * a.ldsS) {
+        if (a.tsc && a.ur && KS == 1) {
+            form = "convt.img2<1,1>";
+            hipLaunchKernelGGL((k_conv_img2<1, true, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (a.tsc && a.ur) {
+            form = "convt.img2<0,1>";
+            hipLaunchKernelGGL((k_conv_img2<0, true, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (a.tsc && KS == 4) {
+            form = "convt.img2<4,0>";
+            hipLaunchKernelGGL((k_conv_img2<4, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (a.tsc && KS == 1) {
+            form = "convt.img2<1,0>";
+            hipLaunchKernelGGL((k_conv_img2<1, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (a.tsc) {
+            form = "convt.img2<0,0>";
+            hipLaunchKernelGGL((k_conv_img2<0, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (ver == 1 && a.ldsS == a.Cpad + 16 && a.ldsR == (a.W + 2 * a.pw) * a.ldsS) {
             form = "conv.img";
             hipLaunchKernelGGL(k_conv_img, g, dim3(256), lds, st, a, x, y, B);  // A/B: its fixed layout only
         } else if (a.ur && KS == 1) {
@@ -1185,8 +1290,9 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
             if (!a.w8[j]) continue;
             const int64_t ncols = static_cast<int64_t>(B) * a.crt.n[j] * a.OH * a.OW;
             dim3 g(static_cast<unsigned>((ncols + 63) / 64), static_cast<unsigned>((a.F + 63) / 64), 1);
-            if (launch_log_on()) launch_log_add("conv.im2col", g, dim3(256));
-            hipLaunchKernelGGL(k_conv_mfma, g, dim3(256), 0, st, a, x, y, j, ncols);
+            if (launch_log_on()) launch_log_add(a.tsc ? "convt.im2col" : "conv.im2col", g, dim3(256));
+            if (a.tsc) hipLaunchKernelGGL(k_conv_mfma<true>, g, dim3(256), 0, st, a, x, y, j, ncols);
+            else hipLaunchKernelGGL(k_conv_mfma<false>, g, dim3(256), 0, st, a, x, y, j, ncols);
         }
         // residues without an int8 image (p > 255) fall through to VALU below
         bool rest = false;
@@ -1195,8 +1301,9 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
     }
     const ZTab& z = ztab_for(a.crt);
     dim3 g(static_cast<unsigned>((a.OH * a.OW + 255) / 256), static_cast<unsigned>(a.F), static_cast<unsigned>(B * z.sumn));
-    if (launch_log_on()) launch_log_add("conv.valu", g, dim3(256));
-    hipLaunchKernelGGL(k_conv_valu, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
+    if (launch_log_on()) launch_log_add(a.tsc ? "convt.valu" : "conv.valu", g, dim3(256));
+    if (a.tsc) hipLaunchKernelGGL(k_conv_valu<true>, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
+    else hipLaunchKernelGGL(k_conv_valu<false>, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
 }
 
 }  // namespace dev

@@ -176,7 +176,36 @@ struct ConvArgs {
     int groups = 0;
     const uint32_t* wg[kMaxRes];
     int gpb = 0, gngb = 0, gband = 0, gnbands = 0, gR = 0, gnpp = 0;
+    // transposed conv (layers.h ConvTGeom): the fields above describe its stride-1 sub-pixel view with
+    // F = tF * tsh * tsw filters, and the epilogue scatters view output (f', qy, qx), f' = (f * tsh + ry) * tsw + rx,
+    // to (f, tsh * qy + ry - tph, tsw * qx + rx - tpw) of the tF x tOH x tOW output; what falls outside is
+    // dropped (depth-to-space + crop). tsc = 0: off (a plain conv); 1: byte stores; 2: tsw = 2 and lanes l, l ^ 1
+    // exchange two bytes so each stores four adjacent output bytes (a dword where aligned), k_conv_img2 only.
+    int tsc = 0, tsh = 1, tsw = 1, tph = 0, tpw = 0, tF = 0, tOH = 0, tOW = 0;
 };
+// Describe a transposed conv's view and scatter in `a` (shape fields only; plan it with conv_layer_plan next).
+// wide: the exchanged four-byte store where it applies (tsw = 2; A/B knob DASH_CONVT_WIDE, default on)
+inline bool convt_wide_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("DASH_CONVT_WIDE");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+inline void convt_view_args(ConvArgs& a, int C, int H, int W, int F, int kh, int kw, int sh, int sw, int ph, int pw,
+                            int OH, int OW) {
+    const int Th = (kh + sh - 1) / sh, Tw = (kw + sw - 1) / sw;
+    a.C = C; a.H = H; a.W = W;
+    a.F = F * sh * sw;
+    a.kh = Th; a.kw = Tw;
+    a.sh = a.sw = 1;
+    a.ph = Th - 1; a.pw = Tw - 1;
+    a.OH = H + Th - 1; a.OW = W + Tw - 1;
+    a.groups = 0;
+    a.tsc = (sw == 2 && convt_wide_enabled()) ? 2 : 1;
+    a.tsh = sh; a.tsw = sw; a.tph = ph; a.tpw = pw;
+    a.tF = F; a.tOH = OH; a.tOW = OW;
+}
 void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream_t st);
 
 // k_conv_img geometry: 64-channel chunks (Cpad), the LDS image's position

@@ -659,6 +659,8 @@ class HipEvaluator {
         switch (l.kind) {
             case K_DENSE: return l.param("out");
             case K_CONV: return ConvGeom(l).out_size();
+            case K_CONVT: return ConvTGeom(l).out_size();
+            case K_UPSAMPLE: return UpGeom(l.p).out_size();
             case K_MAXPOOL: case K_SUMPOOL: return PoolGeom(l.p).out_size();
             case K_MAX: return 1;
             case K_ARGMAX: return l.param("P");
@@ -785,6 +787,8 @@ class HipEvaluator {
     void alloc_output_staging(const Walk& w);
     void plan_dense(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_conv(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_convt(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_upsample(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_relu(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_clip(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_sign(Walk& w, size_t li, const GLayer& g, const std::string& lname);
@@ -928,6 +932,8 @@ void HipEvaluator::build() {
             case K_FLATTEN: break;
             case K_DENSE: plan_dense(w, li, g, lname); break;
             case K_CONV: plan_conv(w, li, g, lname); break;
+            case K_CONVT: plan_convt(w, li, g, lname); break;
+            case K_UPSAMPLE: plan_upsample(w, li, g, lname); break;
             case K_RELU: plan_relu(w, li, g, lname); break;
             case K_CLIP: plan_clip(w, li, g, lname); break;
             case K_SIGN: plan_sign(w, li, g, lname); break;
@@ -1251,6 +1257,71 @@ void HipEvaluator::plan_conv(Walk& w, size_t li, const GLayer& g, const std::str
     const int B = B_;
     add_op(lname, [a, x, y, B](hipStream_t st) { launch_conv(a, x, y, B, st); });
     set_out(w, g, G.out_size(), w.nxt());
+}
+
+// Transposed conv: its stride-1 sub-pixel view (layers.h ConvTGeom) through the dense conv's plan and kernels,
+// whose epilogue scatters the view's F sh sw filters to the output (ConvArgs::tsc). Hardened encoding only: the
+// evaluator computes the bare sum, so the zero counts and the bias rows are all zero.
+void HipEvaluator::plan_convt(Walk& w, size_t, const GLayer& g, const std::string& lname) {
+    DASH_CHECK(hard_, "conv_transpose2d exists in the hardened encoding only");
+    ConvTGeom G(g);
+    DASH_CHECK(G.C * G.H * G.W == w.N, "conv_transpose2d input size mismatch");
+    ConvArgs a{};
+    a.crt = w.crt;
+    convt_view_args(a, static_cast<int>(G.C), static_cast<int>(G.H), static_cast<int>(G.W), static_cast<int>(G.F),
+                    static_cast<int>(G.kh), static_cast<int>(G.kw), static_cast<int>(G.sh), static_cast<int>(G.sw),
+                    static_cast<int>(G.ph), static_cast<int>(G.pw), static_cast<int>(G.OH), static_cast<int>(G.OW));
+    a.use_mfma = mfma_ ? 1 : 0;
+    conv_layer_plan(a, mfma_ && conv_img_enabled());
+    a.img_off[0] = 0;
+    for (int j = 0; j < k_; ++j) a.img_off[j + 1] = a.img_off[j] + static_cast<i64>(B_) * w.crt.n[j];
+    const Array& wt = g.arr("w");
+    DASH_CHECK(static_cast<i64>(wt.count()) == G.F * G.K(), "conv_transpose2d weight shape");
+    const std::vector<i64> wv = G.view_weights(wt.ptr<i64>());
+    const i64 VF = G.VF(), K = G.VK();
+    const std::vector<int32_t> zc(static_cast<size_t>(VF), 0);
+    const int32_t* dzc = upload(zc.data(), zc.size());
+    for (int j = 0; j < k_; ++j) {
+        const int p = crt_[j];
+        std::vector<int16_t> wm(static_cast<size_t>(VF * K));
+        std::vector<int8_t> w8(static_cast<size_t>(VF) * a.Kpad, 0);
+        for (i64 f = 0; f < VF; ++f)
+            for (i64 q = 0; q < K; ++q) {
+                const int v = static_cast<int>(wv[static_cast<size_t>(f * K + q)] % p);
+                wm[static_cast<size_t>(f * K + q)] = static_cast<int16_t>(v);
+                w8[static_cast<size_t>(f) * a.Kpad + q] = static_cast<int8_t>(v > p / 2 ? v - p : v);
+            }
+        a.w[j] = upload(wm.data(), wm.size());
+        a.w8[j] = (mfma_ && p <= 255) ? upload(w8.data(), w8.size()) : nullptr;
+        a.wg[j] = nullptr;
+        a.w8r[j] = nullptr;
+        if (a.nbands > 0 && p <= 255) {
+            const std::vector<int8_t> w8r = conv_w8r(a, w8, static_cast<int>(VF));
+            a.w8r[j] = upload(w8r.data(), w8r.size());
+        }
+        a.zc[j] = dzc;
+        a.bias[j] = zero_i16(static_cast<size_t>(B_) * VF * nr_comps(p));
+    }
+    set_label_rows(a);
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const int B = B_;
+    add_op(lname, [a, x, y, B](hipStream_t st) { launch_conv(a, x, y, B, st); });
+    set_out(w, g, G.out_size(), w.nxt());
+}
+
+// Nearest-neighbour upsampling: a label gather (free: no tables), any moduli
+void HipEvaluator::plan_upsample(Walk& w, size_t, const GLayer& g, const std::string& lname) {
+    UpGeom G(g.p);
+    DASH_CHECK(G.C * G.H * G.W == w.N, "upsample input size mismatch");
+    const i64 No = G.out_size(), NN = w.N;
+    std::vector<i64> idx(static_cast<size_t>(No));
+    for (i64 o = 0; o < No; ++o) idx[static_cast<size_t>(o)] = G.src(o);
+    const int64_t* didx = upload(idx.data(), idx.size());
+    const CrtInfo ci = crt_info(w.mods);
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const int B = B_;
+    add_op(lname, [x, NN, y, No, didx, ci, B](hipStream_t st) { launch_copy_gather(x, NN, y, No, didx, ci, B, st); });
+    set_out(w, g, No, w.nxt());
 }
 
 void HipEvaluator::plan_relu(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
@@ -2201,6 +2272,51 @@ void register_hip_bindings(py::module_& m) {
         return d;
     }, py::arg("C"), py::arg("H"), py::arg("W"), py::arg("F"), py::arg("kh"), py::arg("kw"), py::arg("sh"),
        py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("crt_moduli"), py::arg("mfma") = true);
+    // The same for a transposed conv: the plan of its sub-pixel view (layers.h ConvTGeom, launch.h
+    // convt_view_args) and the scatter description, as plan_convt and the GPU garbler build them.
+    m.def("hip_convt_plan", [](int C, int H, int W, int F, int kh, int kw, int sh, int sw, int ph, int pw, int oph,
+                               int opw, const std::vector<int>& crt_moduli, bool mfma) {
+        DASH_CHECK(!crt_moduli.empty() && static_cast<int>(crt_moduli.size()) <= dev::kMaxRes,
+                   "hip_convt_plan: 1 .. 16 CRT moduli");
+        Params p{{"C", {C}}, {"H", {H}}, {"W", {W}}, {"F", {F}}, {"kh", {kh}}, {"kw", {kw}}, {"sh", {sh}},
+                 {"sw", {sw}}, {"ph", {ph}}, {"pw", {pw}}, {"oph", {oph}}, {"opw", {opw}}};
+        const ConvTGeom G(p);
+        dev::ConvArgs a{};
+        a.crt.k = static_cast<int>(crt_moduli.size());
+        for (int j = 0; j < a.crt.k; ++j) {
+            DASH_CHECK(crt_moduli[j] >= 2, "hip_convt_plan: modulus below 2");
+            a.crt.p[j] = crt_moduli[j];
+            a.crt.n[j] = nr_comps(crt_moduli[j]);
+        }
+        dev::convt_view_args(a, C, H, W, F, kh, kw, sh, sw, ph, pw, static_cast<int>(G.OH), static_cast<int>(G.OW));
+        dev::conv_layer_plan(a, mfma && dev::conv_img_enabled());
+        py::dict d;
+        d["ur"] = a.ur;
+        d["KS"] = a.kh * a.kw * (a.Cpad / 64);
+        d["Cpad"] = a.Cpad;
+        d["Kpad"] = a.Kpad;
+        d["band"] = a.band;
+        d["nbands"] = a.nbands;
+        d["VF"] = a.F;
+        d["VOH"] = a.OH;
+        d["VOW"] = a.OW;
+        d["Th"] = static_cast<int>(G.Th);
+        d["Tw"] = static_cast<int>(G.Tw);
+        d["OH"] = a.tOH;
+        d["OW"] = a.tOW;
+        d["tsc"] = a.tsc;
+        return d;
+    }, py::arg("C"), py::arg("H"), py::arg("W"), py::arg("F"), py::arg("kh"), py::arg("kw"), py::arg("sh"),
+       py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("oph"), py::arg("opw"), py::arg("crt_moduli"),
+       py::arg("mfma") = true);
+    // the view's weights [F sh sw][C][Th][Tw] from w [C][F][kh][kw] (ConvTGeom::view_weights), flat
+    m.def("convt_view_weights", [](const std::vector<i64>& w, int C, int F, int kh, int kw, int sh, int sw) {
+        Params p{{"C", {C}}, {"H", {1}}, {"W", {1}}, {"F", {F}}, {"kh", {kh}}, {"kw", {kw}}, {"sh", {sh}},
+                 {"sw", {sw}}};
+        const ConvTGeom G(p);
+        DASH_CHECK(static_cast<i64>(w.size()) == G.F * G.K(), "convt_view_weights: weight shape");
+        return G.view_weights(w.data());
+    }, py::arg("w"), py::arg("C"), py::arg("F"), py::arg("kh"), py::arg("kw"), py::arg("sh"), py::arg("sw"));
     m.def("hip_device_count", []() {
         int n = 0;
         if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -17,6 +17,39 @@ struct ConvGeom {
     i64 out_size() const { return F * OH * OW; }
 };
 
+// Transposed convolution (PyTorch / ONNX ConvTranspose2d, groups = 1, no dilation): weights [C][F][kh][kw],
+//   y[f][oy][ox] = b[f] + sum w[c][f][dy][dx] x[c][iy][ix] over the taps with oy + ph - dy = sh iy, 0 <= iy < H
+// (likewise in x), OH = (H - 1) sh - 2 ph + kh + oph. Domain: 0 <= ph <= kh - 1, 0 <= oph < sh and
+// oph <= sh Th - kh + ph with Th = ceil(kh / sh) (every output row is reached by the sub-pixel view below).
+//
+// Sub-pixel view (the HIP path): a stride-1 conv with VF = F sh sw filters f' = f sh sw + ry sw + rx, kernel
+// Th x Tw, pads (Th - 1, Tw - 1), weights wv[f'][c][ty][tx] = w[c][f][ry + sh (Th-1-ty)][rx + sw (Tw-1-tx)] (zero
+// past kh / kw); view output (f', qy, qx) is y[f][sh qy + ry - ph][sw qx + rx - pw] where that lies inside.
+struct ConvTGeom {
+    i64 C, H, W, F, kh, kw, sh, sw, ph, pw, oph, opw, OH, OW, Th, Tw;
+    explicit ConvTGeom(const Params& p);
+    explicit ConvTGeom(const GLayer& g) : ConvTGeom(g.p) {}
+    i64 K() const { return C * kh * kw; }
+    i64 out_size() const { return F * OH * OW; }
+    i64 VF() const { return F * sh * sw; }
+    i64 VK() const { return C * Th * Tw; }
+    ConvGeom view() const;
+    // [VF][C][Th][Tw] from w [C][F][kh][kw]
+    std::vector<i64> view_weights(const i64* w) const;
+};
+
+// Nearest-neighbour upsampling by integer factors: y[c][oy][ox] = x[c][oy / fh][ox / fw]
+struct UpGeom {
+    i64 C, H, W, fh, fw;
+    explicit UpGeom(const Params& p);
+    i64 out_size() const { return C * H * fh * W * fw; }
+    i64 src(i64 o) const {
+        const i64 OW = W * fw, OH = H * fh;
+        const i64 c = o / (OH * OW), r = o % (OH * OW);
+        return (c * H + (r / OW) / fh) * W + (r % OW) / fw;
+    }
+};
+
 struct PoolGeom {
     // ph/pw: symmetric padding (at most half the kernel); ceil: ONNX/PyTorch ceil_mode output size
     i64 C, H, W, kh, kw, sh, sw, ph, pw, ceil, OH, OW;

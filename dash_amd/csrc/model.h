@@ -35,6 +35,8 @@ enum Kind : int {
     K_CONCAT = 14,
     K_CLIP = 15,
     K_ARGMAX = 16,
+    K_CONVT = 17,
+    K_UPSAMPLE = 18,
 };
 const char* kind_name(int kind);
 

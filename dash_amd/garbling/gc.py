@@ -27,6 +27,7 @@ from ..native import native
 
 _CLIP = _Kind.CLIP
 _ARGMAX = _Kind.ARGMAX
+_CONVT = _Kind.CONVT
 
 Labels = list  # list[(modulus, np.ndarray int16 [N, n_p])]
 
@@ -199,6 +200,14 @@ class GarbledCircuit:
             raise ValueError("layer %d (argmax): the ArgMax layer exists in the hardened encoding only (%s)" % (
                 argmaxes[0], "hardened=False was asked for" if supported else
                 "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
+        # a ConvTranspose2d has no reference encoding: there every zero-mod-p weight and every padding read adds
+        # Z_p, a count that would differ per output position and phase; hardened, both contribute 0
+        convts = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _CONVT]
+        if convts and not (supported if hardened is None else hardened):
+            raise ValueError("layer %d (conv_transpose2d): the ConvTranspose2d layer exists in the hardened encoding "
+                             "only (%s)" % (convts[0], "hardened=False was asked for" if supported else
+                                            "the resolved constructions cannot be hardened: fused sign and no legacy "
+                                            "DASH rescale are needed"))
         if argmaxes and not mrs_capable(self.crt_base):
             raise ValueError("layer %d (argmax): the ArgMax layer's exact sign needs a CRT base with residue 0 = 2 "
                              "and odd other residues, got %s" % (argmaxes[0], self.crt_base))

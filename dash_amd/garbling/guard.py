@@ -25,8 +25,8 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
   evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
   bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
-  has no Concat, no Clip, no ArgMax and no padded / ceil-mode pooling: circuits with any of them take the
-  torch path on the GPU;
+  has no Concat, no Clip, no ArgMax, no ConvTranspose2d, no Upsample and no padded / ceil-mode pooling: circuits
+  with any of them take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
 * the per-input numpy model (``violations_np``), the exact reference of both and the path of layers without a
@@ -65,11 +65,11 @@ class RangeGuard:
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Projection,
-                                          L.BaseExtension))
+                                          L.BaseExtension, L.ConvTranspose2d, L.Upsample))
                            for l in circuit.layers)
-        # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax and no padded / ceil-mode pooling: such
-        # circuits take the batched torch path
-        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax)) or
+        # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no ConvTranspose2d, no Upsample and no padded
+        # / ceil-mode pooling: such circuits take the batched torch path
+        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.ConvTranspose2d, L.Upsample)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
         self._stream = None
@@ -150,6 +150,9 @@ class RangeGuard:
                 if isinstance(l, L.Conv2d):
                     ws.append((torch.tensor(np.array(l.q_weights.reshape(l.F, -1)), dtype=torch.float64, device=dev),
                                torch.tensor(np.array(l.q_biases), dtype=torch.float64, device=dev)))
+                elif isinstance(l, L.ConvTranspose2d):  # [F kh kw][C]: the columns that fold sums into the output
+                    ws.append((torch.tensor(np.array(l.q_weights.reshape(l.C, -1).T), dtype=torch.float64, device=dev),
+                               torch.tensor(np.array(l.q_biases), dtype=torch.float64, device=dev)))
                 elif isinstance(l, L.Dense):
                     perm = None
                     if l.channel_tf:
@@ -191,6 +194,14 @@ class RangeGuard:
                     y = torch.matmul(W.view(1, g, l.F // g, -1), cols.view(B, g, W.shape[1], -1))
                     y = y.reshape(B, l.F, -1) + b[:, None]
                 out = y.reshape(B, -1).to(torch.int64)
+            elif isinstance(l, L.ConvTranspose2d):
+                W, b = ws[i]
+                cols = torch.matmul(W, inp.to(torch.float64).view(B, l.C, l.H * l.W))
+                y = F.fold(cols, (l.OH, l.OW), (l.kh, l.kw), padding=(l.ph, l.pw), stride=(l.sh, l.sw))
+                out = (y + b[None, :, None, None]).reshape(B, -1).to(torch.int64)
+            elif isinstance(l, L.Upsample):
+                v = inp.view(B, l.C, l.H, l.W)
+                out = v.repeat_interleave(l.fh, dim=2).repeat_interleave(l.fw, dim=3).reshape(B, -1)
             elif isinstance(l, L.Dense):
                 W, b, perm = ws[i]
                 xin = inp if perm is None else inp[:, perm]

@@ -37,6 +37,8 @@ class Kind:
     CONCAT = 14
     CLIP = 15
     ARGMAX = 16
+    CONVT = 17
+    UPSAMPLE = 18
 
 
 def _size(d: Sequence[int]) -> int:
@@ -305,6 +307,173 @@ class Conv2d(Layer):
         if self.groups > 1:  # groups == 1 keeps the dense wire bytes
             spec["g"] = self.groups
         return self.kind, spec
+
+
+def _convt_check(kh, kw, sh, sw, ph, pw, oph, opw, groups=1, dilation=1):
+    """The one domain of ConvTranspose2d (every engine shares it): groups = 1, no dilation, and per axis
+    0 <= p <= k - 1, 0 <= op < s and op <= s * ceil(k / s) - k + p (no output row that no tap reaches)."""
+    if int(groups) != 1:
+        raise ValueError(f"conv_transpose2d: groups={groups} is not supported (groups = 1 only)")
+    if int(dilation) != 1:
+        raise ValueError(f"conv_transpose2d: dilation={dilation} is not supported")
+    for ax, k, s, p, op in (("height", kh, sh, ph, oph), ("width", kw, sw, pw, opw)):
+        if k < 1 or s < 1:
+            raise ValueError(f"conv_transpose2d: kernel and stride must be positive ({ax}: k={k}, s={s})")
+        if not 0 <= p <= k - 1:
+            raise ValueError(f"conv_transpose2d: {ax} padding {p} outside [0, k - 1] = [0, {k - 1}]")
+        if not 0 <= op < s:
+            raise ValueError(f"conv_transpose2d: {ax} output padding {op} outside [0, stride) = [0, {s})")
+        if op > s * ceil_div(k, s) - k + p:
+            raise ValueError(f"conv_transpose2d: {ax} output padding {op} leaves output positions that no tap "
+                             f"reaches (k={k}, s={s}, p={p}: at most {s * ceil_div(k, s) - k + p})")
+
+
+class ConvTranspose2d(Layer):
+    """Transposed 2-D convolution with PyTorch / ONNX semantics: input (C, H, W), weights [C][F][kh][kw], strides
+    (sh, sw), symmetric pads (ph, pw), output padding (oph, opw), OH = (H-1) sh - 2 ph + kh + oph and
+      y[f][oy][ox] = b[f] + sum w[c][f][dy][dx] x[c][iy][ix]
+    over the taps with oy + ph - dy = sh iy, 0 <= iy < H (likewise in x). groups = 1, no dilation; the domain is
+    _convt_check's. Linear, so free of garbled tables; hardened encoding only (docs/CONV_TRANSPOSE.md)."""
+
+    kind = Kind.CONVT
+    name = "conv_transpose2d"
+
+    def __init__(self, weights: np.ndarray, biases: np.ndarray, input_width: int, input_height: int, channel: int,
+                 filter: int, filter_width: int, filter_height: int, stride_width: int = 1, stride_height: int = 1,
+                 q_parameter: int = -1, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
+                 q_const: float = 10.0, pad_width: int = 0, pad_height: int = 0, out_pad_width: int = 0,
+                 out_pad_height: int = 0, groups: int = 1, dilation: int = 1):
+        self.C, self.H, self.W, self.F = int(channel), int(input_height), int(input_width), int(filter)
+        self.kh, self.kw, self.sh, self.sw = int(filter_height), int(filter_width), int(stride_height), int(stride_width)
+        self.ph, self.pw, self.oph, self.opw = int(pad_height), int(pad_width), int(out_pad_height), int(out_pad_width)
+        _convt_check(self.kh, self.kw, self.sh, self.sw, self.ph, self.pw, self.oph, self.opw, groups, dilation)
+        self.OH = (self.H - 1) * self.sh - 2 * self.ph + self.kh + self.oph
+        self.OW = (self.W - 1) * self.sw - 2 * self.pw + self.kw + self.opw
+        if self.OH < 1 or self.OW < 1:
+            raise ValueError(f"conv_transpose2d: empty output ({self.OH} x {self.OW})")
+        super().__init__((self.C, self.H, self.W), (self.F, self.OH, self.OW))
+        w = np.asarray(weights, dtype=np.float32).reshape(self.C, self.F, self.kh, self.kw)
+        b = np.asarray(biases, dtype=np.float32).reshape(self.F)
+        self.weights, self.biases = w, b
+        self.q_method, self.q_parameter, self.q_const = QuantizationMethod(q_method), q_parameter, q_const
+        self.q_weights, self.q_biases = quantize_params(w, b, self.q_method, q_parameter, q_const)
+        self._track_q(self.q_weights, self.q_biases)
+
+    @classmethod
+    def from_quantized(cls, q_weights, q_biases, input_width, input_height, channel, filter, filter_width,
+                       filter_height, stride_width=1, stride_height=1, pad_width=0, pad_height=0, out_pad_width=0,
+                       out_pad_height=0, groups=1, dilation=1):
+        c = cls(np.zeros((channel, filter, filter_height, filter_width), np.float32), np.zeros(filter, np.float32),
+                input_width, input_height, channel, filter, filter_width, filter_height, stride_width, stride_height,
+                q_const=1.0, pad_width=pad_width, pad_height=pad_height, out_pad_width=out_pad_width,
+                out_pad_height=out_pad_height, groups=groups, dilation=dilation)
+        c.q_weights = np.asarray(q_weights, dtype=np.int64).reshape(channel, filter, filter_height, filter_width)
+        c.q_biases = np.asarray(q_biases, dtype=np.int64).reshape(filter)
+        c.weights = c.q_weights.astype(np.float32)
+        c.biases = c.q_biases.astype(np.float32)
+        c.reset_ranges()
+        c._track_q(c.q_weights, c.q_biases)
+        return c
+
+    def quantize(self, q_const):
+        self.q_const = q_const
+        self.q_weights, self.q_biases = quantize_params(self.weights, self.biases, QuantizationMethod.SimpleQuant,
+                                                        -1, q_const)
+        self.reset_ranges()
+
+    def get_q_const(self):
+        return self.q_const
+
+    def _taps(self):
+        """Per tap (dy, dx): the output rows / columns it reaches and the input rows / columns they read."""
+        for dy in range(self.kh):
+            oy = np.arange(self.H) * self.sh + dy - self.ph
+            my = (oy >= 0) & (oy < self.OH)
+            for dx in range(self.kw):
+                ox = np.arange(self.W) * self.sw + dx - self.pw
+                mx = (ox >= 0) & (ox < self.OW)
+                if my.any() and mx.any():
+                    yield dy, dx, oy[my], np.nonzero(my)[0], ox[mx], np.nonzero(mx)[0]
+
+    def _convt(self, x, w, b):
+        x = x.reshape(self.C, self.H, self.W)
+        y = np.zeros((self.F, self.OH, self.OW), dtype=np.result_type(x.dtype, w.dtype))
+        for dy, dx, oy, iy, ox, ix in self._taps():
+            y[:, oy[:, None], ox[None, :]] += np.einsum("cf,cyx->fyx", w[:, :, dy, dx], x[:, iy[:, None], ix[None, :]])
+        return (y + b[:, None, None]).reshape(-1)
+
+    def plain_eval(self, x, track=True, ctx=None):
+        y = self._convt(np.asarray(x, dtype=np.float32).reshape(-1), self.weights, self.biases)
+        if track:
+            self._track_f(x, y, self.weights, self.biases)
+        return y
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        x = np.asarray(x, dtype=np.int64).reshape(-1)
+        y = self._convt(x, self.q_weights, self.q_biases)
+        if track:
+            # products and running partial sums over each output's valid taps, in (c, dy, dx) order (as Conv2d):
+            # terms[c, dy, dx, f, oy, ox], zero where the tap does not reach the output
+            xi = x.reshape(self.C, self.H, self.W)
+            terms = np.zeros((self.C, self.kh, self.kw, self.F, self.OH, self.OW), dtype=np.int64)
+            for dy, dx, oy, iy, ox, ix in self._taps():
+                terms[:, dy, dx][:, :, oy[:, None], ox[None, :]] = (
+                    self.q_weights[:, :, dy, dx][:, :, None, None] * xi[:, None][:, :, iy[:, None], ix[None, :]])
+            terms = terms.reshape(self.C * self.kh * self.kw, -1)
+            self._track_q(terms, np.cumsum(terms, axis=0), y)
+        return y
+
+    def get_min_plain_q_val(self):
+        return min(self.min_q, int(self.q_weights.min()), int(self.q_biases.min()))
+
+    def get_max_plain_q_val(self):
+        return max(self.max_q, int(self.q_weights.max()), int(self.q_biases.max()))
+
+    def garble_spec(self):
+        return self.kind, {"C": self.C, "H": self.H, "W": self.W, "F": self.F, "kh": self.kh, "kw": self.kw,
+                           "sh": self.sh, "sw": self.sw, "ph": self.ph, "pw": self.pw, "oph": self.oph,
+                           "opw": self.opw, "w": self.q_weights.reshape(-1), "b": self.q_biases.reshape(-1)}
+
+
+class Upsample(Layer):
+    """Nearest-neighbour upsampling of a (C, H, W) tensor by integer factors (fh, fw) >= 1, not both 1:
+    y[c][oy][ox] = x[c][oy // fh][ox // fw]. Free in the label domain, like Concat: no tables, no PRG draws, no
+    constants, so it works under both encodings and every quantization scheme."""
+
+    kind = Kind.UPSAMPLE
+    name = "upsample"
+
+    def __init__(self, dims, factor_height: int, factor_width: Optional[int] = None):
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 3:
+            raise ValueError(f"upsample: the input is (C, H, W), got {dims}")
+        self.C, self.H, self.W = dims
+        self.fh = int(factor_height)
+        self.fw = int(factor_height if factor_width is None else factor_width)
+        if self.fh != factor_height or self.fw != (factor_height if factor_width is None else factor_width):
+            raise ValueError("upsample: integer factors only")
+        if self.fh < 1 or self.fw < 1 or self.fh * self.fw == 1:
+            raise ValueError(f"upsample: factors must be >= 1 and not both 1, got ({self.fh}, {self.fw})")
+        super().__init__(dims, (self.C, self.H * self.fh, self.W * self.fw))
+
+    def _up(self, x):
+        x = np.asarray(x).reshape(self.C, self.H, self.W)
+        return np.repeat(np.repeat(x, self.fh, axis=1), self.fw, axis=2).reshape(-1)
+
+    def plain_eval(self, x, track=True, ctx=None):
+        return self._up(x)
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        y = self._up(np.asarray(x, dtype=np.int64))
+        if track:
+            self._track_q(y)
+        return y
+
+    def garble_spec(self):
+        return self.kind, {"C": self.C, "H": self.H, "W": self.W, "fh": self.fh, "fw": self.fw}
+
+    def __repr__(self) -> str:
+        return f"Upsample(in={self.in_dims}, factors=({self.fh}, {self.fw}))"
 
 
 class Relu(Layer):

@@ -35,6 +35,17 @@ is accepted, since the batch-free dims (1,) / (1, H, W) are the same; any
 other axis and `select_last_index = 1` are refused with the node's name. The
 index drops a pending (positive) average factor, as a Sign does.
 
+`ConvTranspose` (strides, symmetric pads, output_padding, group = 1) becomes a
+`ConvTranspose2d` layer; a pending average factor goes into its weights and a
+following BatchNormalization folds along the filter axis (axis 1 of its
+[C][F][kh][kw] weights). Dilations, `auto_pad`, `output_shape`, groups and
+asymmetric pads are refused with the node's name. `Resize` (opset >= 11) and
+`Upsample` (opset <= 9) in mode `nearest` with integer scales [1, 1, fh, fw] (or
+`sizes` that are integer multiples of the input), and for Resize
+`coordinate_transformation_mode = asymmetric` with `nearest_mode = floor` (what
+PyTorch exports for nn.Upsample(mode="nearest")), become an `Upsample` layer;
+everything else is refused with the node's name. A pending factor passes through.
+
 `ReduceSum` over (2, 3) is the plane `SumPool2d` itself (the exporter writes a
 global sum pool that no linear layer follows this way).
 
@@ -63,7 +74,8 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import Add, ArgMax, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
+from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign,
+                     SumPool2d, Upsample, _convt_check, _pool_out)
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -102,6 +114,12 @@ class _Spec:
     def __init__(self, kind: str, **kw):
         self.kind = kind
         self.kw = kw
+
+
+def _sattr(a: dict, key: str, default: str) -> str:
+    """A string attribute (the native reader hands strings over as bytes)."""
+    v = a.get(key, default)
+    return v.decode() if isinstance(v, (bytes, bytearray)) else str(v)
 
 
 def _pool_attrs(node) -> tuple:
@@ -244,14 +262,91 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group), outs[0], j,
                  (F, H, W))
             last_conv_filters = F
+        elif op == "ConvTranspose":
+            j, dims, fac = data_in(node, ins[0])
+            name = node.get("name") or op
+            w = arr(ins[1])  # [C][F/group][kh][kw]
+            if w.ndim != 4 or len(dims) != 3:
+                raise NotImplementedError(f"onnx: {name}: only 2-D ConvTranspose of an image is supported")
+            C, F, kh, kw = (int(v) for v in w.shape)
+            if int(a.get("group", 1)) != 1:
+                raise NotImplementedError(f"onnx: {name}: ConvTranspose with group != 1 is not supported")
+            if any(int(v) != 1 for v in a.get("dilations", [1, 1])):
+                raise NotImplementedError(f"onnx: {name}: dilated ConvTranspose is not supported")
+            if _sattr(a, "auto_pad", "NOTSET") != "NOTSET":
+                raise NotImplementedError(f"onnx: {name}: auto_pad is not supported")
+            if "output_shape" in a:
+                raise NotImplementedError(f"onnx: {name}: output_shape is not supported (give pads / output_padding)")
+            st = [int(v) for v in a.get("strides", [1, 1])]
+            pads = [int(v) for v in a.get("pads", [0, 0, 0, 0])]
+            opad = [int(v) for v in a.get("output_padding", [0, 0])]
+            if pads[0] != pads[2] or pads[1] != pads[3]:
+                raise NotImplementedError(f"onnx: {name}: asymmetric pads {pads} are not supported")
+            if dims[0] != C:
+                raise ValueError(f"onnx: {name}: ConvTranspose expects {C} input channels, got dims {dims}")
+            try:
+                _convt_check(kh, kw, st[0], st[1], pads[0], pads[1], opad[0], opad[1])
+            except ValueError as e:
+                raise ValueError(f"onnx: {name}: {e}") from None
+            bias = arr(ins[2]).reshape(-1) if len(ins) > 2 and ins[2] else np.zeros(F, np.float32)
+            if fac != 1.0:
+                w = (w * np.float32(fac)).astype(np.float32)
+            OH = (dims[1] - 1) * st[0] - 2 * pads[0] + kh + opad[0]
+            OW = (dims[2] - 1) * st[1] - 2 * pads[1] + kw + opad[1]
+            emit(_Spec("convt", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), opad=(opad[0], opad[1])),
+                 outs[0], j, (F, OH, OW))
+            last_conv_filters = F
+        elif op in ("Resize", "Upsample"):
+            j, dims, fac = data_in(node, ins[0])
+            name = node.get("name") or op
+            if tf or len(dims) != 3:
+                raise NotImplementedError(f"onnx: {name}: {op} of an NCHW image only")
+            if _sattr(a, "mode", "nearest") != "nearest":
+                raise NotImplementedError(f"onnx: {name}: {op} mode {_sattr(a, 'mode', 'nearest')!r} is not supported "
+                                          "(nearest only)")
+            if op == "Resize":
+                if int(model.get("opset", 11)) < 11:
+                    raise NotImplementedError(f"onnx: {name}: Resize needs opset >= 11")
+                ctm, nm = _sattr(a, "coordinate_transformation_mode", "half_pixel"), \
+                    _sattr(a, "nearest_mode", "round_prefer_floor")
+                if ctm != "asymmetric" or nm != "floor":
+                    raise NotImplementedError(f"onnx: {name}: Resize is supported with coordinate_transformation_mode="
+                                              f"asymmetric and nearest_mode=floor only, got {ctm!r} / {nm!r}")
+                s_in, z_in = (ins[2] if len(ins) > 2 else ""), (ins[3] if len(ins) > 3 else "")
+            else:
+                s_in, z_in = (ins[1] if len(ins) > 1 else ""), ""
+            full = (1,) + tuple(dims)
+            if s_in and s_in in inits and inits[s_in]["values"].size:
+                sc = [float(v) for v in np.asarray(inits[s_in]["values"]).reshape(-1)]
+            elif op == "Upsample" and "scales" in a:  # opset 7: an attribute
+                sc = [float(v) for v in a["scales"]]
+            elif z_in and z_in in inits:
+                t = inits[z_in]
+                sz = [int(v) for v in (list(t["ivalues"]) or np.asarray(t["values"]).reshape(-1))]
+                if len(sz) != 4 or any(z % d for z, d in zip(sz, full)):
+                    raise NotImplementedError(f"onnx: {name}: sizes {sz} are no integer multiples of the input {full}")
+                sc = [z / d for z, d in zip(sz, full)]
+            else:
+                raise NotImplementedError(f"onnx: {name}: {op} needs constant scales or sizes")
+            if len(sc) != 4 or sc[0] != 1 or sc[1] != 1 or any(v != int(v) or v < 1 for v in sc[2:]) or \
+                    sc[2] * sc[3] == 1:
+                raise NotImplementedError(f"onnx: {name}: {op} scales {sc} are not [1, 1, fh, fw] with integer "
+                                          "factors >= 1 (not both 1)")
+            fh, fw = int(sc[2]), int(sc[3])
+            emit(_Spec("upsample", dims=dims, f=(fh, fw)), outs[0], j, (dims[0], dims[1] * fh, dims[2] * fw), fac)
         elif op == "BatchNormalization":
             j = src_of(ins[0])
-            assert j is not None and j >= 0 and specs[j].kind in ("conv", "dense"), \
-                "onnx: BatchNormalization must follow a Conv or Gemm"
+            assert j is not None and j >= 0 and specs[j].kind in ("conv", "dense", "convt"), \
+                "onnx: BatchNormalization must follow a Conv, ConvTranspose or Gemm"
             scale, shift, mean, var = (arr(n).reshape(-1) for n in ins[1:5])
             eps = float(a.get("epsilon", 1e-5))
             g = scale / np.sqrt(var + eps)
             s = specs[j]
+            if s.kind == "convt":  # the filters are axis 1 of [C][F][kh][kw]
+                s.kw["w"] = s.kw["w"] * g.reshape(1, -1, 1, 1)
+                s.kw["b"] = (s.kw["b"] - mean) * g + shift
+                alias[outs[0]] = res(ins[0])
+                continue
             s.kw["w"] = s.kw["w"] * g.reshape((-1,) + (1,) * (s.kw["w"].ndim - 1))
             s.kw["b"] = (s.kw["b"] - mean) * g + shift
             alias[outs[0]] = res(ins[0])
@@ -404,6 +499,15 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             layers.append(Conv2d(kw["w"], kw["b"], W, H, C, F, kw_, kh, kw["stride"][1], kw["stride"][0],
                                  q_parameter, q_method, q_const, pad_width=kw["pads"][1], pad_height=kw["pads"][0],
                                  groups=kw["group"]))
+        elif s.kind == "convt":
+            C, H, W = kw["dims"]
+            _, F, kh, kw_ = kw["w"].shape
+            layers.append(ConvTranspose2d(kw["w"], kw["b"], W, H, C, F, kw_, kh, kw["stride"][1], kw["stride"][0],
+                                          q_parameter, q_method, q_const, pad_width=kw["pads"][1],
+                                          pad_height=kw["pads"][0], out_pad_width=kw["opad"][1],
+                                          out_pad_height=kw["opad"][0]))
+        elif s.kind == "upsample":
+            layers.append(Upsample(kw["dims"], kw["f"][0], kw["f"][1]))
         elif s.kind in ("maxpool", "sumpool"):
             C, H, W = kw["dims"]
             cls = MaxPool2d if s.kind == "maxpool" else SumPool2d
@@ -424,7 +528,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         if kw.get("in_src") is not None:
             layers[-1].in_src = spec_to_layer[kw["in_src"]]
         spec_to_layer[i] = len(layers) - 1
-        if s.kind in ("dense", "conv"):
+        if s.kind in ("dense", "conv", "convt"):
             out = layers[-1].out_dims
             if q_method == QuantizationMethod.ScaleQuant:
                 layers.append(Rescale(q_parameter, out))
@@ -490,6 +594,10 @@ def _attr_int(name: str, v: int) -> bytes:
     return _ld(5, _s(1, name) + _i(3, int(v)) + _i(20, 2))
 
 
+def _attr_str(name: str, v: str) -> bytes:
+    return _ld(5, _s(1, name) + _ld(4, v.encode()) + _i(20, 3))
+
+
 def _attr_float(name: str, v: float) -> bytes:
     return _ld(5, _s(1, name) + _key(2, 5) + struct.pack("<f", v) + _i(20, 1))
 
@@ -544,6 +652,19 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             attrs = (_attr_ints("dilations", [1, 1]) + _attr_int("group", l.groups) + _attr_ints("kernel_shape", [l.kh, l.kw])
                      + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + _attr_ints("strides", [l.sh, l.sw]))
             nodes.append(_node("Conv", [cur, f"{name}.weight", f"{name}.bias"], [out], name, attrs))
+        elif isinstance(l, ConvTranspose2d):
+            inits += [_tensor(f"{name}.weight", l.weights * np.float32(K)), _tensor(f"{name}.bias", l.biases)]
+            attrs = (_attr_ints("dilations", [1, 1]) + _attr_int("group", 1) + _attr_ints("kernel_shape", [l.kh, l.kw])
+                     + _attr_ints("output_padding", [l.oph, l.opw]) + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw])
+                     + _attr_ints("strides", [l.sh, l.sw]))
+            nodes.append(_node("ConvTranspose", [cur, f"{name}.weight", f"{name}.bias"], [out], name, attrs))
+        elif isinstance(l, Upsample):
+            # what PyTorch writes for nn.Upsample(mode="nearest"): Resize with an empty roi and constant scales
+            inits.append(_tensor(f"{name}.scales", np.asarray([1, 1, l.fh, l.fw], np.float32)))
+            attrs = (_attr_str("coordinate_transformation_mode", "asymmetric") + _attr_str("mode", "nearest")
+                     + _attr_str("nearest_mode", "floor"))
+            nodes.append(_node("Resize", [cur, "", f"{name}.scales"], [out], name, attrs))
+            scale[out] = K
         elif isinstance(l, MaxPool2d):
             attrs = _attr_ints("kernel_shape", [l.kh, l.kw]) + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + \
                 _attr_ints("strides", [l.sh, l.sw])

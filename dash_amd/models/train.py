@@ -20,7 +20,8 @@ from typing import Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import Clip, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d, _pool_out
+from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d,
+                         Upsample, _pool_out)
 from ..ir.quant import QuantizationMethod
 from .zoo import ARCHS, canonical
 
@@ -56,6 +57,11 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
         def forward(self, x):
             return nn.functional.linear(fq(x), fq(self.weight), fq(self.bias))
 
+    class FQConvT(nn.ConvTranspose2d):
+        def forward(self, x):
+            return nn.functional.conv_transpose2d(fq(x), fq(self.weight), fq(self.bias), self.stride, self.padding,
+                                                  self.output_padding)
+
     class FQConv(nn.Conv2d):  # nn.Conv2d's own `groups` keyword (depthwise: groups = in channels)
         def forward(self, x):
             return self._conv_forward(fq(x), fq(self.weight), fq(self.bias))
@@ -76,6 +82,15 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             _, ks, s, p = op
             mods.append(FQConv(dims[0], dims[0], ks, stride=s, padding=p, groups=dims[0]))
             dims = [dims[0], (dims[1] + 2 * p - ks) // s + 1, (dims[2] + 2 * p - ks) // s + 1]
+        elif k == "convt":
+            _, cout, ks, s, p, opad = op
+            mods.append(FQConvT(dims[0], cout, ks, stride=s, padding=p, output_padding=opad))
+            dims = [cout, (dims[1] - 1) * s - 2 * p + ks + opad, (dims[2] - 1) * s - 2 * p + ks + opad]
+        elif k == "up":
+            mods.append(nn.Upsample(scale_factor=int(op[1]), mode="nearest"))
+            dims = [dims[0], dims[1] * int(op[1]), dims[2] * int(op[1])]
+        elif k in ("skip", "cat"):
+            raise NotImplementedError(f"training: op {k} (skip connections) not supported by the sequential trainer")
         elif k == "relu":
             mods.append(nn.ReLU())
         elif k == "relu6":
@@ -138,6 +153,25 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
             layers.append(c)
             dims = c.out_dims
             rescale(dims)
+        elif isinstance(m, nn.ConvTranspose2d):
+            w = m.weight.detach().cpu().numpy()  # [C][F/groups][kh][kw]
+            Cin, Fo, kh, kw = w.shape
+            c = ConvTranspose2d(w, m.bias.detach().cpu().numpy(), dims[2], dims[1], Cin, Fo, kw, kh, m.stride[1],
+                                m.stride[0], q_parameter, qm, q_const, pad_width=m.padding[1],
+                                pad_height=m.padding[0], out_pad_width=m.output_padding[1],
+                                out_pad_height=m.output_padding[0], groups=m.groups, dilation=max(m.dilation))
+            layers.append(c)
+            dims = c.out_dims
+            rescale(dims)
+        elif isinstance(m, nn.Upsample):
+            if m.mode != "nearest" or m.scale_factor is None:
+                raise NotImplementedError("training: only nn.Upsample(scale_factor=f, mode='nearest') maps to a layer")
+            sf = m.scale_factor if isinstance(m.scale_factor, (tuple, list)) else (m.scale_factor, m.scale_factor)
+            if any(float(f) != int(f) for f in sf):
+                raise NotImplementedError("training: nn.Upsample needs integer scale factors")
+            up = Upsample(dims, int(sf[0]), int(sf[1]))
+            layers.append(up)
+            dims = up.out_dims
         elif isinstance(m, nn.ReLU):
             layers.append(Relu(dims))
         elif isinstance(m, nn.Hardtanh):  # nn.ReLU6 is a Hardtanh(0, 6)

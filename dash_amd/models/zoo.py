@@ -12,7 +12,8 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import Add, ArgMax, Clip, Concat, Conv2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d
+from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Relu, Rescale,
+                         Sign, SumPool2d, Upsample)
 from ..ir.quant import QuantizationMethod, quantize_input
 
 # architecture ops: ("conv", out_ch, k, stride, pad) | ("relu",) | ("sign",) | ("flatten",) | ("fc", out)
@@ -25,6 +26,10 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   scheme's activation scale; refused under SimpleQuant)
 #                   | ("argmax",) index of the largest value along the first axis (the class of a logit vector,
 #                   the per-pixel class of a (C, H, W) score map); scale-free
+#                   | ("convt", out_ch, k, stride, pad, out_pad) transposed conv (+ the scheme's rescale, as conv)
+#                   | ("up", f) nearest-neighbour upsampling by f
+#                   | ("skip",) remember the current tensor | ("cat",) channel concat of the most recent open skip
+#                   with the current tensor, skip first (an encoder-decoder's skip connection)
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     # MODEL_A whose decoded output is the class alone, not the ten logits
@@ -87,6 +92,17 @@ ARCHS: dict[str, dict] = {
         ("conv", 16, 3, 2, 1), ("relu",), ("maxpool", 3, 2, 0, True),
         ("fire", 8, 16, 16), ("maxpool", 3, 2, 0, True), ("fire", 8, 16, 16),
         ("conv", 10, 1, 1, 0), ("gap",), ("flatten",)]},
+    # small U-Net: two stride-2 encoder steps (32 -> 16 -> 8), a transposed-conv and a nearest-neighbour decoder
+    # step, each concatenated with the encoder tensor of its size, and a per-pixel class map (1, 32, 32) of 4 classes
+    "UNET_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 8, 3, 1, 1), ("relu",), ("skip",),
+        ("conv", 16, 3, 2, 1), ("relu",), ("skip",),
+        ("conv", 32, 3, 2, 1), ("relu",),
+        ("convt", 16, 2, 2, 0, 0), ("relu",), ("cat",),
+        ("conv", 16, 3, 1, 1), ("relu",),
+        ("up", 2), ("cat",),
+        ("conv", 8, 3, 1, 1), ("relu",),
+        ("conv", 4, 1, 1, 0), ("argmax",)]},
 }
 
 ALIASES = {"MINIONN": "MODEL_F_MINIONN_POOL_REPL", "GNNP": "MODEL_F_GNNP_POOL_REPL", "MLP": "MODEL_A",
@@ -139,9 +155,33 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         rescale_after(c.out_dims)
         return c.out_dims
 
+    skips = []  # open ("skip",) marks: (layer index, dims)
     for op in arch["ops"]:
         kind = op[0]
-        if kind == "flatten":
+        if kind == "convt":
+            _, cout, k, s, p, op_ = op
+            fan_in = cout * k * k  # PyTorch's ConvTranspose2d default: fan-in of the [C][F][k][k] weight's axis 1
+            wt = _init(rng, (dims[0], cout, k, k), fan_in)
+            bs = _init(rng, (cout,), fan_in)
+            ct = ConvTranspose2d(wt, bs, dims[2], dims[1], dims[0], cout, k, k, s, s, q_parameter, qm, q_const,
+                                 pad_width=p, pad_height=p, out_pad_width=op_, out_pad_height=op_)
+            layers.append(ct)
+            dims = ct.out_dims
+            rescale_after(dims)
+        elif kind == "up":
+            up = Upsample(dims, op[1])
+            layers.append(up)
+            dims = up.out_dims
+        elif kind == "skip":
+            skips.append((len(layers) - 1, dims))
+        elif kind == "cat":
+            if not skips:
+                raise ValueError(f"{name}: ('cat',) without an open ('skip',)")
+            src, sd = skips.pop()
+            cat = Concat([sd, dims], [src, len(layers) - 1])
+            layers.append(cat)
+            dims = cat.out_dims
+        elif kind == "flatten":
             layers.append(Flatten(dims))
             dims = (int(np.prod(dims)),)
         elif kind == "fc":
@@ -261,6 +301,8 @@ BENCH_CONFIGS = {
                                  crt=7, mrs=100.0),
     "SQUEEZENET_CIFAR/DASH": dict(model="SQUEEZENET_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
                                   crt=7, mrs=100.0),
+    "UNET_CIFAR/DASH": dict(model="UNET_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5, crt=7,
+                            mrs=100.0),
     "MODEL_A_ARGMAX/SIMPLE": dict(model="MODEL_A_ARGMAX", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8,
                                   mrs=100.0),
     "MODEL_A/SIMPLE": dict(model="MODEL_A", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8, mrs=100.0),
