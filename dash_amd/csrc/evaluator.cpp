@@ -234,7 +234,7 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                                     for (i64 dx = 0; dx < G.kw; ++dx) {
                                         const int32_t wv = wf[(c * G.kh + dy) * G.kw + dx];
                                         if (wv == 0) continue;
-                                        const i64 iy = oy * G.sh - G.ph + dy, ix = ox * G.sw - G.pw + dx;
+                                        const i64 iy = oy * G.sh - G.ph + dy * G.dh, ix = ox * G.sw - G.pw + dx * G.dw;
                                         const comp_t* x = (iy < 0 || iy >= G.H || ix < 0 || ix >= G.W)
                                                               ? Zp
                                                               : I.at(((c0 + c) * G.H + iy) * G.W + ix);

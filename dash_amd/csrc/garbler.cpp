@@ -58,10 +58,17 @@ ConvGeom::ConvGeom(const Params& p) {
     ph = param1(p, "ph", 0);
     pw = param1(p, "pw", 0);
     g = param1(p, "g", 1);
+    dh = param1(p, "dh", 1);
+    dw = param1(p, "dw", 1);
     DASH_CHECK(C > 0 && H > 0 && W > 0 && F > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0, "bad conv geometry");
     DASH_CHECK(g > 0 && C % g == 0 && F % g == 0, "conv groups must divide both C and F");
-    OH = (H + 2 * ph - kh) / sh + 1;
-    OW = (W + 2 * pw - kw) / sw + 1;
+    DASH_CHECK(dh >= 1 && dw >= 1, "conv2d: dilation must be at least 1");
+    if (kh == 1) dh = 1;  // moot: the layer is the plain conv
+    if (kw == 1) dw = 1;
+    const i64 keh = (kh - 1) * dh + 1, kew = (kw - 1) * dw + 1;  // effective kernel
+    DASH_CHECK(H + 2 * ph >= keh && W + 2 * pw >= kew, "conv2d: empty output (the dilated kernel exceeds the padded input)");
+    OH = (H + 2 * ph - keh) / sh + 1;
+    OW = (W + 2 * pw - kew) / sw + 1;
 }
 
 ConvTGeom::ConvTGeom(const Params& p) {
@@ -862,7 +869,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                                             ++zc;
                                             continue;
                                         }
-                                        const i64 iy = oy * G.sh - G.ph + dy, ix = ox * G.sw - G.pw + dx;
+                                        const i64 iy = oy * G.sh - G.ph + dy * G.dh, ix = ox * G.sw - G.pw + dx * G.dw;
                                         const comp_t* x = (iy < 0 || iy >= G.H || ix < 0 || ix >= G.W)
                                                               ? Zp
                                                               : I.at(((c0 + c) * G.H + iy) * G.W + ix);

@@ -3138,7 +3138,8 @@ void GpuGarbler::conv_run(const ConvGeom& G, const ConvTGeom* T, const i64* w0, 
     std::vector<DevBlock> out = I.alloc_labels(mods, Nout);
     dev::ConvArgs a{};
     {
-        ConvPlanKey key{I.device, wh, {G.C, G.H, G.W, G.F, G.kh, G.kw, G.sh, G.sw, G.ph, G.pw, G.g}, mods};
+        // dilation included: a dilated and an undilated layer with the same weights are different plans
+        ConvPlanKey key{I.device, wh, {G.C, G.H, G.W, G.F, G.kh, G.kw, G.sh, G.sw, G.ph, G.pw, G.g, G.dh, G.dw}, mods};
         // a transposed layer's view can equal a plain conv's geometry (and the weights' hash is of another
         // layout): its own geometry goes into the key behind a marker no conv has
         if (T) key.geom.insert(key.geom.end(), {-1, T->F, T->kh, T->kw, T->sh, T->sw, T->ph, T->pw, T->oph, T->opw});
@@ -3161,6 +3162,7 @@ void GpuGarbler::conv_run(const ConvGeom& G, const ConvTGeom* T, const i64* w0, 
             a.sh = static_cast<int>(G.sh); a.sw = static_cast<int>(G.sw);
             a.ph = static_cast<int>(G.ph); a.pw = static_cast<int>(G.pw);
             a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
+            a.dh = static_cast<int>(G.dh); a.dw = static_cast<int>(G.dw);
             a.use_mfma = 1;
             a.groups = static_cast<int>(G.g);
             if (T) {
@@ -3211,7 +3213,8 @@ void GpuGarbler::conv_run(const ConvGeom& G, const ConvTGeom* T, const i64* w0, 
                 a.w8r[j] = nullptr;
                 a.wg[j] = nullptr;
                 if (G.g > 1) {
-                    const std::vector<uint32_t> wg = dev::conv_grp_weights(w, G.F, G.Cg(), a.kh, a.kw, p);
+                    const std::vector<uint32_t> wg =
+                        dev::conv_grp_weights(w, G.F, G.Cg(), a.kh, a.kw, p, dev::conv_dilated(a));
                     a.wg[j] = gg::dconst(wg.data(), wg.size());
                 } else if (a.nbands > 0) {
                     const std::vector<int8_t> w8r = dev::conv_w8r(a, w8, F);

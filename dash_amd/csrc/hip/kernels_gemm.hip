@@ -68,10 +68,12 @@ __device__ __forceinline__ int convt_dst(const ConvArgs& a, int fv, int qy, int 
 }
 
 // VALU conv: grid (ceil(OH*OW/256), F, B*sum_n). SC: the transposed conv's scatter epilogue (a separate
-// instantiation, as for the kernels below)
-template <bool SC>
+// instantiation, as for the kernels below). DL: dilated taps (ConvArgs::dh, dw), separate instantiations too: without
+// DL the dilations are the compile-time constant 1
+template <bool SC, bool DL = false>
 __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, Act x, Act y, const int* zj, const int* zcomp,
                                                    int sumn) {
+    const int dh = DL ? a.dh : 1, dw = DL ? a.dw : 1;
     const int z = blockIdx.z;
     const int b = z / sumn, r = z % sumn;
     const int j = zj[r], c = zcomp[r];
@@ -87,10 +89,10 @@ __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, Act x, Act y, con
     int32_t acc = 0;
     for (int ci = 0; ci < a.C; ++ci) {
         for (int dy = 0; dy < a.kh; ++dy) {
-            const int iy = oy * a.sh - a.ph + dy;
+            const int iy = oy * a.sh - a.ph + dy * dh;
             const bool rowok = iy >= 0 && iy < a.H;
             for (int dx = 0; dx < a.kw; ++dx) {
-                const int ix = ox * a.sw - a.pw + dx;
+                const int ix = ox * a.sw - a.pw + dx * dw;
                 const int32_t w = Wf[(ci * a.kh + dy) * a.kw + dx];
                 const int32_t v = (rowok && ix >= 0 && ix < a.W) ? X[(ci * a.H + iy) * a.W + ix] : zv;
                 acc += w * v;
@@ -119,8 +121,9 @@ __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, Act x, Act y, con
 typedef int32_t v4i __attribute__((ext_vector_type(4)));
 typedef int64_t v2l __attribute__((ext_vector_type(2)));
 
-template <bool SC>
+template <bool SC, bool DL = false>
 __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs a, Act x, Act y, int j, int64_t ncols) {
+    const int dh = DL ? a.dh : 1, dw = DL ? a.dw : 1;
     __shared__ __attribute__((aligned(16))) int8_t As[64 * 64];   // [f][k]
     __shared__ __attribute__((aligned(16))) int8_t Bs[64 * 64];   // [col][k]
     const int p = a.crt.p[j], n = a.crt.n[j];
@@ -168,7 +171,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs a, Act x, Act y, int
                 int v = 0;
                 if (colok && kk < K) {
                     const int ci = kk / (a.kh * a.kw), rr = kk % (a.kh * a.kw), dy = rr / a.kw, dx = rr % a.kw;
-                    const int iy = soy * a.sh - a.ph + dy, ix = sox * a.sw - a.pw + dx;
+                    const int iy = soy * a.sh - a.ph + dy * dh, ix = sox * a.sw - a.pw + dx * dw;
                     v = (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) ? X[(ci * a.H + iy) * a.W + ix] : zv;
                     if (v > half) v -= p;
                 }
@@ -384,9 +387,15 @@ static_assert(kConvFW == 16 || kConvFW == 32, "conv: 16 or 32 filters per wave")
 // registers and code
 // SC: the transposed conv's scatter epilogue (ConvArgs::tsc), separate instantiations again: every `if constexpr
 // (SC)` below is dead in the plain conv's kernels
-template <int KSC, bool UR, bool SC = false>
+// DL: dilated taps (ConvArgs::dh, dw; the unrolled view's udh, udw), separate instantiations once more: without DL
+// the dilations are the compile-time constant 1 and the kernels are the undilated ones. The channel-chunked
+// staging does not depend on the taps: only the band's input rows (conv_band_in_rows) and the MFMA loop's tap
+// offset (dy dh) R + (dx dw) S change; the unrolled staging reads its patch at the dilated row and column.
+template <int KSC, bool UR, bool SC = false, bool DL = false>
 __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int B) {
     constexpr bool AREG = KSC > 0;
+    const int dlh = DL ? a.dh : 1, dlw = DL ? a.dw : 1;            // taps of the MFMA phase (1 in the unrolled view)
+    const int udh = DL && UR ? a.udh : 1, udw = DL && UR ? a.udw : 1;  // taps of the unrolled staging
     extern __shared__ __attribute__((aligned(16))) int8_t img[];
     const int band = static_cast<int>(blockIdx.x % static_cast<unsigned>(a.nbands));
     const int64_t gimg = blockIdx.x / static_cast<unsigned>(a.nbands);
@@ -400,7 +409,7 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int
     const int oy0 = band * a.band;
     const int oy1 = min(a.OH, oy0 + a.band);
     const int iy0 = oy0 * a.sh - a.ph;
-    const int in_rows = (oy1 - oy0 - 1) * a.sh + a.kh;
+    const int in_rows = conv_band_in_rows(oy1 - oy0, a.sh, a.kh, dlh);
     const int S = a.ldsS, R = a.ldsR, Wp = a.W + 2 * a.pw;
     // the layer's input image (the unrolled view's a.C/H/W describe the staged band, not the input)
     const int HW = UR ? a.uH * a.uW : a.H * a.W;
@@ -537,12 +546,12 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int
                 const int ci = static_cast<int>(cqc) - tap * a.uC;
                 const int dy = a.ukw > 1 ? static_cast<int>(__umulhi(static_cast<uint32_t>(tap), mkw)) : tap;
                 const int dx = tap - dy * a.ukw;
-                const int iy = (iy0 + yq) * a.ush - a.uph + dy;
+                const int iy = (iy0 + yq) * a.ush - a.uph + dy * udh;
                 const bool rowin = iy >= 0 && iy < a.uH;
                 const int iyc = min(max(iy, 0), a.uH - 1);
                 const act_t* row = X + static_cast<int64_t>(ci) * HW + static_cast<int64_t>(iyc) * a.uW;
                 uint32_t o[2];
-                fetch8(row, rowin, xo * 8 - a.upw + dx, a.uW, o);
+                fetch8(row, rowin, xo * 8 - a.upw + dx * udw, a.uW, o);
                 raw[q][0] = cin ? o[0] : 0u;
                 raw[q][1] = cin ? o[1] : 0u;
             }
@@ -686,7 +695,7 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int
         for (int s = 0; s < (AREG ? KSC : 1); ++s) {
             const int kk = s / CC, cc = s - kk * CC;
             const int dy = kk / a.kw, dx = kk - dy * a.kw;
-            toff[s] = dy * R + dx * S + cc * 64;
+            toff[s] = dy * dlh * R + dx * dlw * S + cc * 64;
         }
     }
     auto columns = [&](auto u24) {
@@ -737,7 +746,7 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a, Act x, Act y, int
                             for (int g = 0; g < NG; ++g)
                                 av1[g] = fw + 16 * g < a.F ? *reinterpret_cast<const v2l*>(Wr[g] + (dy * a.kw + dx) * a.Cpad + cc * 64)
                                                            : v2l{0, 0};
-                            const int offs = dy * R + dx * S + cc * 64;
+                            const int offs = dy * dlh * R + dx * dlw * S + cc * 64;
     #pragma unroll
                             for (int t = 0; t < NT; ++t) {
                                 const v2l bv = *reinterpret_cast<const v2l*>(img + base[t] + offs);
@@ -1082,26 +1091,48 @@ __device__ __forceinline__ void grp_row(const uint8_t* I, const uint32_t* w, int
         }
     }
 }
-// one lane's 4 outputs: all channels and rows of the filter's group
-template <int KH, int KW, int SW>
-__device__ __forceinline__ void grp_item(const uint8_t* I, const uint32_t* w, int Cg, int kh, int kw, int sw, int chs,
-                                         int R, uint32_t (&acc)[4]) {
+// the same for a dilated layer: one tap per weight dword (the weight in byte 0, so the dot4 is one product), the
+// window of output t at byte t*sw + dx*dw of the row: the dword that holds it, shifted down (I is dword aligned)
+template <int KW, int SW>
+__device__ __forceinline__ void grp_row_dil(const uint8_t* I, const uint32_t* w, int kw, int sw, int dw,
+                                            uint32_t (&acc)[4]) {
+    const int kww = KW ? KW : kw, sww = SW ? SW : sw;
+#pragma unroll
+    for (int dx = 0; dx < kww; ++dx) {
+        const uint32_t wd = w[dx];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int o = t * sww + dx * dw;
+            const uint32_t d = *reinterpret_cast<const uint32_t*>(I + (o & ~3));
+            acc[t] = __builtin_amdgcn_udot4(d >> (8 * (o & 3)), wd, acc[t], false);
+        }
+    }
+}
+// one lane's 4 outputs: all channels and rows of the filter's group. DL: dilated (rows step by dh R, grp_row_dil)
+template <int KH, int KW, int SW, bool DL>
+__device__ __forceinline__ void grp_item(const uint8_t* I, const uint32_t* w, int Cg, int kh, int kw, int sw, int dh,
+                                         int dw, int chs, int R, uint32_t (&acc)[4]) {
     const int khh = KH ? KH : kh;
-    const int kwd = ((KW ? KW : kw) + 3) >> 2;
+    const int kwd = DL ? (KW ? KW : kw) : ((KW ? KW : kw) + 3) >> 2;
     for (int c = 0; c < Cg; ++c) {
 #pragma unroll
-        for (int dy = 0; dy < khh; ++dy) grp_row<KW, SW>(I + dy * R, w + dy * kwd, kw, sw, acc);
+        for (int dy = 0; dy < khh; ++dy) {
+            if constexpr (DL) grp_row_dil<KW, SW>(I + dy * dh * R, w + dy * kwd, kw, sw, dw, acc);
+            else grp_row<KW, SW>(I + dy * R, w + dy * kwd, kw, sw, acc);
+        }
         I += chs;
         w += khh * kwd;
     }
 }
 
-// KH, KW, SW: compile-time taps and column stride; 0, 0, 0: the runtime-tap instance
-template <int KH, int KW, int SW>
+// KH, KW, SW: compile-time taps and column stride; 0, 0, 0: the runtime-tap instance. DL: the dilated forms
+// (separate instantiations; without DL the dilations are the constant 1)
+template <int KH, int KW, int SW, bool DL = false>
 __global__ __launch_bounds__(256) void k_conv_grp(ConvArgs a, Act x, Act y) {
     extern __shared__ __attribute__((aligned(16))) uint8_t gimg[];
     const int kh = KH ? KH : a.kh, kw = KW ? KW : a.kw, sw = SW ? SW : a.sw;
-    const int kwd = (kw + 3) >> 2;
+    const int dh = DL ? a.dh : 1, dw = DL ? a.dw : 1;
+    const int kwd = DL ? kw : (kw + 3) >> 2;
     unsigned bid = blockIdx.x;
     const int band = static_cast<int>(bid % static_cast<unsigned>(a.gnbands));
     bid /= static_cast<unsigned>(a.gnbands);
@@ -1116,7 +1147,7 @@ __global__ __launch_bounds__(256) void k_conv_grp(ConvArgs a, Act x, Act y) {
     const int q0 = gb * a.gpb, nq = min(a.gpb, a.groups - q0);
     const int ch0 = q0 * Cg, nch = nq * Cg, f0 = q0 * Fg, nf = nq * Fg;
     const int oy0 = band * a.gband, nrows = min(a.OH, oy0 + a.gband) - oy0;
-    const int iy0 = oy0 * a.sh - a.ph, in_rows = (nrows - 1) * a.sh + kh;
+    const int iy0 = oy0 * a.sh - a.ph, in_rows = conv_band_in_rows(nrows, a.sh, kh, dh);
     const int R = a.gR, R16 = R >> 4, chs = in_rows * R;
     const int CHW = a.C * a.H * a.W;
     const act_t* X = x.p[j] + (static_cast<int64_t>(b) * n + c) * CHW;
@@ -1164,7 +1195,8 @@ __global__ __launch_bounds__(256) void k_conv_grp(ConvArgs a, Act x, Act y) {
     // the block's weight dwords and, per filter, the epilogue constant zc[f] * Z + bias, behind the image
     const int npp = a.gnpp;
     const int wper = Cg * kh * kwd;  // weight dwords per filter
-    uint32_t* wl = reinterpret_cast<uint32_t*>(gimg + static_cast<size_t>(nch) * ((a.gband - 1) * a.sh + kh) * R);
+    uint32_t* wl =
+        reinterpret_cast<uint32_t*>(gimg + static_cast<size_t>(nch) * conv_band_in_rows(a.gband, a.sh, kh, dh) * R);
     uint32_t* kl = wl + nf * wper;
     {
         const uint32_t* wsrc = a.wg[j] + static_cast<int64_t>(f0) * wper;
@@ -1193,7 +1225,7 @@ __global__ __launch_bounds__(256) void k_conv_grp(ConvArgs a, Act x, Act y) {
         const int ox4 = pos - oyl * OWq;
         uint32_t acc[4] = {0u, 0u, 0u, 0u};
         const uint8_t* I = gimg + static_cast<size_t>((fl / Fg) * Cg) * chs + oyl * a.sh * R + ox4 * 4 * sw;
-        grp_item<KH, KW, SW>(I, wl + fl * wper, Cg, kh, kw, sw, chs, R, acc);
+        grp_item<KH, KW, SW, DL>(I, wl + fl * wper, Cg, kh, kw, sw, dh, dw, chs, R, acc);
         if (!live) continue;
         const int f = f0 + fl;
         const uint32_t k0 = kl[fl];
@@ -1217,7 +1249,16 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
         const size_t lds = conv_grp_lds(a, a.gpb, a.gband);
         dim3 g(static_cast<unsigned>(a.img_off[a.crt.k] * a.gngb * a.gnbands), 1, 1);
         const char* form;
-        if (a.kh == 3 && a.kw == 3 && a.sw == 1) {
+        if (conv_dilated(a) && a.kh == 3 && a.kw == 3 && a.sw == 1) {
+            form = "conv.grpd<3,3,1>";
+            hipLaunchKernelGGL((k_conv_grp<3, 3, 1, true>), g, dim3(256), lds, st, a, x, y);
+        } else if (conv_dilated(a) && a.kh == 3 && a.kw == 3 && a.sw == 2) {
+            form = "conv.grpd<3,3,2>";
+            hipLaunchKernelGGL((k_conv_grp<3, 3, 2, true>), g, dim3(256), lds, st, a, x, y);
+        } else if (conv_dilated(a)) {
+            form = "conv.grpd<0,0,0>";
+            hipLaunchKernelGGL((k_conv_grp<0, 0, 0, true>), g, dim3(256), lds, st, a, x, y);
+        } else if (a.kh == 3 && a.kw == 3 && a.sw == 1) {
             form = "conv.grp<3,3,1>";
             hipLaunchKernelGGL((k_conv_grp<3, 3, 1>), g, dim3(256), lds, st, a, x, y);
         } else if (a.kh == 3 && a.kw == 3 && a.sw == 2) {
@@ -1235,8 +1276,9 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
     }
     if (a.use_mfma && a.nbands > 0) {
         const int64_t nimg = a.img_off[a.crt.k];
-        const int in_rows = (min(a.band, a.OH) - 1) * a.sh + a.kh;
+        const int in_rows = conv_band_in_rows(min(a.band, a.OH), a.sh, a.kh, a.dh);
         const size_t lds = static_cast<size_t>(in_rows) * a.ldsR;
+        const bool dil = conv_dilated(a);
         dim3 g(static_cast<unsigned>(nimg * a.nbands), static_cast<unsigned>((a.F + 63) / 64), 1);
         static const int ver = [] {
             const char* e = std::getenv("DASH_CONV_IMG_VER");
@@ -1259,6 +1301,21 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
         } else if (a.tsc) {
             form = "convt.img2<0,0>";
             hipLaunchKernelGGL((k_conv_img2<0, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (dil && a.ur && KS == 1) {
+            form = "conv.img2d<1,1>";
+            hipLaunchKernelGGL((k_conv_img2<1, true, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (dil && a.ur) {
+            form = "conv.img2d<0,1>";
+            hipLaunchKernelGGL((k_conv_img2<0, true, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (dil && KS == 9) {
+            form = "conv.img2d<9,0>";
+            hipLaunchKernelGGL((k_conv_img2<9, false, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (dil && KS == 4) {
+            form = "conv.img2d<4,0>";
+            hipLaunchKernelGGL((k_conv_img2<4, false, false, true>), g, dim3(256), lds, st, a, x, y, B);
+        } else if (dil) {
+            form = "conv.img2d<0,0>";
+            hipLaunchKernelGGL((k_conv_img2<0, false, false, true>), g, dim3(256), lds, st, a, x, y, B);
         } else if (ver == 1 && a.ldsS == a.Cpad + 16 && a.ldsR == (a.W + 2 * a.pw) * a.ldsS) {
             form = "conv.img";
             hipLaunchKernelGGL(k_conv_img, g, dim3(256), lds, st, a, x, y, B);  // A/B: its fixed layout only
@@ -1290,8 +1347,11 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
             if (!a.w8[j]) continue;
             const int64_t ncols = static_cast<int64_t>(B) * a.crt.n[j] * a.OH * a.OW;
             dim3 g(static_cast<unsigned>((ncols + 63) / 64), static_cast<unsigned>((a.F + 63) / 64), 1);
-            if (launch_log_on()) launch_log_add(a.tsc ? "convt.im2col" : "conv.im2col", g, dim3(256));
+            const bool dil = conv_dilated(a);  // (a transposed layer's view is never dilated)
+            if (launch_log_on())
+                launch_log_add(a.tsc ? "convt.im2col" : (dil ? "conv.im2cold" : "conv.im2col"), g, dim3(256));
             if (a.tsc) hipLaunchKernelGGL(k_conv_mfma<true>, g, dim3(256), 0, st, a, x, y, j, ncols);
+            else if (dil) hipLaunchKernelGGL((k_conv_mfma<false, true>), g, dim3(256), 0, st, a, x, y, j, ncols);
             else hipLaunchKernelGGL(k_conv_mfma<false>, g, dim3(256), 0, st, a, x, y, j, ncols);
         }
         // residues without an int8 image (p > 255) fall through to VALU below
@@ -1301,8 +1361,10 @@ void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream
     }
     const ZTab& z = ztab_for(a.crt);
     dim3 g(static_cast<unsigned>((a.OH * a.OW + 255) / 256), static_cast<unsigned>(a.F), static_cast<unsigned>(B * z.sumn));
-    if (launch_log_on()) launch_log_add(a.tsc ? "convt.valu" : "conv.valu", g, dim3(256));
+    const bool dilv = conv_dilated(a);
+    if (launch_log_on()) launch_log_add(a.tsc ? "convt.valu" : (dilv ? "conv.valud" : "conv.valu"), g, dim3(256));
     if (a.tsc) hipLaunchKernelGGL(k_conv_valu<true>, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
+    else if (dilv) hipLaunchKernelGGL((k_conv_valu<false, true>), g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
     else hipLaunchKernelGGL(k_conv_valu<false>, g, dim3(256), 0, st, a, x, y, z.dj, z.dc, z.sumn);
 }
 

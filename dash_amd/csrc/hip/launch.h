@@ -144,6 +144,9 @@ void prepare_zmap(const CrtInfo& crt);
 struct ConvArgs {
     CrtInfo crt;
     int C, H, W, F, kh, kw, sh, sw, ph, pw, OH, OW;
+    // dilation: tap (dy, dx) reads input (oy sh - ph + dy dh, ox sw - pw + dx dw). Honoured by the dilated kernel
+    // forms only (launch_conv picks them by conv_dilated); the plain forms compile with dh = dw = 1
+    int dh = 1, dw = 1;
     const int16_t* w[kMaxRes];     // [F][C*kh*kw] weights mod p_j
     const int8_t* w8[kMaxRes];     // [F][Kpad] centered int8 (MFMA path) or null
     int Kpad;
@@ -167,10 +170,11 @@ struct ConvArgs {
     // bytes as its channels, the MFMA phase then runs a 1x1 conv (one k-step instead of kh*kw for C << 64).
     // u* hold the layer's own geometry for the staging; the fields above describe the unrolled view.
     int ur = 0;
-    int uC = 0, uH = 0, uW = 0, ukh = 0, ukw = 0, ush = 0, usw = 0, uph = 0, upw = 0;
+    int uC = 0, uH = 0, uW = 0, ukh = 0, ukw = 0, ush = 0, usw = 0, uph = 0, upw = 0, udh = 1, udw = 1;
     // grouped conv (k_conv_grp, groups > 1; 0 and 1 are the dense paths above): group q holds filters
     // [q F/g, (q+1) F/g) and reads channels [q C/g, (q+1) C/g). wg: weights mod p_j as unsigned bytes (not
-    // centered), [F][C/g][kh][ceil(kw/4)] dwords of 4 dx taps each, zero filled. Block geometry from
+    // centered), [F][C/g][kh][ceil(kw/4)] dwords of 4 dx taps each, zero filled (dilated: [F][C/g][kh][kw] dwords
+    // of one tap each in byte 0, conv_grp_kwd). Block geometry from
     // conv_grp_geometry: gpb groups and gband output rows per block, gR bytes per LDS image row, gnpp padded
     // lane slots per filter.
     int groups = 0;
@@ -199,6 +203,7 @@ inline void convt_view_args(ConvArgs& a, int C, int H, int W, int F, int kh, int
     a.F = F * sh * sw;
     a.kh = Th; a.kw = Tw;
     a.sh = a.sw = 1;
+    a.dh = a.dw = 1;
     a.ph = Th - 1; a.pw = Tw - 1;
     a.OH = H + Th - 1; a.OW = W + Tw - 1;
     a.groups = 0;
@@ -207,6 +212,16 @@ inline void convt_view_args(ConvArgs& a, int C, int H, int W, int F, int kh, int
     a.tF = F; a.tOH = OH; a.tOW = OW;
 }
 void launch_conv(const ConvArgs& a, const Act& x, const Act& y, int B, hipStream_t st);
+
+// Input rows a band of `rows` output rows reads: from the first row's first tap to the last row's last tap. The ONE
+// definition of the staged band height: the band-fits-budget loops (conv_img_geometry, conv_grp_lds), the dynamic
+// LDS size (launch_conv) and the kernels' staging and tap loops all call it, so the image a kernel addresses is
+// the image that was allocated.
+__host__ __device__ inline int conv_band_in_rows(int rows, int sh, int kh, int dh) {
+    return (rows - 1) * sh + (kh - 1) * dh + 1;
+}
+// Whether the layer runs a dilated kernel form (the tap-unrolled view carries the layer's own dilation in u*)
+inline bool conv_dilated(const ConvArgs& a) { return a.ur ? (a.udh > 1 || a.udw > 1) : (a.dh > 1 || a.dw > 1); }
 
 // k_conv_img geometry: 64-channel chunks (Cpad), the LDS image's position
 // stride S and row stride R, and the tallest band of output rows whose input
@@ -234,7 +249,7 @@ inline int conv_lds_read_cycles(const ConvArgs& a, int S, int R) {
                     for (int i = 0; i < 16; ++i) {
                         const int l = G[g][i];
                         const int col = t * 16 + (l & 15), oy = col / a.OW, ox = col % a.OW;
-                        const int base = ((oy * a.sh + dy) * R + (ox * a.sw + dx) * S + (l >> 4) * 16) / 4;
+                        const int base = ((oy * a.sh + dy * a.dh) * R + (ox * a.sw + dx * a.dw) * S + (l >> 4) * 16) / 4;
                         for (int d = 0; d < 4; ++d) {
                             const int dw = base + d, bk = dw & 63;
                             bool dup = false;
@@ -281,7 +296,7 @@ inline void conv_img_geometry(ConvArgs& a) {
     // the pick depends on the layer shape only: computed once per shape and process (garbling calls this per GC)
     static std::mutex mu;
     static std::map<std::vector<int>, ConvGeomPick> memo;
-    const std::vector<int> key{a.C, a.W, a.pw, a.OH, a.OW, a.kh, a.kw, a.sh, a.sw};
+    const std::vector<int> key{a.C, a.W, a.pw, a.OH, a.OW, a.kh, a.kw, a.sh, a.sw, a.dh, a.dw};
     {
         std::lock_guard<std::mutex> lk(mu);
         auto it = memo.find(key);
@@ -308,8 +323,8 @@ inline void conv_img_geometry(ConvArgs& a) {
         for (int rpad = 0; rpad < 256; rpad += 16) {
             const int R = Wp * S + rpad;
             int band = a.OH;
-            while (band > 1 && static_cast<int64_t>((band - 1) * a.sh + a.kh) * R > budget) --band;
-            const int64_t lds = static_cast<int64_t>((band - 1) * a.sh + a.kh) * R;
+            while (band > 1 && static_cast<int64_t>(conv_band_in_rows(band, a.sh, a.kh, a.dh)) * R > budget) --band;
+            const int64_t lds = static_cast<int64_t>(conv_band_in_rows(band, a.sh, a.kh, a.dh)) * R;
             if (lds > budget) continue;
             const long cyc = conv_lds_read_cycles(a, S, R);
             if (best_cyc < 0 || cyc < best_cyc || (cyc == best_cyc && lds < best_lds)) {
@@ -328,7 +343,8 @@ inline void conv_img_geometry(ConvArgs& a) {
 
 // Switch a layer to the tap-unrolled image when that cuts the MFMA k-steps (few input channels, e.g. the
 // RGB first layer: 3x3x3 = 27 patch bytes in one 64-wide k-step instead of 9 steps of 3 real channels each)
-// and every residue takes the int8 MFMA path. Unit column stride only (the staging's 8-column loads).
+// and every residue takes the int8 MFMA path. Unit column stride only (the staging's 8-column loads; a dilated
+// tap only shifts where the 8 columns start).
 // Call before conv_img_geometry; the caller lays out w8r with conv_w8r.
 inline void conv_unroll_taps(ConvArgs& a, int max_p) {
     const int K = a.C * a.kh * a.kw;
@@ -340,9 +356,9 @@ inline void conv_unroll_taps(ConvArgs& a, int max_p) {
     if (!ok || a.ur || a.sw != 1 || max_p > 255 || usteps >= steps || a.uW != 0) return;
     a.ur = 1;
     a.uC = a.C; a.uH = a.H; a.uW = a.W; a.ukh = a.kh; a.ukw = a.kw;
-    a.ush = a.sh; a.usw = a.sw; a.uph = a.ph; a.upw = a.pw;
+    a.ush = a.sh; a.usw = a.sw; a.uph = a.ph; a.upw = a.pw; a.udh = a.dh; a.udw = a.dw;
     a.C = K; a.H = a.OH; a.W = a.OW;
-    a.kh = a.kw = a.sh = a.sw = 1;
+    a.kh = a.kw = a.sh = a.sw = a.dh = a.dw = 1;
     a.ph = a.pw = 0;
 }
 
@@ -391,13 +407,18 @@ inline void conv_layer_plan(ConvArgs& a, bool img) {
 //     (several blocks per CU);
 //   * the band then shrinks until a single group's rows and weights fit 64 KiB.
 // gR covers the padded row and the furthest dword any lane reads, in 16-byte staging chunks.
+// Dilated layers (dh > 1 or dw > 1) hold one tap per weight dword (conv_grp_kwd = kw): the four adjacent dx taps
+// of a dot4 are not adjacent bytes there. A lane's furthest tap is then (kw - 1) dw bytes past its last window.
 // Returns the dynamic LDS bytes (rows, weights, constants), or 0 when even one group and one output row do not fit.
 constexpr int kGrpPasses = 8, kGrpMaxGroups = 32;
+// weight dwords per kernel row: 4 dx taps per dword, or one per dword when dilated
+inline int conv_grp_kwd(int kw, bool dilated) { return dilated ? kw : (kw + 3) / 4; }
 inline size_t conv_grp_lds(const ConvArgs& a, int gpb, int band) {
     const int Cg = a.C / a.groups, Fg = a.F / a.groups;
-    const size_t img = static_cast<size_t>(gpb) * Cg * ((band - 1) * a.sh + a.kh) * a.gR;
+    const size_t img = static_cast<size_t>(gpb) * Cg * conv_band_in_rows(band, a.sh, a.kh, a.dh) * a.gR;
     // the groups' weight dwords and one epilogue constant per filter
-    const size_t wl = static_cast<size_t>(gpb) * Fg * (static_cast<size_t>(Cg) * a.kh * ((a.kw + 3) / 4) + 1) * 4;
+    const size_t wl =
+        static_cast<size_t>(gpb) * Fg * (static_cast<size_t>(Cg) * a.kh * conv_grp_kwd(a.kw, conv_dilated(a)) + 1) * 4;
     return img + wl;
 }
 inline int conv_grp_npp(const ConvArgs& a, int band) {
@@ -411,7 +432,10 @@ inline size_t conv_grp_geometry(ConvArgs& a) {
     for (int j = 0; j < a.crt.k; ++j)
         a.mq[j] = static_cast<uint32_t>(0x100000000ull / static_cast<uint32_t>(a.crt.p[j]));
     const int OWq = (a.OW + 3) / 4, kwd = (a.kw + 3) / 4, Fg = a.F / a.groups;
-    const int ext = 4 * (OWq - 1) * a.sw + 3 * a.sw + 4 * kwd + 4;
+    // the last lane's last window starts at byte 4 (OWq - 1) sw + 3 sw; packed taps read the dwords covering
+    // 4 kwd more bytes, a dilated tap the dword that holds byte (kw - 1) dw past it
+    const int ext = conv_dilated(a) ? 4 * (OWq - 1) * a.sw + 3 * a.sw + (a.kw - 1) * a.dw + 4
+                                    : 4 * (OWq - 1) * a.sw + 3 * a.sw + 4 * kwd + 4;
     a.gR = (std::max(a.W + 2 * a.pw, ext) + 15) / 16 * 16;
     const size_t budget = 64 * 1024;
     int band = a.OH;
@@ -429,15 +453,18 @@ inline size_t conv_grp_geometry(ConvArgs& a) {
     const size_t lds = conv_grp_lds(a, gpb, band);
     return lds > budget ? 0 : lds;
 }
-// k_conv_grp weight image of residue p from the [F][C/g][kh][kw] weights (reduced, non-negative)
-inline std::vector<uint32_t> conv_grp_weights(const int64_t* w, int64_t F, int64_t Cg, int kh, int kw, int p) {
-    const int kwd = (kw + 3) / 4;
+// k_conv_grp weight image of residue p from the [F][C/g][kh][kw] weights (reduced, non-negative); dilated: one
+// tap per dword, in byte 0
+inline std::vector<uint32_t> conv_grp_weights(const int64_t* w, int64_t F, int64_t Cg, int kh, int kw, int p,
+                                              bool dilated = false) {
+    const int kwd = conv_grp_kwd(kw, dilated);
     std::vector<uint32_t> r(static_cast<size_t>(F * Cg) * kh * kwd, 0u);
     for (int64_t fc = 0; fc < F * Cg; ++fc)
         for (int dy = 0; dy < kh; ++dy)
             for (int dx = 0; dx < kw; ++dx) {
                 const uint32_t v = static_cast<uint32_t>(w[(fc * kh + dy) * kw + dx] % p);
-                r[(static_cast<size_t>(fc) * kh + dy) * kwd + dx / 4] |= v << (8 * (dx % 4));
+                if (dilated) r[(static_cast<size_t>(fc) * kh + dy) * kwd + dx] = v;
+                else r[(static_cast<size_t>(fc) * kh + dy) * kwd + dx / 4] |= v << (8 * (dx % 4));
             }
     return r;
 }

@@ -1200,6 +1200,7 @@ void HipEvaluator::plan_conv(Walk& w, size_t li, const GLayer& g, const std::str
     a.sh = static_cast<int>(G.sh); a.sw = static_cast<int>(G.sw);
     a.ph = static_cast<int>(G.ph); a.pw = static_cast<int>(G.pw);
     a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
+    a.dh = static_cast<int>(G.dh); a.dw = static_cast<int>(G.dw);
     const i64 K = G.K();
     a.use_mfma = mfma_ ? 1 : 0;
     a.groups = static_cast<int>(G.g);
@@ -1238,7 +1239,8 @@ void HipEvaluator::plan_conv(Walk& w, size_t li, const GLayer& g, const std::str
         a.w8[j] = (mfma_ && p <= 255 && !grp) ? upload(w8.data(), w8.size()) : nullptr;
         a.wg[j] = nullptr;
         if (grp) {
-            const std::vector<uint32_t> wg = conv_grp_weights(wt.ptr<i64>(), G.F, G.Cg(), a.kh, a.kw, p);
+            const std::vector<uint32_t> wg =
+                conv_grp_weights(wt.ptr<i64>(), G.F, G.Cg(), a.kh, a.kw, p, conv_dilated(a));
             a.wg[j] = upload(wg.data(), wg.size());
         }
         if (a.nbands > 0 && p <= 255) {
@@ -2239,10 +2241,16 @@ void register_hip_bindings(py::module_& m) {
     m.def("hip_launch_log_take", []() { return dev::launch_log_take(); });
     // The conv kernel plan of a dense-conv layer, exactly as the evaluator (mfma: its switch) and the GPU garbler
     // plan it (launch.h conv_layer_plan). Host arithmetic only: works without a device.
+    // dh, dw: dilation (a kernel axis of size 1 normalises its dilation to 1, as ConvGeom does). The result also
+    // names the dilation the kernel form is picked by (dil), the input rows of a full band (band_input_rows, the
+    // launch's dynamic LDS is that times ldsR) and the LDS bytes staged per image over all bands (staged_bytes).
     m.def("hip_conv_plan", [](int C, int H, int W, int F, int kh, int kw, int sh, int sw, int ph, int pw,
-                              const std::vector<int>& crt_moduli, bool mfma) {
+                              const std::vector<int>& crt_moduli, bool mfma, int dh, int dw) {
         DASH_CHECK(C > 0 && H > 0 && W > 0 && F > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0,
                    "hip_conv_plan: bad conv geometry");
+        DASH_CHECK(dh >= 1 && dw >= 1, "hip_conv_plan: dilation must be at least 1");
+        if (kh == 1) dh = 1;
+        if (kw == 1) dw = 1;
         DASH_CHECK(!crt_moduli.empty() && static_cast<int>(crt_moduli.size()) <= dev::kMaxRes,
                    "hip_conv_plan: 1 .. 16 CRT moduli");
         dev::ConvArgs a{};
@@ -2253,8 +2261,10 @@ void register_hip_bindings(py::module_& m) {
             a.crt.n[j] = nr_comps(crt_moduli[j]);
         }
         a.C = C; a.H = H; a.W = W; a.F = F; a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
-        a.OH = (H + 2 * ph - kh) / sh + 1;
-        a.OW = (W + 2 * pw - kw) / sw + 1;
+        a.dh = dh; a.dw = dw;
+        DASH_CHECK(H + 2 * ph >= (kh - 1) * dh + 1 && W + 2 * pw >= (kw - 1) * dw + 1, "hip_conv_plan: empty output");
+        a.OH = (H + 2 * ph - (kh - 1) * dh - 1) / sh + 1;
+        a.OW = (W + 2 * pw - (kw - 1) * dw - 1) / sw + 1;
         DASH_CHECK(a.OH > 0 && a.OW > 0, "hip_conv_plan: empty output");
         dev::conv_layer_plan(a, mfma && dev::conv_img_enabled());
         py::dict d;
@@ -2269,9 +2279,60 @@ void register_hip_bindings(py::module_& m) {
         d["OH"] = a.OH;
         d["OW"] = a.OW;
         d["sh24"] = std::vector<int>(a.sh24, a.sh24 + a.crt.k);
+        d["dil"] = dev::conv_dilated(a) ? 1 : 0;
+        d["band_input_rows"] = a.nbands > 0 ? dev::conv_band_in_rows(std::min(a.band, a.OH), a.sh, a.kh, a.dh) : 0;
+        int64_t staged = 0;
+        for (int b = 0; b < a.nbands; ++b)
+            staged += static_cast<int64_t>(dev::conv_band_in_rows(std::min(a.band, a.OH - b * a.band), a.sh, a.kh, a.dh)) *
+                      a.ldsR;
+        d["staged_bytes"] = staged;
         return d;
     }, py::arg("C"), py::arg("H"), py::arg("W"), py::arg("F"), py::arg("kh"), py::arg("kw"), py::arg("sh"),
-       py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("crt_moduli"), py::arg("mfma") = true);
+       py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("crt_moduli"), py::arg("mfma") = true, py::arg("dh") = 1,
+       py::arg("dw") = 1);
+    // The grouped conv's block geometry (launch.h conv_grp_geometry), as plan_conv and the GPU garbler plan it
+    m.def("hip_conv_grp_plan", [](int C, int H, int W, int F, int kh, int kw, int sh, int sw, int ph, int pw,
+                                  int groups, const std::vector<int>& crt_moduli, int dh, int dw) {
+        DASH_CHECK(C > 0 && H > 0 && W > 0 && F > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0,
+                   "hip_conv_grp_plan: bad conv geometry");
+        DASH_CHECK(groups > 1 && C % groups == 0 && F % groups == 0, "hip_conv_grp_plan: groups > 1 dividing C and F");
+        DASH_CHECK(dh >= 1 && dw >= 1, "hip_conv_grp_plan: dilation must be at least 1");
+        DASH_CHECK(!crt_moduli.empty() && static_cast<int>(crt_moduli.size()) <= dev::kMaxRes,
+                   "hip_conv_grp_plan: 1 .. 16 CRT moduli");
+        if (kh == 1) dh = 1;
+        if (kw == 1) dw = 1;
+        dev::ConvArgs a{};
+        a.crt.k = static_cast<int>(crt_moduli.size());
+        for (int j = 0; j < a.crt.k; ++j) {
+            DASH_CHECK(crt_moduli[j] >= 2, "hip_conv_grp_plan: modulus below 2");
+            a.crt.p[j] = crt_moduli[j];
+            a.crt.n[j] = nr_comps(crt_moduli[j]);
+        }
+        a.C = C; a.H = H; a.W = W; a.F = F; a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
+        a.dh = dh; a.dw = dw;
+        a.groups = groups;
+        DASH_CHECK(H + 2 * ph >= (kh - 1) * dh + 1 && W + 2 * pw >= (kw - 1) * dw + 1,
+                   "hip_conv_grp_plan: empty output");
+        a.OH = (H + 2 * ph - (kh - 1) * dh - 1) / sh + 1;
+        a.OW = (W + 2 * pw - (kw - 1) * dw - 1) / sw + 1;
+        const size_t lds = dev::conv_grp_geometry(a);
+        py::dict d;
+        d["dil"] = dev::conv_dilated(a) ? 1 : 0;
+        d["gpb"] = a.gpb;
+        d["gngb"] = a.gngb;
+        d["gband"] = a.gband;
+        d["gnbands"] = a.gnbands;
+        d["gR"] = a.gR;
+        d["gnpp"] = a.gnpp;
+        d["kwd"] = dev::conv_grp_kwd(a.kw, dev::conv_dilated(a));
+        d["band_input_rows"] = dev::conv_band_in_rows(a.gband, a.sh, a.kh, a.dh);
+        d["lds"] = static_cast<int64_t>(lds);
+        d["OH"] = a.OH;
+        d["OW"] = a.OW;
+        return d;
+    }, py::arg("C"), py::arg("H"), py::arg("W"), py::arg("F"), py::arg("kh"), py::arg("kw"), py::arg("sh"),
+       py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("groups"), py::arg("crt_moduli"), py::arg("dh") = 1,
+       py::arg("dw") = 1);
     // The same for a transposed conv: the plan of its sub-pixel view (layers.h ConvTGeom, launch.h
     // convt_view_args) and the scatter description, as plan_convt and the GPU garbler build them.
     m.def("hip_convt_plan", [](int C, int H, int W, int F, int kh, int kw, int sh, int sw, int ph, int pw, int oph,

@@ -7,8 +7,9 @@ namespace dash {
 
 struct ConvGeom {
     // g channel groups: group q holds filters [q*F/g, (q+1)*F/g) and reads
-    // channels [q*C/g, (q+1)*C/g); weights are [F][C/g][kh][kw]
-    i64 C, H, W, F, kh, kw, sh, sw, ph, pw, OH, OW, g;
+    // channels [q*C/g, (q+1)*C/g); weights are [F][C/g][kh][kw]. dh, dw: dilation (atrous conv), tap (dy, dx) of
+    // output (oy, ox) reads input (oy sh - ph + dy dh, ox sw - pw + dx dw); a kernel axis of size 1 has dilation 1
+    i64 C, H, W, F, kh, kw, sh, sw, ph, pw, OH, OW, g, dh, dw;
     explicit ConvGeom(const Params& p);
     explicit ConvGeom(const GLayer& g) : ConvGeom(g.p) {}
     i64 Cg() const { return C / g; }

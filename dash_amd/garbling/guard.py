@@ -67,9 +67,10 @@ class RangeGuard:
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Projection,
                                           L.BaseExtension, L.ConvTranspose2d, L.Upsample))
                            for l in circuit.layers)
-        # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no ConvTranspose2d, no Upsample and no padded
-        # / ceil-mode pooling: such circuits take the batched torch path
+        # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no ConvTranspose2d, no Upsample, no dilated
+        # conv and no padded / ceil-mode pooling: such circuits take the batched torch path
         self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.ConvTranspose2d, L.Upsample)) or
+                                    (isinstance(l, L.Conv2d) and (l.dh > 1 or l.dw > 1)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
         self._stream = None
@@ -186,7 +187,7 @@ class RangeGuard:
             if isinstance(l, L.Conv2d):
                 W, b = ws[i]
                 cols = F.unfold(inp.to(torch.float64).view(B, l.C, l.H, l.W), (l.kh, l.kw), padding=(l.ph, l.pw),
-                                stride=(l.sh, l.sw))
+                                stride=(l.sh, l.sw), dilation=(l.dh, l.dw))
                 if l.groups == 1:
                     y = torch.matmul(W, cols) + b[:, None]
                 else:  # grouped unfold: the group's filters against the group's own rows of cols

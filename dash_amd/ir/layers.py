@@ -193,14 +193,16 @@ class Dense(Layer):
                            "b": self.q_biases.reshape(-1), "channel_tf": self.channel_tf}
 
 
-def _im2col(x: np.ndarray, C, H, W, kh, kw, sh, sw, ph, pw):
+def _im2col(x: np.ndarray, C, H, W, kh, kw, sh, sw, ph, pw, dh=1, dw=1):
+    """Patch matrix [C*kh*kw][OH*OW]; tap (dy, dx) reads the padded image at (oy*sh + dy*dh, ox*sw + dx*dw)."""
     xp = np.pad(x.reshape(C, H, W), ((0, 0), (ph, ph), (pw, pw)))
-    OH = (H + 2 * ph - kh) // sh + 1
-    OW = (W + 2 * pw - kw) // sw + 1
+    OH = (H + 2 * ph - (kh - 1) * dh - 1) // sh + 1
+    OW = (W + 2 * pw - (kw - 1) * dw - 1) // sw + 1
     cols = np.empty((C, kh, kw, OH, OW), dtype=x.dtype)
     for dy in range(kh):
         for dx in range(kw):
-            cols[:, dy, dx] = xp[:, dy:dy + sh * (OH - 1) + 1:sh, dx:dx + sw * (OW - 1) + 1:sw]
+            y0, x0 = dy * dh, dx * dw
+            cols[:, dy, dx] = xp[:, y0:y0 + sh * (OH - 1) + 1:sh, x0:x0 + sw * (OW - 1) + 1:sw]
     return cols.reshape(C * kh * kw, OH * OW), OH, OW
 
 
@@ -209,6 +211,10 @@ class Conv2d(Layer):
     and channel groups (extensions over the reference's 'valid'-only dense
     conv, needed by VGG/ResNet and by depthwise-separable networks). Group q
     holds filters [q*F/g, (q+1)*F/g) and reads channels [q*C/g, (q+1)*C/g).
+    Dilation (atrous convolution, docs/DILATED_CONV.md): with the effective
+    kernel keh = (kh-1)*dh + 1, OH = (H + 2*ph - keh)//sh + 1 and tap (dy, dx)
+    of output (oy, ox) reads x[c][oy*sh - ph + dy*dh][ox*sw - pw + dx*dw]; a
+    kernel axis of size 1 makes its dilation moot and stores it as 1.
     Reference: circuit/layer/conv2d.h (index bug §2.7 #2 fixed)."""
 
     kind = Kind.CONV
@@ -217,7 +223,8 @@ class Conv2d(Layer):
     def __init__(self, weights: np.ndarray, biases: np.ndarray, input_width: int, input_height: int, channel: int,
                  filter: int, filter_width: int, filter_height: int, stride_width: int = 1, stride_height: int = 1,
                  q_parameter: int = -1, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
-                 q_const: float = 10.0, pad_width: int = 0, pad_height: int = 0, groups: int = 1):
+                 q_const: float = 10.0, pad_width: int = 0, pad_height: int = 0, groups: int = 1,
+                 dilation_width: int = 1, dilation_height: int = 1):
         self.C, self.H, self.W, self.F = int(channel), int(input_height), int(input_width), int(filter)
         self.groups = int(groups)
         if self.groups < 1 or self.C % self.groups or self.F % self.groups:
@@ -225,8 +232,20 @@ class Conv2d(Layer):
         self.Cg, self.Fg = self.C // self.groups, self.F // self.groups
         self.kh, self.kw, self.sh, self.sw = int(filter_height), int(filter_width), int(stride_height), int(stride_width)
         self.ph, self.pw = int(pad_height), int(pad_width)
-        self.OH = (self.H + 2 * self.ph - self.kh) // self.sh + 1
-        self.OW = (self.W + 2 * self.pw - self.kw) // self.sw + 1
+        self.dh, self.dw = int(dilation_height), int(dilation_width)
+        if self.dh < 1 or self.dw < 1 or self.dh != dilation_height or self.dw != dilation_width:
+            raise ValueError(f"conv2d: dilation must be an integer >= 1, got ({dilation_height}, {dilation_width})")
+        # a kernel axis of size 1 has no second tap to dilate: the layer is the plain conv and is stored as one
+        if self.kh == 1:
+            self.dh = 1
+        if self.kw == 1:
+            self.dw = 1
+        keh, kew = (self.kh - 1) * self.dh + 1, (self.kw - 1) * self.dw + 1
+        if self.H + 2 * self.ph < keh or self.W + 2 * self.pw < kew:
+            raise ValueError(f"conv2d: empty output: the effective kernel ({keh} x {kew}) exceeds the padded input "
+                             f"({self.H + 2 * self.ph} x {self.W + 2 * self.pw})")
+        self.OH = (self.H + 2 * self.ph - keh) // self.sh + 1
+        self.OW = (self.W + 2 * self.pw - kew) // self.sw + 1
         super().__init__((self.C, self.H, self.W), (self.F, self.OH, self.OW))
         w = np.asarray(weights, dtype=np.float32).reshape(self.F, self.Cg, self.kh, self.kw)
         b = np.asarray(biases, dtype=np.float32).reshape(self.F)
@@ -237,13 +256,15 @@ class Conv2d(Layer):
 
     @classmethod
     def from_quantized(cls, q_weights, q_biases, input_width, input_height, channel, filter, filter_width,
-                       filter_height, stride_width=1, stride_height=1, pad_width=0, pad_height=0, groups=1):
+                       filter_height, stride_width=1, stride_height=1, pad_width=0, pad_height=0, groups=1,
+                       dilation_width=1, dilation_height=1):
         if groups < 1 or channel % groups or filter % groups:
             raise ValueError(f"groups={groups} must be positive and divide channel={channel} and filter={filter}")
         c = cls(np.zeros((filter, channel // groups, filter_height, filter_width), np.float32),
                 np.zeros(filter, np.float32),
                 input_width, input_height, channel, filter, filter_width, filter_height, stride_width, stride_height,
-                q_const=1.0, pad_width=pad_width, pad_height=pad_height, groups=groups)
+                q_const=1.0, pad_width=pad_width, pad_height=pad_height, groups=groups,
+                dilation_width=dilation_width, dilation_height=dilation_height)
         c.q_weights = np.asarray(q_weights, dtype=np.int64).reshape(filter, channel // groups, filter_height,
                                                                     filter_width)
         c.q_biases = np.asarray(q_biases, dtype=np.int64).reshape(filter)
@@ -263,7 +284,8 @@ class Conv2d(Layer):
         return self.q_const
 
     def _conv(self, x, w, b):
-        cols, OH, OW = _im2col(x, self.C, self.H, self.W, self.kh, self.kw, self.sh, self.sw, self.ph, self.pw)
+        cols, OH, OW = _im2col(x, self.C, self.H, self.W, self.kh, self.kw, self.sh, self.sw, self.ph, self.pw,
+                               self.dh, self.dw)
         if self.groups == 1:
             y = w.reshape(self.F, -1) @ cols + b[:, None]
             return y.reshape(-1), cols
@@ -306,6 +328,11 @@ class Conv2d(Layer):
                 "w": self.q_weights.reshape(-1), "b": self.q_biases.reshape(-1)}
         if self.groups > 1:  # groups == 1 keeps the dense wire bytes
             spec["g"] = self.groups
+        # written only when > 1: an undilated layer keeps its wire bytes
+        if self.dh > 1:
+            spec["dh"] = self.dh
+        if self.dw > 1:
+            spec["dw"] = self.dw
         return self.kind, spec
 
 

@@ -11,7 +11,10 @@ factor), q_const = 0.02 for SimpleQuant. Differences (deliberate):
 * attributes are looked up by name and initializers by the node's input
   names, not by position (the reference's positional access, :280-295, is
   exporter-specific);
-* Conv `pads` (symmetric) are honoured, Gemm `transB`/`alpha`/`beta`,
+* Conv `pads` (symmetric) and `dilations` are honoured, and Conv `auto_pad`
+  is resolved from the effective kernel (`VALID`: no pads; `SAME_UPPER` /
+  `SAME_LOWER`: accepted when the pads come out symmetric, refused with the
+  node's name otherwise); Gemm `transB`/`alpha`/`beta`,
   MatMul+Add, BatchNormalization folding into the preceding Conv/Gemm,
   residual Add of two activations, Identity/Dropout are accepted;
 * the import follows the graph: every node's data input is resolved through
@@ -249,18 +252,36 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             C = Cg * group  # weights are [F][C/group][kh][kw]
             if group < 1 or F % group or (len(dims) == 3 and dims[0] % group):
                 raise ValueError(f"onnx: conv group {group} must divide the input channels and the {F} filters")
-            assert all(int(v) == 1 for v in a.get("dilations", [1, 1])), "onnx: dilated convolutions are not supported"
+            name = node.get("name") or op
+            dil = [int(v) for v in a.get("dilations", [1, 1])]
+            if len(dil) != 2 or min(dil) < 1:
+                raise ValueError(f"onnx: {name}: dilations {dil} must be two integers >= 1")
             st = [int(v) for v in a.get("strides", [1, 1])]
-            pads = [int(v) for v in a.get("pads", [0, 0, 0, 0])]
-            assert pads[0] == pads[2] and pads[1] == pads[3], "onnx: only symmetric padding is supported"
-            bias = arr(ins[2]).reshape(-1) if len(ins) > 2 and ins[2] else np.zeros(F, np.float32)
             assert len(dims) == 3 and dims[0] == C, f"onnx: conv expects {C} input channels, got dims {dims}"
+            ke = [(kh - 1) * dil[0] + 1, (kw - 1) * dil[1] + 1]  # effective kernel
+            auto = _sattr(a, "auto_pad", "NOTSET")
+            if auto == "NOTSET":
+                pads = [int(v) for v in a.get("pads", [0, 0, 0, 0])]
+                assert pads[0] == pads[2] and pads[1] == pads[3], "onnx: only symmetric padding is supported"
+            elif auto == "VALID":
+                pads = [0, 0, 0, 0]
+            elif auto in ("SAME_UPPER", "SAME_LOWER"):
+                # output ceil(n / s); the total padding that needs is split in halves, the odd one at the end
+                # (SAME_UPPER) or at the beginning (SAME_LOWER)
+                tot = [max((-(-dims[1 + ax] // st[ax]) - 1) * st[ax] + ke[ax] - dims[1 + ax], 0) for ax in (0, 1)]
+                if tot[0] % 2 or tot[1] % 2:
+                    raise NotImplementedError(f"onnx: {name}: auto_pad {auto} gives asymmetric pads (total {tot} "
+                                              f"over height, width); only symmetric padding is supported")
+                pads = [tot[0] // 2, tot[1] // 2, tot[0] // 2, tot[1] // 2]
+            else:
+                raise NotImplementedError(f"onnx: {name}: auto_pad {auto} is not supported")
+            bias = arr(ins[2]).reshape(-1) if len(ins) > 2 and ins[2] else np.zeros(F, np.float32)
             if fac != 1.0:
                 w = (w * np.float32(fac)).astype(np.float32)
-            H = (dims[1] + 2 * pads[0] - kh) // st[0] + 1
-            W = (dims[2] + 2 * pads[1] - kw) // st[1] + 1
-            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group), outs[0], j,
-                 (F, H, W))
+            H = (dims[1] + 2 * pads[0] - ke[0]) // st[0] + 1
+            W = (dims[2] + 2 * pads[1] - ke[1]) // st[1] + 1
+            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group, dil=dil),
+                 outs[0], j, (F, H, W))
             last_conv_filters = F
         elif op == "ConvTranspose":
             j, dims, fac = data_in(node, ins[0])
@@ -498,7 +519,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             F, _, kh, kw_ = kw["w"].shape
             layers.append(Conv2d(kw["w"], kw["b"], W, H, C, F, kw_, kh, kw["stride"][1], kw["stride"][0],
                                  q_parameter, q_method, q_const, pad_width=kw["pads"][1], pad_height=kw["pads"][0],
-                                 groups=kw["group"]))
+                                 groups=kw["group"], dilation_width=kw["dil"][1], dilation_height=kw["dil"][0]))
         elif s.kind == "convt":
             C, H, W = kw["dims"]
             _, F, kh, kw_ = kw["w"].shape
@@ -649,7 +670,7 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
                                _attr_float("alpha", 1.0) + _attr_float("beta", 1.0) + _attr_int("transB", 1)))
         elif isinstance(l, Conv2d):
             inits += [_tensor(f"{name}.weight", l.weights * np.float32(K)), _tensor(f"{name}.bias", l.biases)]
-            attrs = (_attr_ints("dilations", [1, 1]) + _attr_int("group", l.groups) + _attr_ints("kernel_shape", [l.kh, l.kw])
+            attrs = (_attr_ints("dilations", [l.dh, l.dw]) + _attr_int("group", l.groups) + _attr_ints("kernel_shape", [l.kh, l.kw])
                      + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + _attr_ints("strides", [l.sh, l.sw]))
             nodes.append(_node("Conv", [cur, f"{name}.weight", f"{name}.bias"], [out], name, attrs))
         elif isinstance(l, ConvTranspose2d):

@@ -62,7 +62,7 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             return nn.functional.conv_transpose2d(fq(x), fq(self.weight), fq(self.bias), self.stride, self.padding,
                                                   self.output_padding)
 
-    class FQConv(nn.Conv2d):  # nn.Conv2d's own `groups` keyword (depthwise: groups = in channels)
+    class FQConv(nn.Conv2d):  # nn.Conv2d's own `groups` and `dilation` keywords (depthwise: groups = in channels)
         def forward(self, x):
             return self._conv_forward(fq(x), fq(self.weight), fq(self.bias))
 
@@ -75,13 +75,17 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             mods.append(FQLinear(int(np.prod(dims)), op[1]))
             dims = [op[1]]
         elif k == "conv":
-            _, cout, ks, s, p = op
-            mods.append(FQConv(dims[0], cout, ks, stride=s, padding=p))
-            dims = [cout, (dims[1] + 2 * p - ks) // s + 1, (dims[2] + 2 * p - ks) // s + 1]
+            _, cout, ks, s, p = op[:5]
+            d = op[5] if len(op) > 5 else 1  # optional dilation
+            ke = (ks - 1) * d + 1
+            mods.append(FQConv(dims[0], cout, ks, stride=s, padding=p, dilation=d))
+            dims = [cout, (dims[1] + 2 * p - ke) // s + 1, (dims[2] + 2 * p - ke) // s + 1]
         elif k == "dwconv":
-            _, ks, s, p = op
-            mods.append(FQConv(dims[0], dims[0], ks, stride=s, padding=p, groups=dims[0]))
-            dims = [dims[0], (dims[1] + 2 * p - ks) // s + 1, (dims[2] + 2 * p - ks) // s + 1]
+            _, ks, s, p = op[:4]
+            d = op[4] if len(op) > 4 else 1
+            ke = (ks - 1) * d + 1
+            mods.append(FQConv(dims[0], dims[0], ks, stride=s, padding=p, groups=dims[0], dilation=d))
+            dims = [dims[0], (dims[1] + 2 * p - ke) // s + 1, (dims[2] + 2 * p - ke) // s + 1]
         elif k == "convt":
             _, cout, ks, s, p, opad = op
             mods.append(FQConvT(dims[0], cout, ks, stride=s, padding=p, output_padding=opad))
@@ -112,7 +116,7 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             raise NotImplementedError(f"training: {name} ends in an argmax, which has no gradient; train the model "
                                       "without the op (MODEL_A for MODEL_A_ARGMAX) and append ArgMax to its circuit")
         else:
-            raise NotImplementedError(f"training: op {k} (residual blocks, fire modules, global pooling) not supported "
+            raise NotImplementedError(f"training: op {k} (residual blocks, fire / aspp modules, global pooling) not supported "
                                       "by the sequential trainer")
     seq = nn.Sequential(*mods)
     seq.fq = fq  # set seq.fq.c = 0 to evaluate the float network
@@ -149,7 +153,7 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
             F, Cg, kh, kw = w.shape  # [F][C/groups][kh][kw]
             c = Conv2d(w, m.bias.detach().cpu().numpy(), dims[2], dims[1], Cg * m.groups, F, kw, kh, m.stride[1],
                        m.stride[0], q_parameter, qm, q_const, pad_width=m.padding[1], pad_height=m.padding[0],
-                       groups=m.groups)
+                       groups=m.groups, dilation_width=m.dilation[1], dilation_height=m.dilation[0])
             layers.append(c)
             dims = c.out_dims
             rescale(dims)

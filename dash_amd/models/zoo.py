@@ -28,6 +28,10 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   the per-pixel class of a (C, H, W) score map); scale-free
 #                   | ("convt", out_ch, k, stride, pad, out_pad) transposed conv (+ the scheme's rescale, as conv)
 #                   | ("up", f) nearest-neighbour upsampling by f
+#                   | ("conv", out_ch, k, stride, pad, dilation) and ("dwconv", k, stride, pad, dilation): the
+#                   optional last element dilates the kernel (atrous conv)
+#                   | ("aspp", out_ch, rates) atrous spatial pyramid: one padded 3x3 conv per rate with
+#                   pad = dilation = rate (same size out), each + ReLU, all reading the same tensor, then Concat
 #                   | ("skip",) remember the current tensor | ("cat",) channel concat of the most recent open skip
 #                   with the current tensor, skip first (an encoder-decoder's skip connection)
 ARCHS: dict[str, dict] = {
@@ -103,6 +107,14 @@ ARCHS: dict[str, dict] = {
         ("up", 2), ("cat",),
         ("conv", 8, 3, 1, 1), ("relu",),
         ("conv", 4, 1, 1, 0), ("argmax",)]},
+    # atrous segmentation head: a stride-2 stem (32 -> 16), one 3x3, an ASPP of rates 1, 2, 4 (3 x 16 channels), a
+    # 1x1 fuse, the 4-class 1x1 scores, the per-pixel class and its upsampling back to the (1, 32, 32) input grid
+    "ASPP_SEG_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 2, 1), ("relu",),
+        ("conv", 16, 3, 1, 1), ("relu",),
+        ("aspp", 16, (1, 2, 4)),
+        ("conv", 16, 1, 1, 0), ("relu",),
+        ("conv", 4, 1, 1, 0), ("argmax",), ("up", 2)]},
 }
 
 ALIASES = {"MINIONN": "MODEL_F_MINIONN_POOL_REPL", "GNNP": "MODEL_F_GNNP_POOL_REPL", "MLP": "MODEL_A",
@@ -145,12 +157,12 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         elif qm == QuantizationMethod.ScaleQuantPlus:
             layers.append(Rescale([q_parameter], d))
 
-    def conv(cout, k, s, p, cin, h, w, groups=1):
+    def conv(cout, k, s, p, cin, h, w, groups=1, dil=1):
         fan_in = cin // groups * k * k
         wt = _init(rng, (cout, cin // groups, k, k), fan_in)
         bs = _init(rng, (cout,), fan_in)
         c = Conv2d(wt, bs, w, h, cin, cout, k, k, s, s, q_parameter, qm, q_const, pad_width=p, pad_height=p,
-                   groups=groups)
+                   groups=groups, dilation_width=dil, dilation_height=dil)
         layers.append(c)
         rescale_after(c.out_dims)
         return c.out_dims
@@ -193,11 +205,27 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             dims = d.out_dims
             rescale_after(dims)
         elif kind == "conv":
-            _, cout, k, s, p = op
-            dims = conv(cout, k, s, p, dims[0], dims[1], dims[2])
+            _, cout, k, s, p = op[:5]
+            dims = conv(cout, k, s, p, dims[0], dims[1], dims[2], dil=op[5] if len(op) > 5 else 1)
         elif kind == "dwconv":
-            _, k, s, p = op
-            dims = conv(dims[0], k, s, p, dims[0], dims[1], dims[2], groups=dims[0])
+            _, k, s, p = op[:4]
+            dims = conv(dims[0], k, s, p, dims[0], dims[1], dims[2], groups=dims[0], dil=op[4] if len(op) > 4 else 1)
+        elif kind == "aspp":
+            _, cout, rates = op
+            src = len(layers) - 1  # every branch reads the tensor the module was given
+            cin, h, w = dims
+            ends, bdims = [], []
+            for bi, rate in enumerate(rates):
+                first = len(layers)
+                d_b = conv(cout, 3, 1, rate, cin, h, w, dil=rate)
+                if bi:  # the first branch reads the previous layer anyway
+                    layers[first].in_src = src
+                layers.append(Relu(d_b))
+                ends.append(len(layers) - 1)
+                bdims.append(d_b)
+            cat = Concat(bdims, ends)
+            layers.append(cat)
+            dims = cat.out_dims
         elif kind == "relu":
             layers.append(Relu(dims))
         elif kind == "sign":
@@ -303,6 +331,8 @@ BENCH_CONFIGS = {
                                   crt=7, mrs=100.0),
     "UNET_CIFAR/DASH": dict(model="UNET_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5, crt=7,
                             mrs=100.0),
+    "ASPP_SEG_CIFAR/DASH": dict(model="ASPP_SEG_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5, crt=7,
+                                mrs=100.0),
     "MODEL_A_ARGMAX/SIMPLE": dict(model="MODEL_A_ARGMAX", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8,
                                   mrs=100.0),
     "MODEL_A/SIMPLE": dict(model="MODEL_A", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8, mrs=100.0),
