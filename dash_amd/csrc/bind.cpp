@@ -225,6 +225,9 @@ PYBIND11_MODULE(_dash_native, m) {
         return out;
     });
 
+    // Mul (gadgets.h MulPlan): table entries per output element of a product / a square
+    m.def("mul_entries", [](const std::vector<int>& crt, bool square) { return MulPlan::entries(crt, square); });
+
     // Single gates of the native garbler with caller-chosen labels (wire-compatibility vectors: the tests
     // rebuild the reference's formulas in a pure-Python oracle and compare table bytes). Tables come back as
     // uint64 (entries, 2) = (lo, hi) of each 16-byte entry.

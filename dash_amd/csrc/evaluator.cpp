@@ -132,6 +132,7 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
     std::vector<int> keep(m.layers.size() + 1, 0);
     for (const auto& l : m.layers) {
         if (l.kind == K_ADD) keep[l.param("src") + 1] = 1;
+        if (l.kind == K_MUL && !l.param("sq", 0)) keep[l.param("src") + 1] = 1;
         if (l.kind == K_CONCAT)
             for (i64 s : l.vec("srcs")) {
                 DASH_CHECK(s >= -1 && s < static_cast<i64>(m.layers.size()), "concat: bad source layer");
@@ -738,6 +739,35 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                             gen_mult_eval(cur[j].at(2 * e), cur[j].at(2 * e + 1), mod_info(crt[j]),
                                           ga.ptr<u128>() + e * sum_crt + prefix[j], ea.ptr<u128>() + e * sum_crt + prefix[j],
                                           nxt[j].at(e), hard, stream_id(L, 1, e), j);
+                }, nt);
+                cur = std::move(nxt);
+                break;
+            }
+            case K_MUL: {
+                // gadgets.h MulPlan
+                DASH_CHECK(hard, "mul: the Mul layer exists in the hardened encoding only");
+                const bool sq = g.param("sq", 0) != 0;
+                const MulPlan mp(crt, sq ? 0 : g.param("bc", 0), sq);
+                const CrtLabels& ys = sq ? cur : saved[g.param("src") + 1];
+                DASH_CHECK(!ys.empty() && (mp.bc == 0 || Nin % mp.bc == 0) && ys[0].N == mp.ny(Nin),
+                           "mul: operand size mismatch");
+                for (int j = 0; j < k; ++j) DASH_CHECK(cur[j].p == crt[j] && ys[j].p == crt[j], "mul: operands off the CRT base");
+                const u128* ga = g.arr(sq ? "t" : "g").ptr<u128>();
+                const u128* ea = sq ? nullptr : g.arr("e").ptr<u128>();
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) nxt.emplace_back(crt[j], Nin);
+                parallel_for(Nin, [&](i64 b0, i64 b1) {
+                    std::vector<const comp_t*> xp(k), yp(k);
+                    std::vector<comp_t*> op(k);
+                    for (i64 e = b0; e < b1; ++e) {
+                        for (int j = 0; j < k; ++j) {
+                            xp[j] = cur[j].at(e);
+                            yp[j] = ys[j].at(mp.ysrc(e));
+                            op[j] = nxt[j].at(e);
+                        }
+                        mul_eval_elem(mp, stream_id(L, 1, e), xp.data(), yp.data(), ga + e * sum_crt,
+                                      sq ? nullptr : ea + e * sum_crt, op.data());
+                    }
                 }, nt);
                 cur = std::move(nxt);
                 break;

@@ -1018,4 +1018,31 @@ void argmax_pair_eval(const ArgMaxPlan& P, int lv, u64 s_gate, u64 v_gate, u64 i
     }
 }
 
+// ---------------------------------------------------------------------------
+// Mul (gadgets.h MulPlan)
+void mul_garble_elem(const MulPlan& P, const LabelBank& R, const Prg& prg, u64 stream, const comp_t* const* x0,
+                     const comp_t* const* y0, u128* g, u128* e, comp_t* const* out0) {
+    u64 ctr = 0;
+    for (int j = 0; j < P.k(); ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        if (P.square) {
+            draw(prg, stream, ctr, mp.p, out0[j]);
+            garble_proj(x0[j], R.get(mp.p), mp, out0[j], R.get(mp.p), mp,
+                        [](int v) { return static_cast<i64>(v) * v; }, g + P.prefix[j], 1,
+                        Mask{true, stream, tw_sub(TW_PROJ, j), 0});
+        } else {
+            gen_mult_garble(x0[j], y0[j], mp, R, prg, stream, ctr, g + P.prefix[j], e + P.prefix[j], out0[j], true, j);
+        }
+    }
+}
+
+void mul_eval_elem(const MulPlan& P, u64 gate, const comp_t* const* x, const comp_t* const* y, const u128* g,
+                   const u128* e, comp_t* const* out) {
+    for (int j = 0; j < P.k(); ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        if (P.square) eval_proj(x[j], mp, g + P.prefix[j], mp, out[j], 1, Mask{true, gate, tw_sub(TW_PROJ, j), 0});
+        else gen_mult_eval(x[j], y[j], mp, g + P.prefix[j], e + P.prefix[j], out[j], true, gate, j);
+    }
+}
+
 }  // namespace dash

@@ -533,4 +533,50 @@ void argmax_pair_eval(const ArgMaxPlan& P, int lv, u64 s_gate, u64 v_gate, u64 i
                       const u128* mrs, const u128* g, const u128* e, const u128* idx, const u128* ig, const u128* ie,
                       comp_t* const* vout, comp_t* const* iout);
 
+// ---------------------------------------------------------------------------
+// Mul (product of two secret CRT tensors, or the square of one) per output
+// element e
+//
+// Product: gen_mult_garble as it stands per residue j. r = the colour of y's
+// zero label; the garbler half gate g is keyed by x (row = colour of x, tweak
+// (TW_MMG, j)), the evaluator half gate e by y (row = colour of y, tweak
+// (TW_GME, j)); out = E + colour(y) x - G. Gate id and PRG stream are
+// stream_id(L, 1, e) of the OUTPUT element, draws per element j ascending, sk03
+// then sk04. With a channel broadcast (bc = H W > 0) element e reads y[e / bc]:
+// one y label keys the e rows of bc elements, each under its own gate id, so no
+// two of them share a pad. Tables g [N][P], e [N][P], P = sum_j p_j.
+// Square: one projection v -> v^2 mod p_j per residue (garble_proj, identity
+// offset bank, tweak (TW_PROJ, j)), one fresh output label per residue drawn j
+// ascending from the same stream. Table t [N][P]: half the entries, one hash
+// instead of two, and no label keys two half gates.
+// Hardened encoding only: without a gate tweak a label read by a Mul and by any
+// other gate (a skip tensor, a broadcast y, one tensor into two Muls) would be
+// hashed to the same pad (docs/SECURITY.md).
+struct MulPlan {
+    std::vector<int> crt;
+    i64 bc = 0;  // elements per channel of a broadcast y, 0 = elementwise
+    bool square = false;
+    i64 sum_crt = 0;
+    std::vector<i64> prefix;  // table offset of residue j
+    MulPlan() = default;
+    MulPlan(const std::vector<int>& crt_, i64 bc_, bool square_) : crt(crt_), bc(bc_), square(square_) {
+        DASH_CHECK(bc >= 0 && !(square && bc), "mul: a square has no broadcast operand");
+        for (int p : crt) {
+            prefix.push_back(sum_crt);
+            sum_crt += p;
+        }
+    }
+    int k() const { return static_cast<int>(crt.size()); }
+    i64 ysrc(i64 e) const { return bc ? e / bc : e; }  // y's element of output element e
+    i64 ny(i64 N) const { return bc ? N / bc : N; }     // y's elements for N outputs
+    i64 entries() const { return square ? sum_crt : 2 * sum_crt; }
+    static i64 entries(const std::vector<int>& crt, bool square) { return MulPlan(crt, 0, square).entries(); }
+};
+// One output element. x0 / y0 (x / y): k label pointers; g, e (product) or t (square, passed as g; e unused): the
+// element's table rows. Garbler: base labels.
+void mul_garble_elem(const MulPlan& P, const LabelBank& R, const Prg& prg, u64 stream, const comp_t* const* x0,
+                     const comp_t* const* y0, u128* g, u128* e, comp_t* const* out0);
+void mul_eval_elem(const MulPlan& P, u64 gate, const comp_t* const* x, const comp_t* const* y, const u128* g,
+                   const u128* e, comp_t* const* out);
+
 }  // namespace dash

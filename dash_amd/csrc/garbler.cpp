@@ -36,6 +36,7 @@ const char* kind_name(int kind) {
         case K_CONCAT: return "concat";
         case K_CLIP: return "clip";
         case K_ARGMAX: return "argmax";
+        case K_MUL: return "mul";
         case K_CONVT: return "conv_transpose2d";
         case K_UPSAMPLE: return "upsample";
     }
@@ -643,6 +644,11 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
     std::vector<int> keep(layers.size() + 1, 0);
     for (const auto& l : layers) {
         if (l.kind == K_ADD) keep[param1(l.p, "src") + 1] = 1;
+        if (l.kind == K_MUL && !param1(l.p, "sq", 0)) {
+            const i64 s = param1(l.p, "src");
+            DASH_CHECK(s >= -1 && s < static_cast<i64>(layers.size()), "mul: bad source layer");
+            keep[s + 1] = 1;
+        }
         if (l.kind == K_CONCAT)
             for (i64 s : paramv(l.p, "srcs")) {
                 DASH_CHECK(s >= -1 && s < static_cast<i64>(layers.size()), "concat: bad source layer");
@@ -741,6 +747,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                                     (spec.kind == K_RELU || spec.kind == K_SIGN ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
                                     spec.kind == K_CLIP || spec.kind == K_ARGMAX ||
+                                    (spec.kind == K_MUL && GpuGarbler::mul_fits(k, param1(spec.p, "sq", 0) != 0)) ||
                                     (spec.kind == K_RESCALE && (param1(spec.p, "mode", 0) != 0 || crt_[0] == 2)))));
         const bool passthru = spec.kind == K_FLATTEN;
         if (on_gpu && !dev_ok) {
@@ -1664,6 +1671,60 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 g.a["e"] = ea;
                 cur = std::move(nxt);
                 dims = {No};
+                break;
+            }
+            case K_MUL: {
+                // gadgets.h MulPlan: x = cur, y = the saved output of layer src (element e / bc with a broadcast)
+                DASH_CHECK(is_crt(), "mul needs CRT-base labels");
+                DASH_CHECK(hard, "mul: the Mul layer exists in the hardened encoding only");
+                const bool sq = param1(spec.p, "sq", 0) != 0;
+                const i64 src = sq ? -2 : param1(spec.p, "src");
+                const MulPlan mp(crt_, sq ? 0 : param1(spec.p, "bc", 0), sq);
+                if (!sq) {
+                    DASH_CHECK(src >= -1 && src < static_cast<i64>(li), "mul: bad source layer");
+                    DASH_CHECK(saved_mod[src + 1] == crt_, "mul: the operand is not on the CRT base");
+                    i64 ny = 1;
+                    for (i64 v : saved_dims[src + 1]) ny *= v;
+                    DASH_CHECK((mp.bc == 0 || Nin % mp.bc == 0) && ny == mp.ny(Nin), "mul: operand size mismatch");
+                }
+                Array ga(DType::u128, {Nin, sum_crt}), ea;
+                if (!sq) ea = Array(DType::u128, {Nin, sum_crt});
+                if (on_gpu) {
+                    sinkify(ga, sq ? "t" : "g");
+                    sinkify(ea, "e");
+                    gpu->mul(L, mp, sq ? 0 : static_cast<size_t>(src + 1), cur, ga, ea);
+                } else {
+                    CrtLabels other;
+                    if (!sq && gpu) {  // the saved outputs live on the device: fetch this one (the device cur is stale)
+                        gpu->restore(static_cast<size_t>(src + 1), other);
+                        gpu->to_host(other);
+                    }
+                    const CrtLabels& ys = sq ? cur : (gpu ? other : saved[src + 1]);
+                    DASH_CHECK(!ys.empty() && ys[0].N == mp.ny(Nin), "mul: operand size mismatch");
+                    CrtLabels nxt;
+                    for (int j = 0; j < k; ++j) nxt.emplace_back(crt_[j], Nin);
+                    parallel_for(Nin, [&](i64 b0, i64 b1) {
+                        std::vector<const comp_t*> xp(k), yp(k);
+                        std::vector<comp_t*> op(k);
+                        for (i64 e = b0; e < b1; ++e) {
+                            for (int j = 0; j < k; ++j) {
+                                xp[j] = cur[j].at(e);
+                                yp[j] = ys[j].at(mp.ysrc(e));
+                                op[j] = nxt[j].at(e);
+                            }
+                            mul_garble_elem(mp, R_, prg_, stream_id(L, 1, e), xp.data(), yp.data(),
+                                            ga.ptr<u128>() + e * sum_crt, sq ? nullptr : ea.ptr<u128>() + e * sum_crt,
+                                            op.data());
+                        }
+                    }, nt);
+                    cur = std::move(nxt);
+                }
+                if (sq) {
+                    g.a["t"] = ga;
+                } else {
+                    g.a["g"] = ga;
+                    g.a["e"] = ea;
+                }
                 break;
             }
             case K_MMULT: {

@@ -99,7 +99,10 @@ static inline LaunchDims aes_dims(const char* kernel, int64_t n, int y, int z) {
 // accesses, U of them in flight per thread. Lanes then walk their own element's components in LDS. A lane
 // streaming its own column from HBM moves one byte per lane per load (64 B per wave instruction) with a
 // few loads in flight: the streaming kernels sat at 0.2-1.5 TB/s, 65-70 % of cycles waiting (r03 roofline).
-template <int BS, int U>
+// ZERO defines every slot of the in-flight group before its load: left undefined, the slots of skipped units keep
+// the group in scratch (80 B per lane at U = 4); zeroed first it stays in registers. The kernels written before the
+// flag keep ZERO = false and compile as they did.
+template <int BS, int U, bool ZERO = false>
 __device__ __forceinline__ void lds_stage_rows(uint8_t* S, const act_t* L, int64_t N, int64_t e0, int c0, int cnt) {
     constexpr int W = BS / 16;  // 16-byte units per row
     const int units = cnt * W;
@@ -109,6 +112,7 @@ __device__ __forceinline__ void lds_stage_rows(uint8_t* S, const act_t* L, int64
         for (int h = 0; h < U; ++h) {
             const int x = x0 + h * BS;
             const int64_t e = e0 + 16 * (x % W);
+            if constexpr (ZERO) v[h] = make_uint4(0u, 0u, 0u, 0u);
             if (x < units && e < N) v[h] = *reinterpret_cast<const uint4*>(L + static_cast<int64_t>(c0 + x / W) * N + e);
         }
 #pragma unroll

@@ -2990,6 +2990,7 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     clip_hi_hook() = &GpuGarbler::clip_hi_dev;
     clip_joint_hook() = &GpuGarbler::clip_joint_dev;
     argmax_hook() = &GpuGarbler::argmax_level_dev;
+    mul_hook() = &GpuGarbler::mul_dev;
     convt_hook() = &GpuGarbler::convt_dev;
     upsample_hook() = &GpuGarbler::upsample_dev;
     Impl& I = *impl_;
@@ -4351,6 +4352,142 @@ void GpuGarbler::concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& i
     I.cur_mod = mods;
     I.cur_N = Ntot;
     set_stale(cur, I.cur_mod, Ntot);
+}
+
+// Mul (garbler.cpp K_MUL, gadgets.h MulPlan), byte-identical to mul_garble_elem: PRG stream and gate
+// stream_id(layer, 1, e), draws j ascending.
+// Product: sk03 / sk04 of residue j in slots 2j / 2j + 1; x is input residue j, y (the saved output, gathered to
+// one label per output element where it broadcasts) input residue k + j. The garbler half gate is F_MULR keyed by
+// x with r = the colour of y's base label (rows (TW_MMG, j), table 4), the evaluator half gate F_NEGR keyed by y
+// with the same r and x's base label as its payload offset (rows (TW_GME, j), table 5); out = sk04 - sk03.
+// Square: the output label of residue j in slot j, one projection v -> v^2 (rows (TW_PROJ, j), table 4).
+void GpuGarbler::mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& ga,
+                         Array& ea) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("mul");
+    const int64_t N = I.cur_N;
+    const int k = I.k;
+    DASH_CHECK(I.c.hard, "gpu garbler: the Mul layer exists in the hardened encoding only");
+    DASH_CHECK(I.cur_mod == I.crt && mp.k() == k, "gpu garbler: mul needs CRT-base labels");
+    static_assert(kMaxRes == 16, "GpuGarbler::mul_fits states the input set's size");
+    DASH_CHECK(mul_fits(k, mp.square), "gpu garbler: mul: x and y do not fit the 16 input residues of one projection set");
+    gg::In in = labels_in(I.cur, I.crt, N);
+    std::vector<DevBlock> ybc;  // a broadcast operand, one label per output element
+    if (!mp.square) {
+        auto it = I.saved.find(src_idx);
+        DASH_CHECK(it != I.saved.end() && it->second.mods == I.crt && it->second.N == mp.ny(N) &&
+                       (mp.bc == 0 || N % mp.bc == 0),
+                   "gpu garbler: mul operand missing, off the CRT base or of another shape");
+        const std::vector<DevBlock>* yl = &it->second.L;
+        if (mp.bc) {
+            ybc = I.alloc_labels(I.crt, N);
+            std::vector<int32_t> map(static_cast<size_t>(N));
+            for (int64_t e = 0; e < N; ++e) map[static_cast<size_t>(e)] = static_cast<int32_t>(e / mp.bc);
+            launch_gsum(I.c, ybc, *yl, I.crt, N, it->second.N, gg::dconst(map.data(), map.size()), 1, false,
+                        [](int, int) { return 1; });
+            yl = &ybc;
+        }
+        for (int j = 0; j < k; ++j) {
+            in.p[k + j] = (*yl)[j].as<int16_t>();
+            in.n[k + j] = nr_comps(I.crt[j]);
+            in.es[k + j] = gg::kCh;
+            in.cs[k + j] = N * gg::kCh;
+        }
+    }
+    const int nslots = mp.square ? k : 2 * k;
+    gg::Gadget g{};
+    g.layer = layer;
+    g.sslot = 1;
+    g.mask = 0;
+    g.S = I.scratch(static_cast<size_t>(N) * nslots * gg::kW * sizeof(int16_t));
+    g.N = N;
+    g.nslots = nslots;
+    g.PB = I.pbank(2, N);
+    DevTable tG, tE;
+    tG.alloc(I.device, N, ga.shape[1], ga);
+    gg::Tables tb{};
+    tb.t[4] = tG.p(); tb.row[4] = tG.row;
+    std::vector<gg::Draw> dr;
+    std::vector<gg::Proj> pr;
+    std::vector<int> fan;
+    std::vector<int16_t> flut;
+    int ctr = 0;
+    int64_t first = 0;
+    if (mp.square) {
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            dr.push_back({j, p, ctr});
+            ctr += prg_blocks(p);
+            const int a0 = static_cast<int>(flut.size()), a1 = static_cast<int>(fan.size());
+            for (int v = 0; v < p; ++v) flut.push_back(static_cast<int16_t>(v * v % p));
+            fan.push_back(p);
+            gg::Proj q{};
+            q.in_kind = gg::S_INPUT; q.in_idx = j; q.pin = p;
+            q.out_slot = j; q.pout = p; q.fn = gg::F_FAN; q.a0 = a0; q.a1 = a1;
+            q.outr_kind = gg::R_BANK; q.table = 4; q.stride = 1; q.off = mp.prefix[j]; q.first = first;
+            q.hsub = tw_sub(kTwProj, static_cast<uint32_t>(j));
+            first += p;
+            pr.push_back(q);
+        }
+    } else {
+        tE.alloc(I.device, N, ea.shape[1], ea);
+        tb.t[5] = tE.p(); tb.row[5] = tE.row;
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            dr.push_back({2 * j, p, ctr});
+            ctr += prg_blocks(p);
+            dr.push_back({2 * j + 1, p, ctr});
+            ctr += prg_blocks(p);
+        }
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            gg::Proj q{gg::S_INPUT, j, p, 2 * j, p, gg::F_MULR, k + j, 0, 0, gg::R_BANK, 0, 4, 1, mp.prefix[j], first};
+            q.hsub = tw_sub(kTwMmg, static_cast<uint32_t>(j));
+            first += p;
+            pr.push_back(q);
+        }
+        for (int j = 0; j < k; ++j) {
+            const int p = I.crt[j];
+            gg::Proj q{gg::S_INPUT, k + j, p, 2 * j + 1, p, gg::F_NEGR, k + j, 0, 0, gg::R_INPUT, j, 5, 1, mp.prefix[j],
+                       first};
+            q.hsub = tw_sub(kTwGme, static_cast<uint32_t>(j));
+            first += p;
+            pr.push_back(q);
+        }
+    }
+    g.draws = gg::dconst(dr.data(), dr.size());
+    g.ndraws = static_cast<int>(dr.size());
+    g.projs = gg::dconst(pr.data(), pr.size());
+    g.nprojs = static_cast<int>(pr.size());
+    g.entries = first;
+    g.nblk = draw_blocks(dr);
+    check_desc(g);
+    hipLaunchKernelGGL(gg::draw_kernel(), dim3(draw_grid(g)), dim3(gg::kGB), 0, gg::tl_st, I.c, g);
+    if (mp.square) project(I.c, g, in, tb, pr, ProjFns{&flut, &fan});
+    else project(I.c, g, in, tb, pr);
+    std::vector<DevBlock> out = I.alloc_labels(I.crt, N);
+    std::vector<gg::LinJob> jobs;
+    for (int j = 0; j < k; ++j) {
+        gg::LinJob J = lin_job(out[j].as<int16_t>(), I.crt[j]);
+        if (mp.square) {
+            lin_a(J, gg::slot_base(g, j), N, 1);
+        } else {
+            lin_a(J, gg::slot_base(g, 2 * j + 1), N, 1);
+            lin_b(J, gg::slot_base(g, 2 * j), N, -1);
+        }
+        jobs.push_back(J);
+    }
+    launch_lin(I.c, jobs, N);
+    HIPCHECK(hipGetLastError());
+    std::vector<void*> tmp;
+    gg::end_layer(tmp);
+    tr_.mark("kernels");
+    tG.to_array(ga, I.device);
+    if (!mp.square) tE.to_array(ea, I.device);
+    I.cur = std::move(out);
+    set_stale(cur, I.crt, N);
 }
 
 // dense base labels (garbler.cpp K_DENSE): y_o = sum_{w != 0 mod p} w x_src(i) + (1 + #zero weights) Z_p

@@ -157,6 +157,20 @@ class GpuGarbler {
         DASH_CHECK(argmax_hook() != nullptr, "gpu garbler: argmax is not linked in");
         argmax_hook()(*this, layer, lv, ap, P, prefix, cur, mrs, mmg, mme, idx, img, ime);
     }
+    // Mul (gadgets.h MulPlan): x = the device cur, y = the saved output `src_idx` (unused for a square); tables g, e
+    // (product) or g = t (square); device cur -> next. A hook as for clip.
+    using MulFn = void (*)(GpuGarbler&, uint64_t, const MulPlan&, size_t, CrtLabels&, Array&, Array&);
+    static MulFn& mul_hook() {
+        static MulFn f = nullptr;
+        return f;
+    }
+    // x and y enter the projection descriptors as input residues j and k + j of one 16-entry set: a product needs
+    // 2 k <= 16, a square k <= 16. The host garbler takes the layers that do not fit.
+    static bool mul_fits(int k, bool square) { return (square ? k : 2 * k) <= 16; }
+    void mul(uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& g, Array& e) {
+        DASH_CHECK(mul_hook() != nullptr, "gpu garbler: mul is not linked in");
+        mul_hook()(*this, layer, mp, src_idx, cur, g, e);
+    }
     // ReDash rescale iteration (base-extension plan) on the device cur, in place
     void rescale_redash(uint64_t layer, int it, const RescalePlan& P, CrtLabels& cur,
                         const std::vector<std::vector<comp_t>>& up, const std::vector<std::vector<comp_t>>& down,
@@ -182,6 +196,8 @@ class GpuGarbler {
     static void argmax_level_dev(GpuGarbler& self, uint64_t layer, int lv, const ArgMaxPlan& ap, i64 P,
                                  const std::vector<i64>& prefix, CrtLabels& cur, Array& mrs, Array& mmg, Array& mme,
                                  Array& idx, Array& img, Array& ime);
+    static void mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& g,
+                        Array& e);
     std::unique_ptr<Impl> impl_;
 };
 

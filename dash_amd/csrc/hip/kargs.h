@@ -205,5 +205,17 @@ struct MultArgs {
     uint64_t gate0;
 };
 
+// A Mul layer (gadgets.h MulPlan; hardened only): out[e] = x[e] * y[bc ? e / bc : e] over N outputs per GC, or
+// the square x[e]^2 (g = the table t, e unused). y is a saved output of Ny elements per GC, read for its
+// compressed label and colour only.
+struct MulArgs {
+    CrtInfo crt;
+    int64_t N, Ny;
+    int64_t bc;     // elements per channel of a broadcast y, 0 = elementwise
+    const u128* g;  // [B][N][sum] rows (TW_MMG, j) keyed by x; the square's rows (TW_PROJ, j)
+    const u128* e;  // [B][N][sum] rows (TW_GME, j) keyed by y
+    uint64_t gate0;
+};
+
 }  // namespace dev
 }  // namespace dash

@@ -1815,6 +1815,116 @@ __global__ __launch_bounds__(kAesBlock, kAesMinBlocks) void k_mult(MultArgs a, A
 }
 
 // ---------------------------------------------------------------------------
+// Mul layer (gadgets.h MulPlan; kargs.h MulArgs): out_j = E + colour(y_j) x_j - G, the generalized half gates
+// of x[e] and y[e / bc] under the output element's gate. Hardened only: no AES prologue, both pads are ChaCha
+// pads derived here from the two compressed labels (rows (TW_MMG, j) of x and (TW_GME, j) of y), so no hash pass
+// precedes the multiply. y is read for its compressed label and colour alone.
+struct MulLane {
+    u128 G, E;
+    uint32_t ypr;
+};
+// The evaluator half gate's row and multiplier from y's column (HBM, stride Ny)
+__device__ __forceinline__ void mul_y_ops(const MulArgs& a, const Act& ys, int j, int b, int64_t e, uint64_t gt,
+                                          const ModC& m, MulLane& r) {
+    const int64_t ey = a.bc ? e / a.bc : e;
+    const act_t* Yl = ys.p[j] + static_cast<int64_t>(b) * m.n * a.Ny + ey;
+    const uint32_t coly = Yl[0];
+    const u128 Eraw = a.e[(static_cast<int64_t>(b) * a.N + e) * a.crt.sum + a.crt.prefix[j] + coly];
+    const u128 Cy = compress_cm(Yl, a.Ny, m);
+    r.E = Eraw - hard_pad(Cy, gt, tw_sub(kTwGme, j), 0);
+    r.ypr = coly;
+}
+
+// grid (ceil(N/256), k, B)
+__global__ __launch_bounds__(256) void k_mul(MulArgs a, Act x, Act ys, Act y, const ModC* mc) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const uint64_t gt = a.gate0 ^ static_cast<uint64_t>(e);
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    const uint32_t colx = X[0];
+    const u128 Graw = a.g[(static_cast<int64_t>(b) * N + e) * a.crt.sum + a.crt.prefix[j] + colx];
+    MulLane c;
+    mul_y_ops(a, ys, j, b, e, gt, m, c);
+    c.G = Graw - hard_pad(compress_cm(X, N, m), gt, tw_sub(kTwMmg, j), 0);
+    DigitStream sg, se;
+    sg.init(c.G);
+    se.init(c.E);
+    col_walk<kChunk>(X, y.p[j] + static_cast<int64_t>(b) * m.n * N + e, N, static_cast<int>(m.n), [&](int, uint32_t xv) {
+        const uint32_t g = sg.next(m);
+        return mult_digit(se.next(m), c.ypr, xv, p, g, m);
+    });
+}
+
+// k_mul with the labels staged in LDS (mult_grid; as k_relu_mult_s): a block = (256-element tile, residue j, GC b).
+// The table gathers go out first (the two colours are one byte each from HBM), the block's x_j rows come in as
+// 16-byte loads, a lane compresses its column from the image (x is read from HBM once, the lane form reads it
+// twice), rewrites it in place and the block stores the rows as 16-byte stores. An elementwise y has x's layout: its
+// tile passes through the same image first, for its compressed label alone. A broadcast y is never staged: the
+// lanes of a channel read one column, which the cache serves. BC: a.bc != 0, one instantiation per path.
+template <bool BC>
+__global__ __launch_bounds__(kRmBS) void k_mul_s(MulArgs a, Act x, Act ys, Act y, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[128 * kRmBS];
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int n = static_cast<int>(m.n);
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * n * N;
+    const act_t* Ys = ys.p[j] + static_cast<int64_t>(b) * n * a.Ny;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N;
+    for (int64_t e0 = static_cast<int64_t>(blockIdx.x) * kRmBS; e0 < N; e0 += static_cast<int64_t>(gridDim.x) * kRmBS) {
+        const int64_t e = min(e0 + tid, N - 1);  // lanes past the end redo the last element (their column is not stored)
+        const uint64_t gt = a.gate0 ^ static_cast<uint64_t>(e);
+        const int64_t ey = BC ? e / a.bc : e;
+        const uint32_t colx = X[e], coly = Ys[ey];
+        const int64_t row = (static_cast<int64_t>(b) * N + e) * a.crt.sum + a.crt.prefix[j];
+        const u128 Graw = a.g[row + colx], Eraw = a.e[row + coly];
+        u128 E;
+        if (BC) E = Eraw - hard_pad(compress_cm(Ys + ey, a.Ny, m), gt, tw_sub(kTwGme, j), 0);
+        __syncthreads();  // the previous tile's stores have read the image
+        if (!BC) {  // Ny == N
+            lds_stage_rows<kRmBS, 4, true>(stg, Ys, N, e0, 0, n);
+            __syncthreads();
+            const u128 Cy = compress_cm(stg + tid, kRmBS, m);
+            __syncthreads();
+            lds_stage_rows<kRmBS, 4, true>(stg, X, N, e0, 0, n);
+            E = Eraw - hard_pad(Cy, gt, tw_sub(kTwGme, j), 0);  // while the other waves still stage
+        } else {
+            lds_stage_rows<kRmBS, 4, true>(stg, X, N, e0, 0, n);
+        }
+        __syncthreads();
+        // a lane past the end compresses rows nobody staged: its keys, pads and column are never stored
+        const u128 G = Graw - hard_pad(compress_cm(stg + tid, kRmBS, m), gt, tw_sub(kTwMmg, j), 0);
+        lds_mult_walk<kRmBS, false>(stg + tid, n, G, E, 0, coly, p, m);
+        __syncthreads();
+        lds_store_rows<kRmBS>(Y, stg, N, e0, 0, n);
+    }
+}
+
+// The square: one projection v -> v^2 per residue (rows (TW_PROJ, j)), k_proj's body with a ChaCha pad.
+// grid (ceil(N/256), k, B)
+__global__ __launch_bounds__(256) void k_mul_sq(MulArgs a, Act x, Act y, const ModC* mc) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const ModC m = mc[a.crt.p[j]];
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    const uint32_t colx = X[0];
+    const u128 Traw = a.g[(static_cast<int64_t>(b) * N + e) * a.crt.sum + a.crt.prefix[j] + colx];
+    const u128 H = hard_pad(compress_cm(X, N, m), a.gate0 ^ static_cast<uint64_t>(e), tw_sub(kTwProj, j), 0);
+    DigitStream s;
+    s.init(Traw - H);
+    act_t* O = y.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    for (int i = 0; i < static_cast<int>(m.n); ++i) O[static_cast<int64_t>(i) * N] = static_cast<act_t>(s.next(m));
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 static inline dim3 grid_for(int64_t n, int bs, int y, int z) {
     return dim3(static_cast<unsigned>((n + bs - 1) / bs), y, z);
@@ -1933,6 +2043,21 @@ void launch_base_ext(const BEArgs& a, const Act& x, int B, const ModC* mc, const
 void launch_proj(const ProjArgs& a, const Act& x, const Act& y, int B, const ModC* mc, const AesGlobals& g,
                  hipStream_t st) {
     AES_LAUNCH_GGL(k_proj, a.N, a.k, B, kAesLds, st, a, x, y, mc, g.te0, g.rk);
+}
+void launch_mul(const MulArgs& a, bool square, const Act& x, const Act& ys, const Act& y, int B, const ModC* mc,
+                hipStream_t st) {
+    if (square) {
+        const dim3 grid = grid_for(a.N, 256, a.crt.k, B);
+        if (launch_log_on()) launch_log_add("mul.sq", grid, dim3(256));
+        hipLaunchKernelGGL(k_mul_sq, grid, dim3(256), 0, st, a, x, y, mc);
+        return;
+    }
+    dim3 grid;
+    if (mult_grid("mul", a.N, a.crt.k, B, x, y, grid)) {
+        if (a.bc) hipLaunchKernelGGL(k_mul_s<true>, grid, dim3(kRmBS), 0, st, a, x, ys, y, mc);
+        else hipLaunchKernelGGL(k_mul_s<false>, grid, dim3(kRmBS), 0, st, a, x, ys, y, mc);
+    } else
+        hipLaunchKernelGGL(k_mul, grid, dim3(256), 0, st, a, x, ys, y, mc);
 }
 void launch_mult(const MultArgs& a, const Act& x, const Act& y, int B, const ModC* mc, const AesGlobals& g,
                  hipStream_t st) {

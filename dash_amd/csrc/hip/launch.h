@@ -92,6 +92,10 @@ void launch_relu_mrs(const MrsArgs& a, const SignArgs& sa, const Act& x, const A
 void launch_base_ext(const BEArgs& a, const Act& x, int B, const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_proj(const ProjArgs& a, const Act& x, const Act& y, int B, const ModC* mc, const AesGlobals& g,
                  hipStream_t st);
+// Mul layer: x * ys (ys = the saved operand) or, with square, x^2. Logs "mul.lane" / "mul.staged" (mult_grid's
+// pick) or "mul.sq".
+void launch_mul(const MulArgs& a, bool square, const Act& x, const Act& ys, const Act& y, int B, const ModC* mc,
+                hipStream_t st);
 void launch_mult(const MultArgs& a, const Act& x, const Act& y, int B, const ModC* mc, const AesGlobals& g,
                  hipStream_t st);
 

@@ -804,6 +804,7 @@ class HipEvaluator {
     void plan_concat(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_proj(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_mult(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_mul(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname);
 
     std::shared_ptr<GarbledModel> tmpl_;  // build() only
@@ -913,6 +914,11 @@ void HipEvaluator::build() {
     w.keep.assign(L + 1, 0);
     for (auto& l : m0.layers) {
         if (l.kind == K_ADD) w.keep[l.param("src") + 1] = 1;
+        if (l.kind == K_MUL && !l.param("sq", 0)) {
+            const i64 s = l.param("src");
+            DASH_CHECK(s >= -1 && s < static_cast<i64>(L), "mul: bad source layer");
+            w.keep[s + 1] = 1;
+        }
         if (l.kind == K_CONCAT)
             for (i64 s : l.vec("srcs")) w.keep[s + 1] = 1;
         if (l.p.count("in_src")) w.keep[l.param("in_src") + 1] = 1;
@@ -945,6 +951,7 @@ void HipEvaluator::build() {
             case K_CONCAT: plan_concat(w, li, g, lname); break;
             case K_PROJ: plan_proj(w, li, g, lname); break;
             case K_MULT: case K_MMULT: plan_mult(w, li, g, lname); break;
+            case K_MUL: plan_mul(w, li, g, lname); break;
             case K_BASEEXT: plan_base_ext(w, li, g, lname); break;
             default:
                 throw std::runtime_error(std::string("dash: HIP evaluator cannot run layer kind ") + kind_name(g.kind));
@@ -1969,6 +1976,38 @@ void HipEvaluator::plan_mult(Walk& w, size_t li, const GLayer& g, const std::str
     const Env e = w.env;
     add_op(lname, [a, x, y, e](hipStream_t st) { launch_mult(a, x, y, e.B, e.mc, e.ag, st); });
     set_out(w, g, a.No, w.nxt());
+}
+
+// gadgets.h MulPlan: x = the current activation, y = the saved copy of layer src's output (save_if_needed's own
+// buffer, written by its "save" op every run, eagerly and in a replayed graph alike), read in place
+void HipEvaluator::plan_mul(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    DASH_CHECK(hard_, "the Mul layer exists in the hardened encoding only");
+    DASH_CHECK(w.mods == crt_, "mul: the input is not on the CRT base");
+    const bool sq = g.param("sq", 0) != 0;
+    MulArgs a{};
+    a.crt = w.crt;
+    a.N = w.N;
+    a.gate0 = gate_base(li + 1, 1);
+    Act x = act_of(w.cur), y = act_of(w.nxt()), ys{};
+    if (sq) {
+        a.Ny = w.N;
+        a.g = upload_tables(li, "t");
+    } else {
+        const i64 src = g.param("src");
+        DASH_CHECK(src >= -1 && src < static_cast<i64>(li) && !saved_[src + 1].empty(), "mul: operand not saved");
+        DASH_CHECK(w.saved_mods[src + 1] == crt_, "mul: the operand is not on the CRT base");
+        a.bc = g.param("bc", 0);
+        a.Ny = w.saved_n[src + 1];
+        DASH_CHECK(a.bc >= 0 && (a.bc ? (w.N % a.bc == 0 && a.Ny == w.N / a.bc) : a.Ny == w.N),
+                   "mul: operand size mismatch");
+        for (int j = 0; j < k_; ++j) ys.p[j] = saved_[src + 1][j];
+        ys.N = a.Ny;
+        a.g = upload_tables(li, "g");
+        a.e = upload_tables(li, "e");
+    }
+    const Env e = w.env;
+    add_op(lname, [a, sq, x, ys, y, e](hipStream_t st) { launch_mul(a, sq, x, ys, y, e.B, e.mc, st); });
+    set_out(w, g, w.N, w.nxt());
 }
 
 void HipEvaluator::plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname) {

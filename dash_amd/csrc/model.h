@@ -37,6 +37,7 @@ enum Kind : int {
     K_ARGMAX = 16,
     K_CONVT = 17,
     K_UPSAMPLE = 18,
+    K_MUL = 19,  // params src, bc (broadcast only), sq (square only); arrays g, e (product) or t (square)
 };
 const char* kind_name(int kind);
 

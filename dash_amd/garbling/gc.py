@@ -27,6 +27,7 @@ from ..native import native
 
 _CLIP = _Kind.CLIP
 _ARGMAX = _Kind.ARGMAX
+_MUL = _Kind.MUL
 _CONVT = _Kind.CONVT
 
 Labels = list  # list[(modulus, np.ndarray int16 [N, n_p])]
@@ -208,6 +209,13 @@ class GarbledCircuit:
                              "only (%s)" % (convts[0], "hardened=False was asked for" if supported else
                                             "the resolved constructions cannot be hardened: fused sign and no legacy "
                                             "DASH rescale are needed"))
+        # a Mul's operands are read by other gates too (a skip tensor, a broadcast operand across a plane, one
+        # tensor into two Muls): without the hardened encoding's gate tweak those reads would share a pad
+        muls = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _MUL]
+        if muls and not (supported if hardened is None else hardened):
+            raise ValueError("layer %d (mul): the Mul layer exists in the hardened encoding only (%s)" % (
+                muls[0], "hardened=False was asked for" if supported else
+                "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
         if argmaxes and not mrs_capable(self.crt_base):
             raise ValueError("layer %d (argmax): the ArgMax layer's exact sign needs a CRT base with residue 0 = 2 "
                              "and odd other residues, got %s" % (argmaxes[0], self.crt_base))

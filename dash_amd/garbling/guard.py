@@ -25,12 +25,16 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
   evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
   bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
-  has no Concat, no Clip, no ArgMax, no ConvTranspose2d, no Upsample and no padded / ceil-mode pooling: circuits
-  with any of them take the torch path on the GPU;
+  has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample and no padded / ceil-mode pooling:
+  circuits with any of them take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
 * the per-input numpy model (``violations_np``), the exact reference of both and the path of layers without a
   batched form (test-only Mult / Max).
+
+A ``Mul`` sets no limit of its own: its product is checked where a gadget or the output next reads it. The torch
+path multiplies in int64, exact like the numpy model; operands whose product could reach 2^62, where the numpy
+model raises ``OverflowError`` instead of wrapping, are flagged.
 """
 from __future__ import annotations
 
@@ -64,12 +68,12 @@ class RangeGuard:
         self.joint_clips = {int(i): int(t) for i, t in (joint_clips or {}).items()}
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
-                                          L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Projection,
+                                          L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Mul, L.Projection,
                                           L.BaseExtension, L.ConvTranspose2d, L.Upsample))
                            for l in circuit.layers)
-        # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no ConvTranspose2d, no Upsample, no dilated
-        # conv and no padded / ceil-mode pooling: such circuits take the batched torch path
-        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.ConvTranspose2d, L.Upsample)) or
+        # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no
+        # dilated conv and no padded / ceil-mode pooling: such circuits take the batched torch path
+        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.Mul, L.ConvTranspose2d, L.Upsample)) or
                                     (isinstance(l, L.Conv2d) and (l.dh > 1 or l.dw > 1)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
@@ -127,7 +131,11 @@ class RangeGuard:
                 span = int((v.max(axis=0) - v.min(axis=0)).max())
                 if span > self.span_max():
                     bad.append((i, "span", span, 0, self.span_max()))
-            cur = l.plain_q_eval(inp, False, ctx, M)
+            try:
+                cur = l.plain_q_eval(inp, False, ctx, M)
+            except OverflowError:  # a Mul whose product leaves int64: far beyond any signed CRT value
+                bad.append((i, "overflow", 0, -_half(M), M - _half(M)))
+                return bad
             ctx.append(cur)
         h = _half(M)
         if cur.size and (int(cur.min()) < -h or int(cur.max()) >= M - h):
@@ -254,6 +262,17 @@ class RangeGuard:
                 out = out.reshape(B, -1)
             elif isinstance(l, L.Add):
                 out = inp + ctx[l.src + 1]
+            elif isinstance(l, L.Mul):
+                y = inp if l.src is None else ctx[l.src + 1].reshape(B, -1)
+                if l.bc:
+                    y = y.repeat_interleave(l.bc, dim=1)
+                # int64 products are exact below 2^63; where the numpy model raises OverflowError (2^62) the
+                # input is flagged and the operands are zeroed so nothing wraps
+                # max|x| max|y| >= 2^62 in exact integers: ax > floor((2^62 - 1) / ay)
+                ax, ay = inp.abs().amax(dim=1), y.abs().amax(dim=1)
+                big = (ay > 0) & (ax > torch.div((1 << 62) - 1, ay.clamp_min(1), rounding_mode="floor"))
+                bad |= big
+                out = torch.where(big[:, None], 0, inp) * y
             elif isinstance(l, L.Concat):
                 out = torch.cat([ctx[s + 1].reshape(B, -1) for s in l.srcs], dim=1)
             else:  # Flatten, Projection, BaseExtension: value-preserving

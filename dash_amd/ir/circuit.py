@@ -7,7 +7,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .bases import crt_modulus, first_primes
-from .layers import Layer
+from .layers import Layer, Mul
 from .quant import quantize_simple
 
 
@@ -226,8 +226,10 @@ class Circuit:
 
     def garble_specs(self) -> list:
         specs = []
-        for l in self.layers:
+        for i, l in enumerate(self.layers):
             kind, params = l.garble_spec()
+            if isinstance(l, Mul) and l.squares_at(i):  # src names the layer's own input: the same tensor twice
+                params = {"sq": 1}
             if getattr(l, "in_src", None) is not None:
                 params = dict(params, in_src=int(l.in_src))
             specs.append((kind, params))

@@ -39,6 +39,7 @@ class Kind:
     ARGMAX = 16
     CONVT = 17
     UPSAMPLE = 18
+    MUL = 19
 
 
 def _size(d: Sequence[int]) -> int:
@@ -887,6 +888,93 @@ class Concat(Layer):
 
     def garble_spec(self):
         return self.kind, {"srcs": list(self.srcs)}
+
+
+class Mul(Layer):
+    """Product of two secret tensors: x, the layer's input, times y, the output
+    of layer `src` (-1 = circuit input), as for Add. `src_dims` equal to `dims`
+    (the default) multiplies elementwise; dims (C, H, W) with src_dims (C,) or
+    (C, 1, 1) broadcasts y over the plane, out[c, h, w] = x[c, h, w] * y[c]. The
+    full tensor is always x. Mul.square(dims), or a `src` that resolves to the
+    layer's own input (its in_src, or the layer before it), is the square x * x. Scale-free: whoever builds the circuit
+    puts the scheme's rescale behind it, as after a conv. Garbled as the
+    generalized half gates, or one projection per residue for the square
+    (csrc/gadgets.h MulPlan); hardened encoding only."""
+
+    kind = Kind.MUL
+    name = "mul"
+
+    def __init__(self, dims, src: Optional[int], src_dims=None):
+        dims = tuple(int(d) for d in dims)
+        sd = dims if src_dims is None else tuple(int(d) for d in src_dims)
+        # an explicit channel operand broadcasts even over a 1 x 1 plane (bc = 1)
+        if src_dims is not None and len(dims) == 3 and sd in ((dims[0],), (dims[0], 1, 1)):
+            self.bc = dims[1] * dims[2]
+        elif sd == dims:
+            self.bc = 0
+        else:
+            raise ValueError(f"mul: operand dims {sd} neither equal {dims} nor are its channels, "
+                             "(C,) or (C, 1, 1) against (C, H, W); the full tensor is the layer's input")
+        if src is None and self.bc:
+            raise ValueError(f"mul: a square has no second operand, got src_dims {sd}")
+        super().__init__(dims, dims)
+        self.src_dims = sd
+        self.src = None if src is None else int(src)
+
+    @classmethod
+    def square(cls, dims) -> "Mul":
+        return cls(dims, None)
+
+    @property
+    def is_square(self) -> bool:
+        """The layer alone can tell: no src, or a src that is its own in_src. A sequential layer whose src is the
+        layer before it is a square too, which only its place in the circuit shows: squares_at."""
+        return self.src is None or (self.in_src is not None and int(self.in_src) == self.src and not self.bc)
+
+    def squares_at(self, index: int) -> bool:
+        """As layer `index` of a circuit: does src resolve to the same tensor as the input? (Circuit.garble_specs
+        garbles such a layer as the square.)"""
+        x_src = int(self.in_src) if self.in_src is not None else index - 1
+        return self.src is None or (not self.bc and self.src == x_src)
+
+    def _y(self, x, ctx, dtype):
+        if self.is_square:
+            return x
+        y = np.asarray(ctx[self.src + 1], dtype=dtype).reshape(-1)
+        assert y.size == _size(self.src_dims), "mul operand size mismatch"
+        return np.repeat(y, self.bc) if self.bc else y
+
+    def plain_eval(self, x, track=True, ctx=None):
+        x = np.asarray(x, dtype=np.float32).reshape(-1)
+        out = x * self._y(x, ctx, np.float32)
+        if track:
+            self._track_f(out)
+        return out
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        x = np.asarray(x, dtype=np.int64).reshape(-1)
+        y = self._y(x, ctx, np.int64)
+        if x.size:
+            ax = max(abs(int(x.min())), abs(int(x.max())))
+            ay = max(abs(int(y.min())), abs(int(y.max())))
+            if ax * ay >= 1 << 62:
+                raise OverflowError(f"mul: the product of operands up to {ax} and {ay} does not fit 62 bits")
+        out = x * y
+        if track:
+            self._track_q(x, y, out)
+        return out
+
+    def garble_spec(self):
+        if self.is_square:
+            return self.kind, {"sq": 1}
+        p = {"src": self.src}
+        if self.bc:
+            p["bc"] = self.bc
+        return self.kind, p
+
+    def __repr__(self) -> str:
+        return (f"Mul.square({self.in_dims})" if self.is_square else
+                f"Mul({self.in_dims}, src={self.src}, src_dims={self.src_dims})")
 
 
 # ---- test-only layers (reference: projection.h, mult_layer.h, mixed_mod_mult_layer.h, max.h, base_extension.h)

@@ -49,6 +49,15 @@ asymmetric pads are refused with the node's name. `Resize` (opset >= 11) and
 PyTorch exports for nn.Upsample(mode="nearest")), become an `Upsample` layer;
 everything else is refused with the node's name. A pending factor passes through.
 
+`Mul` of two produced tensors becomes a `Mul` layer: equal dims multiply
+elementwise, `[N, C, 1, 1]` or `[N, C]` against `[N, C, H, W]` (either order;
+the full tensor becomes the layer's input) broadcasts over the plane, and the
+same tensor twice is a square, as is `Pow` with the constant scalar exponent 2.
+Pending average factors multiply and pass through. The scheme's rescale
+follows the layer exactly as after a conv. A `Mul` with an initializer
+operand, any other broadcast and any other exponent are refused with the
+node's name.
+
 `ReduceSum` over (2, 3) is the plane `SumPool2d` itself (the exporter writes a
 global sum pool that no linear layer follows this way).
 
@@ -77,8 +86,8 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign,
-                     SumPool2d, Upsample, _convt_check, _pool_out)
+from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Mul, Relu, Rescale,
+                     Sign, SumPool2d, Upsample, _convt_check, _pool_out)
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -176,6 +185,17 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         vals = np.asarray(t["values"], dtype=np.float64).reshape(-1) if isinstance(t, dict) else np.zeros(0)
         if uses and all(o == "Clip" and pos in (1, 2) for o, pos in uses) and vals.size == 1:
             clip_consts[out] = float(vals[0])
+
+    # scalar Constant nodes that feed only the exponent of Pow nodes
+    pow_consts: dict[str, float] = {}
+    for node in nodes:
+        if node["op_type"] != "Constant" or "value" not in node["attrs"]:
+            continue
+        out, t = node["outputs"][0], node["attrs"]["value"]
+        uses = [(n["op_type"], pos) for n in nodes for pos, x in enumerate(n["inputs"]) if x == out]
+        vals = np.asarray(t["values"], dtype=np.float64).reshape(-1) if isinstance(t, dict) else np.zeros(0)
+        if uses and all(o == "Pow" and pos == 1 for o, pos in uses) and vals.size == 1:
+            pow_consts[out] = float(vals[0])
 
     def res(name: str) -> str:
         return alias.get(name, name)
@@ -418,7 +438,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         elif op == "Relu":
             j, dims, fac = data_in(node, ins[0])
             emit(_Spec("relu", dims=dims), outs[0], j, dims, fac)
-        elif op == "Constant" and outs[0] in clip_consts:
+        elif op == "Constant" and (outs[0] in clip_consts or outs[0] in pow_consts):
             continue
         elif op == "Clip":
             j, dims, fac = data_in(node, ins[0])
@@ -481,6 +501,45 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             if j1 == len(specs) - 1:  # the current tensor is the previous layer's where possible
                 j0, j1 = j1, j0
             emit(_Spec("add", dims=d0, src=j1), outs[0], j0, d0)
+        elif op == "Mul":
+            name = node.get("name") or op
+            const = [x for x in ins if x in inits]
+            if const:
+                raise NotImplementedError(f"onnx: {name}: Mul by the constant {const[0]!r} is not supported (only the "
+                                          "product of two produced tensors)")
+            (j0, d0, f0), (j1, d1, f1) = data_in(node, ins[0]), data_in(node, ins[1])
+            if res(ins[0]) == res(ins[1]):
+                emit(_Spec("mul", dims=d0, sq=True), outs[0], j0, d0, f0 * f0)
+            else:
+                def chan(full, d):
+                    return len(full) == 3 and tuple(d) in ((full[0],), (full[0], 1, 1))
+
+                if tuple(d0) == tuple(d1):
+                    if j1 == len(specs) - 1:  # the current tensor is the previous layer's where possible
+                        (j0, d0), (j1, d1) = (j1, d1), (j0, d0)
+                    sd = None
+                elif chan(d0, d1):
+                    sd = tuple(d1)
+                elif chan(d1, d0):  # the full tensor is the layer's input
+                    (j0, d0), (j1, d1) = (j1, d1), (j0, d0)
+                    sd = tuple(d1)
+                else:
+                    raise NotImplementedError(f"onnx: {name}: Mul of dims {tuple(d0)} and {tuple(d1)}: only equal dims "
+                                              "and a per-channel operand ([N, C, 1, 1] or [N, C] against "
+                                              "[N, C, H, W]) are supported")
+                emit(_Spec("mul", dims=d0, sq=False, src=j1, src_dims=sd), outs[0], j0, d0, f0 * f1)
+        elif op == "Pow":
+            name = node.get("name") or op
+            j, dims, fac = data_in(node, ins[0])
+            ex = None
+            if len(ins) > 1 and ins[1] in inits and arr(ins[1]).size == 1:
+                ex = float(arr(ins[1]).reshape(-1)[0])
+            elif len(ins) > 1 and ins[1] in pow_consts:
+                ex = pow_consts[ins[1]]
+            if ex != 2.0:
+                raise NotImplementedError(f"onnx: {name}: Pow is supported with the constant scalar exponent 2 only"
+                                          + ("" if ex is None else f", got {ex}"))
+            emit(_Spec("mul", dims=dims, sq=True), outs[0], j, dims, fac * fac)
         elif op == "Concat":
             name = node.get("name") or op
             ops_ = [data_in(node, x) for x in ins]
@@ -546,10 +605,13 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             layers.append(Add(kw["dims"], spec_to_layer[kw["src"]]))
         elif s.kind == "concat":
             layers.append(Concat(kw["dims_list"], [spec_to_layer[j] for j in kw["srcs"]]))
+        elif s.kind == "mul":
+            layers.append(Mul.square(kw["dims"]) if kw["sq"] else
+                          Mul(kw["dims"], spec_to_layer[kw["src"]], kw["src_dims"]))
         if kw.get("in_src") is not None:
             layers[-1].in_src = spec_to_layer[kw["in_src"]]
         spec_to_layer[i] = len(layers) - 1
-        if s.kind in ("dense", "conv", "convt"):
+        if s.kind in ("dense", "conv", "convt", "mul"):  # a product carries both operands' scales, as a conv's does
             out = layers[-1].out_dims
             if q_method == QuantizationMethod.ScaleQuant:
                 layers.append(Rescale(q_parameter, out))
@@ -729,6 +791,10 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             nodes.append(_node("ArgMax", [cur], [out], name, _attr_int("axis", 1) + _attr_int("keepdims", 1)))
         elif isinstance(l, Add):
             nodes.append(_node("Add", [cur, names[l.src]], [out], name))
+        elif isinstance(l, Mul):  # the operands' pending average ratios multiply
+            other = cur if l.is_square else names[l.src]
+            nodes.append(_node("Mul", [cur, other], [out], name))
+            scale[out] = K * scale[other]
         elif isinstance(l, Concat):
             nodes.append(_node("Concat", [names[s] for s in l.srcs], [out], name, _attr_int("axis", 1)))
         else:

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Relu, Rescale, Sign, SumPool2d,
+from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Mul, Relu, Rescale, Sign, SumPool2d,
                          Upsample, _pool_out)
 from ..ir.quant import QuantizationMethod
 from .zoo import ARCHS, canonical
@@ -31,6 +31,23 @@ def _torch():
     import torch.nn as nn
 
     return torch, nn
+
+
+_SQUARE = None
+
+
+def _square_module():
+    """nn.Module of the zoo's ("square",) op, x -> x * x (one class per process, so to_circuit recognises it)."""
+    global _SQUARE
+    if _SQUARE is None:
+        _, nn = _torch()
+
+        class Square(nn.Module):
+            def forward(self, x):
+                return x * x
+
+        _SQUARE = Square
+    return _SQUARE
 
 
 class _FakeQuant:
@@ -97,6 +114,11 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             raise NotImplementedError(f"training: op {k} (skip connections) not supported by the sequential trainer")
         elif k == "relu":
             mods.append(nn.ReLU())
+        elif k == "square":
+            mods.append(_square_module()())
+        elif k == "se":
+            raise NotImplementedError(f"training: op {k} (squeeze-and-excitation reads its input twice) not supported "
+                                      "by the sequential trainer")
         elif k == "relu6":
             mods.append(nn.ReLU6())
         elif k == "clip":
@@ -178,6 +200,9 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
             dims = up.out_dims
         elif isinstance(m, nn.ReLU):
             layers.append(Relu(dims))
+        elif isinstance(m, _square_module()):
+            layers.append(Mul.square(dims))
+            rescale(dims)
         elif isinstance(m, nn.Hardtanh):  # nn.ReLU6 is a Hardtanh(0, 6)
             layers.append(Clip(dims, float(m.min_val), float(m.max_val), q_parameter, qm))
         elif isinstance(m, nn.Tanh):

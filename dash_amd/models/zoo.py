@@ -12,8 +12,8 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Relu, Rescale,
-                         Sign, SumPool2d, Upsample)
+from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Mul, Relu,
+                         Rescale, Sign, SumPool2d, Upsample)
 from ..ir.quant import QuantizationMethod, quantize_input
 
 # architecture ops: ("conv", out_ch, k, stride, pad) | ("relu",) | ("sign",) | ("flatten",) | ("fc", out)
@@ -34,6 +34,10 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   pad = dilation = rate (same size out), each + ReLU, all reading the same tensor, then Concat
 #                   | ("skip",) remember the current tensor | ("cat",) channel concat of the most recent open skip
 #                   with the current tensor, skip first (an encoder-decoder's skip connection)
+#                   | ("square",) x^2 (a polynomial activation) + the scheme's rescale, as after a conv
+#                   | ("se", r) squeeze-and-excitation: the current (C, H, W) tensor is kept, then gap, a 1x1 conv to
+#                   C / r + ReLU, a 1x1 conv to C, Clip(0, 1) (a hard sigmoid's range) and the channel-broadcast Mul
+#                   of the kept tensor with that gate + the scheme's rescale (refused under SimpleQuant, as a clip)
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     # MODEL_A whose decoded output is the class alone, not the ten logits
@@ -90,6 +94,16 @@ ARCHS: dict[str, dict] = {
         ("dwconv", 3, 2, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("relu6",),
         ("dwconv", 3, 1, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("relu6",),
         ("gap",), ("flatten",), ("fc", 10)]},
+    # MOBILENET_CIFAR with a squeeze-and-excitation gate (reduction 4) behind every pointwise conv
+    "SE_MOBILENET_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 1, 1), ("relu6",),
+        ("dwconv", 3, 2, 1), ("relu6",), ("conv", 32, 1, 1, 0), ("se", 4), ("relu6",),
+        ("dwconv", 3, 2, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("se", 4), ("relu6",),
+        ("dwconv", 3, 1, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("se", 4), ("relu6",),
+        ("gap",), ("flatten",), ("fc", 10)]},
+    # the CryptoNets MNIST network: squares are the only non-linearity (no sign anywhere)
+    "CRYPTONETS_MNIST": {"input": (1, 28, 28), "ops": [
+        ("conv", 5, 5, 2, 1), ("square",), ("flatten",), ("fc", 100), ("square",), ("fc", 10)]},
     # SqueezeNet-style CIFAR net: a stride-2 stem (32 -> 16), ceil-mode 3x3/2 max pools whose last window is cut at
     # the edge (16 -> 8 -> 4), two fire modules, a 1x1 classifier conv and a global average over the 4x4 plane
     "SQUEEZENET_CIFAR": {"input": (3, 32, 32), "ops": [
@@ -236,6 +250,26 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
                 raise ValueError(f"{name}: op {len(layers)} ({kind}): a clip layer has no quantization under "
                                  "SimpleQuant (no single activation scale); use ScaleQuant or ScaleQuantPlus")
             layers.append(Clip(dims, lo, hi, q_parameter, qm))
+        elif kind == "square":
+            layers.append(Mul.square(dims))
+            rescale_after(dims)
+        elif kind == "se":
+            if len(dims) != 3 or dims[0] % op[1]:
+                raise ValueError(f"{name}: op {len(layers)} (se): needs a (C, H, W) tensor whose channels {op[1]} divides")
+            if qm == QuantizationMethod.SimpleQuant:
+                raise ValueError(f"{name}: op {len(layers)} (se): its Clip(0, 1) gate has no quantization under "
+                                 "SimpleQuant (no single activation scale); use ScaleQuant or ScaleQuantPlus")
+            full, fd = len(layers) - 1, dims
+            sp = SumPool2d(fd[2], fd[1], fd[0], fd[2], fd[1])
+            layers.append(sp)
+            d_sq = conv(fd[0] // op[1], 1, 1, 0, fd[0], 1, 1)
+            layers.append(Relu(d_sq))
+            d_ex = conv(fd[0], 1, 1, 0, d_sq[0], 1, 1)
+            layers.append(Clip(d_ex, 0.0, 1.0, q_parameter, qm))
+            mul = Mul(fd, len(layers) - 1, (fd[0], 1, 1))
+            mul.in_src = full  # the full tensor is the Mul's input, the gate its operand
+            layers.append(mul)
+            rescale_after(fd)
         elif kind == "argmax":
             am = ArgMax(dims)
             layers.append(am)
