@@ -26,7 +26,9 @@ __device__ __forceinline__ u128 add_packed(u128 a, u128 b, u128 hmask) {
 // the next chunk's loads issued before the current one is consumed. The
 // payloads P_{l,j} of digit l for later residues j go to a per-lane scratch
 // (a.ps, [B][pair][N], coalesced) and are read back when digit j starts:
-// holding them in registers (up to K(K-1)/2 u128) spilled.
+// holding them in registers (up to K(K-1)/2 u128) spilled. (The staged form k_mrs_chain_s folds the sign
+// position's payloads and keeps some of the others in LDS; folding them here too raised this form's registers and
+// scratch, mode 2: 92 -> 120 B per lane, mode 1: 94 -> 119 VGPRs, so it stays as it was.)
 #ifndef DASH_MRS_CHUNK
 #define DASH_MRS_CHUNK 4  // 8: mode-2 chain spilled 84 B/lane, 4: 28 (mode 0: 52 -> 0); 24 GCs 13.07 -> 12.96 ms
 #endif
@@ -169,8 +171,159 @@ __global__ __launch_bounds__(kAesBlock, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_
 // components from LDS. The per-lane form (k_mrs_chain) loaded one byte per lane per component, kMrsChunk
 // at a time: ~n / 4 dependent HBM round trips per position, 65 % of its cycles waiting (r03 roofline:
 // 0.87 TB/s fetched). Outputs, payload scratch and table gathers are per lane as before.
+//
+// Pair payloads. Position l's row holds a payload P[l][j] for every later position j, read when j starts. They went
+// through the HBM scratch a.ps (16 B stored and 16 B loaded per pair and element: 29 % of the kernel's bytes at
+// K = 7). Here:
+//  * modes 1 and 2: the payloads aimed at the last position (residue 0, mod 2) are only ever XORed into its key,
+//    so they fold into one running accumulator (sx) and are never stored;
+//  * the others live in kChainSlots LDS slots of one u128 per lane, psl[slot][kMrsBS]. A lane touches only its own
+//    column (no barrier; 16 B lane stride, conflict-free b128 accesses), and a slot is reused once its pair has
+//    been read. Pairs that do not fit keep the a.ps path, the longest-lived first (chain_slot_map).
+// Two 512-lane blocks per CU (4 waves per SIMD, the register budget) leave a block 80 KiB of LDS: 6 slots of 8 KiB
+// beside the 32 KiB staging image, or 8 slots beside a 16 KiB image. On one stream the kernel is fastest with 6
+// slots, but the headline runs three groups at once and the LDS the chain holds is LDS the other groups' kernels
+// cannot have: from 2 slots on (96 KiB for the two blocks) a CU no longer fits four 20 KiB blocks of
+// k_rescale_relu_out_t beside them and the step is 2 % slower than with none. One slot (the neighbour pairs
+// (i, i + 1) share it) is the most that costs nothing there, and is the default. DASH_CHAIN_LDS_SLOTS=0 restores
+// the all-HBM payload path, =6 / =8 are the single-stream forms (A/B, profiles/ab/chain_lds/README.md).
 constexpr int kMrsBS = 512;   // elements (lanes) per block
-constexpr int kMrsCap = 64;   // components staged per pass (kMrsCap * kMrsBS = 32 KiB)
+#ifndef DASH_CHAIN_LDS_SLOTS
+#define DASH_CHAIN_LDS_SLOTS 1
+#endif
+constexpr int kChainSlots = DASH_CHAIN_LDS_SLOTS;
+#ifndef DASH_CHAIN_FOLD
+#define DASH_CHAIN_FOLD 1  // 0: the sign position's payloads are stored and read back like the others (A/B)
+#endif
+constexpr bool kChainFold = DASH_CHAIN_FOLD != 0;
+#ifndef DASH_MRS_CAP
+#define DASH_MRS_CAP (DASH_CHAIN_LDS_SLOTS > 6 ? 32 : 64)
+#endif
+constexpr int kMrsCap = DASH_MRS_CAP;   // components staged per pass (kMrsCap * kMrsBS bytes: 32 KiB at 64)
+constexpr int kChainLds = kChainSlots * 16 * kMrsBS + kMrsCap * kMrsBS;  // slots first: their offsets fit a ds offset field
+static_assert(kChainSlots >= 0 && kChainSlots * 16 * kMrsBS <= (64 << 10), "slot offsets are instruction immediates (16 bits)");
+static_assert(kChainLds <= (80 << 10), "two staged-chain blocks per CU: at most 80 KiB of LDS each");
+static_assert(kMrsCap >= 20 && kMrsCap % 4 == 0, "a staging pass holds whole chunks: m.c <= 20 (p = 3)");
+
+constexpr int kPsHbm = -1;   // pair kept in a.ps
+constexpr int kPsFold = -2;  // pair folded into the sign position's XOR accumulator
+constexpr int kPsNone = -3;  // (allocator: not placed yet)
+constexpr int chain_pair_idx(int K, int l, int j) { return l * (2 * K - l - 1) / 2 + (j - l - 1); }  // = mrs_pair<K>
+template <int K>
+struct ChainSlotMap {
+    int slot[K * (K - 1) / 2 > 0 ? K * (K - 1) / 2 : 1];
+};
+// Where each pair (l, j) of a K-position chain lives, with S LDS slots. Pair (l, j) is live from the end of position
+// l to the start of position j, i.e. over the position boundaries l .. j - 1. While more than S pairs are live at
+// some boundary, the longest-lived pair live at the first fullest boundary goes to a.ps (earliest l on ties); the
+// rest are interval-coloured in order of their start, which needs no more slots than the fullest boundary holds.
+template <int K, int MODE, int S>
+constexpr ChainSlotMap<K> chain_slot_map() {
+    ChainSlotMap<K> r{};
+    constexpr int jmax = MODE >= 1 && kChainFold ? K - 2 : K - 1;  // the last position that reads stored pairs
+    int live[K + 1] = {};
+    for (int l = 0; l < K; ++l)
+        for (int j = l + 1; j < K; ++j) {
+            const int p = chain_pair_idx(K, l, j);
+            if (j > jmax) r.slot[p] = kPsFold;
+            else if (S <= 0) r.slot[p] = kPsHbm;
+            else {
+                r.slot[p] = kPsNone;
+                for (int t = l; t < j; ++t) ++live[t];
+            }
+        }
+    while (true) {
+        int tp = 0;
+        for (int t = 1; t < K; ++t)
+            if (live[t] > live[tp]) tp = t;
+        if (live[tp] <= S) break;
+        int bl = -1, bj = -1;
+        for (int l = 0; l <= tp; ++l)
+            for (int j = tp + 1; j <= jmax; ++j)
+                if (r.slot[chain_pair_idx(K, l, j)] == kPsNone && (bl < 0 || j - l > bj - bl)) bl = l, bj = j;
+        r.slot[chain_pair_idx(K, bl, bj)] = kPsHbm;
+        for (int t = bl; t < bj; ++t) --live[t];
+    }
+    int busy_to[S > 0 ? S : 1] = {};  // the position that reads the slot's pair (slots are free from its start on)
+    for (int l = 0; l < K; ++l)
+        for (int j = l + 1; j <= jmax; ++j) {
+            const int p = chain_pair_idx(K, l, j);
+            if (r.slot[p] != kPsNone) continue;
+            for (int s = 0; s < S; ++s)
+                if (busy_to[s] <= l) {
+                    r.slot[p] = s;
+                    busy_to[s] = j;
+                    break;
+                }
+        }
+    return r;
+}
+// every pair is placed (folded exactly where the mode folds, else a.ps or a slot below S), and two pairs that are
+// live at the same time never share a slot
+template <int K, int MODE, int S>
+constexpr bool chain_slot_map_ok() {
+    const ChainSlotMap<K> m = chain_slot_map<K, MODE, S>();
+    for (int l = 0; l < K; ++l)
+        for (int j = l + 1; j < K; ++j) {
+            const int s = m.slot[chain_pair_idx(K, l, j)];
+            if (MODE >= 1 && kChainFold && j == K - 1) {
+                if (s != kPsFold) return false;
+                continue;
+            }
+            if (s != kPsHbm && (s < 0 || s >= S)) return false;
+            if (s < 0) continue;
+            for (int l2 = 0; l2 < K; ++l2)
+                for (int j2 = l2 + 1; j2 < K; ++j2)
+                    if ((l2 != l || j2 != j) && m.slot[chain_pair_idx(K, l2, j2)] == s && l < j2 && l2 < j) return false;
+        }
+    return true;
+}
+template <int S, int... Ks>
+constexpr bool chain_slot_maps_ok() {
+    return ((chain_slot_map_ok<Ks, 0, S>() && chain_slot_map_ok<Ks, 1, S>() && chain_slot_map_ok<Ks, 2, S>()) && ...);
+}
+static_assert(chain_slot_maps_ok<kChainSlots, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>(), "pair slot map (build's slot count)");
+static_assert(chain_slot_maps_ok<6, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>() && chain_slot_maps_ok<8, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>() &&
+                  chain_slot_maps_ok<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>() && chain_slot_maps_ok<0, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>(),
+              "pair slot map (the measured slot counts, one slot, none)");
+// K = 7, joint mode, 6 slots: 6 pairs folded, 12 in LDS, (0,4), (0,5), (1,5) in a.ps
+static_assert(!kChainFold ||
+                  (chain_slot_map<7, 2, 6>().slot[chain_pair_idx(7, 0, 4)] == kPsHbm && chain_slot_map<7, 2, 6>().slot[chain_pair_idx(7, 0, 5)] == kPsHbm &&
+                   chain_slot_map<7, 2, 6>().slot[chain_pair_idx(7, 1, 5)] == kPsHbm && chain_slot_map<7, 2, 6>().slot[chain_pair_idx(7, 0, 3)] >= 0),
+              "K = 7 joint chain: the three longest-lived pairs overflow");
+template <int K, int MODE>
+struct ChainSlotsOf {
+    static constexpr ChainSlotMap<K> map = chain_slot_map<K, MODE, kChainSlots>();
+};
+// position I's stored row entries: E[t] is the payload of pair (I, I + 1 + t)
+template <int K, int MODE, int I, int T = 0, int NT>
+__device__ __forceinline__ void chain_s_put(const u128 (&E)[NT], u128* PS, u128* psl, int64_t N, bool valid, u128& sx) {
+    if constexpr (T < K - 1 - I) {
+        constexpr int p = chain_pair_idx(K, I, I + 1 + T);
+        constexpr int s = ChainSlotsOf<K, MODE>::map.slot[p];
+        if constexpr (s == kPsFold) {
+            // the empty asm pins the running value: the optimiser otherwise rebuilds the whole XOR chain at its last
+            // use, and every position's term stays live until the tail (K = 7 joint chain: 212 B of scratch per lane)
+            uint64_t lo = static_cast<uint64_t>(sx ^ E[T]), hi = static_cast<uint64_t>((sx ^ E[T]) >> 64);
+            asm("" : "+v"(lo), "+v"(hi));
+            sx = (static_cast<u128>(hi) << 64) | lo;
+        } else if constexpr (s >= 0) psl[s * kMrsBS] = E[T];  // spare lanes write their own column
+        else if (valid) PS[static_cast<int64_t>(p) * N] = E[T];
+        chain_s_put<K, MODE, I, T + 1>(E, PS, psl, N, valid, sx);
+    }
+}
+// position I's payload streams Q[l] = P[l][I]: the pairs kept in a.ps (LDS = false) or those in LDS slots
+template <int K, int MODE, int I, bool LDS, int L = 0, int NQ>
+__device__ __forceinline__ void chain_s_get(u128 (&Q)[NQ], const u128* PS, const u128* psl, int64_t N) {
+    if constexpr (L < I) {
+        constexpr int p = chain_pair_idx(K, L, I);
+        constexpr int s = ChainSlotsOf<K, MODE>::map.slot[p];
+        static_assert(s != kPsFold && s != kPsNone, "a folded pair has no reader");
+        if constexpr (LDS && s >= 0) Q[L] = psl[s * kMrsBS];
+        if constexpr (!LDS && s < 0) Q[L] = PS[static_cast<int64_t>(p) * N];
+        chain_s_get<K, MODE, I, LDS, L + 1>(Q, PS, psl, N);
+    }
+}
 #ifndef DASH_STAGE_U
 #define DASH_STAGE_U 2  // 16-byte loads in flight per thread while staging (4 pushed the chain into spills)
 #endif
@@ -183,8 +336,9 @@ constexpr int kStageRd = DASH_STAGE_RD;
 template <int K, int MODE, int I>
 __device__ __forceinline__ void chain_s_pos(const MrsArgs& a, uint64_t gate, const ModC* mc, const Act& x,
                                             uint8_t* stg, int b, int64_t N, int64_t e0, int tid, bool valid,
-                                            const u128* row0, u128* PS, u128& acc) {
+                                            const u128* row0, u128* PS, u128* psl, u128& acc, u128& sx) {
     constexpr int kLast = MODE >= 1 ? K - 1 : K;
+    constexpr int NQ = I > 0 ? I : 1;
     if constexpr (I < kLast) {
         constexpr int i = I;
         {
@@ -198,15 +352,18 @@ __device__ __forceinline__ void chain_s_pos(const MrsArgs& a, uint64_t gate, con
             constexpr int nt = K - 1 - i + kExtra;
             u128 pf0 = 0, pf1 = 0;  // the row's first and last entries, loaded as soon as the row index is known
             if constexpr (r == 0) {  // residue 0, the base's power of two (mrs_staged checks): per-digit streams
-                DigitStream ds[K > 1 ? K - 1 : 1];
+                u128 Q[NQ];
+                chain_s_get<K, MODE, I, false>(Q, PS, psl, N);
+                chain_s_get<K, MODE, I, true>(Q, PS, psl, N);
+                DigitStream ds[NQ];
 #pragma unroll
-                for (int l = 0; l < i; ++l) ds[l].init(PS[static_cast<int64_t>(mrs_pair<K>(l, i)) * N]);
+                for (int l = 0; l < i; ++l) ds[l].init(Q[l]);
                 CompressFwd cf;
                 cf.init();
                 for (int c0 = 0; c0 < n; c0 += kMrsCap) {
                     const int cnt = min(kMrsCap, n - c0);
                     __syncthreads();
-                    lds_stage_rows<kMrsBS, kStageU>(stg, L, N, e0, c0, cnt);
+                    lds_stage_rows<kMrsBS, kStageU, true>(stg, L, N, e0, c0, cnt);
                     __syncthreads();
                     for (int c = 0; c < cnt; ++c) {
                         uint32_t d = valid ? stg[c * kMrsBS + tid] : 0u;  // spare lanes read no staged bytes
@@ -230,19 +387,21 @@ __device__ __forceinline__ void chain_s_pos(const MrsArgs& a, uint64_t gate, con
             } else {
                 // chunk-major walk (as k_mrs_chain_w): passes of whole chunks, one divmod per stream per chunk of
                 // m.c digits, wave-uniform digit loops, one compress flush per chunk
-                u128 Q[K > 1 ? K - 1 : 1];
-#pragma unroll
-                for (int l = 0; l < i; ++l) Q[l] = PS[static_cast<int64_t>(mrs_pair<K>(l, i)) * N];
+                // the streams kept in a.ps load across the first staging pass; those in LDS slots are read after it,
+                // so they are not live over its barriers
+                u128 Q[NQ];
+                chain_s_get<K, MODE, I, false>(Q, PS, psl, N);
                 u128 C = 0, PW = 1;
                 const int mcn = static_cast<int>(m.c);
                 const int pass = kMrsCap / mcn * mcn;
                 for (int p0 = 0; p0 < n; p0 += pass) {
                     const int pcnt = min(pass, n - p0);
                     __syncthreads();
-                    lds_stage_rows<kMrsBS, kStageU>(stg, L, N, e0, p0, pcnt);
+                    lds_stage_rows<kMrsBS, kStageU, true>(stg, L, N, e0, p0, pcnt);
                     __syncthreads();
+                    if (p0 == 0) chain_s_get<K, MODE, I, true>(Q, PS, psl, N);
                     for (int c0 = 0; c0 < pcnt; c0 += mcn) {
-                        uint32_t rr[K > 1 ? K - 1 : 1];
+                        uint32_t rr[NQ];
 #pragma unroll
                         for (int l = 0; l < i; ++l) rr[l] = divmod128(Q[l], m);
                         const int cnt = min(mcn, pcnt - c0);
@@ -281,19 +440,16 @@ __device__ __forceinline__ void chain_s_pos(const MrsArgs& a, uint64_t gate, con
                 key = C;
             }
             const u128* row = row0 + a.dig_off[i] + static_cast<int64_t>(col) * nt;
-            u128 E[K];
+            u128 E[nt];
             E[0] = pf0;
 #pragma unroll
             for (int t = 1; t < nt - 1; ++t) E[t] = row[t];  // the lines were brought in by the early loads
-            if (nt > 1) E[nt - 1] = pf1;
-            hard_unmask_n<K>(E, nt, key, gate, mrs_row_sub<MODE>(i));
-            if (valid) {
-#pragma unroll
-                for (int t = 0; t < K - 1 - i; ++t) PS[static_cast<int64_t>(mrs_pair<K>(i, i + 1 + t)) * N] = E[t];
-            }
+            if constexpr (nt > 1) E[nt - 1] = pf1;
+            hard_unmask<nt>(E, key, gate, mrs_row_sub<MODE>(i));
+            chain_s_put<K, MODE, I>(E, PS, psl, N, valid, sx);
             if constexpr (MODE != 1) acc = add_packed(acc, E[K - 1 - i], a.hmask);
         }
-        chain_s_pos<K, MODE, I + 1>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, acc);
+        chain_s_pos<K, MODE, I + 1>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, psl, acc, sx);
     }
 }
 
@@ -302,19 +458,22 @@ __global__ __launch_bounds__(kMrsBS, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_MIN
     MrsArgs a, Act x, const ModC* mc, const uint32_t* te0, const uint32_t* rk) {
     (void)te0;
     (void)rk;
-    __shared__ __attribute__((aligned(16))) uint8_t stg[kMrsCap * kMrsBS];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kChainLds];  // pair slots [slot][kMrsBS] of u128, then the staging image
     const int b = blockIdx.z;
     const int64_t N = a.N;
     constexpr int NP = K * (K - 1) / 2 > 0 ? K * (K - 1) / 2 : 1;
     const int tid = static_cast<int>(threadIdx.x);
+    u128* psl = reinterpret_cast<u128*>(lds) + tid;  // this lane's column: slot s at psl[s * kMrsBS]
+    uint8_t* stg = lds + kChainSlots * 16 * kMrsBS;
     for (int64_t e0 = static_cast<int64_t>(blockIdx.x) * kMrsBS; e0 < N; e0 += static_cast<int64_t>(gridDim.x) * kMrsBS) {
         const bool valid = e0 + tid < N;
         const int64_t e = valid ? e0 + tid : N - 1;  // spare lanes shadow a real element, store nothing
         const u128* row0 = a.tab + (static_cast<int64_t>(b) * N + e) * a.n_tab;
         u128* PS = a.ps + static_cast<int64_t>(b) * NP * N + e;
         u128 acc = 0;
+        u128 sx = 0;  // modes 1, 2: XOR of the payloads aimed at the sign position (reset per tile)
         const uint64_t gate = a.gate0 ^ static_cast<uint64_t>(e);
-        chain_s_pos<K, MODE, 0>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, acc);
+        chain_s_pos<K, MODE, 0>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, psl, acc, sx);
         if (MODE >= 1) {
             const ModC m = mc[a.crt.p[0]];
             const int n = static_cast<int>(m.n);
@@ -325,7 +484,7 @@ __global__ __launch_bounds__(kMrsBS, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_MIN
             for (int c0 = 0; c0 < n; c0 += kMrsCap) {
                 const int cnt = min(kMrsCap, n - c0);
                 __syncthreads();
-                lds_stage_rows<kMrsBS, kStageU>(stg, L, N, e0, c0, cnt);
+                lds_stage_rows<kMrsBS, kStageU, true>(stg, L, N, e0, c0, cnt);
                 __syncthreads();
                 if (m.bits == 1) {
                     for (int w0 = 0; w0 < cnt; w0 += 32) {
@@ -340,8 +499,15 @@ __global__ __launch_bounds__(kMrsBS, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_MIN
                 }
             }
             u128 key = m.bits == 1 ? kb : cf.finish();
+            if constexpr (kChainFold) {
+                key ^= sx;  // mod-2 subtraction of the K - 1 payloads aimed here
+            } else {
+                u128 Q[K > 1 ? K - 1 : 1];
+                chain_s_get<K, MODE, K - 1, false>(Q, PS, psl, N);
+                chain_s_get<K, MODE, K - 1, true>(Q, PS, psl, N);
 #pragma unroll
-            for (int l = 0; l < K - 1; ++l) key ^= PS[static_cast<int64_t>(mrs_pair<K>(l, K - 1)) * N];
+                for (int l = 0; l < K - 1; ++l) key ^= Q[l];
+            }
             const uint32_t c = static_cast<uint32_t>(key) & 1u;
             u128 E = 0;
             if (MODE == 2) E = row0[a.dig_off[K - 1] + c] - hard_pad(key, gate, mrs_row_sub<MODE>(K - 1), 0);
