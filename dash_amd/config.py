@@ -43,6 +43,7 @@ class DashConfig:
     q_method: Optional[str] = None            # override: SimpleQuant | ScaleQuant | ScaleQuantPlus
     q_parameter: Optional[int] = None
     q_const: float = 0.02                     # SimpleQuant constant (onnx_modelloader.h:377)
+    leaky_bits: int = 4                       # slope bits s of LeakyRelu / PRelu layers: slope = round(alpha 2^s) / 2^s, 1..8 (docs/LEAKY_RELU.md)
     # garbling
     crt: Union[int, list, None] = None        # k (first k primes) or explicit base
     mrs: Union[float, list, None] = None      # ReLU accuracy (table lookup) or explicit MRS base

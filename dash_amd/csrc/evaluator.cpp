@@ -161,6 +161,8 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
         const u64 L = li + 1;  // the garbler's layer index (stream ids / hardened tweak gates)
         if (g.p.count("in_src")) cur = saved[g.param("in_src") + 1];
         const i64 Nin = cur[0].N;
+        CrtLabels leaky_x;  // LeakyRelu: the input labels outlive the ReLU (gadgets.h LeakyPlan)
+        if (g.kind == K_LEAKY) leaky_x = cur;
         switch (g.kind) {
             case K_FLATTEN:
                 break;
@@ -308,7 +310,8 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 cur = std::move(nxt);
                 break;
             }
-            case K_RELU: {
+            case K_RELU:
+            case K_LEAKY: {
                 if (trace) trace->relu_in[li] = cur;
                 if (g.param("smode", 0) == 2) {  // sign from the preceding rescale (RescaleMrsPlan::sign_last)
                     DASH_CHECK(sig_joint.N == Nin, "joint ReLU without a preceding sign-producing rescale");
@@ -814,6 +817,8 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
             default:
                 throw std::runtime_error("dash: cannot evaluate layer kind " + std::to_string(g.kind));
         }
+        if (g.kind == K_LEAKY)  // active labels: out = (n_c mod p) x + ((2^s - n_c) mod p) relu
+            LeakyPlan(g.param("s"), g.vec("n"), g.param("bc"), Nin).map(leaky_x, cur, cur);
         if (keep[li + 1]) saved[li + 1] = cur;
         if (layer_ms)
             (*layer_ms)[li] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_layer).count();

@@ -579,4 +579,49 @@ void mul_garble_elem(const MulPlan& P, const LabelBank& R, const Prg& prg, u64 s
 void mul_eval_elem(const MulPlan& P, u64 gate, const comp_t* const* x, const comp_t* const* y, const u128* g,
                    const u128* e, comp_t* const* out);
 
+// ----------------------------------------------------------------------------
+// LeakyRelu (wire kind 20, docs/LEAKY_RELU.md): y = 2^s x (x >= 0), n_c x (x < 0), n_c in [0, 2^s) per
+// channel c = e / bc, which is n_c x + (2^s - n_c) relu(x). A public multiple and a sum of labels of one
+// residue are free, so the layer garbles exactly the ReLU of its resolved sign construction (same arrays,
+// layouts, PRG streams and gate ids: the tables are a ReLU's byte for byte) and then maps the labels per
+// residue p: out = (n_c mod p) x + ((2^s - n_c) mod p) relu. The garbler maps the zero labels, the evaluator
+// the active ones.
+struct LeakyPlan {
+    int s = 0;
+    std::vector<i64> n;  // one slope numerator, or one per channel
+    i64 bc = 0;          // elements per channel
+    LeakyPlan() = default;
+    LeakyPlan(i64 s_, const std::vector<i64>& n_, i64 bc_, i64 N) : s(static_cast<int>(s_)), n(n_), bc(bc_) {
+        DASH_CHECK(s_ >= 1 && s_ <= 8, "leaky_relu: slope_bits outside [1, 8]");
+        DASH_CHECK(!n.empty() && bc >= 1 && (n.size() == 1 || static_cast<i64>(n.size()) * bc == N),
+                   "leaky_relu: slope table does not match the tensor");
+        for (i64 v : n) DASH_CHECK(v >= 0 && v < (i64{1} << s), "leaky_relu: slope numerator outside [0, 2^s)");
+    }
+    i64 channel(i64 e) const { return n.size() == 1 ? 0 : e / bc; }
+    int b(i64 ch, int p) const { return static_cast<int>(n[ch] % p); }
+    int c(i64 ch, int p) const { return static_cast<int>(((i64{1} << s) - n[ch]) % p); }
+    // the device tables: [channel][residue] pairs (b, c) as b | c << 8 (p <= 251)
+    std::vector<uint16_t> table(const std::vector<int>& crt) const {
+        std::vector<uint16_t> t(n.size() * crt.size());
+        for (size_t ch = 0; ch < n.size(); ++ch)
+            for (size_t j = 0; j < crt.size(); ++j)
+                t[ch * crt.size() + j] = static_cast<uint16_t>(b(ch, crt[j]) | (c(ch, crt[j]) << 8));
+        return t;
+    }
+    // out = b x + c relu per element and residue; out may alias relu
+    void map(const CrtLabels& x, const CrtLabels& relu, CrtLabels& out) const {
+        for (size_t j = 0; j < x.size(); ++j) {
+            const int p = x[j].p, nn = x[j].n;
+            for (i64 e = 0; e < x[j].N; ++e) {
+                const i64 ch = channel(e);
+                const int bb = b(ch, p), cc = c(ch, p);
+                const comp_t* xe = x[j].at(e);
+                const comp_t* re = relu[j].at(e);
+                comp_t* oe = out[j].at(e);
+                for (int i = 0; i < nn; ++i) oe[i] = static_cast<comp_t>((bb * xe[i] + cc * re[i]) % p);
+            }
+        }
+    }
+};
+
 }  // namespace dash

@@ -37,6 +37,7 @@ const char* kind_name(int kind) {
         case K_CLIP: return "clip";
         case K_ARGMAX: return "argmax";
         case K_MUL: return "mul";
+        case K_LEAKY: return "leaky_relu";
         case K_CONVT: return "conv_transpose2d";
         case K_UPSAMPLE: return "upsample";
     }
@@ -729,9 +730,11 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
 
         // legacy rescale as one mixed-radix gadget (RescaleMrsPlan)
         const bool mrs_rescale = opt.rescale_mrs && spec.kind == K_RESCALE && param1(spec.p, "mode", 0) == 0;
-        const bool relu_mrs = opt.relu_mrs && spec.kind == K_RELU;
+        const bool leaky = spec.kind == K_LEAKY;  // a ReLU's garbling, then the free label map (gadgets.h LeakyPlan)
+        const bool relu_mrs = opt.relu_mrs && (spec.kind == K_RELU || leaky);
         const bool relu_next = mrs_rescale && opt.relu_joint && li + 1 < layers.size() &&
-                               layers[li + 1].kind == K_RELU && param1(layers[li + 1].p, "in_src", -2) == -2;
+                               (layers[li + 1].kind == K_RELU || layers[li + 1].kind == K_LEAKY) &&
+                               param1(layers[li + 1].p, "in_src", -2) == -2;
         // a Clip(0, q_hi) directly behind this rescale takes its lower sign from the conversion too, and its
         // upper sign is garbled here, on the rescale's input labels (gadgets.h ClipPlan, joint variant)
         const bool clip_next = mrs_rescale && opt.clip_joint && hard && li + 1 < layers.size() &&
@@ -744,7 +747,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                               spec.kind == K_ADD || spec.kind == K_CONCAT || spec.kind == K_CONVT ||
                               spec.kind == K_UPSAMPLE;
         const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
-                                    (spec.kind == K_RELU || spec.kind == K_SIGN ||
+                                    (spec.kind == K_RELU || spec.kind == K_SIGN || spec.kind == K_LEAKY ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
                                     spec.kind == K_CLIP || spec.kind == K_ARGMAX ||
                                     (spec.kind == K_MUL && GpuGarbler::mul_fits(k, param1(spec.p, "sq", 0) != 0)) ||
@@ -756,6 +759,15 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         } else if (!on_gpu && !passthru && !host_ok) {
             gpu->to_host(cur);
             host_ok = true;
+        }
+        // LeakyRelu: the input zero labels x0 outlive the ReLU garbling (host copy, or a device copy in the GPU
+        // garbler)
+        CrtLabels leaky_x0;
+        LeakyPlan leaky_plan;
+        if (leaky) {
+            leaky_plan = LeakyPlan(param1(spec.p, "s"), paramv(spec.p, "n"), param1(spec.p, "bc"), Nin);
+            if (on_gpu) gpu->leaky_keep(cur);
+            else leaky_x0 = cur;
         }
         switch (spec.kind) {
             case K_FLATTEN: {
@@ -969,7 +981,8 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 cur = std::move(nxt);
                 break;
             }
-            case K_RELU: {
+            case K_RELU:
+            case K_LEAKY: {
                 DASH_CHECK(is_crt(), "relu needs CRT-base labels");
                 if (sig_in) {
                     // sign from the preceding rescale (RescaleMrsPlan::sign_last): mixed-modulus half gates only
@@ -1788,6 +1801,10 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
             }
             default:
                 throw std::runtime_error(std::string("dash: cannot garble layer kind ") + std::to_string(spec.kind));
+        }
+        if (leaky) {  // zero labels: out0 = (n_c mod p) x0 + ((2^s - n_c) mod p) relu0
+            if (on_gpu) gpu->leaky_map(leaky_plan, cur);
+            else leaky_plan.map(leaky_x0, cur, cur);
         }
         if (on_gpu) host_ok = false;
         else if (!passthru) dev_ok = false;

@@ -70,6 +70,30 @@ __device__ __forceinline__ uint32_t mult_digit(uint32_t ev, uint32_t ypr, uint32
     return modq(ev + ypr * x + static_cast<uint32_t>(p) - g, m);
 }
 
+// LeakyRelu (gadgets.h LeakyPlan): a lane's two public factors, b = n_c mod p and c = (2^s - n_c) mod p, read
+// once per lane from the layer's table [channel][residue] (b | c << 8), channel = e / bc.
+struct LeakyLane {
+    uint32_t fb, fc;
+};
+__device__ __forceinline__ LeakyLane leaky_lane(const LeakyTab& lk, int64_t e, int j, int k) {
+    const uint32_t ch = static_cast<uint32_t>(e) / lk.bc;  // N < 2^32 (plan_leaky)
+    const uint32_t v = lk.t[static_cast<int64_t>(ch) * k + j];
+    return LeakyLane{v & 0xffu, v >> 8};
+}
+// The x multiplier of a leaky digit, folded once per lane: yl = (c ypr + b) mod p; c ypr + b < p^2
+__device__ __forceinline__ uint32_t leaky_mult(uint32_t ypr, const LeakyLane& l, const ModC& m) {
+    return modq(l.fc * ypr + l.fb, m);
+}
+// One digit of the leaky multiply: b x + c t with the ReLU digit t = ev + ypr x - g, computed as
+// c (ev + p - g) + yl x in one reduction. All of ev, g, x, c, yl in [0, p), so the sum stays below
+// (p - 1)(2p - 1) + (p - 1)^2 = (p - 1)(3p - 2): outside mult_digit's p^2 + 3p, inside the range in which modq's
+// reciprocal (one correction) is exact, x < 2^32. tests/test_leaky_relu.py checks this formula with the same
+// constants for every prime <= 37 and all operand values.
+__device__ __forceinline__ uint32_t leaky_digit(uint32_t ev, uint32_t yl, uint32_t x, int p, uint32_t g, uint32_t fc,
+                                                const ModC& m) {
+    return modq(fc * (ev + static_cast<uint32_t>(p) - g) + yl * x, m);
+}
+
 // ---------------------------------------------------------------------------
 // Per-lane HBM column walk: dst[c * N] = f(c, src[c * N]) for c < n in component order, G components per round
 // trip (dst may alias src). The loads of group c+1 go out before the stores of group c: vmcnt retires in issue
@@ -144,11 +168,13 @@ __device__ __forceinline__ void lds_bit_rows(uint8_t* col, int cnt, u128 W, F&& 
 }
 
 // Chunk-major multiply walk (odd moduli, chunk_digit): one divmod per stream per chunk, uniform digit loops.
-// CLIP adds the cap row's stream C.
-template <int BS, bool CLIP>
+// CLIP adds the cap row's stream C. LEAKY: the digit becomes b x + c t (leaky_digit; no Clip form).
+template <int BS, bool CLIP, bool LEAKY = false>
 __device__ __forceinline__ void lds_mult_chunks(uint8_t* col, int n, u128 G, u128 E, u128 C, uint32_t ypr, int p,
-                                                const ModC& m) {
+                                                const ModC& m, LeakyLane lk = LeakyLane{0u, 0u}) {
+    static_assert(!(CLIP && LEAKY), "no leaky Clip");
     const int c = static_cast<int>(m.c);
+    const uint32_t yl = LEAKY ? leaky_mult(ypr, lk, m) : 0u;
     for (int k0 = 0; k0 < n; k0 += c) {
         uint32_t rg = divmod128(G, m), re = divmod128(E, m), rc = CLIP ? divmod128(C, m) : 0u;
         const int kc = min(c, n - k0);
@@ -157,32 +183,45 @@ __device__ __forceinline__ void lds_mult_chunks(uint8_t* col, int n, u128 G, u12
             const uint32_t g = chunk_digit(rg, m);
             const uint32_t ev = chunk_digit(re, m) + (CLIP ? chunk_digit(rc, m) : 0u);
             uint8_t& v = col[(k0 + t) * BS];
-            v = static_cast<uint8_t>(mult_digit(ev, ypr, v, p, g, m));
+            if (LEAKY)
+                v = static_cast<uint8_t>(leaky_digit(ev, yl, v, p, g, lk.fc, m));
+            else
+                v = static_cast<uint8_t>(mult_digit(ev, ypr, v, p, g, m));
         }
     }
 }
 
 // The staged multiply of a whole column, in place: p = 2 as bit logic ((e + ypr x + 2 - g + c) mod 2 =
 // e ^ g ^ c ^ (ypr & x); the residue with the most components, 128), other power-of-two moduli as digit
-// streams, odd moduli chunk-major.
-template <int BS, bool CLIP>
+// streams, odd moduli chunk-major. LEAKY: b x + c t per digit, p = 2 still bit logic, (b & x) ^ (c & t).
+template <int BS, bool CLIP, bool LEAKY = false>
 __device__ __forceinline__ void lds_mult_walk(uint8_t* col, int n, u128 G, u128 E, u128 C, uint32_t ypr, int p,
-                                              const ModC& m) {
+                                              const ModC& m, LeakyLane lk = LeakyLane{0u, 0u}) {
+    static_assert(!(CLIP && LEAKY), "no leaky Clip");
     if (m.bits == 1) {
-        lds_bit_rows<BS>(col, n, CLIP ? G ^ E ^ C : G ^ E, [=](uint32_t bit, uint32_t x) { return bit ^ (x & ypr); });
+        if (LEAKY)
+            lds_bit_rows<BS>(col, n, G ^ E, [=](uint32_t bit, uint32_t x) {
+                return (lk.fb & x) ^ (lk.fc & (bit ^ (x & ypr)));
+            });
+        else
+            lds_bit_rows<BS>(col, n, CLIP ? G ^ E ^ C : G ^ E, [=](uint32_t bit, uint32_t x) { return bit ^ (x & ypr); });
     } else if (m.bits) {
         DigitStream sg, se, sc;
         sg.init(G);
         se.init(E);
         sc.init(C);
+        const uint32_t yl = LEAKY ? leaky_mult(ypr, lk, m) : 0u;
         for (int c = 0; c < n; ++c) {
             const uint32_t g = sg.next(m);
             const uint32_t ev = se.next(m) + (CLIP ? sc.next(m) : 0u);
             uint8_t& v = col[c * BS];
-            v = static_cast<uint8_t>(mult_digit(ev, ypr, v, p, g, m));
+            if (LEAKY)
+                v = static_cast<uint8_t>(leaky_digit(ev, yl, v, p, g, lk.fc, m));
+            else
+                v = static_cast<uint8_t>(mult_digit(ev, ypr, v, p, g, m));
         }
     } else {
-        lds_mult_chunks<BS, CLIP>(col, n, G, E, C, ypr, p, m);
+        lds_mult_chunks<BS, CLIP, LEAKY>(col, n, G, E, C, ypr, p, m, lk);
     }
 }
 

@@ -1826,6 +1826,38 @@ __global__ __launch_bounds__(256) void k_fold(Ctx c, FoldArgs a) {
     }
 }
 
+// LeakyRelu (gadgets.h LeakyPlan): the zero-label map y_e = b x_e + c y_e (mod p) with (b, c) = tab[e / bc]
+// (b | c << 8, one entry per channel; a scalar slope has bc = N). Grid (element x chunk work, residue j).
+struct LeakyJob {
+    int16_t* dst;            // the ReLU's output zero labels, mapped in place
+    const int16_t* x;        // the input zero labels
+    const uint16_t* tab;     // [channels]
+    int p, nc;
+};
+struct LeakyArgs {
+    LeakyJob j[kMaxRes];
+    int64_t N, bc;
+};
+__global__ __launch_bounds__(256) void k_leaky_map(Ctx c, LeakyArgs a) {
+    const LeakyJob& J = a.j[blockIdx.y];
+    const ModC m = c.mc[J.p];
+    const int64_t N = a.N, total = N * J.nc;
+    for (int64_t x = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; x < total;
+         x += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int c8 = static_cast<int>(x / N);
+        const int64_t e = x - static_cast<int64_t>(c8) * N;
+        const int64_t off = (static_cast<int64_t>(c8) * N + e) * kCh;
+        const uint32_t bc2 = J.tab[e / a.bc];
+        const uint32_t fb = bc2 & 0xffu, fc = bc2 >> 8;
+        uint32_t acc[8], t[8];
+        unpack8(*reinterpret_cast<const u32x4a*>(J.dst + off), acc);
+        unpack8(*reinterpret_cast<const u32x4a*>(J.x + off), t);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] = modq(fc * acc[u] + fb * t[u], m);  // < 2 p^2
+        st_chunk(J.dst + off, pack8(acc));
+    }
+}
+
 // Clip (gadgets.h ClipPlan): u = s_lo + s_hi (mod 2) of two sign-label slots into a third (whole slots, kW
 // components: mod-2 labels fill them)
 __global__ __launch_bounds__(256) void k_clip_u(Gadget g, int lo_slot, int hi_slot, int u_slot) {
@@ -2948,6 +2980,9 @@ struct GpuGarbler::Impl {
         int64_t N = 0;
     };
     std::map<size_t, Saved> saved;
+    // LeakyRelu in progress: the layer's input zero labels (leaky_keep), read by leaky_map
+    std::vector<DevBlock> leaky_x0;
+    int64_t leaky_N = 0;
     // max pool in progress: value slots [Nout][cnt] (output-major) of the current tree level
     std::vector<DevBlock> mp_V;
     int64_t mp_Nout = 0, mp_cnt = 0;
@@ -2991,6 +3026,8 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     clip_joint_hook() = &GpuGarbler::clip_joint_dev;
     argmax_hook() = &GpuGarbler::argmax_level_dev;
     mul_hook() = &GpuGarbler::mul_dev;
+    leaky_keep_hook() = &GpuGarbler::leaky_keep_dev;
+    leaky_map_hook() = &GpuGarbler::leaky_map_dev;
     convt_hook() = &GpuGarbler::convt_dev;
     upsample_hook() = &GpuGarbler::upsample_dev;
     Impl& I = *impl_;
@@ -4567,6 +4604,47 @@ void GpuGarbler::fold_constants(const std::vector<i64>& c, i64 group, CrtLabels&
     const int blocks = static_cast<int>(std::min<int64_t>((work + 255) / 256, 4096));
     hipLaunchKernelGGL(gg::k_fold, dim3(blocks, k), dim3(256), 0, gg::tl_st, I.c, a);
     HIPCHECK(hipGetLastError());
+}
+
+// LeakyRelu (garbler.cpp K_LEAKY): a copy of the device cur before the ReLU garbling, and the zero-label map
+// y_e = (n_c mod p) x0_e + ((2^s - n_c) mod p) relu0_e on the device cur after it
+void GpuGarbler::leaky_keep_dev(GpuGarbler& self, CrtLabels& cur) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    I.leaky_x0 = I.alloc_labels(I.cur_mod, I.cur_N);
+    I.leaky_N = I.cur_N;
+    for (size_t j = 0; j < I.cur_mod.size(); ++j)
+        HIPCHECK(hipMemcpyAsync(I.leaky_x0[j].p, I.cur[j].p, label_bytes(I.cur_mod[j], I.cur_N), hipMemcpyDeviceToDevice,
+                                gg::tl_st));
+}
+
+void GpuGarbler::leaky_map_dev(GpuGarbler& self, const LeakyPlan& lp, CrtLabels& cur) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    const int k = static_cast<int>(I.cur_mod.size());
+    DASH_CHECK(I.leaky_N == I.cur_N && static_cast<int>(I.leaky_x0.size()) == k && k <= kMaxRes,
+               "gpu garbler: leaky_relu input labels missing or of another shape");
+    gg::LeakyArgs a{};
+    a.N = I.cur_N;
+    a.bc = lp.n.size() == 1 ? I.cur_N : lp.bc;
+    int ncmax = 1;
+    for (int j = 0; j < k; ++j) {
+        const int p = I.cur_mod[j];
+        std::vector<uint16_t> tj(lp.n.size());
+        for (size_t ch = 0; ch < lp.n.size(); ++ch)
+            tj[ch] = static_cast<uint16_t>(lp.b(static_cast<i64>(ch), p) | (lp.c(static_cast<i64>(ch), p) << 8));
+        a.j[j] = gg::LeakyJob{I.cur[j].as<int16_t>(), I.leaky_x0[j].as<int16_t>(), gg::dconst(tj.data(), tj.size()), p,
+                              static_cast<int>(gg::chunks_of(nr_comps(p)))};
+        ncmax = std::max(ncmax, a.j[j].nc);
+    }
+    const int64_t work = I.cur_N * ncmax;
+    const int blocks = static_cast<int>(std::min<int64_t>((work + 255) / 256, 4096));
+    hipLaunchKernelGGL(gg::k_leaky_map, dim3(blocks, k), dim3(256), 0, gg::tl_st, I.c, a);
+    HIPCHECK(hipGetLastError());
+    I.leaky_x0.clear();  // released in stream order
+    I.leaky_N = 0;
 }
 
 // sum pool (garbler.cpp K_SUMPOOL): window sums of base labels

@@ -171,6 +171,27 @@ class GpuGarbler {
         DASH_CHECK(mul_hook() != nullptr, "gpu garbler: mul is not linked in");
         mul_hook()(*this, layer, mp, src_idx, cur, g, e);
     }
+    // LeakyRelu (gadgets.h LeakyPlan), two calls around the ReLU garbling of the same layer (sign_layer, relu_mrs
+    // or relu_mult): leaky_keep copies the device cur (the input zero labels x0) aside, leaky_map turns the ReLU's
+    // output zero labels into (n_c mod p) x0 + ((2^s - n_c) mod p) relu0 in place. Hooks as for clip.
+    using LeakyKeepFn = void (*)(GpuGarbler&, CrtLabels&);
+    using LeakyMapFn = void (*)(GpuGarbler&, const LeakyPlan&, CrtLabels&);
+    static LeakyKeepFn& leaky_keep_hook() {
+        static LeakyKeepFn f = nullptr;
+        return f;
+    }
+    static LeakyMapFn& leaky_map_hook() {
+        static LeakyMapFn f = nullptr;
+        return f;
+    }
+    void leaky_keep(CrtLabels& cur) {
+        DASH_CHECK(leaky_keep_hook() != nullptr, "gpu garbler: leaky_relu is not linked in");
+        leaky_keep_hook()(*this, cur);
+    }
+    void leaky_map(const LeakyPlan& lp, CrtLabels& cur) {
+        DASH_CHECK(leaky_map_hook() != nullptr, "gpu garbler: leaky_relu is not linked in");
+        leaky_map_hook()(*this, lp, cur);
+    }
     // ReDash rescale iteration (base-extension plan) on the device cur, in place
     void rescale_redash(uint64_t layer, int it, const RescalePlan& P, CrtLabels& cur,
                         const std::vector<std::vector<comp_t>>& up, const std::vector<std::vector<comp_t>>& down,
@@ -196,6 +217,8 @@ class GpuGarbler {
     static void argmax_level_dev(GpuGarbler& self, uint64_t layer, int lv, const ArgMaxPlan& ap, i64 P,
                                  const std::vector<i64>& prefix, CrtLabels& cur, Array& mrs, Array& mmg, Array& mme,
                                  Array& idx, Array& img, Array& ime);
+    static void leaky_keep_dev(GpuGarbler& self, CrtLabels& cur);
+    static void leaky_map_dev(GpuGarbler& self, const LeakyPlan& lp, CrtLabels& cur);
     static void mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& g,
                         Array& e);
     std::unique_ptr<Impl> impl_;

@@ -83,6 +83,13 @@ struct SignArgs {
 };
 constexpr int kCsumComps = 64;
 
+// LeakyRelu epilogue of the ReLU multiply (gadgets.h LeakyPlan): t[channel][k] = b | c << 8 with b = n_c mod p_j,
+// c = (2^s - n_c) mod p_j; channel = e / bc (a scalar slope: one channel, bc = N)
+struct LeakyTab {
+    const uint16_t* t;
+    uint32_t bc;
+};
+
 struct RescaleArgs {
     CrtInfo crt;
     int64_t N;

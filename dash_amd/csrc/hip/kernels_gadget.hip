@@ -418,6 +418,79 @@ __global__ __launch_bounds__(kRmBS) void k_relu_mult_s(SignArgs a, Act x, Act y,
 }
 
 // ---------------------------------------------------------------------------
+// LeakyRelu multiply (gadgets.h LeakyPlan): leaky_j = b x_j + c relu_j per digit, the ReLU multiply's operands
+// and walks with the leaky epilogue (gadget_walks.h leaky_digit; p = 2 as bit logic). b, c: one table read per
+// lane. grid (ceil(N/256), k, B), as k_relu_mult.
+__global__ __launch_bounds__(256) void k_leaky_mult(SignArgs a, LeakyTab lk, Act x, Act y, const u128* gtab,
+                                                    const u128* etab, const ModC* mc) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const int k = a.crt.k;
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
+    const u128 Hx = a.hx[bke];
+    const uint32_t colx = a.colx[bke];
+    const int64_t be = static_cast<int64_t>(b) * N + e;
+    const LeakyLane ll = leaky_lane(lk, e, j, k);
+    const ReluOps o = relu_ops(a.hard ? nullptr : a.hs, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
+    const u128 G = gtab[be * a.crt.sum + a.crt.prefix[j] + colx] - Hx;
+    const uint32_t ypr = mini_mult(o.mini, o.cS, o.HM, p, m);
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    DigitStream sg, se;
+    sg.init(G);
+    se.init(o.Eraw - o.HS);
+    if (m.bits == 1) {
+        col_walk<kChunk>(X, Y, N, static_cast<int>(m.n), [&](int, uint32_t xv) {
+            const uint32_t t = se.next(m) ^ sg.next(m) ^ (xv & ypr);
+            return (ll.fb & xv) ^ (ll.fc & t);
+        });
+    } else {
+        const uint32_t yl = leaky_mult(ypr, ll, m);
+        col_walk<kChunk>(X, Y, N, static_cast<int>(m.n), [&](int, uint32_t xv) {
+            const uint32_t g = sg.next(m);
+            return leaky_digit(se.next(m), yl, xv, p, g, ll.fc, m);
+        });
+    }
+}
+
+// k_leaky_mult with the label staged in LDS (stage_ok), as k_relu_mult_s: a block = (256-element tile, residue j,
+// GC b). A tile may span channels: every lane reads its own element's factors.
+__global__ __launch_bounds__(kRmBS) void k_leaky_mult_s(SignArgs a, LeakyTab lk, Act x, Act y, const u128* gtab,
+                                                        const u128* etab, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[128 * kRmBS];
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int k = a.crt.k;
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int n = static_cast<int>(m.n);
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * n * N;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N;
+    for (int64_t e0 = static_cast<int64_t>(blockIdx.x) * kRmBS; e0 < N; e0 += static_cast<int64_t>(gridDim.x) * kRmBS) {
+        const int64_t e = min(e0 + tid, N - 1);
+        const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
+        const int64_t be = static_cast<int64_t>(b) * N + e;
+        const u128 Hx = a.hx[bke];
+        const uint32_t colx = a.colx[bke];
+        const LeakyLane ll = leaky_lane(lk, e, j, k);
+        const ReluOps o = relu_ops(a.hard ? nullptr : a.hs, a.ys, a.ny, a.cs, etab, b, j, k, N, e);
+        const u128 Graw = gtab[be * a.crt.sum + a.crt.prefix[j] + colx];
+        __syncthreads();  // the previous tile's stores have read the image
+        lds_stage_rows<kRmBS, 4>(stg, X, N, e0, 0, n);
+        __syncthreads();
+        lds_mult_walk<kRmBS, false, true>(stg + tid, n, Graw - Hx, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m),
+                                          p, m, ll);
+        __syncthreads();
+        lds_store_rows<kRmBS>(Y, stg, N, e0, 0, n);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Clip multiply (gadgets.h ClipPlan): clip_j = E + ypr x_j - G + C, the ReLU multiply keyed by the label of
 // u = s_lo + s_hi plus the cap row C of s_hi, from the two sign labels themselves. Mod-2 labels compress to
 // their bit pack, so the compressed label of u is the XOR of the two sign labels; the lane derives u's
@@ -1226,9 +1299,12 @@ __device__ __forceinline__ void rrt_stage_rows(uint8_t* S, const act_t* L, int64
         st(x0 + 3 * kRrtBS, v3);
     }
 }
-__global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignArgs sa, Act x, Act y, const u128* gtab,
-                                                                const u128* etab, const ModC* mc) {
-    __shared__ __attribute__((aligned(16))) uint8_t stg[kRrtCap * kRrtBS];
+// The kernel's body. LEAKY (k_rescale_leaky_out_t): pass 2 and residue 0 take the leaky epilogue b Y_j + c relu_j
+// (gadgets.h LeakyPlan); the ReLU instantiation never reads lk.
+template <bool LEAKY>
+__device__ __forceinline__ void rescale_relu_out_t_body(uint8_t* stg, const MrsArgs& a, const SignArgs& sa,
+                                                        const LeakyTab& lk, const Act& x, const Act& y,
+                                                        const u128* gtab, const u128* etab, const ModC* mc) {
     const int j = blockIdx.y, b = blockIdx.z;
     const int64_t N = a.N;
     const int k = a.crt.k;
@@ -1253,7 +1329,11 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignAr
         const u128 E = o.Eraw - o.HS;
         const uint32_t t16 = static_cast<uint32_t>(o.mini >> (16 * o.cS)), hm = static_cast<uint32_t>(o.HM);
         // (e + ypr y + 2 - g) mod 2 = e ^ g ^ (ypr & y) with ypr = (t16 - hm) mod 2
-        const u128 R = (G ^ E) ^ (((t16 ^ hm) & 1u) ? P : static_cast<u128>(0));
+        u128 R = (G ^ E) ^ (((t16 ^ hm) & 1u) ? P : static_cast<u128>(0));
+        if (LEAKY) {  // (b & Y_0) ^ (c & relu_0) on the 128-bit words
+            const LeakyLane ll = leaky_lane(lk, e, 0, k);
+            R = (ll.fb ? P : static_cast<u128>(0)) ^ (ll.fc ? R : static_cast<u128>(0));
+        }
         for (int q0 = 0; q0 < n; q0 += kRrtCap) {
             const int cnt = min(kRrtCap, n - q0);
             if (q0) __syncthreads();  // the previous window's row stores have read the image
@@ -1292,9 +1372,24 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignAr
     ck.walk<kRrtBS>(col, n, inv, false, m);
     const u128 G = Graw - hard_pad(ck.C, gate, tw_sub(kTwMmg, j), 0);
     // pass 2: relu_j = E + ypr Y_j - G in place
-    lds_mult_chunks<kRrtBS, false>(col, n, G, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m), p, m);
+    if (LEAKY)
+        lds_mult_chunks<kRrtBS, false, true>(col, n, G, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m), p, m,
+                                             leaky_lane(lk, e, j, k));
+    else
+        lds_mult_chunks<kRrtBS, false>(col, n, G, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m), p, m);
     __syncthreads();
     lds_store_rows<kRrtBS>(Y, stg, N, e0, 0, n);
+}
+__global__ __launch_bounds__(kRrtBS) void k_rescale_relu_out_t(MrsArgs a, SignArgs sa, Act x, Act y, const u128* gtab,
+                                                                const u128* etab, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[kRrtCap * kRrtBS];
+    rescale_relu_out_t_body<false>(stg, a, sa, LeakyTab{nullptr, 1u}, x, y, gtab, etab, mc);
+}
+// k_rescale_relu_out_t for a joint LeakyRelu: the same block, image and passes with the leaky epilogue
+__global__ __launch_bounds__(kRrtBS) void k_rescale_leaky_out_t(MrsArgs a, SignArgs sa, LeakyTab lk, Act x, Act y,
+                                                                 const u128* gtab, const u128* etab, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[kRrtCap * kRrtBS];
+    rescale_relu_out_t_body<true>(stg, a, sa, lk, x, y, gtab, etab, mc);
 }
 
 // k_rescale_relu_out_t for a joint Clip (gadgets.h ClipPlan, joint variant): the same block, image and two
@@ -1497,6 +1592,11 @@ bool joint_fuse(int64_t N, int B) {
     return mode >= 0 ? mode == 1 : joint_fuse_pick(N, B);
 }
 
+bool leaky_fuse(int64_t N, int B) {
+    const int mode = joint_fuse_mode();
+    return mode >= 0 ? mode == 1 : (B >= 3 && joint_fuse_pick(N, B));
+}
+
 void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x, const Act& y, const u128* gtab,
                              const u128* etab, int B, const ModC* mc, const AesGlobals& g, hipStream_t st) {
     static const bool rro_stage = [] {  // DASH_RRO_STAGE=0: the per-lane form (A/B)
@@ -1523,6 +1623,26 @@ void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x,
     }
     const LaunchDims d = aes_dims("relu_out.lane", a.N, a.crt.k, B);
     hipLaunchKernelGGL(k_rescale_relu_out, d.grid, d.block, kAesLds, st, a, sa, x, y, gtab, etab, mc, g.te0, g.rk);
+}
+
+// The deferred outputs of a rescale with a joint LeakyRelu behind it. The throughput form where
+// launch_rescale_relu_out takes its own (the same rule); the small-batch fused forms (quad, staged, lane) have
+// no leaky counterpart: those launches run the rescale's output-hash kernel and the leaky multiply.
+void launch_rescale_leaky_out(const MrsArgs& a, const SignArgs& sa, const LeakyTab& lk, const Act& x, const Act& y,
+                              const u128* gtab, const u128* etab, int B, const ModC* mc, const AesGlobals& g,
+                              hipStream_t st) {
+    static const bool rro_stage = [] {  // DASH_RRO_STAGE=0, as launch_rescale_relu_out
+        const char* e = std::getenv("DASH_RRO_STAGE");
+        return !(e && e[0] == '0');
+    }();
+    if (!out_quad_fits(a, B) && rro_stage && B >= 3 && stage_ok(a.N, kRrtBS) && rrt_fits(a)) {
+        const dim3 gt(static_cast<unsigned>((a.N + kRrtBS - 1) / kRrtBS), a.crt.k, B);
+        if (launch_log_on()) launch_log_add("leaky_out.tput", gt, dim3(kRrtBS));
+        hipLaunchKernelGGL(k_rescale_leaky_out_t, gt, dim3(kRrtBS), 0, st, a, sa, lk, x, y, gtab, etab, mc);
+        return;
+    }
+    launch_rescale_mrs_out(a, x, B, mc, g, st);
+    launch_leaky_mult(sa, lk, x, y, gtab, etab, mc, st);
 }
 
 // Joint Clip: whether the planner defers the rescale's outputs to launch_rescale_clip_out. The joint-fuse mode
@@ -1597,6 +1717,14 @@ void launch_relu_mrs(const MrsArgs& a, const SignArgs& sa, const Act& x, const A
                    sa.hard, sa.mgate0);
     dispatch_mrs_chain(a, x, B, mc, g, st);
     launch_relu_mult(sa, x, y, gtab, etab, mc, st);
+}
+
+void launch_leaky_mrs(const MrsArgs& a, const SignArgs& sa, const LeakyTab& lk, const Act& x, const Act& y,
+                      const u128* gtab, const u128* etab, int B, const ModC* mc, const AesGlobals& g, hipStream_t st) {
+    AES_LAUNCH_GGL(k_label_hash, a.N, a.crt.k, B, kAesLds, st, x, a.crt, a.N, sa.hx, sa.colx, mc, g.te0, g.rk,
+                   sa.hard, sa.mgate0);
+    dispatch_mrs_chain(a, x, B, mc, g, st);
+    launch_leaky_mult(sa, lk, x, y, gtab, etab, mc, st);
 }
 
 // ReLU after a sign-producing rescale: the rescale wrote the sign's hash / color (chain MODE 2) and the
@@ -1984,6 +2112,14 @@ void launch_relu_mult(const SignArgs& a, const Act& x, const Act& y, const u128*
         hipLaunchKernelGGL(k_relu_mult_s, grid, dim3(kRmBS), 0, st, a, x, y, gtab, etab, mc);
     else
         hipLaunchKernelGGL(k_relu_mult, grid, dim3(256), 0, st, a, x, y, gtab, etab, mc);
+}
+void launch_leaky_mult(const SignArgs& a, const LeakyTab& lk, const Act& x, const Act& y, const u128* gtab,
+                       const u128* etab, const ModC* mc, hipStream_t st) {
+    dim3 grid;
+    if (mult_grid("leaky_mult", a.N, a.crt.k, a.B, x, y, grid))
+        hipLaunchKernelGGL(k_leaky_mult_s, grid, dim3(kRmBS), 0, st, a, lk, x, y, gtab, etab, mc);
+    else
+        hipLaunchKernelGGL(k_leaky_mult, grid, dim3(256), 0, st, a, lk, x, y, gtab, etab, mc);
 }
 // Clip: the half gates' keys of x (as launch_relu_mrs), then one sign per bound into its own scratch, then the
 // multiply. The multiply's picker is launch_relu_mult's (mult_grid).

@@ -38,6 +38,9 @@ bool joint_fuse_pick(int64_t N, int B);
 bool joint_fuse(int64_t N, int B);  // the mode applied to the rule
 // The same for a joint Clip behind the rescale (launch_rescale_clip_out): the mode forces it, the auto rule
 // clip_fuse_pick is the Clip's own (not joint_fuse_pick's threshold).
+// A joint LeakyRelu defers where joint_fuse_pick's throughput branch does (batches of at least 3 GCs, the same
+// element threshold); the mode forces it as it does the ReLU's.
+bool leaky_fuse(int64_t N, int B);
 bool clip_fuse_pick(int64_t N, int B);
 bool clip_fuse(int64_t N, int B);
 // Launch log: off by default (one relaxed load per host-side launch, nothing under graph replay, where no picker
@@ -63,6 +66,16 @@ void launch_argmax_hash(const Act& d, const CrtInfo& crt, int64_t N, u128* hx, u
                         const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_argmax_mult(const ArgMaxArgs& a, bool val, bool l0, const Act& v, const Act& d, const Act& i, const Act& ed,
                         const Act& nv, const Act& ni, int B, const ModC* mc, hipStream_t st);
+// LeakyRelu: the ReLU multiply with the leaky epilogue (k_leaky_mult / k_leaky_mult_s, mult_grid's picker), and
+// the deferred outputs of a joint rescale with a LeakyRelu behind it (k_rescale_leaky_out_t where
+// launch_rescale_relu_out takes its throughput form; elsewhere the output-hash kernel and the leaky multiply)
+void launch_leaky_mult(const SignArgs& a, const LeakyTab& lk, const Act& x, const Act& y, const u128* gtab,
+                       const u128* etab, const ModC* mc, hipStream_t st);
+void launch_leaky_mrs(const MrsArgs& a, const SignArgs& sa, const LeakyTab& lk, const Act& x, const Act& y,
+                      const u128* gtab, const u128* etab, int B, const ModC* mc, const AesGlobals& g, hipStream_t st);
+void launch_rescale_leaky_out(const MrsArgs& a, const SignArgs& sa, const LeakyTab& lk, const Act& x, const Act& y,
+                              const u128* gtab, const u128* etab, int B, const ModC* mc, const AesGlobals& g,
+                              hipStream_t st);
 void launch_relu_mult(const SignArgs& a, const Act& x, const Act& y, const u128* gtab, const u128* etab,
                       const ModC* mc, hipStream_t st);
 void launch_rescale_hash(const Act& x, int fi, int s, const int16_t* up, int up_stride, int add_up, int64_t N, int B,

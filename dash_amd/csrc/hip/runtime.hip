@@ -649,7 +649,7 @@ class HipEvaluator {
         std::vector<std::vector<int>> saved_mods;
         // a sign-producing rescale whose outputs the next layer's op writes in its own pass: a joint ReLU's
         // launch_rescale_relu_out or a joint Clip's launch_rescale_clip_out. At most one is pending.
-        enum class Pending { none, relu, clip } pending = Pending::none;
+        enum class Pending { none, relu, clip, leaky } pending = Pending::none;
         MrsArgs pending_a{};
         int nxt() const { return (cur + 1) % 2; }
     };
@@ -805,6 +805,7 @@ class HipEvaluator {
     void plan_proj(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_mult(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_mul(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_leaky(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname);
 
     std::shared_ptr<GarbledModel> tmpl_;  // build() only
@@ -952,6 +953,7 @@ void HipEvaluator::build() {
             case K_PROJ: plan_proj(w, li, g, lname); break;
             case K_MULT: case K_MMULT: plan_mult(w, li, g, lname); break;
             case K_MUL: plan_mul(w, li, g, lname); break;
+            case K_LEAKY: plan_leaky(w, li, g, lname); break;
             case K_BASEEXT: plan_base_ext(w, li, g, lname); break;
             default:
                 throw std::runtime_error(std::string("dash: HIP evaluator cannot run layer kind ") + kind_name(g.kind));
@@ -1032,7 +1034,9 @@ HipEvaluator::Caps HipEvaluator::shape_pass() const {
         if (l.p.count("in_src")) N = c.outN.at(l.param("in_src") + 1);
         const i64 No = out_elems(l, N, c.outN);
         switch (l.kind) {
-            case K_RELU: case K_SIGN: case K_RESCALE: case K_CLIP: c.maxSignN = std::max(c.maxSignN, N); break;
+            case K_RELU: case K_SIGN: case K_RESCALE: case K_CLIP: case K_LEAKY:
+                c.maxSignN = std::max(c.maxSignN, N);
+                break;
             case K_MAXPOOL: {
                 PoolGeom G(l.p);
                 c.maxPoolSlots = std::max(c.maxPoolSlots, No * G.kh * G.kw);
@@ -1378,6 +1382,54 @@ void HipEvaluator::plan_relu(Walk& w, size_t li, const GLayer& g, const std::str
     set_out(w, g, w.N, w.nxt());
 }
 
+// gadgets.h LeakyPlan: plan_relu's ops for the layer's resolved sign construction with the leaky multiply in the
+// ReLU multiply's place; the layer's factor table [channel][residue] is public and uploaded once
+void HipEvaluator::plan_leaky(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    const Env e = w.env;
+    const i64 smode = g.param("smode", 0);
+    DASH_CHECK(w.mods == crt_, "leaky_relu: the input is not on the CRT base");
+    DASH_CHECK(w.N < (i64{1} << 32), "leaky_relu: more than 2^32 elements");
+    const LeakyPlan lp(g.param("s"), g.vec("n"), g.param("bc"), w.N);
+    const std::vector<uint16_t> tab = lp.table(crt_);
+    LeakyTab lk{upload(tab.data(), tab.size()), static_cast<uint32_t>(lp.n.size() == 1 ? w.N : lp.bc)};
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const u128* gt = upload_tables(li, "mm.g");
+    const u128* et = upload_tables(li, "mm.e");
+    if (smode == 2) {
+        DASH_CHECK(li > 0 && m0.layers[li - 1].kind == K_RESCALE && m0.layers[li - 1].param("sign_out", 0) == 1,
+                   "joint LeakyRelu must follow a sign-producing rescale");
+        const SignArgs sa = joint_sign_args(w, li, w.N);
+        if (w.pending == Walk::Pending::leaky) {
+            const MrsArgs ma = w.pending_a;
+            w.pending = Walk::Pending::none;
+            add_op(lname + ".C", [ma, sa, lk, x, y, gt, et, e](hipStream_t st) {
+                launch_rescale_leaky_out(ma, sa, lk, x, y, gt, et, e.B, e.mc, e.ag, st);
+            });
+        } else {
+            add_op(lname + ".C", [sa, lk, x, y, gt, et, e](hipStream_t st) {
+                launch_leaky_mult(sa, lk, x, y, gt, et, e.mc, st);
+            });
+        }
+    } else if (smode == 1) {
+        DASH_CHECK(hard_, "the mixed-radix sign exists in the hardened encoding only");
+        const MrsArgs a = mrs_sign_args(w, li, "mrs", w.N, gate_base(li + 1, 1), gate_base(li + 1, 2), ny_, nullptr);
+        const SignArgs sa = joint_sign_args(w, li, w.N);
+        add_op(lname + ".mrs", [a, sa, lk, x, y, gt, et, e](hipStream_t st) {
+            launch_leaky_mrs(a, sa, lk, x, y, gt, et, e.B, e.mc, e.ag, st);
+        });
+    } else {
+        SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
+        const Sign s = make_sign(li, "", sp, w.N, 1, gate_base(li + 1, 1), gate_base(li + 1, 2));
+        const SignArgs a = s.a;
+        const int maxn = s.maxn;
+        add_op(lname + ".A", [a, x, e](hipStream_t st) { launch_sign_approx(a, x, e.mc, e.ag, st); });
+        add_op(lname + ".B", [a, maxn, e](hipStream_t st) { launch_sign_chain(a, maxn, e.mc, e.ag, st); });
+        add_op(lname + ".C", [a, lk, x, y, gt, et, e](hipStream_t st) { launch_leaky_mult(a, lk, x, y, gt, et, e.mc, st); });
+    }
+    set_out(w, g, w.N, w.nxt());
+}
+
 // gadgets.h ClipPlan: the half gates' keys of x, the sign evaluation once per bound on the same labels (each into
 // its own scratch), then the multiply + cap
 void HipEvaluator::plan_clip(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
@@ -1532,13 +1584,19 @@ void HipEvaluator::plan_rescale_mrs(Walk& w, size_t li, const GLayer& g, const s
     const bool defer = dev::joint_fuse(N, B_) && so && has_next && m0.layers[li + 1].kind == K_RELU &&
                        m0.layers[li + 1].param("smode", 0) == 2 && !w.keep[li + 1] &&
                        !m0.layers[li + 1].p.count("in_src");
-    if (defer) {
+    // a joint LeakyRelu next: the same deferral where the throughput form runs (launch.h leaky_fuse); the
+    // small-batch fused forms have no leaky counterpart, so those launches keep the output-hash kernel here
+    const bool defer_leaky = dev::leaky_fuse(N, B_) && so && has_next && m0.layers[li + 1].kind == K_LEAKY &&
+                             m0.layers[li + 1].param("smode", 0) == 2 && !w.keep[li + 1] &&
+                             !m0.layers[li + 1].p.count("in_src");
+    if (defer || defer_leaky) {
         w.pending_a = a;
-        w.pending = Walk::Pending::relu;
+        w.pending = defer ? Walk::Pending::relu : Walk::Pending::leaky;
     }
     Act x = act_of(w.cur);
     const Env e = w.env;
-    add_op(lname + ".mrs", [a, x, e, defer](hipStream_t st) { launch_rescale_mrs(a, x, e.B, e.mc, e.ag, st, defer); });
+    const bool dfr = defer || defer_leaky;
+    add_op(lname + ".mrs", [a, x, e, dfr](hipStream_t st) { launch_rescale_mrs(a, x, e.B, e.mc, e.ag, st, dfr); });
 }
 
 // A joint Clip next (gadgets.h ClipPlan, joint variant): the chain keeps its mod-2 key as the Clip's lower sign

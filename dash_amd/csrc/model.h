@@ -38,6 +38,7 @@ enum Kind : int {
     K_CONVT = 17,
     K_UPSAMPLE = 18,
     K_MUL = 19,  // params src, bc (broadcast only), sq (square only); arrays g, e (product) or t (square)
+    K_LEAKY = 20,  // params s, n (one or one per channel), bc; arrays and smode exactly a K_RELU's
 };
 const char* kind_name(int kind);
 

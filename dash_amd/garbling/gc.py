@@ -372,7 +372,7 @@ class GarbledCircuit:
         specs = self.circuit.garble_specs()
         dash = [i for i, (k, p) in enumerate(specs) if k == Kind.RESCALE and p.get("mode") == 0]
         redash = [i for i, (k, p) in enumerate(specs) if k == Kind.RESCALE and p.get("mode") == 1]
-        relus = [i for i, (k, p) in enumerate(specs) if k == Kind.RELU]
+        relus = [i for i, (k, p) in enumerate(specs) if k in (Kind.RELU, Kind.LEAKY)]
         mrs = self.rescale == "mrs" and bool(dash)
         parts = []
         if dash:

@@ -25,7 +25,7 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
   evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
   bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
-  has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample and no padded / ceil-mode pooling:
+  has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no LeakyRelu and no padded / ceil-mode pooling:
   circuits with any of them take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
@@ -69,11 +69,12 @@ class RangeGuard:
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Mul, L.Projection,
-                                          L.BaseExtension, L.ConvTranspose2d, L.Upsample))
+                                          L.BaseExtension, L.ConvTranspose2d, L.Upsample, L.LeakyRelu))
                            for l in circuit.layers)
         # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no
-        # dilated conv and no padded / ceil-mode pooling: such circuits take the batched torch path
-        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.Mul, L.ConvTranspose2d, L.Upsample)) or
+        # LeakyRelu, no dilated conv and no padded / ceil-mode pooling: such circuits take the batched torch path
+        self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.Mul, L.ConvTranspose2d, L.Upsample,
+                                                   L.LeakyRelu)) or
                                     (isinstance(l, L.Conv2d) and (l.dh > 1 or l.dw > 1)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
@@ -92,7 +93,8 @@ class RangeGuard:
             if idx + 1 in self.joint_clips:  # the joint Clip's upper sign input x - t_hi is a signed CRT value
                 lo = lo + self.joint_clips[idx + 1]
             return lo, hi
-        if isinstance(layer, (L.Relu, L.Sign, L.MaxPool2d, L.Max, L.ArgMax)):
+        # a LeakyRelu's sign reads its input; its output 2^s x is checked where a gadget or the output next reads it
+        if isinstance(layer, (L.Relu, L.Sign, L.MaxPool2d, L.Max, L.ArgMax, L.LeakyRelu)):
             return lo, hi
         if isinstance(layer, L.Clip):
             if idx in self.joint_clips:  # its signs were taken at the rescale before it
@@ -225,6 +227,9 @@ class RangeGuard:
                     out = torch.div(inp + h % S, S, rounding_mode="floor")
             elif isinstance(l, L.Relu):
                 out = torch.clamp_min(inp, 0)
+            elif isinstance(l, L.LeakyRelu):
+                n = torch.as_tensor(np.repeat(l.n, l.bc) if l.n.size > 1 else l.n, device=X.device)
+                out = torch.where(inp >= 0, inp * (1 << l.slope_bits), inp * n[None, :])
             elif isinstance(l, L.Sign):
                 out = torch.where(inp >= 0, 1, -1).to(torch.int64)
             elif isinstance(l, L.Clip):

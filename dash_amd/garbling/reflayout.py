@@ -62,10 +62,10 @@ def _tables(model):
                          "garble with fused_sign=False")
     for li in range(model.num_layers):
         kind = model.layer_kind(li)
-        if kind not in (Kind.RELU, Kind.SIGN, Kind.RESCALE):
+        if kind not in (Kind.RELU, Kind.LEAKY, Kind.SIGN, Kind.RESCALE):
             continue
         params = model.layer_params(li)
-        if kind == Kind.RESCALE and params.get("mode", [0])[0] == 2 or kind == Kind.RELU and "smode" in params:
+        if kind == Kind.RESCALE and params.get("mode", [0])[0] == 2 or kind in (Kind.RELU, Kind.LEAKY) and "smode" in params:
             raise ValueError(f"layer {li} uses a mixed-radix construction, which has no reference layout")
         for name, arr in model.layer_arrays(li).items():
             if name.split(".", 1)[-1] in SIGN_FAMILY or name in SIGN_FAMILY:

@@ -40,6 +40,7 @@ class Kind:
     CONVT = 17
     UPSAMPLE = 18
     MUL = 19
+    LEAKY = 20
 
 
 def _size(d: Sequence[int]) -> int:
@@ -127,7 +128,7 @@ class Dense(Layer):
 
     def __init__(self, weights: np.ndarray, biases: np.ndarray, q_parameter: int = -1,
                  q_method: QuantizationMethod = QuantizationMethod.SimpleQuant, q_const: float = 10.0,
-                 channel_tf: int = 0):
+                 channel_tf: int = 0, in_scale_bits: int = 0):
         w = np.asarray(weights, dtype=np.float32)
         b = np.asarray(biases, dtype=np.float32).reshape(-1)
         assert w.ndim == 2 and w.shape[0] == b.shape[0], "weights/biases shape mismatch"
@@ -135,7 +136,8 @@ class Dense(Layer):
         self.weights, self.biases = w, b
         self.q_method, self.q_parameter, self.q_const = QuantizationMethod(q_method), q_parameter, q_const
         self.channel_tf = int(channel_tf)
-        self.q_weights, self.q_biases = quantize_params(w, b, self.q_method, q_parameter, q_const)
+        self.in_scale_bits = int(in_scale_bits)
+        self.q_weights, self.q_biases = quantize_params(w, b, self.q_method, q_parameter, q_const, self.in_scale_bits)
         self._track_q(self.q_weights, self.q_biases)
 
     @classmethod
@@ -225,9 +227,10 @@ class Conv2d(Layer):
                  filter: int, filter_width: int, filter_height: int, stride_width: int = 1, stride_height: int = 1,
                  q_parameter: int = -1, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
                  q_const: float = 10.0, pad_width: int = 0, pad_height: int = 0, groups: int = 1,
-                 dilation_width: int = 1, dilation_height: int = 1):
+                 dilation_width: int = 1, dilation_height: int = 1, in_scale_bits: int = 0):
         self.C, self.H, self.W, self.F = int(channel), int(input_height), int(input_width), int(filter)
         self.groups = int(groups)
+        self.in_scale_bits = int(in_scale_bits)
         if self.groups < 1 or self.C % self.groups or self.F % self.groups:
             raise ValueError(f"groups={groups} must be positive and divide channel={channel} and filter={filter}")
         self.Cg, self.Fg = self.C // self.groups, self.F // self.groups
@@ -252,7 +255,8 @@ class Conv2d(Layer):
         b = np.asarray(biases, dtype=np.float32).reshape(self.F)
         self.weights, self.biases = w, b
         self.q_method, self.q_parameter, self.q_const = QuantizationMethod(q_method), q_parameter, q_const
-        self.q_weights, self.q_biases = quantize_params(w, b, self.q_method, q_parameter, q_const)
+        self.q_weights, self.q_biases = quantize_params(w, b, self.q_method, q_parameter, q_const,
+                                                        self.in_scale_bits)
         self._track_q(self.q_weights, self.q_biases)
 
     @classmethod
@@ -370,8 +374,9 @@ class ConvTranspose2d(Layer):
                  filter: int, filter_width: int, filter_height: int, stride_width: int = 1, stride_height: int = 1,
                  q_parameter: int = -1, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
                  q_const: float = 10.0, pad_width: int = 0, pad_height: int = 0, out_pad_width: int = 0,
-                 out_pad_height: int = 0, groups: int = 1, dilation: int = 1):
+                 out_pad_height: int = 0, groups: int = 1, dilation: int = 1, in_scale_bits: int = 0):
         self.C, self.H, self.W, self.F = int(channel), int(input_height), int(input_width), int(filter)
+        self.in_scale_bits = int(in_scale_bits)
         self.kh, self.kw, self.sh, self.sw = int(filter_height), int(filter_width), int(stride_height), int(stride_width)
         self.ph, self.pw, self.oph, self.opw = int(pad_height), int(pad_width), int(out_pad_height), int(out_pad_width)
         _convt_check(self.kh, self.kw, self.sh, self.sw, self.ph, self.pw, self.oph, self.opw, groups, dilation)
@@ -384,7 +389,8 @@ class ConvTranspose2d(Layer):
         b = np.asarray(biases, dtype=np.float32).reshape(self.F)
         self.weights, self.biases = w, b
         self.q_method, self.q_parameter, self.q_const = QuantizationMethod(q_method), q_parameter, q_const
-        self.q_weights, self.q_biases = quantize_params(w, b, self.q_method, q_parameter, q_const)
+        self.q_weights, self.q_biases = quantize_params(w, b, self.q_method, q_parameter, q_const,
+                                                        self.in_scale_bits)
         self._track_q(self.q_weights, self.q_biases)
 
     @classmethod
@@ -528,6 +534,89 @@ class Relu(Layer):
 
     def quantize(self, q_const):
         self.reset_ranges()
+
+
+class LeakyRelu(Layer):
+    """Leaky ReLU / PReLU with a dyadic slope (docs/LEAKY_RELU.md): slope_bits = s in [1, 8] and a numerator
+    n_c = round(alpha_c 2^s) in [0, 2^s) per channel (a scalar slope is one channel group). The quantized
+    function is y = 2^s x for x >= 0 and n_c x otherwise, exact: the output carries a scale 2^s larger than the
+    input, which the next linear layer absorbs (in_scale_bits). y = n x + (2^s - n) relu(x), and a public
+    multiple or a sum of labels is free, so the garbled tables are exactly a ReLU's."""
+
+    kind = Kind.LEAKY
+    name = "leaky_relu"
+    MAX_SLOPE_BITS = 8
+
+    def __init__(self, dims, alpha, slope_bits: int = 4):
+        super().__init__(dims, dims)
+        s = self._check_bits(slope_bits)
+        a = np.asarray(alpha, dtype=np.float64).reshape(-1)
+        if not np.all(np.isfinite(a)) or np.any(a < 0) or np.any(a >= 1):
+            raise ValueError(f"leaky_relu: every slope must lie in [0, 1), got {a.tolist()}")
+        n = np.floor(a * (1 << s) + 0.5).astype(np.int64)
+        lost = (a > 0) & (n == 0)
+        if lost.any():
+            amin = float(a[lost].min())
+            need = next(t for t in range(s + 1, 1100) if np.floor(amin * 2.0 ** t + 0.5) >= 1)
+            raise ValueError(f"leaky_relu: slope {amin:g} rounds to 0 at slope_bits={s}; the smallest slope_bits "
+                             f"that keeps it is {need}")
+        if np.any(n >= (1 << s)):
+            raise ValueError(f"leaky_relu: slope {float(a.max()):g} rounds to 1 at slope_bits={s}; slopes must "
+                             f"stay below 1")
+        self.alpha = a.astype(np.float32)
+        self._set_n(n, s)
+
+    @staticmethod
+    def _check_bits(slope_bits) -> int:
+        s = int(slope_bits)
+        if s != slope_bits or not 1 <= s <= LeakyRelu.MAX_SLOPE_BITS:
+            raise ValueError(f"leaky_relu: slope_bits must be an integer in [1, {LeakyRelu.MAX_SLOPE_BITS}], "
+                             f"got {slope_bits}")
+        return s
+
+    def _set_n(self, n, s: int):
+        n = np.asarray(n, dtype=np.int64).reshape(-1)
+        if n.size not in (1, self.in_dims[0]):
+            raise ValueError(f"leaky_relu: one slope or one per channel ({self.in_dims[0]}), got {n.size}")
+        if np.any(n < 0) or np.any(n >= (1 << s)):
+            raise ValueError(f"leaky_relu: slope numerators must lie in [0, 2^{s}), got {n.tolist()}")
+        self.slope_bits, self.n = s, n
+        # elements per channel group (channel of element e = e // bc)
+        self.bc = self.out_size if n.size == 1 else self.out_size // n.size
+
+    @classmethod
+    def from_quantized(cls, dims, n, slope_bits: int) -> "LeakyRelu":
+        s = cls._check_bits(slope_bits)
+        l = cls(dims, 0.0, s)
+        l._set_n(n, s)
+        l.alpha = (l.n.astype(np.float64) / (1 << s)).astype(np.float32)
+        return l
+
+    def _per_elem(self, v):
+        return np.repeat(np.asarray(v), self.bc) if len(v) > 1 else np.asarray(v)[0]
+
+    def plain_eval(self, x, track=True, ctx=None):
+        x = np.asarray(x, dtype=np.float32).reshape(-1)
+        y = np.where(x >= 0, x, x * self._per_elem(self.alpha)).astype(np.float32)
+        if track:
+            self._track_f(y)
+        return y
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        x = np.asarray(x, dtype=np.int64).reshape(-1)
+        y = np.where(x >= 0, x * (1 << self.slope_bits), x * self._per_elem(self.n))
+        if track:
+            self._track_q(x, y)
+        return y
+
+    def quantize(self, q_const):
+        self.reset_ranges()
+
+    def garble_spec(self):
+        return self.kind, {"s": self.slope_bits, "n": [int(v) for v in self.n], "bc": int(self.bc)}
+
+    def __repr__(self) -> str:
+        return f"LeakyRelu(dims={self.in_dims}, n={self.n.tolist()}, slope_bits={self.slope_bits})"
 
 
 class Clip(Layer):

@@ -71,6 +71,19 @@ that raises NotImplementedError naming the node. Refused as well, because no
 single factor exists: `AveragePool` with pads and `count_include_pad=0`, with
 pads and `ceil_mode`, or with a `ceil_mode` that cuts the last window.
 
+`LeakyRelu` (attribute `alpha`, default 0.01) and `PRelu` (a slope initializer:
+a scalar, `(C,)`, `(C, 1, 1)` or `(1, C, 1, 1)` against a `(C, H, W)` tensor,
+`(C,)` against a dense `(C,)` tensor) become a `LeakyRelu` layer with the dyadic
+slope round(alpha 2^s) / 2^s, s = `leaky_bits` (docs/LEAKY_RELU.md). ScaleQuant
+only: the layer's output carries a scale 2^s larger than its input, kept per
+tensor as *pending scale bits* e next to the pending factor. Relu, MaxPool, sum
+and average pooling, Flatten, Upsample, Identity and Dropout pass e through, a
+Sign and an ArgMax drop it, and the next Conv / ConvTranspose / Gemm / MatMul
+consumes it: its bias is quantized at 2^(2l + e) (`in_scale_bits=e`) and the
+`Rescale` behind it is `Rescale(l + e)`. A `Mul` adds its operands' bits and
+rescales by l + e. `Add` and `Concat` need equal bits on all operands; a `Clip`
+or a graph output with pending bits is refused.
+
 `save_onnx_model(path, circuit)` writes a pytorch-style ONNX graph of a float
 circuit with a small protobuf encoder (the python `onnx` package is not
 available on the target image), so that models built or trained here can be
@@ -86,8 +99,8 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Mul, Relu, Rescale,
-                     Sign, SumPool2d, Upsample, _convt_check, _pool_out)
+from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, Relu,
+                     Rescale, Sign, SumPool2d, Upsample, _convt_check, _pool_out)
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -150,7 +163,7 @@ def _pool_attrs(node) -> tuple:
 
 
 def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
-                             q_const: float = DEFAULT_Q_CONST, q_parameter: int = -1) -> Circuit:
+                             q_const: float = DEFAULT_Q_CONST, q_parameter: int = -1, leaky_bits: int = 4) -> Circuit:
     q_method = QuantizationMethod(q_method)
     inits = {t["name"]: t for t in model["initializers"]}
     tf = model["producer_name"] == "tf2onnx"
@@ -165,10 +178,12 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
     producer: dict[str, int] = {}
     tdims: dict[str, tuple] = {}
     tfac: dict[str, float] = {}
+    tbits: dict[str, int] = {}  # pending scale bits e (a LeakyRelu's 2^s, see the module docstring)
     data_inputs = [i["name"] for i in model["inputs"] if i["name"] not in inits]
     producer[data_inputs[0]] = -1
     tdims[data_inputs[0]] = _input_dims(model, set(inits))
     tfac[data_inputs[0]] = 1.0
+    tbits[data_inputs[0]] = 0
     alias: dict[str, str] = {}
     first_dense = True
     last_conv_filters = 0
@@ -211,19 +226,30 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                                       "an unsupported node")
         return producer[r], tdims[r], tfac[r]
 
-    def emit(spec: _Spec, out_name: str, src: int, dims: tuple, fac: float = 1.0):
+    def bits(name: str) -> int:
+        return tbits.get(res(name), 0)
+
+    def emit(spec: _Spec, out_name: str, src: int, dims: tuple, fac: float = 1.0, e: int = 0):
         # a layer that does not read the previous layer's output names its source
         spec.kw["in_src"] = None if src == len(specs) - 1 else src
         specs.append(spec)
         producer[out_name] = len(specs) - 1
         tdims[out_name] = tuple(int(v) for v in dims)
         tfac[out_name] = fac
+        tbits[out_name] = int(e)
 
     def no_factor(node, fac: float):
         if fac != 1.0:
             raise NotImplementedError(
                 f"onnx: {node.get('name') or node['op_type']}: an average's 1/K factor reaches this "
                 f"{node['op_type']} before a Conv/Gemm could absorb it")
+
+    def same_bits(node, names):
+        eb_ = [bits(x) for x in names]
+        if len(set(eb_)) > 1:
+            raise NotImplementedError(
+                f"onnx: {node.get('name') or node['op_type']}: the operands of this {node['op_type']} carry "
+                f"different LeakyRelu scales (2^e with e = {eb_}); no Conv/Gemm absorbed them")
 
     for ni, node in enumerate(nodes):
         if ni in skip:
@@ -233,12 +259,13 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         if op in ("Identity", "Dropout"):
             alias[outs[0]] = res(ins[0])
             continue
+        eb = bits(ins[0]) if ins else 0  # the data input's pending scale bits
         if op == "Flatten" or op == "Reshape":
             j, dims, fac = data_in(node, ins[0])
             if op == "Reshape" and len(dims) == 1:
                 alias[outs[0]] = res(ins[0])
                 continue
-            emit(_Spec("flatten", dims=dims), outs[0], j, (int(np.prod(dims)),), fac)
+            emit(_Spec("flatten", dims=dims), outs[0], j, (int(np.prod(dims)),), fac, eb)
         elif op in ("Gemm", "MatMul"):
             j, dims, fac = data_in(node, ins[0])
             w = arr(ins[1])
@@ -263,7 +290,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             first_dense = False
             if fac != 1.0:  # pending average: into the weights, never the bias
                 w = (w * np.float32(fac)).astype(np.float32)
-            emit(_Spec("dense", w=w, b=bias, channel_tf=channel_tf), out_name, j, (w.shape[0],))
+            emit(_Spec("dense", w=w, b=bias, channel_tf=channel_tf, e=eb), out_name, j, (w.shape[0],))
         elif op == "Conv":
             j, dims, fac = data_in(node, ins[0])
             w = arr(ins[1])
@@ -300,8 +327,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                 w = (w * np.float32(fac)).astype(np.float32)
             H = (dims[1] + 2 * pads[0] - ke[0]) // st[0] + 1
             W = (dims[2] + 2 * pads[1] - ke[1]) // st[1] + 1
-            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group, dil=dil),
-                 outs[0], j, (F, H, W))
+            emit(_Spec("conv", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), group=group, dil=dil,
+                       e=eb), outs[0], j, (F, H, W))
             last_conv_filters = F
         elif op == "ConvTranspose":
             j, dims, fac = data_in(node, ins[0])
@@ -334,8 +361,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                 w = (w * np.float32(fac)).astype(np.float32)
             OH = (dims[1] - 1) * st[0] - 2 * pads[0] + kh + opad[0]
             OW = (dims[2] - 1) * st[1] - 2 * pads[1] + kw + opad[1]
-            emit(_Spec("convt", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), opad=(opad[0], opad[1])),
-                 outs[0], j, (F, OH, OW))
+            emit(_Spec("convt", w=w, b=bias, dims=dims, stride=st, pads=(pads[0], pads[1]), opad=(opad[0], opad[1]),
+                       e=eb), outs[0], j, (F, OH, OW))
             last_conv_filters = F
         elif op in ("Resize", "Upsample"):
             j, dims, fac = data_in(node, ins[0])
@@ -374,7 +401,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                 raise NotImplementedError(f"onnx: {name}: {op} scales {sc} are not [1, 1, fh, fw] with integer "
                                           "factors >= 1 (not both 1)")
             fh, fw = int(sc[2]), int(sc[3])
-            emit(_Spec("upsample", dims=dims, f=(fh, fw)), outs[0], j, (dims[0], dims[1] * fh, dims[2] * fw), fac)
+            emit(_Spec("upsample", dims=dims, f=(fh, fw)), outs[0], j, (dims[0], dims[1] * fh, dims[2] * fw), fac, eb)
         elif op == "BatchNormalization":
             j = src_of(ins[0])
             assert j is not None and j >= 0 and specs[j].kind in ("conv", "dense", "convt"), \
@@ -396,7 +423,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             k, st, pads, ceil = _pool_attrs(node)
             assert len(dims) == 3, f"onnx: MaxPool expects an image, got dims {dims}"
             out = (dims[0], _pool_out(dims[1], k[0], st[0], pads[0], ceil), _pool_out(dims[2], k[1], st[1], pads[1], ceil))
-            emit(_Spec("maxpool", dims=dims, k=k, stride=st, pads=pads, ceil=ceil), outs[0], j, out, fac)
+            emit(_Spec("maxpool", dims=dims, k=k, stride=st, pads=pads, ceil=ceil), outs[0], j, out, fac, eb)
         elif op in ("AveragePool", "GlobalAveragePool", "ReduceMean", "ReduceSum"):
             j, dims, fac = data_in(node, ins[0])
             name = node.get("name") or op
@@ -432,12 +459,33 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             out = (dims[0], _pool_out(dims[1], k[0], st[0], pads[0], ceil), _pool_out(dims[2], k[1], st[1], pads[1], ceil))
             if op != "ReduceSum":  # the plane sum is the SumPool2d itself
                 fac = fac / float(k[0] * k[1])
-            emit(_Spec("sumpool", dims=dims, k=k, stride=st, pads=pads, ceil=ceil), outs[0], j, out, fac)
+            emit(_Spec("sumpool", dims=dims, k=k, stride=st, pads=pads, ceil=ceil), outs[0], j, out, fac, eb)
             if flat:  # keepdims=0: (C, 1, 1) -> (C,)
-                emit(_Spec("flatten", dims=out), outs[0], len(specs) - 1, (out[0],), fac)
+                emit(_Spec("flatten", dims=out), outs[0], len(specs) - 1, (out[0],), fac, eb)
         elif op == "Relu":
             j, dims, fac = data_in(node, ins[0])
-            emit(_Spec("relu", dims=dims), outs[0], j, dims, fac)
+            emit(_Spec("relu", dims=dims), outs[0], j, dims, fac, eb)
+        elif op in ("LeakyRelu", "PRelu"):
+            j, dims, fac = data_in(node, ins[0])
+            name = node.get("name") or op
+            if q_method != QuantizationMethod.ScaleQuant:
+                raise ValueError(f"onnx: {name}: a {op} is imported under ScaleQuant only: its output carries a scale "
+                                 f"2^{leaky_bits} that the next power-of-two Rescale absorbs (SimpleQuant has no "
+                                 "rescale, a ScaleQuantPlus rescale divides by CRT moduli)")
+            if op == "LeakyRelu":
+                alpha = np.asarray([float(a.get("alpha", 0.01))], np.float32)
+            else:
+                if len(ins) < 2 or ins[1] not in inits:
+                    raise NotImplementedError(f"onnx: {name}: the PRelu slope must be an initializer")
+                sl = arr(ins[1])
+                shape, C = tuple(int(v) for v in sl.shape), int(dims[0])
+                ok = [(C,)] + ([(C, 1, 1), (1, C, 1, 1)] if len(dims) == 3 else [])
+                if sl.size != 1 and shape not in ok:
+                    raise NotImplementedError(f"onnx: {name}: PRelu slope of shape {shape} against a tensor of dims "
+                                              f"{tuple(dims)}: only a scalar or one slope per channel is supported")
+                alpha = sl.reshape(-1)
+            # leaky(f x) = f leaky(x) for f > 0: the pending factor passes through
+            emit(_Spec("leaky", dims=dims, alpha=alpha), outs[0], j, dims, fac, eb + int(leaky_bits))
         elif op == "Constant" and (outs[0] in clip_consts or outs[0] in pow_consts):
             continue
         elif op == "Clip":
@@ -464,7 +512,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             lo = None if lo is None or not np.isfinite(lo) or lo <= -3.4e38 else lo
             hi = None if hi is None or not np.isfinite(hi) or hi >= 3.4e38 else hi
             if lo == 0.0 and hi is None:
-                emit(_Spec("relu", dims=dims), outs[0], j, dims, fac)
+                emit(_Spec("relu", dims=dims), outs[0], j, dims, fac, eb)
             elif lo is None or hi is None:
                 raise NotImplementedError(f"onnx: {name}: a Clip needs finite min and max (only min=0 without max "
                                           "is accepted, as a Relu)")
@@ -474,6 +522,9 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                                      "activation scale for its bounds); use ScaleQuant or ScaleQuantPlus")
                 if not lo < hi:
                     raise ValueError(f"onnx: {name}: Clip needs min < max, got ({lo}, {hi})")
+                if eb:
+                    raise NotImplementedError(f"onnx: {name}: a LeakyRelu's 2^{eb} scale reaches this Clip before a "
+                                              "Conv/Gemm could absorb it")
                 # clip(f x, lo, hi) = f clip(x, lo / f, hi / f): the pending factor passes through
                 emit(_Spec("clip", dims=dims, lo=lo / fac, hi=hi / fac), outs[0], j, dims, fac)
         elif op == "ArgMax":
@@ -497,10 +548,11 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             (j0, d0, f0), (j1, d1, f1) = data_in(node, ins[0]), data_in(node, ins[1])
             no_factor(node, f0)
             no_factor(node, f1)
+            same_bits(node, ins)
             assert d0 == d1, f"onnx: Add operands of different dims {d0} and {d1}"
             if j1 == len(specs) - 1:  # the current tensor is the previous layer's where possible
                 j0, j1 = j1, j0
-            emit(_Spec("add", dims=d0, src=j1), outs[0], j0, d0)
+            emit(_Spec("add", dims=d0, src=j1), outs[0], j0, d0, 1.0, eb)
         elif op == "Mul":
             name = node.get("name") or op
             const = [x for x in ins if x in inits]
@@ -509,7 +561,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                                           "product of two produced tensors)")
             (j0, d0, f0), (j1, d1, f1) = data_in(node, ins[0]), data_in(node, ins[1])
             if res(ins[0]) == res(ins[1]):
-                emit(_Spec("mul", dims=d0, sq=True), outs[0], j0, d0, f0 * f0)
+                emit(_Spec("mul", dims=d0, sq=True, e=2 * eb), outs[0], j0, d0, f0 * f0)
             else:
                 def chan(full, d):
                     return len(full) == 3 and tuple(d) in ((full[0],), (full[0], 1, 1))
@@ -527,7 +579,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                     raise NotImplementedError(f"onnx: {name}: Mul of dims {tuple(d0)} and {tuple(d1)}: only equal dims "
                                               "and a per-channel operand ([N, C, 1, 1] or [N, C] against "
                                               "[N, C, H, W]) are supported")
-                emit(_Spec("mul", dims=d0, sq=False, src=j1, src_dims=sd), outs[0], j0, d0, f0 * f1)
+                emit(_Spec("mul", dims=d0, sq=False, src=j1, src_dims=sd, e=bits(ins[0]) + bits(ins[1])), outs[0], j0,
+                     d0, f0 * f1)
         elif op == "Pow":
             name = node.get("name") or op
             j, dims, fac = data_in(node, ins[0])
@@ -539,7 +592,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             if ex != 2.0:
                 raise NotImplementedError(f"onnx: {name}: Pow is supported with the constant scalar exponent 2 only"
                                           + ("" if ex is None else f", got {ex}"))
-            emit(_Spec("mul", dims=dims, sq=True), outs[0], j, dims, fac * fac)
+            emit(_Spec("mul", dims=dims, sq=True, e=2 * eb), outs[0], j, dims, fac * fac)
         elif op == "Concat":
             name = node.get("name") or op
             ops_ = [data_in(node, x) for x in ins]
@@ -548,13 +601,14 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             if tf or nd not in (1, 3) or axis % (nd + 1) != 1:
                 raise NotImplementedError(f"onnx: {name}: Concat is supported along the channel axis (axis=1 of "
                                           "NCHW or 2-D tensors) only")
+            same_bits(node, ins)
             for _, d_, f_ in ops_:
                 no_factor(node, f_)
                 if len(d_) != nd or d_[1:] != ops_[0][1][1:]:
                     raise ValueError(f"onnx: {name}: Concat operands of different H x W")
             dl = [d_ for _, d_, _ in ops_]
             out = (sum(d_[0] for d_ in dl),) + tuple(dl[0][1:])
-            emit(_Spec("concat", dims_list=dl, srcs=[j_ for j_, _, _ in ops_]), outs[0], len(specs) - 1, out)
+            emit(_Spec("concat", dims_list=dl, srcs=[j_ for j_, _, _ in ops_]), outs[0], len(specs) - 1, out, 1.0, eb)
         else:
             raise NotImplementedError(f"onnx: unsupported operator {op}")
 
@@ -563,6 +617,9 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         if r in tfac and tfac[r] != 1.0:
             raise NotImplementedError(f"onnx: graph output {o['name']!r} carries an average's 1/K factor that no "
                                       "Conv/Gemm absorbs")
+        if tbits.get(r, 0):
+            raise NotImplementedError(f"onnx: graph output {o['name']!r} carries a LeakyRelu's 2^{tbits[r]} scale that "
+                                      "no Conv/Gemm absorbs")
 
     # materialize: quantize weights, insert rescales, remap spec indices -> layer indices
     layers = []
@@ -572,20 +629,22 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         if s.kind == "flatten":
             layers.append(Flatten(kw["dims"]))
         elif s.kind == "dense":
-            layers.append(Dense(kw["w"], kw["b"], q_parameter, q_method, q_const, channel_tf=kw["channel_tf"]))
+            layers.append(Dense(kw["w"], kw["b"], q_parameter, q_method, q_const, channel_tf=kw["channel_tf"],
+                                in_scale_bits=kw["e"]))
         elif s.kind == "conv":
             C, H, W = kw["dims"]
             F, _, kh, kw_ = kw["w"].shape
             layers.append(Conv2d(kw["w"], kw["b"], W, H, C, F, kw_, kh, kw["stride"][1], kw["stride"][0],
                                  q_parameter, q_method, q_const, pad_width=kw["pads"][1], pad_height=kw["pads"][0],
-                                 groups=kw["group"], dilation_width=kw["dil"][1], dilation_height=kw["dil"][0]))
+                                 groups=kw["group"], dilation_width=kw["dil"][1], dilation_height=kw["dil"][0],
+                                 in_scale_bits=kw["e"]))
         elif s.kind == "convt":
             C, H, W = kw["dims"]
             _, F, kh, kw_ = kw["w"].shape
             layers.append(ConvTranspose2d(kw["w"], kw["b"], W, H, C, F, kw_, kh, kw["stride"][1], kw["stride"][0],
                                           q_parameter, q_method, q_const, pad_width=kw["pads"][1],
                                           pad_height=kw["pads"][0], out_pad_width=kw["opad"][1],
-                                          out_pad_height=kw["opad"][0]))
+                                          out_pad_height=kw["opad"][0], in_scale_bits=kw["e"]))
         elif s.kind == "upsample":
             layers.append(Upsample(kw["dims"], kw["f"][0], kw["f"][1]))
         elif s.kind in ("maxpool", "sumpool"):
@@ -595,6 +654,12 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                               pad_width=kw["pads"][1], pad_height=kw["pads"][0], ceil_mode=kw["ceil"]))
         elif s.kind == "relu":
             layers.append(Relu(kw["dims"]))
+        elif s.kind == "leaky":
+            al = kw["alpha"]
+            try:
+                layers.append(LeakyRelu(kw["dims"], al if al.size > 1 else float(al[0]), leaky_bits))
+            except ValueError as ex:
+                raise ValueError(f"onnx: {ex}") from None
         elif s.kind == "sign":
             layers.append(Sign(kw["dims"]))
         elif s.kind == "clip":
@@ -613,8 +678,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         spec_to_layer[i] = len(layers) - 1
         if s.kind in ("dense", "conv", "convt", "mul"):  # a product carries both operands' scales, as a conv's does
             out = layers[-1].out_dims
-            if q_method == QuantizationMethod.ScaleQuant:
-                layers.append(Rescale(q_parameter, out))
+            if q_method == QuantizationMethod.ScaleQuant:  # + the input's pending scale bits
+                layers.append(Rescale(q_parameter + kw.get("e", 0), out))
                 spec_to_layer[i] = len(layers) - 1
             elif q_method == QuantizationMethod.ScaleQuantPlus:
                 layers.append(Rescale([q_parameter], out))
@@ -623,9 +688,10 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
 
 
 def load_onnx_model(path, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant, q_parameter: int = -1,
-                    q_const: float = DEFAULT_Q_CONST) -> Circuit:
-    """Reference: load_onnx_model (onnx_modelloader.h:371-406)."""
-    return create_circuit_from_onnx(parse_onnx(path), q_method, q_const, q_parameter)
+                    q_const: float = DEFAULT_Q_CONST, leaky_bits: int = 4) -> Circuit:
+    """Reference: load_onnx_model (onnx_modelloader.h:371-406). leaky_bits: the slope bits of imported LeakyRelu /
+    PRelu nodes (docs/LEAKY_RELU.md)."""
+    return create_circuit_from_onnx(parse_onnx(path), q_method, q_const, q_parameter, leaky_bits)
 
 
 # ------------------------------------------------------------------ export
@@ -779,6 +845,14 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             scale[out] = K * l.kh * l.kw
         elif isinstance(l, Relu):
             nodes.append(_node("Relu", [cur], [out], name))
+            scale[out] = K
+        elif isinstance(l, LeakyRelu):  # positive-homogeneous: a pending average ratio passes through
+            if l.alpha.size == 1:
+                nodes.append(_node("LeakyRelu", [cur], [out], name, _attr_float("alpha", float(l.alpha[0]))))
+            else:
+                shape = (l.alpha.size, 1, 1) if len(l.in_dims) == 3 else (l.alpha.size,)
+                inits.append(_tensor(f"{name}.slope", l.alpha.reshape(shape)))
+                nodes.append(_node("PRelu", [cur, f"{name}.slope"], [out], name))
             scale[out] = K
         elif isinstance(l, Clip):
             # opset-11 form: min / max are scalar inputs; on an average the bounds of the sum shrink by K

@@ -40,12 +40,20 @@ def quantize_scale(values: np.ndarray, s: int) -> np.ndarray:
     return llround(v * np.float32(s))
 
 
-def quantize_params(w: np.ndarray, b: np.ndarray, method: QuantizationMethod, q_parameter: int, q_const: float):
-    """Returns (w_q, b_q) as int64 arrays."""
+def quantize_params(w: np.ndarray, b: np.ndarray, method: QuantizationMethod, q_parameter: int, q_const: float,
+                    in_scale_bits: int = 0):
+    """Returns (w_q, b_q) as int64 arrays. `in_scale_bits` = e: the layer's input carries a pending scale 2^e
+    beyond the activation scale (a LeakyRelu's 2^s, docs/LEAKY_RELU.md), so a ScaleQuant bias is quantized at
+    2^(2l + e); the weights are untouched."""
+    in_scale_bits = int(in_scale_bits)
+    if in_scale_bits < 0:
+        raise ValueError(f"in_scale_bits must be >= 0, got {in_scale_bits}")
+    if in_scale_bits and method != QuantizationMethod.ScaleQuant:
+        raise ValueError("in_scale_bits: pending scale bits exist under ScaleQuant only")
     if method == QuantizationMethod.SimpleQuant:
         return quantize_simple(w, q_const), quantize_simple(b, q_const)
     if method == QuantizationMethod.ScaleQuant:
-        return quantize_scale(w, 1 << q_parameter), quantize_scale(b, 1 << (2 * q_parameter))
+        return quantize_scale(w, 1 << q_parameter), quantize_scale(b, 1 << (2 * q_parameter + in_scale_bits))
     if method == QuantizationMethod.ScaleQuantPlus:
         return quantize_scale(w, q_parameter), quantize_scale(b, q_parameter * q_parameter)
     raise ValueError(f"unknown quantization method {method}")

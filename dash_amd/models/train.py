@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Mul, Relu, Rescale, Sign, SumPool2d,
+from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, Relu, Rescale, Sign, SumPool2d,
                          Upsample, _pool_out)
 from ..ir.quant import QuantizationMethod
 from .zoo import ARCHS, canonical
@@ -114,6 +114,10 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             raise NotImplementedError(f"training: op {k} (skip connections) not supported by the sequential trainer")
         elif k == "relu":
             mods.append(nn.ReLU())
+        elif k == "leaky":
+            mods.append(nn.LeakyReLU(float(op[1])))
+        elif k == "prelu":
+            mods.append(nn.PReLU(dims[0]))
         elif k == "square":
             mods.append(_square_module()())
         elif k == "se":
@@ -146,8 +150,9 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
 
 
 def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_parameter: int = 5,
-               q_const: float = 0.02) -> Circuit:
-    """Convert a trained sequential model to a Dash circuit (float weights, quantized per q_method)."""
+               q_const: float = 0.02, leaky_bits: int = 4) -> Circuit:
+    """Convert a trained sequential model to a Dash circuit (float weights, quantized per q_method). A LeakyReLU /
+    PReLU becomes a LeakyRelu(slope_bits=leaky_bits); the next linear layer absorbs its 2^s (docs/LEAKY_RELU.md)."""
     torch, nn = _torch()
     arch = ARCHS[canonical(name)]
     C, H, W = arch["input"]
@@ -155,18 +160,33 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
     qm = QuantizationMethod(q_method)
     layers = []
 
-    def rescale(d):
+    pend = [0]  # pending scale bits of the current tensor
+
+    def rescale(d):  # consumes the pending bits
         if qm == QuantizationMethod.ScaleQuant:
-            layers.append(Rescale(q_parameter, d))
+            layers.append(Rescale(q_parameter + pend[0], d))
         elif qm == QuantizationMethod.ScaleQuantPlus:
             layers.append(Rescale([q_parameter], d))
+        pend[0] = 0
 
     for m in model:
-        if isinstance(m, nn.Flatten):
+        if pend[0] and isinstance(m, (nn.ConvTranspose2d, nn.Hardtanh, nn.Tanh, _square_module())):
+            raise NotImplementedError(f"training: a leaky ReLU's 2^{pend[0]} scale reaches {type(m).__name__} before a "
+                                      "Linear or Conv2d could absorb it")
+        if isinstance(m, (nn.LeakyReLU, nn.PReLU)):
+            if qm != QuantizationMethod.ScaleQuant:
+                raise ValueError("training: a leaky ReLU exists under ScaleQuant only")
+            alpha = float(m.negative_slope) if isinstance(m, nn.LeakyReLU) else m.weight.detach().cpu().numpy()
+            if not isinstance(alpha, float) and alpha.size == 1:
+                alpha = float(alpha.reshape(-1)[0])
+            layers.append(LeakyRelu(dims, alpha, leaky_bits))
+            pend[0] += leaky_bits
+        elif isinstance(m, nn.Flatten):
             layers.append(Flatten(dims))
             dims = (int(np.prod(dims)),)
         elif isinstance(m, nn.Linear):
-            d = Dense(m.weight.detach().cpu().numpy(), m.bias.detach().cpu().numpy(), q_parameter, qm, q_const)
+            d = Dense(m.weight.detach().cpu().numpy(), m.bias.detach().cpu().numpy(), q_parameter, qm, q_const,
+                      in_scale_bits=pend[0])
             layers.append(d)
             dims = d.out_dims
             rescale(dims)
@@ -175,7 +195,8 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
             F, Cg, kh, kw = w.shape  # [F][C/groups][kh][kw]
             c = Conv2d(w, m.bias.detach().cpu().numpy(), dims[2], dims[1], Cg * m.groups, F, kw, kh, m.stride[1],
                        m.stride[0], q_parameter, qm, q_const, pad_width=m.padding[1], pad_height=m.padding[0],
-                       groups=m.groups, dilation_width=m.dilation[1], dilation_height=m.dilation[0])
+                       groups=m.groups, dilation_width=m.dilation[1], dilation_height=m.dilation[0],
+                       in_scale_bits=pend[0])
             layers.append(c)
             dims = c.out_dims
             rescale(dims)

@@ -12,7 +12,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, MaxPool2d, Mul, Relu,
+from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, Relu,
                          Rescale, Sign, SumPool2d, Upsample)
 from ..ir.quant import QuantizationMethod, quantize_input
 
@@ -34,6 +34,10 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   pad = dilation = rate (same size out), each + ReLU, all reading the same tensor, then Concat
 #                   | ("skip",) remember the current tensor | ("cat",) channel concat of the most recent open skip
 #                   with the current tensor, skip first (an encoder-decoder's skip connection)
+#                   | ("leaky", alpha) LeakyRelu with the dyadic slope round(alpha 2^s) / 2^s, s = leaky_bits, and
+#                   ("prelu",) the same with one slope per channel (PyTorch's initial 0.25): ScaleQuant only; the
+#                   output's 2^s passes through relu / maxpool / sumpool / gap / flatten / up to the next conv or fc,
+#                   which quantizes its bias at 2^(2l + s) and rescales by l + s (docs/LEAKY_RELU.md)
 #                   | ("square",) x^2 (a polynomial activation) + the scheme's rescale, as after a conv
 #                   | ("se", r) squeeze-and-excitation: the current (C, H, W) tensor is kept, then gap, a 1x1 conv to
 #                   C / r + ReLU, a 1x1 conv to C, Clip(0, 1) (a hard sigmoid's range) and the channel-broadcast Mul
@@ -102,6 +106,14 @@ ARCHS: dict[str, dict] = {
         ("dwconv", 3, 1, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("se", 4), ("relu6",),
         ("gap",), ("flatten",), ("fc", 10)]},
     # the CryptoNets MNIST network: squares are the only non-linearity (no sign anywhere)
+    # DarkNet-style CIFAR net (the tiny-YOLO backbone's pattern): 3x3 convs with LeakyReLU(0.1) and 2x2 max pools
+    # (32 -> 16 -> 8 -> 4 -> 2), a 1x1 classifier conv, a global average and a dense head
+    "DARKNET_TINY_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 8, 3, 1, 1), ("leaky", 0.1), ("maxpool", 2, 2),
+        ("conv", 16, 3, 1, 1), ("leaky", 0.1), ("maxpool", 2, 2),
+        ("conv", 32, 3, 1, 1), ("leaky", 0.1), ("maxpool", 2, 2),
+        ("conv", 32, 3, 1, 1), ("leaky", 0.1), ("maxpool", 2, 2),
+        ("conv", 16, 1, 1, 0), ("leaky", 0.1), ("gap",), ("flatten",), ("fc", 10)]},
     "CRYPTONETS_MNIST": {"input": (1, 28, 28), "ops": [
         ("conv", 5, 5, 2, 1), ("square",), ("flatten",), ("fc", 100), ("square",), ("fc", 10)]},
     # SqueezeNet-style CIFAR net: a stride-2 stem (32 -> 16), ceil-mode 3x3/2 max pools whose last window is cut at
@@ -156,8 +168,9 @@ def _init(rng, shape, fan_in):
 
 
 def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.ScaleQuant, q_parameter: int = 5,
-                  q_const: float = 0.02, seed: int = 0, weights: Optional[dict] = None) -> Circuit:
-    """Random-init (or given float weights) circuit with Dash quantization."""
+                  q_const: float = 0.02, seed: int = 0, weights: Optional[dict] = None, leaky_bits: int = 4) -> Circuit:
+    """Random-init (or given float weights) circuit with Dash quantization. leaky_bits: the slope bits of the
+    ("leaky", alpha) and ("prelu",) ops."""
     arch = ARCHS[canonical(name)]
     rng = np.random.default_rng(seed)
     C, H, W = arch["input"]
@@ -165,9 +178,11 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
     layers = []
     qm = QuantizationMethod(q_method)
 
-    def rescale_after(d):
+    pend = [0]  # pending scale bits of the current tensor (a LeakyRelu's 2^s, docs/LEAKY_RELU.md)
+
+    def rescale_after(d, e=0):
         if qm == QuantizationMethod.ScaleQuant:
-            layers.append(Rescale(q_parameter, d))
+            layers.append(Rescale(q_parameter + e, d))
         elif qm == QuantizationMethod.ScaleQuantPlus:
             layers.append(Rescale([q_parameter], d))
 
@@ -176,14 +191,19 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         wt = _init(rng, (cout, cin // groups, k, k), fan_in)
         bs = _init(rng, (cout,), fan_in)
         c = Conv2d(wt, bs, w, h, cin, cout, k, k, s, s, q_parameter, qm, q_const, pad_width=p, pad_height=p,
-                   groups=groups, dilation_width=dil, dilation_height=dil)
+                   groups=groups, dilation_width=dil, dilation_height=dil, in_scale_bits=pend[0])
         layers.append(c)
-        rescale_after(c.out_dims)
+        rescale_after(c.out_dims, pend[0])
+        pend[0] = 0
         return c.out_dims
 
     skips = []  # open ("skip",) marks: (layer index, dims)
     for op in arch["ops"]:
         kind = op[0]
+        if pend[0] and kind not in ("conv", "dwconv", "fc", "relu", "leaky", "prelu", "maxpool", "sumpool", "gap",
+                                    "flatten", "up"):
+            raise NotImplementedError(f"{name}: op {len(layers)} ({kind}): a leaky ReLU's 2^{pend[0]} scale reaches it "
+                                      "before a conv or fc could absorb it")
         if kind == "convt":
             _, cout, k, s, p, op_ = op
             fan_in = cout * k * k  # PyTorch's ConvTranspose2d default: fan-in of the [C][F][k][k] weight's axis 1
@@ -214,10 +234,11 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             fin = int(np.prod(dims))
             wt = _init(rng, (op[1], fin), fin)
             bs = _init(rng, (op[1],), fin)
-            d = Dense(wt, bs, q_parameter, qm, q_const)
+            d = Dense(wt, bs, q_parameter, qm, q_const, in_scale_bits=pend[0])
             layers.append(d)
             dims = d.out_dims
-            rescale_after(dims)
+            rescale_after(dims, pend[0])
+            pend[0] = 0
         elif kind == "conv":
             _, cout, k, s, p = op[:5]
             dims = conv(cout, k, s, p, dims[0], dims[1], dims[2], dil=op[5] if len(op) > 5 else 1)
@@ -242,6 +263,13 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             dims = cat.out_dims
         elif kind == "relu":
             layers.append(Relu(dims))
+        elif kind in ("leaky", "prelu"):
+            if qm != QuantizationMethod.ScaleQuant:
+                raise ValueError(f"{name}: op {len(layers)} ({kind}): a leaky ReLU exists under ScaleQuant only (its "
+                                 "2^s output scale needs a power-of-two rescale behind it)")
+            alpha = float(op[1]) if kind == "leaky" else np.full(dims[0], 0.25, np.float32)
+            layers.append(LeakyRelu(dims, alpha, leaky_bits))
+            pend[0] += leaky_bits
         elif kind == "sign":
             layers.append(Sign(dims))
         elif kind in ("relu6", "clip"):
