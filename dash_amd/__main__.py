@@ -28,9 +28,11 @@ def _circuit_and_inputs(cfg):
     if cfg.model_file:
         from .ir.onnx import load_onnx_model
 
-        circuit = load_onnx_model(cfg.model_file, qm, qp, cfg.q_const, leaky_bits=cfg.leaky_bits)
+        circuit = load_onnx_model(cfg.model_file, qm, qp, cfg.q_const, leaky_bits=cfg.leaky_bits, tanh=cfg.tanh,
+                                  pwl_bits=cfg.pwl_bits)
     else:
-        circuit = build_circuit(cfg.model, qm, qp, cfg.q_const, seed=0, leaky_bits=cfg.leaky_bits)
+        circuit = build_circuit(cfg.model, qm, qp, cfg.q_const, seed=0, leaky_bits=cfg.leaky_bits,
+                                pwl_bits=cfg.pwl_bits)
     labels = None
     if cfg.dataset and cfg.data_dir:
         from . import data
@@ -48,7 +50,7 @@ def _circuit_and_inputs(cfg):
         xq = [quantize_input(x, qm, -1, circuit.get_q_const()) for x in imgs]
     else:
         xq = [quantize_input(x, qm, qp, cfg.q_const) for x in imgs]
-        if any(l.name in ("clip", "argmax", "conv_transpose2d", "mul", "leaky_relu") for l in circuit.layers):
+        if any(l.name in ("clip", "argmax", "conv_transpose2d", "mul", "leaky_relu", "pwl") for l in circuit.layers):
             # these layers exist in the hardened encoding only: track the ranges so that rescale="auto" can resolve
             # to the mixed-radix rescale (the legacy one cannot be hardened)
             circuit.calibrate(xq)

@@ -44,6 +44,8 @@ class DashConfig:
     q_parameter: Optional[int] = None
     q_const: float = 0.02                     # SimpleQuant constant (onnx_modelloader.h:377)
     leaky_bits: int = 4                       # slope bits s of LeakyRelu / PRelu layers: slope = round(alpha 2^s) / 2^s, 1..8 (docs/LEAKY_RELU.md)
+    pwl_bits: int = 8                         # slope bits s of piecewise-linear activations (Sigmoid, Tanh, HardSigmoid), 1..8 (docs/PWL.md)
+    tanh: str = "sign"                        # ONNX Tanh: "sign" (the reference's BNN convention) | "pwl" (piecewise-linear tanh)
     # garbling
     crt: Union[int, list, None] = None        # k (first k primes) or explicit base
     mrs: Union[float, list, None] = None      # ReLU accuracy (table lookup) or explicit MRS base

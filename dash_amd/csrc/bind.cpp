@@ -215,6 +215,25 @@ PYBIND11_MODULE(_dash_native, m) {
     m.def("clip_joint_threshold", [](const std::vector<int>& crt, int l, i64 q_hi) {
         return ClipPlan(crt, q_hi, RescaleMrsPlan(crt, l, true)).t_hi;
     });
+    // PiecewiseLinear (gadgets.h PwlPlan), from the plan itself: the kept breakpoints (T_i, D_i), the constant
+    // V - A_0 T_1, the PRG stream / gate slots (sign, multiply) per kept breakpoint, the table entries per element
+    // for a sign of n_sign entries, and the device factor table [residue][m + 1]
+    m.def("pwl_plan", [](const std::vector<int>& crt, i64 s, const std::vector<i64>& T, const std::vector<i64>& A, i64 V,
+                         i64 n_sign) {
+        const PwlPlan P(crt, s, T, A, V);
+        std::vector<std::pair<int, int>> slots;
+        for (int i = 0; i < P.m(); ++i) slots.emplace_back(PwlPlan::sign_slot(i), PwlPlan::mult_slot(i));
+        const std::vector<uint8_t> tab = P.table();
+        py::dict d;
+        d["T"] = P.T;
+        d["D"] = P.D;
+        d["C"] = P.C;
+        d["slots"] = slots;
+        d["entries"] = P.entries(n_sign);
+        d["table"] = std::vector<int>(tab.begin(), tab.end());
+        return d;
+    });
+    m.def("stream_id", [](u64 layer, u64 slot, u64 elem) { return stream_id(layer, slot, elem); });
     // ArgMax (gadgets.h ArgMaxPlan): table entries per output position over K candidates, and per pair
     // operation of every level
     m.def("argmax_entries", [](const std::vector<int>& crt, i64 K) { return ArgMaxPlan::entries(crt, K); });

@@ -1,5 +1,6 @@
 // Host (oracle) evaluator and decoder. Bit-exact with the HIP evaluator; the
 // CPU path of the reference (gci.h:345-380 + every GarbledX::cpu_evaluate).
+#include <array>
 #include <chrono>
 #include "layers.h"
 
@@ -432,6 +433,62 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                         }
                         clip_eval_elem(cp, exact ? nullptr : &sp_a, exact ? &sp_m : nullptr, Z, x.data(), T, e, y.data(),
                                        stream_id(L, 1, e), stream_id(L, 2, e), stream_id(L, 3, e));
+                    }
+                }, nt);
+                cur = std::move(nxt);
+                break;
+            }
+            case K_PWL: {
+                DASH_CHECK(hard, "pwl: the PiecewiseLinear layer exists in the hardened encoding only");
+                const PwlPlan pp(crt, g.param("s"), g.vec("T"), g.vec("A"), g.param("V"));
+                const int nb = pp.m();
+                const bool exact = g.param("smode", 0) == 1;
+                SignPlan sp_a;
+                SignMrsPlan sp_m;
+                if (exact) sp_m = SignMrsPlan(crt);
+                else sp_a = SignPlan(crt, m.h.mrs, {2}, 0, 1, fused);
+                std::vector<std::array<const Array*, 5>> T(nb);
+                for (int i = 0; i < nb; ++i) {
+                    const std::string pre = PwlPlan::prefix_of(i);
+                    T[i] = {nullptr, nullptr, nullptr, &g.arr(pre + "mm.g"), &g.arr(pre + "mm.e")};
+                    if (exact) {
+                        T[i][0] = &g.arr(pre + "mrs");
+                    } else {
+                        T[i][0] = &g.arr(pre + "s.approx");
+                        T[i][1] = &g.arr(pre + "s.cast2");
+                        T[i][2] = &g.arr(pre + "s.sign");
+                    }
+                    DASH_CHECK(T[i][3]->shape[0] == Nin && T[i][3]->shape[1] == pp.sum_crt && T[i][4]->shape[0] == Nin &&
+                                   T[i][0]->shape[0] == Nin, "pwl table shape");
+                }
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) nxt.emplace_back(crt[j], Nin);
+                parallel_for(Nin, [&](i64 b0, i64 b1) {
+                    std::vector<const comp_t*> x(k);
+                    std::vector<comp_t*> y(k);
+                    u64 sg[PwlPlan::kMaxBreaks], mg[PwlPlan::kMaxBreaks];
+                    PwlRows r;
+                    auto row = [](const Array* a, i64 e) { return const_cast<u128*>(a->ptr<u128>()) + e * a->shape[1]; };
+                    for (i64 e = b0; e < b1; ++e) {
+                        for (int j = 0; j < k; ++j) {
+                            x[j] = cur[j].at(e);
+                            y[j] = nxt[j].at(e);
+                        }
+                        for (int i = 0; i < nb; ++i) {
+                            sg[i] = stream_id(L, PwlPlan::sign_slot(i), e);
+                            mg[i] = stream_id(L, PwlPlan::mult_slot(i), e);
+                            if (exact) {
+                                r.mrs[i] = row(T[i][0], e);
+                            } else {
+                                r.approx[i] = row(T[i][0], e);
+                                r.cast2[i] = row(T[i][1], e);
+                                r.sign[i] = row(T[i][2], e);
+                            }
+                            r.g[i] = row(T[i][3], e);
+                            r.e[i] = const_cast<u128*>(T[i][4]->ptr<u128>()) + e * k * 3;
+                        }
+                        pwl_eval_elem(pp, exact ? nullptr : &sp_a, exact ? &sp_m : nullptr, Z, sg, mg, x.data(), r,
+                                      y.data());
                     }
                 }, nt);
                 cur = std::move(nxt);

@@ -904,6 +904,71 @@ void clip_mult_eval(const ClipPlan& P, const comp_t* const* x, const comp_t* slo
 }
 
 // ---------------------------------------------------------------------------
+// PiecewiseLinear (gadgets.h PwlPlan)
+void pwl_garble_elem(const PwlPlan& P, const SignPlan* sp_a, const SignMrsPlan* sp_m, const LabelBank& R,
+                     const LabelBank& Z, const Prg& prg, const u64* sign_streams, const u64* mult_streams,
+                     const comp_t* const* x0, const PwlRows& t, comp_t* const* out0) {
+    const int k = P.k();
+    DASH_CHECK(k <= 16, "pwl: at most 16 residues");
+    comp_t xs[16 * 128], sig[128], tj[128];
+    const comp_t* xp[16];
+    const ModInfo& m2 = mod_info(2);
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        xp[j] = xs + static_cast<size_t>(128) * j;
+        // a0 x0_j - c R_j: the linear term and the constant V - A_0 T_1
+        for (int c = 0; c < mp.n; ++c)
+            out0[j][c] = static_cast<comp_t>((P.a0(mp.p) * x0[j][c] + (mp.p - P.c(mp.p)) * R.get(mp.p)[c]) % mp.p);
+    }
+    for (int i = 0; i < P.m(); ++i) {
+        for (int j = 0; j < k; ++j) {  // the wire x - T_i on the labels of x
+            const int p = P.crt[j];
+            lab_affine(xs + static_cast<size_t>(128) * j, x0[j], pmod(P.T[i], p), R.get(p), nr_comps(p), p);
+        }
+        if (sp_m) {
+            sign_mrs_garble_elem(*sp_m, R, prg, sign_streams[i], xp, t.mrs[i], sig, true);
+        } else {
+            comp_t* outs[1] = {sig};
+            sign_garble_elem(*sp_a, R, Z, prg, sign_streams[i], xp, t.approx[i], nullptr, t.cast2[i], t.sign[i], outs,
+                             true);
+        }
+        u64 ctr = 0;
+        for (int j = 0; j < k; ++j) {
+            const ModInfo& mp = mod_info(P.crt[j]);
+            mixed_mult_garble(xp[j], mp, sig, m2, R, prg, mult_streams[i], ctr, t.g[i] + P.prefix[j], t.e[i] + 3 * j, tj,
+                              MMTw{true, mult_streams[i], j, k, true});
+            lab_axpy(out0[j], P.d(i, mp.p), tj, mp.n, mp.p);
+        }
+    }
+}
+
+void pwl_eval_elem(const PwlPlan& P, const SignPlan* sp_a, const SignMrsPlan* sp_m, const LabelBank& Z,
+                   const u64* sign_gates, const u64* mult_gates, const comp_t* const* x, const PwlRows& t,
+                   comp_t* const* out) {
+    const int k = P.k();
+    comp_t sig[128], tj[128];
+    const ModInfo& m2 = mod_info(2);
+    for (int j = 0; j < k; ++j) {
+        const ModInfo& mp = mod_info(P.crt[j]);
+        for (int c = 0; c < mp.n; ++c) out[j][c] = static_cast<comp_t>((P.a0(mp.p) * x[j][c]) % mp.p);
+    }
+    for (int i = 0; i < P.m(); ++i) {
+        if (sp_m) {
+            sign_mrs_eval_elem(*sp_m, x, t.mrs[i], sig, true, sign_gates[i]);
+        } else {
+            comp_t* outs[1] = {sig};
+            sign_eval_elem(*sp_a, Z, x, t.approx[i], nullptr, t.cast2[i], t.sign[i], outs, true, sign_gates[i]);
+        }
+        for (int j = 0; j < k; ++j) {
+            const ModInfo& mp = mod_info(P.crt[j]);
+            mixed_mult_eval(x[j], mp, sig, m2, t.g[i] + P.prefix[j], t.e[i] + 3 * j, tj,
+                            MMTw{true, mult_gates[i], j, k, true});
+            lab_axpy(out[j], P.d(i, mp.p), tj, mp.n, mp.p);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // ArgMax (gadgets.h ArgMaxPlan)
 ArgMaxPlan::ArgMaxPlan(const std::vector<int>& crt_, i64 K_) : crt(crt_), K(K_), sign(crt_) {
     DASH_CHECK(K >= 2, "argmax needs at least 2 candidates");

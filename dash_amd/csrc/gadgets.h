@@ -624,4 +624,84 @@ struct LeakyPlan {
     }
 };
 
+// ----------------------------------------------------------------------------
+// PiecewiseLinear (wire kind 21, docs/PWL.md): y = V + A_0 (x - T_1) + sum_i D_i relu(x - T_i) with m <= 8
+// breakpoints T_1 < ... < T_m, slope numerators A_0 .. A_m over 2^s and D_i = A_i - A_(i-1); breakpoints with
+// D_i = 0 are dropped. Per kept breakpoint i (in order, i = 0 .. m-1): one sign s_i = [x - T_i >= 0] of the
+// layer's resolved sign construction and the ReLU's mixed-modulus half gates keyed by s_i, both on the evaluator's
+// labels of x: T_i is folded into the garbler's base labels (x0_j + T_i R_j is the base of the wire x - T_i, as
+// the Clip folds its bounds). The output is the free combination per residue p
+//   out = (A_0 mod p) x + sum_i (D_i mod p) t_i,   t_i = relu(x - T_i),
+// of zero labels on the garbler (shifted bases, and the constant V - A_0 T_1 folded in: out0 -= (V - A_0 T_1) R)
+// and of active labels on the evaluator. Arrays under "b<i>.": mrs or s.approx / s.cast2 / s.sign, mm.g [P],
+// mm.e [k][3]. PRG stream slot of sign i: 1 + 2i, of multiply i: 2 + 2i (at most 16 < ArgMax's 20): distinct
+// slots give distinct gate ids, so no two breakpoints share a pad although they read the same labels.
+// Hardened encoding only. Entries per element: m (n_sign + P + 3k).
+struct PwlPlan {
+    static constexpr int kMaxBreaks = 8;
+    std::vector<int> crt;
+    int s = 0;
+    std::vector<i64> T, D;  // the kept breakpoints and their slope steps (D != 0)
+    i64 A0 = 0, C = 0;      // first slope numerator; the constant V - A_0 T_1 (T_1: the first breakpoint given)
+    i64 sum_crt = 0;
+    std::vector<i64> prefix;  // mm.g offset of residue j
+    PwlPlan() = default;
+    PwlPlan(const std::vector<int>& crt_, i64 s_, const std::vector<i64>& T_, const std::vector<i64>& A_, i64 V)
+        : crt(crt_), s(static_cast<int>(s_)) {
+        DASH_CHECK(s_ >= 1 && s_ <= 8, "pwl: slope_bits outside [1, 8]");
+        DASH_CHECK(!T_.empty() && static_cast<int>(T_.size()) <= kMaxBreaks && A_.size() == T_.size() + 1,
+                   "pwl: between 1 and 8 breakpoints and one more slope");
+        for (size_t i = 0; i + 1 < T_.size(); ++i) DASH_CHECK(T_[i] < T_[i + 1], "pwl: breakpoints must increase");
+        for (i64 a : A_) DASH_CHECK(a >= -(i64{2} << s) && a <= (i64{2} << s), "pwl: slope numerator beyond 2 * 2^s");
+        for (size_t i = 0; i < T_.size(); ++i)
+            if (A_[i + 1] != A_[i]) {
+                T.push_back(T_[i]);
+                D.push_back(A_[i + 1] - A_[i]);
+            }
+        DASH_CHECK(!T.empty(), "pwl: no breakpoint left (every slope step is 0)");
+        A0 = A_[0];
+        C = V - A0 * T_[0];
+        for (int p : crt) {
+            prefix.push_back(sum_crt);
+            sum_crt += p;
+        }
+    }
+    int k() const { return static_cast<int>(crt.size()); }
+    int m() const { return static_cast<int>(T.size()); }
+    static int sign_slot(int i) { return 1 + 2 * i; }
+    static int mult_slot(int i) { return 2 + 2 * i; }
+    static std::string prefix_of(int i) { return "b" + std::to_string(i) + "."; }
+    i64 entries(i64 n_sign) const { return m() * (n_sign + sum_crt + 3 * k()); }
+    int a0(int p) const { return static_cast<int>(((A0 % p) + p) % p); }
+    int d(int i, int p) const { return static_cast<int>(((D[i] % p) + p) % p); }
+    int c(int p) const { return static_cast<int>(((C % p) + p) % p); }
+    // the device table [residue][m + 1]: A_0 mod p, then D_i mod p
+    std::vector<uint8_t> table() const {
+        std::vector<uint8_t> t;
+        for (int p : crt) {
+            t.push_back(static_cast<uint8_t>(a0(p)));
+            for (int i = 0; i < m(); ++i) t.push_back(static_cast<uint8_t>(d(i, p)));
+        }
+        return t;
+    }
+};
+// One element's table rows per kept breakpoint: the exact sign's row (mrs) or the approximate sign's three
+// (approx, cast2, sign), and the multiply's g [sum_crt] and e [k][3].
+struct PwlRows {
+    u128* mrs[PwlPlan::kMaxBreaks] = {};
+    u128* approx[PwlPlan::kMaxBreaks] = {};
+    u128* cast2[PwlPlan::kMaxBreaks] = {};
+    u128* sign[PwlPlan::kMaxBreaks] = {};
+    u128* g[PwlPlan::kMaxBreaks] = {};
+    u128* e[PwlPlan::kMaxBreaks] = {};
+};
+// sp_m: the exact sign (rows mrs) or, when null, sp_a: the approximate fused sign. stream(slot) is the PRG stream
+// / gate id of the element for a slot (stream_id(L, slot, e)). x0 / out0: base labels; x / out: active labels.
+void pwl_garble_elem(const PwlPlan& P, const SignPlan* sp_a, const SignMrsPlan* sp_m, const LabelBank& R,
+                     const LabelBank& Z, const Prg& prg, const u64* sign_streams, const u64* mult_streams,
+                     const comp_t* const* x0, const PwlRows& t, comp_t* const* out0);
+void pwl_eval_elem(const PwlPlan& P, const SignPlan* sp_a, const SignMrsPlan* sp_m, const LabelBank& Z,
+                   const u64* sign_gates, const u64* mult_gates, const comp_t* const* x, const PwlRows& t,
+                   comp_t* const* out);
+
 }  // namespace dash

@@ -1,3 +1,4 @@
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 // Host garbler: turns a quantized layer list into a GarbledModel.
@@ -38,6 +39,7 @@ const char* kind_name(int kind) {
         case K_ARGMAX: return "argmax";
         case K_MUL: return "mul";
         case K_LEAKY: return "leaky_relu";
+        case K_PWL: return "pwl";
         case K_CONVT: return "conv_transpose2d";
         case K_UPSAMPLE: return "upsample";
     }
@@ -749,7 +751,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
                                     (spec.kind == K_RELU || spec.kind == K_SIGN || spec.kind == K_LEAKY ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
-                                    spec.kind == K_CLIP || spec.kind == K_ARGMAX ||
+                                    spec.kind == K_CLIP || spec.kind == K_ARGMAX || spec.kind == K_PWL ||
                                     (spec.kind == K_MUL && GpuGarbler::mul_fits(k, param1(spec.p, "sq", 0) != 0)) ||
                                     (spec.kind == K_RESCALE && (param1(spec.p, "mode", 0) != 0 || crt_[0] == 2)))));
         const bool passthru = spec.kind == K_FLATTEN;
@@ -1201,6 +1203,95 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 g.a["mm.g"] = t.g;
                 g.a["mm.e"] = t.e;
                 g.a["cap"] = t.cap;
+                g.p["smode"] = {exact ? 1 : 0};
+                break;
+            }
+            case K_PWL: {
+                // gadgets.h PwlPlan: per kept breakpoint one sign (stream slot 1 + 2i) and one set of half gates
+                // (slot 2 + 2i) on the labels shifted by T_i, then the free combination of the base labels
+                DASH_CHECK(is_crt(), "pwl needs CRT-base labels");
+                DASH_CHECK(hard, "pwl: the PiecewiseLinear layer exists in the hardened encoding only");
+                const PwlPlan pp(crt_, param1(spec.p, "s"), paramv(spec.p, "T"), paramv(spec.p, "A"), param1(spec.p, "V"));
+                const int m = pp.m();
+                // the sign construction follows the ReLU's: exact with relu_mrs / relu_joint, else approximate
+                const bool exact = opt.relu_mrs || opt.relu_joint;
+                SignPlan sp_a;
+                SignMrsPlan sp_m;
+                if (exact) sp_m = SignMrsPlan(crt_);
+                else sp_a = SignPlan(crt_, mrs_, {2}, 0, 1, fused);
+                // per breakpoint: sign arrays [0..2] (mrs | approx, cast2, sign), then mm.g, mm.e
+                std::vector<std::array<Array, 5>> t(m);
+                for (int i = 0; i < m; ++i) {
+                    const std::string pre = PwlPlan::prefix_of(i);
+                    if (exact) {
+                        t[i][0] = Array(DType::u128, {Nin, std::max<i64>(sp_m.n_tab, 1)});
+                        if (on_gpu) sinkify(t[i][0], pre + "mrs");
+                    } else {
+                        t[i][0] = Array(DType::u128, {Nin, sp_a.n_approx});
+                        t[i][1] = Array(DType::u128, {Nin, std::max<i64>(sp_a.n_cast, 1)});
+                        t[i][2] = Array(DType::u128, {Nin, sp_a.n_sign});
+                        if (on_gpu) {
+                            sinkify(t[i][0], pre + "s.approx");
+                            sinkify(t[i][1], pre + "s.cast2");
+                            sinkify(t[i][2], pre + "s.sign");
+                        }
+                    }
+                    t[i][3] = Array(DType::u128, {Nin, sum_crt});
+                    t[i][4] = Array(DType::u128, {Nin, static_cast<i64>(k), 3});
+                    if (on_gpu) {
+                        sinkify(t[i][3], pre + "mm.g");
+                        sinkify(t[i][4], pre + "mm.e");
+                    }
+                }
+                if (on_gpu) {
+                    std::vector<Array*> tp;
+                    for (int i = 0; i < m; ++i)
+                        for (int q = 0; q < 5; ++q) tp.push_back(&t[i][q]);
+                    gpu->pwl(L, pp, exact ? &sp_m : nullptr, exact ? nullptr : &sp_a, cur, tp, &prefix);
+                } else {
+                    CrtLabels nxt;
+                    for (int j = 0; j < k; ++j) nxt.emplace_back(crt_[j], Nin);
+                    parallel_for(Nin, [&](i64 b0, i64 b1) {
+                        std::vector<const comp_t*> x(k);
+                        std::vector<comp_t*> y(k);
+                        u64 ss[PwlPlan::kMaxBreaks], ms[PwlPlan::kMaxBreaks];
+                        PwlRows r;
+                        for (i64 e = b0; e < b1; ++e) {
+                            for (int j = 0; j < k; ++j) {
+                                x[j] = cur[j].at(e);
+                                y[j] = nxt[j].at(e);
+                            }
+                            for (int i = 0; i < m; ++i) {
+                                ss[i] = stream_id(L, PwlPlan::sign_slot(i), e);
+                                ms[i] = stream_id(L, PwlPlan::mult_slot(i), e);
+                                if (exact) {
+                                    r.mrs[i] = t[i][0].ptr<u128>() + e * t[i][0].shape[1];
+                                } else {
+                                    r.approx[i] = t[i][0].ptr<u128>() + e * t[i][0].shape[1];
+                                    r.cast2[i] = t[i][1].ptr<u128>() + e * t[i][1].shape[1];
+                                    r.sign[i] = t[i][2].ptr<u128>() + e * t[i][2].shape[1];
+                                }
+                                r.g[i] = t[i][3].ptr<u128>() + e * sum_crt;
+                                r.e[i] = t[i][4].ptr<u128>() + e * k * 3;
+                            }
+                            pwl_garble_elem(pp, exact ? nullptr : &sp_a, exact ? &sp_m : nullptr, R_, Z_, prg_, ss, ms,
+                                            x.data(), r, y.data());
+                        }
+                    }, nt);
+                    cur = std::move(nxt);
+                }
+                for (int i = 0; i < m; ++i) {
+                    const std::string pre = PwlPlan::prefix_of(i);
+                    if (exact) {
+                        g.a[pre + "mrs"] = t[i][0];
+                    } else {
+                        g.a[pre + "s.approx"] = t[i][0];
+                        g.a[pre + "s.cast2"] = t[i][1];
+                        g.a[pre + "s.sign"] = t[i][2];
+                    }
+                    g.a[pre + "mm.g"] = t[i][3];
+                    g.a[pre + "mm.e"] = t[i][4];
+                }
                 g.p["smode"] = {exact ? 1 : 0};
                 break;
             }

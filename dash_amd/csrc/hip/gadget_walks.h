@@ -94,6 +94,35 @@ __device__ __forceinline__ uint32_t leaky_digit(uint32_t ev, uint32_t yl, uint32
     return modq(fc * (ev + static_cast<uint32_t>(p) - g) + yl * x, m);
 }
 
+// PiecewiseLinear (gadgets.h PwlPlan): one digit of a0 x + sum_i d_i t_i with the ReLU digits
+// t_i = ev_i + ypr_i x - g_i, computed as yl x + sum_i d_i (ev_i + p - g_i) with the x multiplier folded once per
+// lane, yl = (a0 + sum_i d_i ypr_i) mod p, accumulated unreduced and reduced once. All of ev, g, x, d, yl lie in
+// [0, p), so with M <= 8 the sum stays below (p - 1)^2 + 8 (p - 1)(2p - 1) (22320 at p = 37): far inside the
+// range in which modq's reciprocal (one correction) is exact. tests/test_pwl.py checks the formula and modq on
+// the whole range with the same constants for every prime of the shipped bases.
+template <int M>
+struct PwlLane {
+    u128 G[M], E[M];  // the garbler / evaluator half gates' rows minus their pads, per breakpoint
+    uint32_t d[M];    // D_i mod p
+    uint32_t yl;      // the folded x multiplier
+};
+template <int M, class FG, class FE>
+__device__ __forceinline__ uint32_t pwl_digit(uint32_t x, const PwlLane<M>& l, int p, const ModC& m, FG&& g, FE&& ev) {
+    uint32_t acc = l.yl * x;
+#pragma unroll
+    for (int i = 0; i < M; ++i) acc += l.d[i] * (ev(i) + static_cast<uint32_t>(p) - g(i));
+    return modq(acc, m);
+}
+// p = 2: (a0 & x) ^ XOR_i (d_i & (e_i ^ g_i ^ (ypr_i & x))) = W ^ (yl & x) per bit with one word
+// W = XOR_i (d_i ? G_i ^ E_i : 0)
+template <int M>
+__device__ __forceinline__ u128 pwl_bit_word(const PwlLane<M>& l) {
+    u128 W = 0;
+#pragma unroll
+    for (int i = 0; i < M; ++i) W ^= (l.d[i] & 1u) ? (l.G[i] ^ l.E[i]) : static_cast<u128>(0);
+    return W;
+}
+
 // ---------------------------------------------------------------------------
 // Per-lane HBM column walk: dst[c * N] = f(c, src[c * N]) for c < n in component order, G components per round
 // trip (dst may alias src). The loads of group c+1 go out before the stores of group c: vmcnt retires in issue
@@ -222,6 +251,44 @@ __device__ __forceinline__ void lds_mult_walk(uint8_t* col, int n, u128 G, u128 
         }
     } else {
         lds_mult_chunks<BS, CLIP, LEAKY>(col, n, G, E, C, ypr, p, m, lk);
+    }
+}
+
+// The staged PiecewiseLinear multiply of a whole column, in place (pwl_digit): p = 2 as bit logic on one word,
+// other power-of-two moduli as digit streams, odd moduli chunk-major with one divmod per stream per chunk.
+template <int BS, int M>
+__device__ __forceinline__ void lds_pwl_walk(uint8_t* col, int n, PwlLane<M>& l, int p, const ModC& m) {
+    if (m.bits == 1) {
+        const uint32_t yl = l.yl & 1u;
+        lds_bit_rows<BS>(col, n, pwl_bit_word(l), [=](uint32_t bit, uint32_t x) { return bit ^ (x & yl); });
+    } else if (m.bits) {
+        DigitStream sg[M], se[M];
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            sg[i].init(l.G[i]);
+            se[i].init(l.E[i]);
+        }
+        for (int c = 0; c < n; ++c) {
+            uint8_t& v = col[c * BS];
+            v = static_cast<uint8_t>(pwl_digit(v, l, p, m, [&](int i) { return sg[i].next(m); },
+                                               [&](int i) { return se[i].next(m); }));
+        }
+    } else {
+        const int c = static_cast<int>(m.c);
+        for (int k0 = 0; k0 < n; k0 += c) {
+            uint32_t rg[M], re[M];
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+                rg[i] = divmod128(l.G[i], m);
+                re[i] = divmod128(l.E[i], m);
+            }
+            const int kc = min(c, n - k0);
+            for (int t = 0; t < kc; ++t) {
+                uint8_t& v = col[(k0 + t) * BS];
+                v = static_cast<uint8_t>(pwl_digit(v, l, p, m, [&](int i) { return chunk_digit(rg[i], m); },
+                                                   [&](int i) { return chunk_digit(re[i], m); }));
+            }
+        }
     }
 }
 

@@ -3026,6 +3026,7 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     clip_joint_hook() = &GpuGarbler::clip_joint_dev;
     argmax_hook() = &GpuGarbler::argmax_level_dev;
     mul_hook() = &GpuGarbler::mul_dev;
+    pwl_hook() = &GpuGarbler::pwl_dev;
     leaky_keep_hook() = &GpuGarbler::leaky_keep_dev;
     leaky_map_hook() = &GpuGarbler::leaky_map_dev;
     convt_hook() = &GpuGarbler::convt_dev;
@@ -3646,15 +3647,12 @@ static MrsSignDesc mrs_sign_desc(const SignMrsPlan& P, int slot0) {
 
 // ReLU with the mixed-radix sign: draw the digit-target labels (sign_mrs_garble_elem order) -> keys ->
 // fan-out projections; residue 0's key slot is the sign label; then the mixed-modulus half gates exactly as
-// in sign_layer's ReLU branch.
-void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, Array& tab,
-                          const std::vector<int>* relu_crt, const std::vector<i64>* prefix, Array& mmg, Array& mme) {
-    Impl& I = *impl_;
-    I.enter();
-    I.check_cur(cur);
-    PhaseTrace tr_("relu_mrs");
-    (void)relu_crt;
-    const int64_t N = I.cur_N;
+// in sign_layer's ReLU branch. The core runs on the input labels `in` with the PRG stream slots sslot_s (sign)
+// and sslot_m (half gates) and returns the output base labels (a ReLU: slots 1 and 2 on the device cur; a
+// PiecewiseLinear: one call per breakpoint).
+static std::vector<DevBlock> relu_mrs_core(GpuGarbler::Impl& I, uint64_t layer, int sslot_s, int sslot_m,
+                                           const SignMrsPlan& P, const gg::In& in, int64_t N, Array& tab,
+                                           const std::vector<i64>& prefix, Array& mmg, Array& mme) {
     const int k = I.k;
     DASH_CHECK(P.k() == k, "gpu garbler: mixed-radix sign plan mismatch");
     MrsSignDesc D = mrs_sign_desc(P, 0);
@@ -3673,16 +3671,9 @@ void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, 
     tb.t[0] = tT.p(); tb.row[0] = tT.row;
     tb.t[4] = tG.p(); tb.row[4] = tG.row;
     tb.t[5] = tE.p(); tb.row[5] = tE.row;
-    gg::In in{};
-    for (int j = 0; j < k; ++j) {
-        in.p[j] = I.cur[j].as<int16_t>();
-        in.n[j] = nr_comps(I.crt[j]);
-        in.es[j] = gg::kCh;  // chunked component-major
-        in.cs[j] = N * gg::kCh;
-    }
     gg::Gadget g{};
     g.layer = layer;
-    g.sslot = 1;
+    g.sslot = sslot_s;
     g.mask = 0;
     g.S = I.scratch(static_cast<size_t>(N) * nslots * gg::kW * sizeof(int16_t));
     g.PB = I.pbank(2, N);
@@ -3696,18 +3687,30 @@ void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, 
     g.nblk = draw_blocks(dr);
 
     check_desc(g);
-    std::vector<void*> tmp;
     hipLaunchKernelGGL(gg::draw_kernel(), dim3(draw_grid(g)), dim3(gg::kGB), 0, gg::tl_st, I.c, g);
     hipLaunchKernelGGL(gg::k_mrs_sign_derive, dim3(blocks_for(N, 256), k), dim3(256), 0, gg::tl_st, I.c, g, in, a);
     project(I.c, g, in, tb, pr, ProjFns{&flut, &fan});
     // mixed-modulus half gates (as sign_layer's ReLU branch, sign label = residue 0's key slot)
-    std::vector<DevBlock> out = relu_mult_gates(I, g, in, tb, sig_slot, sk0, *prefix);
+    std::vector<DevBlock> out = relu_mult_gates(I, g, in, tb, sig_slot, sk0, prefix, sslot_m);
     HIPCHECK(hipGetLastError());
-    gg::end_layer(tmp);
-    tr_.mark("kernels");
     tT.to_array(tab, I.device);
     tG.to_array(mmg, I.device);
     tE.to_array(mme, I.device);
+    return out;
+}
+
+void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, Array& tab,
+                          const std::vector<int>* relu_crt, const std::vector<i64>* prefix, Array& mmg, Array& mme) {
+    Impl& I = *impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("relu_mrs");
+    (void)relu_crt;
+    const int64_t N = I.cur_N;
+    std::vector<void*> tmp;
+    std::vector<DevBlock> out = relu_mrs_core(I, layer, 1, 2, P, labels_in(I.cur, I.crt, N), N, tab, *prefix, mmg, mme);
+    gg::end_layer(tmp);
+    tr_.mark("kernels");
     I.cur = std::move(out);
     set_stale(cur, I.crt, N);
 }
@@ -3891,6 +3894,74 @@ void GpuGarbler::clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* p
                           CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,
                           Array& cap) {
     clip_core(*self.impl_, layer, pm, pa, lo, hi, cur, st, prefix, mmg, mme, cap, nullptr);
+}
+
+// PiecewiseLinear (garbler.cpp K_PWL, pwl_garble_elem's order). acc = a0 x0; per kept breakpoint the device cur
+// moves on to x0 + T_i R (fold_cur by the step from the previous breakpoint), a ReLU of the resolved sign
+// construction runs on it with the breakpoint's stream slots and tables, and k_leaky_map adds d_i times its
+// output labels; at the end acc - c R becomes the device cur.
+static void pwl_axpy(GpuGarbler::Impl& I, std::vector<DevBlock>& acc, const std::vector<DevBlock>& x, int64_t N,
+                     const std::vector<int>& fx, const std::vector<int>& facc) {
+    const int k = I.k;
+    gg::LeakyArgs a{};
+    a.N = N;
+    a.bc = N;  // one entry per residue
+    int ncmax = 1;
+    for (int j = 0; j < k; ++j) {
+        const uint16_t t = static_cast<uint16_t>(fx[j] | (facc[j] << 8));
+        a.j[j] = gg::LeakyJob{acc[j].as<int16_t>(), x[j].as<int16_t>(), gg::dconst(&t, 1), I.crt[j],
+                              static_cast<int>(gg::chunks_of(nr_comps(I.crt[j])))};
+        ncmax = std::max(ncmax, a.j[j].nc);
+    }
+    const int blocks = static_cast<int>(std::min<int64_t>((N * ncmax + 255) / 256, 4096));
+    hipLaunchKernelGGL(gg::k_leaky_map, dim3(blocks, k), dim3(256), 0, gg::tl_st, I.c, a);
+}
+
+void GpuGarbler::pwl_dev(GpuGarbler& self, uint64_t layer, const PwlPlan& pp, const SignMrsPlan* pm, const SignPlan* pa,
+                         CrtLabels& cur, const std::vector<Array*>& t, const std::vector<i64>* prefix) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("pwl");
+    const int64_t N = I.cur_N;
+    const int k = I.k, m = pp.m();
+    DASH_CHECK((pm != nullptr) != (pa != nullptr), "gpu garbler: pwl needs exactly one sign plan");
+    DASH_CHECK(static_cast<int>(t.size()) == 5 * m && k <= kMaxRes && pp.k() == k, "gpu garbler: pwl tables");
+    for (int j = 0; j < k; ++j) DASH_CHECK(I.crt[j] <= 255, "gpu garbler: pwl factors are bytes");
+    std::vector<void*> tmp;
+    std::vector<DevBlock> acc = I.alloc_labels(I.crt, N);
+    std::vector<int> f0(k, 0), fa(k), one(k, 1), fd(k);
+    for (int j = 0; j < k; ++j) {
+        const size_t bytes = static_cast<size_t>(N) * gg::chunks_of(nr_comps(I.crt[j])) * gg::kCh * sizeof(int16_t);
+        HIPCHECK(hipMemcpyAsync(acc[j].p, I.cur[j].p, bytes, hipMemcpyDeviceToDevice, gg::tl_st));
+        fa[j] = pp.a0(I.crt[j]);
+    }
+    pwl_axpy(I, acc, acc, N, f0, fa);  // acc = a0 x0
+    i64 at = 0;
+    Array none;
+    for (int i = 0; i < m; ++i) {
+        fold_cur(I, pp.T[i] - at);  // the wire x - T_i
+        at = pp.T[i];
+        const gg::In in = labels_in(I.cur, I.crt, N);
+        Array* const* ti = &t[5 * static_cast<size_t>(i)];
+        std::vector<DevBlock> out;
+        if (pm) {
+            out = relu_mrs_core(I, layer, PwlPlan::sign_slot(i), PwlPlan::mult_slot(i), *pm, in, N, *ti[0], *prefix,
+                                *ti[3], *ti[4]);
+        } else {
+            std::vector<int> omods;
+            out = sign_core(I, layer, PwlPlan::sign_slot(i), PwlPlan::mult_slot(i), *pa, in, N, *ti[0], none, *ti[1],
+                            *ti[2], prefix, ti[3], ti[4], omods);
+        }
+        for (int j = 0; j < k; ++j) fd[j] = pp.d(i, I.crt[j]);
+        pwl_axpy(I, acc, out, N, fd, one);  // acc += d_i t_i
+    }
+    I.cur = std::move(acc);
+    fold_cur(I, -pp.C);  // the constant V - A_0 T_1: base - c R
+    HIPCHECK(hipGetLastError());
+    gg::end_layer(tmp);
+    tr_.mark("kernels");
+    set_stale(cur, I.crt, N);
 }
 
 // Joint Clip, first half (gpu_garbler.h clip_hi_sign): the exact sign of x - t_hi on the device cur, which the

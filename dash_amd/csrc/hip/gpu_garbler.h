@@ -171,6 +171,22 @@ class GpuGarbler {
         DASH_CHECK(mul_hook() != nullptr, "gpu garbler: mul is not linked in");
         mul_hook()(*this, layer, mp, src_idx, cur, g, e);
     }
+    // PiecewiseLinear (gadgets.h PwlPlan): per kept breakpoint i the device cur shifted to x0 + T_i R, the sign's
+    // draw / derive / fan-out passes on stream slot 1 + 2i (pm: exact, pa: approximate fused) and the ReLU half
+    // gates on slot 2 + 2i, each breakpoint's output zero labels added into the combination
+    // a0 x0 + sum_i d_i t_i - c R, which becomes the device cur. t: five arrays per breakpoint (mrs | approx,
+    // cast2, sign; mm.g; mm.e). Hook as for clip.
+    using PwlFn = void (*)(GpuGarbler&, uint64_t, const PwlPlan&, const SignMrsPlan*, const SignPlan*, CrtLabels&,
+                           const std::vector<Array*>&, const std::vector<i64>*);
+    static PwlFn& pwl_hook() {
+        static PwlFn f = nullptr;
+        return f;
+    }
+    void pwl(uint64_t layer, const PwlPlan& pp, const SignMrsPlan* pm, const SignPlan* pa, CrtLabels& cur,
+             const std::vector<Array*>& t, const std::vector<i64>* prefix) {
+        DASH_CHECK(pwl_hook() != nullptr, "gpu garbler: pwl is not linked in");
+        pwl_hook()(*this, layer, pp, pm, pa, cur, t, prefix);
+    }
     // LeakyRelu (gadgets.h LeakyPlan), two calls around the ReLU garbling of the same layer (sign_layer, relu_mrs
     // or relu_mult): leaky_keep copies the device cur (the input zero labels x0) aside, leaky_map turns the ReLU's
     // output zero labels into (n_c mod p) x0 + ((2^s - n_c) mod p) relu0 in place. Hooks as for clip.
@@ -217,6 +233,8 @@ class GpuGarbler {
     static void argmax_level_dev(GpuGarbler& self, uint64_t layer, int lv, const ArgMaxPlan& ap, i64 P,
                                  const std::vector<i64>& prefix, CrtLabels& cur, Array& mrs, Array& mmg, Array& mme,
                                  Array& idx, Array& img, Array& ime);
+    static void pwl_dev(GpuGarbler& self, uint64_t layer, const PwlPlan& pp, const SignMrsPlan* pm, const SignPlan* pa,
+                        CrtLabels& cur, const std::vector<Array*>& t, const std::vector<i64>* prefix);
     static void leaky_keep_dev(GpuGarbler& self, CrtLabels& cur);
     static void leaky_map_dev(GpuGarbler& self, const LeakyPlan& lp, CrtLabels& cur);
     static void mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& g,

@@ -90,6 +90,24 @@ struct LeakyTab {
     uint32_t bc;
 };
 
+// PiecewiseLinear multiply (gadgets.h PwlPlan): the m kept breakpoints' half gates in one pass over the label of
+// x. kx / colx: the compressed labels and colours of x (k_label_key; every breakpoint's (TW_MMG, j) pad is
+// derived from kx under its own gate). key[i]: breakpoint i's sign label [B][N]; gtab / etab: its b<i>.mm.g /
+// b<i>.mm.e; mgate0[i] = gate_base(L, 2 + 2i). fac[residue][m + 1] = A_0 mod p, then D_i mod p.
+constexpr int kPwlMax = 8;
+struct PwlArgs {
+    CrtInfo crt;
+    int64_t N;
+    int m;
+    const u128* kx;
+    const uint16_t* colx;
+    const u128* key[kPwlMax];
+    const u128* gtab[kPwlMax];
+    const u128* etab[kPwlMax];
+    uint64_t mgate0[kPwlMax];
+    const uint8_t* fac;
+};
+
 struct RescaleArgs {
     CrtInfo crt;
     int64_t N;

@@ -577,6 +577,113 @@ __global__ __launch_bounds__(kRmBS) void k_clip_mult_s(ClipArgs a, Act x, Act y,
 }
 
 // ---------------------------------------------------------------------------
+// PiecewiseLinear multiply (gadgets.h PwlPlan; kargs.h PwlArgs): out_j = a0 x_j + sum_i d_i relu_i,j with
+// relu_i,j = E_i + ypr_i x_j - G_i, all M kept breakpoints' half gates in one pass over the label: it is read
+// once and written once. Every breakpoint has its own gate, so the lane derives the (TW_MMG, j) pad of x_j and
+// the y-row pads of the sign label (keyed_ops) per breakpoint from the compressed labels.
+//
+// kx[b][j][e] = compress(x_j), colx = colour (the pads are gate-dependent: no hash here). grid (x, k, B)
+__global__ __launch_bounds__(256) void k_label_key(Act x, CrtInfo crt, int64_t N, u128* kx, uint16_t* colx,
+                                                   const ModC* mc) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const ModC m = mc[crt.p[j]];
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < N;
+         e += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const act_t* L = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+        const int64_t bke = (static_cast<int64_t>(b) * crt.k + j) * N + e;
+        colx[bke] = static_cast<uint16_t>(static_cast<uint16_t>(L[0]) % m.q);
+        kx[bke] = compress_cm(L, N, m);
+    }
+}
+
+template <int M>
+__device__ __forceinline__ PwlLane<M> pwl_lane(const PwlArgs& a, int j, int b, int64_t e, int p, const ModC& m) {
+    const int k = a.crt.k;
+    const int64_t N = a.N;
+    const int64_t bke = (static_cast<int64_t>(b) * k + j) * N + e;
+    const int64_t be = static_cast<int64_t>(b) * N + e;
+    // the gathers go out before the pads are computed
+    const u128 Kx = a.kx[bke];
+    const uint32_t colx = a.colx[bke];
+    u128 Ky[M], Graw[M];
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        Ky[i] = a.key[i][be];
+        Graw[i] = a.gtab[i][be * a.crt.sum + a.crt.prefix[j] + colx];
+    }
+    const uint8_t* f = a.fac + j * (M + 1);
+    PwlLane<M> l;
+    uint32_t ys = f[0];  // a0 + sum_i d_i ypr_i <= (p - 1) + M (p - 1)^2
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        const uint64_t gate = a.mgate0[i] ^ static_cast<uint64_t>(e);
+        const KeyedOps o = keyed_ops(Ky[i], gate, a.etab[i] + (be * k + j) * 3, j, k, p, m);
+        l.G[i] = Graw[i] - hard_pad(Kx, gate, tw_sub(kTwMmg, j), 0);
+        l.E[i] = o.E;
+        l.d[i] = f[1 + i];
+        ys += l.d[i] * o.ypr;
+    }
+    l.yl = modq(ys, m);
+    return l;
+}
+
+// per-lane HBM column walk. grid (ceil(N/256), k, B)
+template <int M>
+__global__ __launch_bounds__(256) void k_pwl_mult(PwlArgs a, Act x, Act y, const ModC* mc) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const PwlLane<M> l = pwl_lane<M>(a, j, b, e, p, m);
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * m.n * N + e;
+    if (m.bits == 1) {
+        DigitStream sw;
+        sw.init(pwl_bit_word(l));
+        const uint32_t yl = l.yl & 1u;
+        col_walk<kChunk>(X, Y, N, static_cast<int>(m.n), [&](int, uint32_t xv) { return sw.next(m) ^ (xv & yl); });
+    } else {
+        DigitStream sg[M], se[M];
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            sg[i].init(l.G[i]);
+            se[i].init(l.E[i]);
+        }
+        col_walk<kChunk>(X, Y, N, static_cast<int>(m.n), [&](int, uint32_t xv) {
+            return pwl_digit(xv, l, p, m, [&](int i) { return sg[i].next(m); }, [&](int i) { return se[i].next(m); });
+        });
+    }
+}
+
+// k_pwl_mult with the label staged in LDS (stage_ok; as k_relu_mult_s): a block = (256-element tile, residue j,
+// GC b). The units past the end of a partial last tile are staged as zeros, so its spare lanes (which redo the
+// last element's operands) walk zero digits; their columns are not stored.
+template <int M>
+__global__ __launch_bounds__(kRmBS) void k_pwl_mult_s(PwlArgs a, Act x, Act y, const ModC* mc) {
+    __shared__ __attribute__((aligned(16))) uint8_t stg[128 * kRmBS];
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int64_t N = a.N;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int p = a.crt.p[j];
+    const ModC m = mc[p];
+    const int n = static_cast<int>(m.n);
+    const act_t* X = x.p[j] + static_cast<int64_t>(b) * n * N;
+    act_t* Y = y.p[j] + static_cast<int64_t>(b) * n * N;
+    for (int64_t e0 = static_cast<int64_t>(blockIdx.x) * kRmBS; e0 < N; e0 += static_cast<int64_t>(gridDim.x) * kRmBS) {
+        const int64_t e = min(e0 + tid, N - 1);
+        PwlLane<M> l = pwl_lane<M>(a, j, b, e, p, m);
+        __syncthreads();  // the previous tile's stores have read the image
+        lds_stage_rows<kRmBS, 4, true>(stg, X, N, e0, 0, n);
+        __syncthreads();
+        lds_pwl_walk<kRmBS, M>(stg + tid, n, l, p, m);
+        __syncthreads();
+        lds_store_rows<kRmBS>(Y, stg, N, e0, 0, n);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // ArgMax (gadgets.h ArgMaxPlan; kargs.h ArgMaxArgs for the element layout).
 // Pair differences of one level: d[e] = v[slot 2q] - v[slot 2q + 1], e = q P + o; the operation pubq has no b
 // labels (a public index folded into the garbler's bases), its difference is a's label. grid (x, k, B)
@@ -2136,6 +2243,32 @@ void launch_clip_mult(const ClipArgs& a, const Act& x, const Act& y, int B, cons
         hipLaunchKernelGGL(k_clip_mult_s, grid, dim3(kRmBS), 0, st, a, x, y, mc);
     else
         hipLaunchKernelGGL(k_clip_mult, grid, dim3(256), 0, st, a, x, y, mc);
+}
+// PiecewiseLinear: the compressed labels of x once, then (after the m sign launches, each into its own key
+// buffer) the multiply, instantiated per kept-breakpoint count. The picker is launch_relu_mult's (mult_grid).
+void launch_pwl_key(const PwlArgs& a, u128* kx, uint16_t* colx, const Act& x, int B, const ModC* mc, hipStream_t st) {
+    hipLaunchKernelGGL(k_label_key, grid_for(a.N, 256, a.crt.k, B), dim3(256), 0, st, x, a.crt, a.N, kx, colx, mc);
+}
+template <int M>
+static void launch_pwl_mult_m(const PwlArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st) {
+    dim3 grid;
+    if (mult_grid("pwl_mult", a.N, a.crt.k, B, x, y, grid))
+        hipLaunchKernelGGL(k_pwl_mult_s<M>, grid, dim3(kRmBS), 0, st, a, x, y, mc);
+    else
+        hipLaunchKernelGGL(k_pwl_mult<M>, grid, dim3(256), 0, st, a, x, y, mc);
+}
+void launch_pwl_mult(const PwlArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st) {
+    switch (a.m) {
+        case 1: launch_pwl_mult_m<1>(a, x, y, B, mc, st); break;
+        case 2: launch_pwl_mult_m<2>(a, x, y, B, mc, st); break;
+        case 3: launch_pwl_mult_m<3>(a, x, y, B, mc, st); break;
+        case 4: launch_pwl_mult_m<4>(a, x, y, B, mc, st); break;
+        case 5: launch_pwl_mult_m<5>(a, x, y, B, mc, st); break;
+        case 6: launch_pwl_mult_m<6>(a, x, y, B, mc, st); break;
+        case 7: launch_pwl_mult_m<7>(a, x, y, B, mc, st); break;
+        case 8: launch_pwl_mult_m<8>(a, x, y, B, mc, st); break;
+        default: std::fprintf(stderr, "dash: a PiecewiseLinear layer has 1..8 breakpoints\n"); std::abort();
+    }
 }
 // ArgMax (gadgets.h ArgMaxPlan), per level: the pair differences, the half gates' keys of a difference under one
 // gate set's gate, the sign chain (launch_clip_sign_mrs) and the multiply, whose form is the level's shape.

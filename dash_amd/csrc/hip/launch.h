@@ -66,6 +66,11 @@ void launch_argmax_hash(const Act& d, const CrtInfo& crt, int64_t N, u128* hx, u
                         const ModC* mc, const AesGlobals& g, hipStream_t st);
 void launch_argmax_mult(const ArgMaxArgs& a, bool val, bool l0, const Act& v, const Act& d, const Act& i, const Act& ed,
                         const Act& nv, const Act& ni, int B, const ModC* mc, hipStream_t st);
+// PiecewiseLinear (gadgets.h PwlPlan): the compressed labels / colours of x (k_label_key), and all kept
+// breakpoints' half gates plus the linear combination in one pass (k_pwl_mult / k_pwl_mult_s, mult_grid's picker;
+// log names pwl_mult.lane / pwl_mult.staged). The sign launches between the two are the Clip's.
+void launch_pwl_key(const PwlArgs& a, u128* kx, uint16_t* colx, const Act& x, int B, const ModC* mc, hipStream_t st);
+void launch_pwl_mult(const PwlArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st);
 // LeakyRelu: the ReLU multiply with the leaky epilogue (k_leaky_mult / k_leaky_mult_s, mult_grid's picker), and
 // the deferred outputs of a joint rescale with a LeakyRelu behind it (k_rescale_leaky_out_t where
 // launch_rescale_relu_out takes its throughput form; elsewhere the output-hash kernel and the leaky multiply)

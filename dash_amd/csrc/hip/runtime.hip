@@ -710,6 +710,15 @@ class HipEvaluator {
         for (int side = 0; side < sides; ++side)
             if (!ks_[side]) ks_[side] = dalloc<u128>(static_cast<size_t>(B_) * w.caps.maxSignN);
     }
+    // a PiecewiseLinear's sign labels, one buffer per kept breakpoint: sized by the model's largest count
+    void ensure_kpwl(const Walk& w) {
+        int mmax = 0;
+        for (const GLayer& l : tmpl_->layers)
+            if (l.kind == K_PWL)
+                mmax = std::max(mmax, PwlPlan(crt_, l.param("s"), l.vec("T"), l.vec("A"), l.param("V")).m());
+        for (int i = 0; i < mmax; ++i)
+            if (!kpwl_[i]) kpwl_[i] = dalloc<u128>(static_cast<size_t>(B_) * w.caps.maxSignN);
+    }
     // The exact mixed-radix sign's chain (mode 1, gadgets.h SignMrsPlan) over N elements with layer li's table
     // `table`: a ReLU's (ny = ny_: the sign label's y-row pads), or with the label itself kept in `ks` and ny = 0
     // for a Clip's two signs, a joint Clip's upper sign and an ArgMax level.
@@ -806,6 +815,7 @@ class HipEvaluator {
     void plan_mult(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_mul(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_leaky(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_pwl(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname);
 
     std::shared_ptr<GarbledModel> tmpl_;  // build() only
@@ -880,6 +890,7 @@ class HipEvaluator {
     const int16_t* zero_rows_ = nullptr;
     const int16_t* up_rows_ = nullptr;
     u128* mrs_ps_ = nullptr;  // mixed-radix rescale chain scratch (allocated by the first such layer)
+    u128* kpwl_[kPwlMax] = {};  // [B][maxSignN] a PiecewiseLinear's sign labels (allocated by the first such layer)
     u128* ks_[2] = {nullptr, nullptr};  // [B][maxSignN] a Clip's two sign labels (allocated by the first Clip)
     // ArgMax scratch (allocated by the first ArgMax): candidate values / index labels of the odd levels, the value
     // and index differences; the index gates' garbler-half pads and colours
@@ -954,6 +965,7 @@ void HipEvaluator::build() {
             case K_MULT: case K_MMULT: plan_mult(w, li, g, lname); break;
             case K_MUL: plan_mul(w, li, g, lname); break;
             case K_LEAKY: plan_leaky(w, li, g, lname); break;
+            case K_PWL: plan_pwl(w, li, g, lname); break;
             case K_BASEEXT: plan_base_ext(w, li, g, lname); break;
             default:
                 throw std::runtime_error(std::string("dash: HIP evaluator cannot run layer kind ") + kind_name(g.kind));
@@ -1034,7 +1046,7 @@ HipEvaluator::Caps HipEvaluator::shape_pass() const {
         if (l.p.count("in_src")) N = c.outN.at(l.param("in_src") + 1);
         const i64 No = out_elems(l, N, c.outN);
         switch (l.kind) {
-            case K_RELU: case K_SIGN: case K_RESCALE: case K_CLIP: case K_LEAKY:
+            case K_RELU: case K_SIGN: case K_RESCALE: case K_CLIP: case K_LEAKY: case K_PWL:
                 c.maxSignN = std::max(c.maxSignN, N);
                 break;
             case K_MAXPOOL: {
@@ -1427,6 +1439,58 @@ void HipEvaluator::plan_leaky(Walk& w, size_t li, const GLayer& g, const std::st
         add_op(lname + ".B", [a, maxn, e](hipStream_t st) { launch_sign_chain(a, maxn, e.mc, e.ag, st); });
         add_op(lname + ".C", [a, lk, x, y, gt, et, e](hipStream_t st) { launch_leaky_mult(a, lk, x, y, gt, et, e.mc, st); });
     }
+    set_out(w, g, w.N, w.nxt());
+}
+
+// gadgets.h PwlPlan: the compressed labels of x, one sign evaluation per kept breakpoint on the same labels (each
+// with its own tables and gate, into its own key buffer), then one multiply pass that applies every breakpoint's
+// half gates and the linear combination
+void HipEvaluator::plan_pwl(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    const GarbledModel& m0 = *tmpl_;
+    DASH_CHECK(hard_, "the PiecewiseLinear layer exists in the hardened encoding only");
+    DASH_CHECK(w.mods == crt_, "pwl: the input is not on the CRT base");
+    const PwlPlan pp(crt_, g.param("s"), g.vec("T"), g.vec("A"), g.param("V"));
+    for (int p : crt_) DASH_CHECK(p <= 255, "pwl: the factor table holds bytes");
+    ensure_kpwl(w);
+    const std::vector<uint8_t> fac = pp.table();
+    PwlArgs pa{};
+    pa.crt = w.crt;
+    pa.N = w.N;
+    pa.m = pp.m();
+    pa.kx = hx_;
+    pa.colx = colx_;
+    pa.fac = upload(fac.data(), fac.size());
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    const Env e = w.env;
+    const bool exact = g.param("smode", 0) == 1;
+    {
+        u128* kx = hx_;
+        uint16_t* colx = colx_;
+        add_op(lname + ".K", [pa, kx, colx, x, e](hipStream_t st) { launch_pwl_key(pa, kx, colx, x, e.B, e.mc, st); });
+    }
+    for (int i = 0; i < pp.m(); ++i) {
+        const std::string pre = PwlPlan::prefix_of(i);
+        const uint64_t sgate = gate_base(li + 1, PwlPlan::sign_slot(i));
+        pa.mgate0[i] = gate_base(li + 1, PwlPlan::mult_slot(i));
+        pa.key[i] = kpwl_[i];
+        pa.gtab[i] = upload_tables(li, pre + "mm.g");
+        pa.etab[i] = upload_tables(li, pre + "mm.e");
+        if (exact) {  // the label itself kept, no y-row pads: the multiply derives them (as a Clip's)
+            const MrsArgs a = mrs_sign_args(w, li, pre + "mrs", w.N, sgate, pa.mgate0[i], 0, kpwl_[i]);
+            add_op(lname + "." + pre + "mrs", [a, x, e](hipStream_t st) {
+                launch_clip_sign_mrs(a, x, e.B, e.mc, e.ag, st);
+            });
+        } else {
+            SignPlan sp(crt_, m0.h.mrs, {2}, 0, 1, m0.h.sign_fused != 0);
+            const Sign s = make_sign(li, pre, sp, w.N, 0, sgate, 0);
+            SignArgs a = s.a;
+            a.outP = kpwl_[i];  // nout = 1: [B][N]
+            const int maxn = s.maxn;
+            add_op(lname + "." + pre + "A", [a, x, e](hipStream_t st) { launch_sign_approx(a, x, e.mc, e.ag, st); });
+            add_op(lname + "." + pre + "B", [a, maxn, e](hipStream_t st) { launch_sign_chain(a, maxn, e.mc, e.ag, st); });
+        }
+    }
+    add_op(lname + ".C", [pa, x, y, e](hipStream_t st) { launch_pwl_mult(pa, x, y, e.B, e.mc, st); });
     set_out(w, g, w.N, w.nxt());
 }
 

@@ -29,6 +29,7 @@ _CLIP = _Kind.CLIP
 _ARGMAX = _Kind.ARGMAX
 _MUL = _Kind.MUL
 _CONVT = _Kind.CONVT
+_PWL = _Kind.PWL
 
 Labels = list  # list[(modulus, np.ndarray int16 [N, n_p])]
 
@@ -216,6 +217,13 @@ class GarbledCircuit:
             raise ValueError("layer %d (mul): the Mul layer exists in the hardened encoding only (%s)" % (
                 muls[0], "hardened=False was asked for" if supported else
                 "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
+        # a PiecewiseLinear folds its breakpoints into base labels and runs several signs and multiplies on the
+        # labels of one wire (gadgets.h PwlPlan): hardened encoding only, for the Clip's reasons (docs/CLIP.md)
+        pwls = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _PWL]
+        if pwls and not (supported if hardened is None else hardened):
+            raise ValueError("layer %d (pwl): the PiecewiseLinear layer exists in the hardened encoding only (%s)" % (
+                pwls[0], "hardened=False was asked for" if supported else
+                "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
         if argmaxes and not mrs_capable(self.crt_base):
             raise ValueError("layer %d (argmax): the ArgMax layer's exact sign needs a CRT base with residue 0 = 2 "
                              "and odd other residues, got %s" % (argmaxes[0], self.crt_base))
@@ -269,9 +277,10 @@ class GarbledCircuit:
             range_guard = os.environ["DASH_RANGE_GUARD"]  # A/B knob (bench records say which was used)
         if range_guard not in ("auto", "on", "off"):
             raise ValueError("range_guard must be 'auto', 'on' or 'off'")
-        # a Clip narrows the domain too: x - q_lo and x - q_hi must both be signed CRT values (docs/CLIP.md)
+        # a Clip narrows the domain too: x - q_lo and x - q_hi must both be signed CRT values (docs/CLIP.md); so
+        # does a PiecewiseLinear with every x - T_i (docs/PWL.md)
         self.guard_enabled = range_guard == "on" or (range_guard == "auto" and (
-            (self.rescale == "mrs" and bool(circuit._dash_rescales())) or bool(clips)))
+            (self.rescale == "mrs" and bool(circuit._dash_rescales())) or bool(clips) or bool(pwls)))
         self.sink = sink
         self._n = native()
         self.garbler = self._n.Garbler(self.crt_base, self.mrs_base, self.seed, int(max_modulus))

@@ -25,7 +25,8 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
   evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
   bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
-  has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no LeakyRelu and no padded / ceil-mode pooling:
+  has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no LeakyRelu, no PiecewiseLinear and no padded / ceil-mode
+  pooling:
   circuits with any of them take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
@@ -69,12 +70,13 @@ class RangeGuard:
         self.device = device
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Mul, L.Projection,
-                                          L.BaseExtension, L.ConvTranspose2d, L.Upsample, L.LeakyRelu))
+                                          L.BaseExtension, L.ConvTranspose2d, L.Upsample, L.LeakyRelu,
+                                          L.PiecewiseLinear))
                            for l in circuit.layers)
         # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no
-        # LeakyRelu, no dilated conv and no padded / ceil-mode pooling: such circuits take the batched torch path
+        # LeakyRelu, no PiecewiseLinear, no dilated conv and no padded / ceil-mode pooling: such circuits take the batched torch path
         self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.Mul, L.ConvTranspose2d, L.Upsample,
-                                                   L.LeakyRelu)) or
+                                                   L.LeakyRelu, L.PiecewiseLinear)) or
                                     (isinstance(l, L.Conv2d) and (l.dh > 1 or l.dw > 1)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
@@ -101,6 +103,8 @@ class RangeGuard:
                 return lo, hi
             # both sign inputs x - q_lo and x - q_hi are signed CRT values
             return lo + layer.q_hi, hi + layer.q_lo
+        if isinstance(layer, L.PiecewiseLinear):  # every sign input x - T_i is a signed CRT value
+            return lo + int(layer.T[-1]), hi + int(layer.T[0])
         return None
 
     def span_max(self) -> int:
@@ -230,6 +234,10 @@ class RangeGuard:
             elif isinstance(l, L.LeakyRelu):
                 n = torch.as_tensor(np.repeat(l.n, l.bc) if l.n.size > 1 else l.n, device=X.device)
                 out = torch.where(inp >= 0, inp * (1 << l.slope_bits), inp * n[None, :])
+            elif isinstance(l, L.PiecewiseLinear):
+                out = int(l.V) + int(l.A[0]) * (inp - int(l.T[0]))
+                for T, D in zip(l.T, l.D):
+                    out = out + int(D) * torch.clamp_min(inp - int(T), 0)
             elif isinstance(l, L.Sign):
                 out = torch.where(inp >= 0, 1, -1).to(torch.int64)
             elif isinstance(l, L.Clip):

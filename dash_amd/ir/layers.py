@@ -41,6 +41,7 @@ class Kind:
     UPSAMPLE = 18
     MUL = 19
     LEAKY = 20
+    PWL = 21
 
 
 def _size(d: Sequence[int]) -> int:
@@ -617,6 +618,170 @@ class LeakyRelu(Layer):
 
     def __repr__(self) -> str:
         return f"LeakyRelu(dims={self.in_dims}, n={self.n.tolist()}, slope_bits={self.slope_bits})"
+
+
+class PiecewiseLinear(Layer):
+    """Continuous piecewise-linear activation with m <= 8 breakpoints (docs/PWL.md): float breakpoints
+    t_1 < ... < t_m, m + 1 segment slopes a_0 .. a_m (|a_j| <= 2), the value v at t_1 and slope_bits = s in [1, 8].
+    Quantized under ScaleQuant (act_scale = 2^l) exactly and in integers:
+      T_i = llround(t_i 2^l), A_j = round(a_j 2^s), D_i = A_i - A_(i-1), V = llround(v 2^(l+s)),
+      y_q(x) = V + A_0 (x - T_1) + sum_i D_i relu(x - T_i).
+    l = q_parameter (default 5, the zoo's). The output carries a scale 2^s larger than the input (pending scale bits, as a LeakyRelu's). Garbled as one sign
+    and one set of mixed-modulus half gates per breakpoint with D_i != 0, all on the labels of x, and a free linear
+    combination of the labels (csrc/gadgets.h PwlPlan). The named constructors tag the layer for the ONNX exporter."""
+
+    kind = Kind.PWL
+    name = "pwl"
+    MAX_BREAKS = 8
+    MAX_SLOPE_BITS = 8
+    MAX_SLOPE = 2.0
+    FN_CODES = {None: 0, "sigmoid": 1, "tanh": 2, "hard_sigmoid": 3}
+
+    def __init__(self, dims, knots, slopes, value, slope_bits: int = 8, q_parameter: int = 5,
+                 q_method: QuantizationMethod = QuantizationMethod.ScaleQuant):
+        super().__init__(dims, dims)
+        s = self._check_bits(slope_bits)
+        self.q_method, self.q_parameter = QuantizationMethod(q_method), int(q_parameter)
+        if self.q_method != QuantizationMethod.ScaleQuant:
+            raise ValueError(f"pwl: a piecewise-linear activation exists under ScaleQuant only (its output carries a "
+                             f"power-of-two scale 2^{s} that the next Rescale absorbs), not {self.q_method.name}")
+        if self.q_parameter < 0:
+            raise ValueError(f"pwl: q_parameter must be >= 0, got {q_parameter}")
+        t = np.asarray(knots, dtype=np.float64).reshape(-1)
+        a = np.asarray(slopes, dtype=np.float64).reshape(-1)
+        if not 1 <= t.size <= self.MAX_BREAKS:
+            raise ValueError(f"pwl: between 1 and {self.MAX_BREAKS} breakpoints, got {t.size}")
+        if a.size != t.size + 1:
+            raise ValueError(f"pwl: {t.size} breakpoints need {t.size + 1} slopes, got {a.size}")
+        if not (np.all(np.isfinite(t)) and np.all(np.isfinite(a)) and np.isfinite(value)):
+            raise ValueError("pwl: breakpoints, slopes and value must be finite")
+        if np.any(np.abs(a) > self.MAX_SLOPE):
+            raise ValueError(f"pwl: every slope must satisfy |a| <= {self.MAX_SLOPE:g}, got {a.tolist()}")
+        self.t, self.a, self.v = t, a, float(value)
+        self.fn, self.fn_params = None, {}
+        scale = 1 << self.q_parameter
+        T = quantize_scale(t, scale)
+        A = np.floor(a * (1 << s) + 0.5).astype(np.int64)
+        V = int(quantize_scale(np.asarray([self.v]), scale * (1 << s))[0])
+        self._set_q(T, A, V, s)
+
+    @staticmethod
+    def _check_bits(slope_bits) -> int:
+        s = int(slope_bits)
+        if s != slope_bits or not 1 <= s <= PiecewiseLinear.MAX_SLOPE_BITS:
+            raise ValueError(f"pwl: slope_bits must be an integer in [1, {PiecewiseLinear.MAX_SLOPE_BITS}], "
+                             f"got {slope_bits}")
+        return s
+
+    def _set_q(self, T, A, V, s: int):
+        T = np.asarray(T, dtype=np.int64).reshape(-1)
+        A = np.asarray(A, dtype=np.int64).reshape(-1)
+        if not 1 <= T.size <= self.MAX_BREAKS:
+            raise ValueError(f"pwl: between 1 and {self.MAX_BREAKS} breakpoints, got {T.size}")
+        if A.size != T.size + 1:
+            raise ValueError(f"pwl: {T.size} breakpoints need {T.size + 1} slopes, got {A.size}")
+        if np.any(np.diff(T) <= 0):
+            raise ValueError(f"pwl: the quantized breakpoints must increase strictly, got {T.tolist()} (a larger "
+                             f"q_parameter separates them)")
+        if np.any(np.abs(A) > int(self.MAX_SLOPE * (1 << s))):
+            raise ValueError(f"pwl: every slope numerator must satisfy |A| <= {int(self.MAX_SLOPE * (1 << s))}, "
+                             f"got {A.tolist()}")
+        D = np.diff(A)
+        if not np.any(D != 0):
+            raise ValueError(f"pwl: no breakpoint is left at slope_bits={s}: every slope change rounds to 0")
+        self.slope_bits, self.T, self.A, self.D, self.V = s, T, A, D, int(V)
+
+    @property
+    def kept(self) -> list:
+        """Indices of the breakpoints of the garbled form (D_i != 0)."""
+        return [int(i) for i in np.flatnonzero(self.D)]
+
+    @classmethod
+    def from_quantized(cls, dims, T, A, V, slope_bits: int) -> "PiecewiseLinear":
+        s = cls._check_bits(slope_bits)
+        T = np.asarray(T, dtype=np.int64).reshape(-1)
+        A = np.asarray(A, dtype=np.int64).reshape(-1)
+        if not 1 <= T.size <= cls.MAX_BREAKS or A.size != T.size + 1:
+            raise ValueError(f"pwl: between 1 and {cls.MAX_BREAKS} breakpoints and one more slope, got {T.size} and "
+                             f"{A.size}")
+        if np.any(np.abs(A) > int(cls.MAX_SLOPE * (1 << s))):
+            raise ValueError(f"pwl: every slope numerator must satisfy |A| <= {int(cls.MAX_SLOPE * (1 << s))}, "
+                             f"got {A.tolist()}")
+        l = cls(dims, T.astype(np.float64), A.astype(np.float64) / (1 << s), float(V) / (1 << s), s, 0)
+        l._set_q(T, A, V, s)
+        return l
+
+    @classmethod
+    def interpolate(cls, dims, xs, ys, slope_bits: int = 8, q_parameter: int = 5,
+                    q_method: QuantizationMethod = QuantizationMethod.ScaleQuant) -> "PiecewiseLinear":
+        """The interpolant through (xs_i, ys_i), constant outside [xs_1, xs_m]."""
+        xs = np.asarray(xs, dtype=np.float64).reshape(-1)
+        ys = np.asarray(ys, dtype=np.float64).reshape(-1)
+        if xs.size != ys.size or xs.size < 1:
+            raise ValueError(f"pwl: interpolate needs as many values as knots, got {xs.size} and {ys.size}")
+        if np.any(np.diff(xs) <= 0):
+            raise ValueError(f"pwl: the knots must increase strictly, got {xs.tolist()}")
+        inner = np.diff(ys) / np.diff(xs) if xs.size > 1 else np.zeros(0)
+        return cls(dims, xs, np.concatenate([[0.0], inner, [0.0]]), ys[0], slope_bits, q_parameter, q_method)
+
+    SIGMOID_KNOTS = (-5.0, -3.0, -2.0, -1.0, 1.0, 2.0, 3.0, 5.0)
+
+    @classmethod
+    def sigmoid(cls, dims, slope_bits: int = 8, q_parameter: int = 5,
+                q_method: QuantizationMethod = QuantizationMethod.ScaleQuant) -> "PiecewiseLinear":
+        xs = np.asarray(cls.SIGMOID_KNOTS)
+        l = cls.interpolate(dims, xs, 1.0 / (1.0 + np.exp(-xs)), slope_bits, q_parameter, q_method)
+        l.fn = "sigmoid"
+        return l
+
+    @classmethod
+    def tanh(cls, dims, slope_bits: int = 8, q_parameter: int = 5,
+             q_method: QuantizationMethod = QuantizationMethod.ScaleQuant) -> "PiecewiseLinear":
+        xs = np.asarray(cls.SIGMOID_KNOTS) / 2.0
+        l = cls.interpolate(dims, xs, np.tanh(xs), slope_bits, q_parameter, q_method)
+        l.fn = "tanh"
+        return l
+
+    @classmethod
+    def hard_sigmoid(cls, dims, alpha: float = 0.2, beta: float = 0.5, slope_bits: int = 8, q_parameter: int = 5,
+                     q_method: QuantizationMethod = QuantizationMethod.ScaleQuant) -> "PiecewiseLinear":
+        alpha, beta = float(alpha), float(beta)
+        if not (np.isfinite(alpha) and np.isfinite(beta) and alpha > 0):
+            raise ValueError(f"pwl: hard_sigmoid needs a finite alpha > 0 and a finite beta, got ({alpha}, {beta})")
+        l = cls(dims, [-beta / alpha, (1.0 - beta) / alpha], [0.0, alpha, 0.0], 0.0, slope_bits, q_parameter, q_method)
+        l.fn, l.fn_params = "hard_sigmoid", {"alpha": alpha, "beta": beta}
+        return l
+
+    def plain_eval(self, x, track=True, ctx=None):
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        y = self.v + self.a[0] * (x - self.t[0])
+        for i, d in enumerate(np.diff(self.a)):
+            y = y + d * np.maximum(x - self.t[i], 0.0)
+        y = y.astype(np.float32)
+        if track:
+            self._track_f(y)
+        return y
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        x = np.asarray(x, dtype=np.int64).reshape(-1)
+        y = self.V + int(self.A[0]) * (x - int(self.T[0]))
+        for T, D in zip(self.T, self.D):
+            y = y + int(D) * np.maximum(x - int(T), 0)
+        if track:
+            # every sign input x - T_i must lie in [-M/2, M/2)
+            self._track_q(x, y, x - int(self.T[0]), x - int(self.T[-1]))
+        return y
+
+    def quantize(self, q_const):
+        self.reset_ranges()
+
+    def garble_spec(self):
+        return self.kind, {"s": self.slope_bits, "T": [int(v) for v in self.T], "A": [int(v) for v in self.A],
+                           "V": int(self.V), "fn": self.FN_CODES[self.fn]}
+
+    def __repr__(self) -> str:
+        return (f"PiecewiseLinear(dims={self.in_dims}, T={self.T.tolist()}, A={self.A.tolist()}, V={self.V}, "
+                f"slope_bits={self.slope_bits}" + (f", fn={self.fn}" if self.fn else "") + ")")
 
 
 class Clip(Layer):

@@ -84,6 +84,23 @@ consumes it: its bias is quantized at 2^(2l + e) (`in_scale_bits=e`) and the
 rescales by l + e. `Add` and `Concat` need equal bits on all operands; a `Clip`
 or a graph output with pending bits is refused.
 
+`Sigmoid`, `HardSigmoid` (attributes `alpha` / `beta`, ONNX defaults 0.2 / 0.5)
+and, with the keyword `tanh="pwl"`, `Tanh` become a `PiecewiseLinear` layer
+(docs/PWL.md) with `pwl_bits` slope bits; the default `tanh="sign"` keeps the
+reference's BNN convention (Tanh -> Sign). ScaleQuant only. The layer's input
+must carry no pending scale bits and no pending factor (refused with the node's
+name); its output carries e = `pwl_bits`, consumed like a LeakyRelu's:
+
+    operator                         pending scale bits e
+    LeakyRelu / PRelu                e + leaky_bits
+    Sigmoid / HardSigmoid / Tanh     0 required -> pwl_bits
+    Relu, pools, Flatten, Upsample   passed through
+    Conv / ConvTranspose / Gemm      consumed: in_scale_bits = e, Rescale(l + e)
+    Mul                              e0 + e1 consumed: Rescale(l + e0 + e1)
+    Add / Concat                     equal on all operands
+    Sign / ArgMax                    dropped
+    Clip, graph output               0 required
+
 `save_onnx_model(path, circuit)` writes a pytorch-style ONNX graph of a float
 circuit with a small protobuf encoder (the python `onnx` package is not
 available on the target image), so that models built or trained here can be
@@ -99,8 +116,8 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, Relu,
-                     Rescale, Sign, SumPool2d, Upsample, _convt_check, _pool_out)
+from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul,
+                     PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _convt_check, _pool_out)
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -163,8 +180,11 @@ def _pool_attrs(node) -> tuple:
 
 
 def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
-                             q_const: float = DEFAULT_Q_CONST, q_parameter: int = -1, leaky_bits: int = 4) -> Circuit:
+                             q_const: float = DEFAULT_Q_CONST, q_parameter: int = -1, leaky_bits: int = 4,
+                             tanh: str = "sign", pwl_bits: int = 8) -> Circuit:
     q_method = QuantizationMethod(q_method)
+    if tanh not in ("sign", "pwl"):
+        raise ValueError(f"onnx: tanh must be 'sign' or 'pwl', got {tanh!r}")
     inits = {t["name"]: t for t in model["initializers"]}
     tf = model["producer_name"] == "tf2onnx"
 
@@ -539,6 +559,22 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                                           "to the lowest index)")
             # keepdims only shapes the output; the index drops a pending positive factor
             emit(_Spec("argmax", dims=dims, keepdims=int(a.get("keepdims", 1))), outs[0], j, (1,) + tuple(dims[1:]))
+        elif op in ("Sigmoid", "HardSigmoid") or (op == "Tanh" and tanh == "pwl"):
+            j, dims, fac = data_in(node, ins[0])
+            name = node.get("name") or op
+            if q_method != QuantizationMethod.ScaleQuant:
+                raise ValueError(f"onnx: {name}: a {op} is imported as a piecewise-linear layer (pwl) under ScaleQuant "
+                                 f"only: its output carries a scale 2^{pwl_bits} that the next power-of-two Rescale "
+                                 "absorbs")
+            if eb:
+                raise NotImplementedError(f"onnx: {name}: a pending 2^{eb} scale reaches this {op} before a Conv/Gemm "
+                                          "could absorb it (its breakpoints are quantized at the activation scale)")
+            if fac != 1.0:
+                raise NotImplementedError(f"onnx: {name}: an average's 1/K factor reaches this {op} before a "
+                                          "Conv/Gemm could absorb it")
+            fn = {"Sigmoid": "sigmoid", "Tanh": "tanh", "HardSigmoid": "hard_sigmoid"}[op]
+            emit(_Spec("pwl", dims=dims, fn=fn, alpha=float(a.get("alpha", 0.2)), beta=float(a.get("beta", 0.5)),
+                       name=name), outs[0], j, dims, 1.0, int(pwl_bits))
         elif op in ("Tanh", "SignTanh", "Sign"):
             j, dims, fac = data_in(node, ins[0])
             emit(_Spec("sign", dims=dims), outs[0], j, dims)  # the sign drops a positive factor
@@ -660,6 +696,15 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                 layers.append(LeakyRelu(kw["dims"], al if al.size > 1 else float(al[0]), leaky_bits))
             except ValueError as ex:
                 raise ValueError(f"onnx: {ex}") from None
+        elif s.kind == "pwl":
+            try:
+                if kw["fn"] == "hard_sigmoid":
+                    layers.append(PiecewiseLinear.hard_sigmoid(kw["dims"], kw["alpha"], kw["beta"], pwl_bits,
+                                                               q_parameter, q_method))
+                else:
+                    layers.append(getattr(PiecewiseLinear, kw["fn"])(kw["dims"], pwl_bits, q_parameter, q_method))
+            except ValueError as ex:
+                raise ValueError(f"onnx: {kw['name']}: {ex}") from None
         elif s.kind == "sign":
             layers.append(Sign(kw["dims"]))
         elif s.kind == "clip":
@@ -688,10 +733,12 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
 
 
 def load_onnx_model(path, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant, q_parameter: int = -1,
-                    q_const: float = DEFAULT_Q_CONST, leaky_bits: int = 4) -> Circuit:
+                    q_const: float = DEFAULT_Q_CONST, leaky_bits: int = 4, tanh: str = "sign",
+                    pwl_bits: int = 8) -> Circuit:
     """Reference: load_onnx_model (onnx_modelloader.h:371-406). leaky_bits: the slope bits of imported LeakyRelu /
-    PRelu nodes (docs/LEAKY_RELU.md)."""
-    return create_circuit_from_onnx(parse_onnx(path), q_method, q_const, q_parameter, leaky_bits)
+    PRelu nodes (docs/LEAKY_RELU.md). tanh: "sign" imports Tanh as Sign (the reference's convention), "pwl" as a
+    PiecewiseLinear; pwl_bits: the slope bits of imported Sigmoid / HardSigmoid / Tanh nodes (docs/PWL.md)."""
+    return create_circuit_from_onnx(parse_onnx(path), q_method, q_const, q_parameter, leaky_bits, tanh, pwl_bits)
 
 
 # ------------------------------------------------------------------ export
@@ -859,6 +906,21 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             inits += [_tensor(f"{name}.min", np.float32(l.lo / K)), _tensor(f"{name}.max", np.float32(l.hi / K))]
             nodes.append(_node("Clip", [cur, f"{name}.min", f"{name}.max"], [out], name))
             scale[out] = K
+        elif isinstance(l, PiecewiseLinear):
+            if K != 1:
+                raise NotImplementedError(f"onnx export: the average before layer {i} ({l.name}) has no linear layer "
+                                          "to fold its window size into")
+            if l.fn == "sigmoid":
+                nodes.append(_node("Sigmoid", [cur], [out], name))
+            elif l.fn == "tanh":
+                nodes.append(_node("Tanh", [cur], [out], name))
+            elif l.fn == "hard_sigmoid":
+                nodes.append(_node("HardSigmoid", [cur], [out], name, _attr_float("alpha", l.fn_params["alpha"])
+                                   + _attr_float("beta", l.fn_params["beta"])))
+            else:
+                raise NotImplementedError(f"onnx export: layer {i} ({l.name}) is an untagged piecewise-linear function "
+                                          "with no ONNX operator; only the sigmoid, tanh and hard_sigmoid "
+                                          "constructors are exported")
         elif isinstance(l, Sign):
             nodes.append(_node("Sign", [cur], [out], name))
         elif isinstance(l, ArgMax):  # scale-free: a pending average ratio ends here

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, Relu, Rescale, Sign, SumPool2d,
+from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, PiecewiseLinear, Relu, Rescale, Sign, SumPool2d,
                          Upsample, _pool_out)
 from ..ir.quant import QuantizationMethod
 from .zoo import ARCHS, canonical
@@ -127,6 +127,15 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
             mods.append(nn.ReLU6())
         elif k == "clip":
             mods.append(nn.Hardtanh(float(op[1]), float(op[2])))
+        elif k == "sigmoid":
+            mods.append(nn.Sigmoid())
+        elif k == "hsigmoid":
+            if abs(float(op[1]) - 1.0 / 6.0) > 1e-6 or float(op[2]) != 0.5:
+                raise NotImplementedError("training: nn.Hardsigmoid is hard_sigmoid(alpha=1/6, beta=1/2) only")
+            mods.append(nn.Hardsigmoid())
+        elif k == "tanh":
+            raise NotImplementedError("training: nn.Tanh stands for the sign activation here (trained as tanh, garbled "
+                                      "as sign); the piecewise-linear tanh op has no module of its own")
         elif k == "sign":
             mods.append(nn.Tanh())  # trained as tanh, garbled as sign (onnx_modelloader.h Tanh -> Sign)
         elif k == "maxpool":
@@ -150,9 +159,11 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
 
 
 def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_parameter: int = 5,
-               q_const: float = 0.02, leaky_bits: int = 4) -> Circuit:
+               q_const: float = 0.02, leaky_bits: int = 4, pwl_bits: int = 8) -> Circuit:
     """Convert a trained sequential model to a Dash circuit (float weights, quantized per q_method). A LeakyReLU /
-    PReLU becomes a LeakyRelu(slope_bits=leaky_bits); the next linear layer absorbs its 2^s (docs/LEAKY_RELU.md)."""
+    PReLU becomes a LeakyRelu(slope_bits=leaky_bits); the next linear layer absorbs its 2^s (docs/LEAKY_RELU.md).
+    An nn.Sigmoid / nn.Hardsigmoid becomes a PiecewiseLinear(slope_bits=pwl_bits) under the same scale rule
+    (docs/PWL.md); an nn.Tanh stays the sign activation."""
     torch, nn = _torch()
     arch = ARCHS[canonical(name)]
     C, H, W = arch["input"]
@@ -170,7 +181,8 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
         pend[0] = 0
 
     for m in model:
-        if pend[0] and isinstance(m, (nn.ConvTranspose2d, nn.Hardtanh, nn.Tanh, _square_module())):
+        if pend[0] and isinstance(m, (nn.ConvTranspose2d, nn.Hardtanh, nn.Tanh, nn.Sigmoid, nn.Hardsigmoid,
+                                      _square_module())):
             raise NotImplementedError(f"training: a leaky ReLU's 2^{pend[0]} scale reaches {type(m).__name__} before a "
                                       "Linear or Conv2d could absorb it")
         if isinstance(m, (nn.LeakyReLU, nn.PReLU)):
@@ -181,6 +193,14 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
                 alpha = float(alpha.reshape(-1)[0])
             layers.append(LeakyRelu(dims, alpha, leaky_bits))
             pend[0] += leaky_bits
+        elif isinstance(m, (nn.Sigmoid, nn.Hardsigmoid)):
+            if qm != QuantizationMethod.ScaleQuant:
+                raise ValueError("training: a piecewise-linear activation exists under ScaleQuant only")
+            if isinstance(m, nn.Sigmoid):
+                layers.append(PiecewiseLinear.sigmoid(dims, pwl_bits, q_parameter, qm))
+            else:  # relu6(x + 3) / 6
+                layers.append(PiecewiseLinear.hard_sigmoid(dims, 1.0 / 6.0, 0.5, pwl_bits, q_parameter, qm))
+            pend[0] += pwl_bits
         elif isinstance(m, nn.Flatten):
             layers.append(Flatten(dims))
             dims = (int(np.prod(dims)),)

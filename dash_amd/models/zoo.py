@@ -12,7 +12,8 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, Relu,
+from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, PiecewiseLinear,
+                         Relu,
                          Rescale, Sign, SumPool2d, Upsample)
 from ..ir.quant import QuantizationMethod, quantize_input
 
@@ -42,6 +43,11 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   | ("se", r) squeeze-and-excitation: the current (C, H, W) tensor is kept, then gap, a 1x1 conv to
 #                   C / r + ReLU, a 1x1 conv to C, Clip(0, 1) (a hard sigmoid's range) and the channel-broadcast Mul
 #                   of the kept tensor with that gate + the scheme's rescale (refused under SimpleQuant, as a clip)
+#                   | ("sigmoid",) | ("tanh",) | ("hsigmoid", alpha, beta) piecewise-linear activations
+#                   (PiecewiseLinear.sigmoid / .tanh / .hard_sigmoid, slope bits pwl_bits): ScaleQuant only, no
+#                   pending scale on their input; the output's 2^pwl_bits travels like a leaky ReLU's (docs/PWL.md)
+#                   | ("se", r, "sigmoid") the same block gated by the piecewise-linear sigmoid instead of
+#                   Clip(0, 1): the Mul's rescale is then l + pwl_bits (ScaleQuant only)
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     # MODEL_A whose decoded output is the class alone, not the ten logits
@@ -114,6 +120,14 @@ ARCHS: dict[str, dict] = {
         ("conv", 32, 3, 1, 1), ("leaky", 0.1), ("maxpool", 2, 2),
         ("conv", 32, 3, 1, 1), ("leaky", 0.1), ("maxpool", 2, 2),
         ("conv", 16, 1, 1, 0), ("leaky", 0.1), ("gap",), ("flatten",), ("fc", 10)]},
+    # LeNet-5 in its original form: tanh activations (piecewise-linear, docs/PWL.md) instead of ReLUs
+    "LENET5_TANH_MNIST": {"input": (1, 28, 28), "ops": [
+        ("conv", 6, 5, 1, 2), ("tanh",), ("maxpool", 2, 2), ("conv", 16, 5, 1, 0), ("tanh",), ("maxpool", 2, 2),
+        ("flatten",), ("fc", 120), ("tanh",), ("fc", 84), ("tanh",), ("fc", 10)]},
+    # a small squeeze-and-excitation CIFAR net whose gates are sigmoids, as in the SE paper
+    "SE_SIGMOID_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 8, 3, 2, 1), ("relu",), ("conv", 16, 3, 2, 1), ("se", 4, "sigmoid"), ("relu",),
+        ("conv", 16, 3, 2, 1), ("se", 4, "sigmoid"), ("relu",), ("gap",), ("flatten",), ("fc", 10)]},
     "CRYPTONETS_MNIST": {"input": (1, 28, 28), "ops": [
         ("conv", 5, 5, 2, 1), ("square",), ("flatten",), ("fc", 100), ("square",), ("fc", 10)]},
     # SqueezeNet-style CIFAR net: a stride-2 stem (32 -> 16), ceil-mode 3x3/2 max pools whose last window is cut at
@@ -168,9 +182,11 @@ def _init(rng, shape, fan_in):
 
 
 def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.ScaleQuant, q_parameter: int = 5,
-                  q_const: float = 0.02, seed: int = 0, weights: Optional[dict] = None, leaky_bits: int = 4) -> Circuit:
+                  q_const: float = 0.02, seed: int = 0, weights: Optional[dict] = None, leaky_bits: int = 4,
+                  pwl_bits: int = 8) -> Circuit:
     """Random-init (or given float weights) circuit with Dash quantization. leaky_bits: the slope bits of the
-    ("leaky", alpha) and ("prelu",) ops."""
+    ("leaky", alpha) and ("prelu",) ops; pwl_bits: those of the ("sigmoid",), ("tanh",), ("hsigmoid", ...) ops and
+    of a sigmoid-gated ("se", r, "sigmoid")."""
     arch = ARCHS[canonical(name)]
     rng = np.random.default_rng(seed)
     C, H, W = arch["input"]
@@ -270,6 +286,15 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             alpha = float(op[1]) if kind == "leaky" else np.full(dims[0], 0.25, np.float32)
             layers.append(LeakyRelu(dims, alpha, leaky_bits))
             pend[0] += leaky_bits
+        elif kind in ("sigmoid", "tanh", "hsigmoid"):
+            if qm != QuantizationMethod.ScaleQuant:
+                raise ValueError(f"{name}: op {len(layers)} ({kind}): a piecewise-linear activation exists under "
+                                 "ScaleQuant only (its 2^s output scale needs a power-of-two rescale behind it)")
+            if kind == "hsigmoid":
+                layers.append(PiecewiseLinear.hard_sigmoid(dims, op[1], op[2], pwl_bits, q_parameter, qm))
+            else:
+                layers.append(getattr(PiecewiseLinear, kind)(dims, pwl_bits, q_parameter, qm))
+            pend[0] += pwl_bits
         elif kind == "sign":
             layers.append(Sign(dims))
         elif kind in ("relu6", "clip"):
@@ -284,6 +309,12 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         elif kind == "se":
             if len(dims) != 3 or dims[0] % op[1]:
                 raise ValueError(f"{name}: op {len(layers)} (se): needs a (C, H, W) tensor whose channels {op[1]} divides")
+            gate = op[2] if len(op) > 2 else "clip"
+            if gate not in ("clip", "sigmoid"):
+                raise ValueError(f"{name}: op {len(layers)} (se): the gate is 'clip' or 'sigmoid', got {gate!r}")
+            if gate == "sigmoid" and qm != QuantizationMethod.ScaleQuant:
+                raise ValueError(f"{name}: op {len(layers)} (se): a sigmoid gate exists under ScaleQuant only (its 2^s "
+                                 "output scale needs a power-of-two rescale behind it)")
             if qm == QuantizationMethod.SimpleQuant:
                 raise ValueError(f"{name}: op {len(layers)} (se): its Clip(0, 1) gate has no quantization under "
                                  "SimpleQuant (no single activation scale); use ScaleQuant or ScaleQuantPlus")
@@ -293,11 +324,14 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             d_sq = conv(fd[0] // op[1], 1, 1, 0, fd[0], 1, 1)
             layers.append(Relu(d_sq))
             d_ex = conv(fd[0], 1, 1, 0, d_sq[0], 1, 1)
-            layers.append(Clip(d_ex, 0.0, 1.0, q_parameter, qm))
+            if gate == "sigmoid":
+                layers.append(PiecewiseLinear.sigmoid(d_ex, pwl_bits, q_parameter, qm))
+            else:
+                layers.append(Clip(d_ex, 0.0, 1.0, q_parameter, qm))
             mul = Mul(fd, len(layers) - 1, (fd[0], 1, 1))
             mul.in_src = full  # the full tensor is the Mul's input, the gate its operand
             layers.append(mul)
-            rescale_after(fd)
+            rescale_after(fd, pwl_bits if gate == "sigmoid" else 0)  # the gate's 2^s leaves with the product's
         elif kind == "argmax":
             am = ArgMax(dims)
             layers.append(am)
