@@ -246,6 +246,8 @@ PYBIND11_MODULE(_dash_native, m) {
 
     // Mul (gadgets.h MulPlan): table entries per output element of a product / a square
     m.def("mul_entries", [](const std::vector<int>& crt, bool square) { return MulPlan::entries(crt, square); });
+    // MatMul (gadgets.h MatMulPlan): table entries per output element of a contraction over T
+    m.def("matmul_entries", [](const std::vector<int>& crt, i64 T) { return MatMulPlan::entries(crt, T); });
 
     // Single gates of the native garbler with caller-chosen labels (wire-compatibility vectors: the tests
     // rebuild the reference's formulas in a pure-Python oracle and compare table bytes). Tables come back as

@@ -134,6 +134,11 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
     for (const auto& l : m.layers) {
         if (l.kind == K_ADD) keep[l.param("src") + 1] = 1;
         if (l.kind == K_MUL && !l.param("sq", 0)) keep[l.param("src") + 1] = 1;
+        if (l.kind == K_MATMUL) {
+            DASH_CHECK(l.param("src") >= -1 && l.param("src") < static_cast<i64>(m.layers.size()),
+                       "matmul: bad source layer");
+            keep[l.param("src") + 1] = 1;
+        }
         if (l.kind == K_CONCAT)
             for (i64 s : l.vec("srcs")) {
                 DASH_CHECK(s >= -1 && s < static_cast<i64>(m.layers.size()), "concat: bad source layer");
@@ -827,6 +832,43 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                         }
                         mul_eval_elem(mp, stream_id(L, 1, e), xp.data(), yp.data(), ga + e * sum_crt,
                                       sq ? nullptr : ea + e * sum_crt, op.data());
+                    }
+                }, nt);
+                cur = std::move(nxt);
+                break;
+            }
+            case K_MATMUL: {
+                // gadgets.h MatMulPlan
+                DASH_CHECK(hard, "matmul: the MatMul layer exists in the hardened encoding only");
+                const MatMulPlan mp(crt, g.param("M"), g.param("T"), g.param("N"), g.param("ta", 0) != 0,
+                                    g.param("tb", 0) != 0);
+                const i64 src = g.param("src");
+                DASH_CHECK(src >= -1 && src < static_cast<i64>(li), "matmul: bad source layer");
+                const CrtLabels& ys = saved[src + 1];
+                DASH_CHECK(!ys.empty() && Nin == mp.nx() && ys[0].N == mp.ny(), "matmul: operand size mismatch");
+                for (int j = 0; j < k; ++j)
+                    DASH_CHECK(cur[j].p == crt[j] && ys[j].p == crt[j], "matmul: operands off the CRT base");
+                const i64 No = mp.nout(), T = mp.T;
+                const Array& gA = g.arr("g");
+                const Array& eA = g.arr("e");
+                DASH_CHECK(static_cast<i64>(gA.count()) == No * T * sum_crt &&
+                               static_cast<i64>(eA.count()) == No * T * sum_crt, "matmul: table shape");
+                const u128* ga = gA.ptr<u128>();
+                const u128* ea = eA.ptr<u128>();
+                CrtLabels nxt;
+                for (int j = 0; j < k; ++j) nxt.emplace_back(crt[j], No);
+                parallel_for(No, [&](i64 b0, i64 b1) {
+                    std::vector<const comp_t*> xp(T * k), yp(T * k);
+                    std::vector<comp_t*> op(k);
+                    for (i64 o = b0; o < b1; ++o) {
+                        for (i64 t = 0; t < T; ++t)
+                            for (int j = 0; j < k; ++j) {
+                                xp[t * k + j] = cur[j].at(mp.xidx(o, t));
+                                yp[t * k + j] = ys[j].at(mp.yidx(o, t));
+                            }
+                        for (int j = 0; j < k; ++j) op[j] = nxt[j].at(o);
+                        matmul_eval_elem(mp, L, o, xp.data(), yp.data(), ga + o * T * sum_crt, ea + o * T * sum_crt,
+                                         op.data());
                     }
                 }, nt);
                 cur = std::move(nxt);

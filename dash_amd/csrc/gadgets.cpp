@@ -1110,4 +1110,39 @@ void mul_eval_elem(const MulPlan& P, u64 gate, const comp_t* const* x, const com
     }
 }
 
+// ---------------------------------------------------------------------------
+// MatMul (gadgets.h MatMulPlan): T MulPlan products per output element, summed
+void matmul_garble_elem(const MatMulPlan& P, const LabelBank& R, const Prg& prg, u64 layer, i64 o,
+                        const comp_t* const* x0, const comp_t* const* y0, u128* g, u128* e, comp_t* const* out0) {
+    const int k = P.k();
+    comp_t prod[128];  // nr_comps(2), the longest label
+    for (int j = 0; j < k; ++j) std::memset(out0[j], 0, sizeof(comp_t) * mod_info(P.crt[j]).n);
+    for (i64 t = 0; t < P.T; ++t) {
+        const u64 stream = stream_id(layer, 1, static_cast<u64>(o * P.T + t));
+        u64 ctr = 0;
+        for (int j = 0; j < k; ++j) {
+            const ModInfo& mp = mod_info(P.crt[j]);
+            const i64 off = t * P.sum_crt + P.prefix[j];
+            gen_mult_garble(x0[t * k + j], y0[t * k + j], mp, R, prg, stream, ctr, g + off, e + off, prod, true, j);
+            lab_add(out0[j], prod, mp.n, mp.p);
+        }
+    }
+}
+
+void matmul_eval_elem(const MatMulPlan& P, u64 layer, i64 o, const comp_t* const* x, const comp_t* const* y,
+                      const u128* g, const u128* e, comp_t* const* out) {
+    const int k = P.k();
+    comp_t prod[128];
+    for (int j = 0; j < k; ++j) std::memset(out[j], 0, sizeof(comp_t) * mod_info(P.crt[j]).n);
+    for (i64 t = 0; t < P.T; ++t) {
+        const u64 gate = stream_id(layer, 1, static_cast<u64>(o * P.T + t));
+        for (int j = 0; j < k; ++j) {
+            const ModInfo& mp = mod_info(P.crt[j]);
+            const i64 off = t * P.sum_crt + P.prefix[j];
+            gen_mult_eval(x[t * k + j], y[t * k + j], mp, g + off, e + off, prod, true, gate, j);
+            lab_add(out[j], prod, mp.n, mp.p);
+        }
+    }
+}
+
 }  // namespace dash

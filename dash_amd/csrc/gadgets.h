@@ -579,6 +579,59 @@ void mul_garble_elem(const MulPlan& P, const LabelBank& R, const Prg& prg, u64 s
 void mul_eval_elem(const MulPlan& P, u64 gate, const comp_t* const* x, const comp_t* const* y, const u128* g,
                    const u128* e, comp_t* const* out);
 
+// ---------------------------------------------------------------------------
+// MatMul (wire kind 22, docs/MATMUL.md): out[i, l] = sum_t x[i, t] y[t, l], the
+// contraction of two secret CRT tensors. x is M x T and y is T x N after the
+// transpose flags, which only change the strides into the flat tensors:
+// x[i, t] = flat_x[i xsi + t xst], y[t, l] = flat_y[t yst + l ysl].
+// Per output element o = i N + l the products t = 0..T-1 are MulPlan products as
+// they stand (gen_mult_garble / gen_mult_eval per residue j): product (o, t) has
+// gate id and PRG stream stream_id(L, 1, o T + t) and MulPlan's draw order. The
+// output zero label is the sum over t of the products' output zero labels mod
+// p per component; the evaluator sums the products' output labels. One x label
+// keys the g rows of N products and one y label the e rows of M, each under
+// its own gate id, and the two half gates of a product differ in their tweak
+// (TW_MMG / TW_GME), so a label that is both operands (x x^T) still gets two
+// distinct pads. Tables g, e [M N T][P], output-major with t innermost: one
+// output's rows are contiguous. Hardened encoding only, for MulPlan's reasons.
+struct MatMulPlan {
+    std::vector<int> crt;
+    i64 M = 0, T = 0, N = 0;
+    bool ta = false, tb = false;
+    i64 xsi = 0, xst = 0, yst = 0, ysl = 0;
+    i64 sum_crt = 0;
+    std::vector<i64> prefix;  // table offset of residue j
+    MatMulPlan() = default;
+    MatMulPlan(const std::vector<int>& crt_, i64 M_, i64 T_, i64 N_, bool ta_, bool tb_)
+        : crt(crt_), M(M_), T(T_), N(N_), ta(ta_), tb(tb_) {
+        DASH_CHECK(M >= 1 && T >= 1 && N >= 1, "matmul: empty operand");
+        DASH_CHECK(M <= (i64(1) << 36) / T && M * T <= (i64(1) << 36) / N && M * T * N <= (i64(1) << 36),
+                   "matmul: M N T products do not fit the 36-bit element field of a stream id");
+        xsi = ta ? 1 : T;
+        xst = ta ? M : 1;
+        yst = tb ? 1 : N;
+        ysl = tb ? T : 1;
+        for (int p : crt) {
+            prefix.push_back(sum_crt);
+            sum_crt += p;
+        }
+    }
+    int k() const { return static_cast<int>(crt.size()); }
+    i64 nout() const { return M * N; }
+    i64 nx() const { return M * T; }
+    i64 ny() const { return T * N; }
+    i64 xidx(i64 o, i64 t) const { return (o / N) * xsi + t * xst; }  // x's flat element of product (o, t)
+    i64 yidx(i64 o, i64 t) const { return t * yst + (o % N) * ysl; }  // y's
+    i64 entries() const { return 2 * sum_crt * T; }                   // per output element
+    static i64 entries(const std::vector<int>& crt, i64 T) { return MatMulPlan(crt, 1, T, 1, false, false).entries(); }
+};
+// One output element o. x0 / y0 (x / y): label pointers [t k + j] of the products' operands; g, e: the output's
+// T P table rows; out0 / out: k label pointers. Garbler: base labels.
+void matmul_garble_elem(const MatMulPlan& P, const LabelBank& R, const Prg& prg, u64 layer, i64 o,
+                        const comp_t* const* x0, const comp_t* const* y0, u128* g, u128* e, comp_t* const* out0);
+void matmul_eval_elem(const MatMulPlan& P, u64 layer, i64 o, const comp_t* const* x, const comp_t* const* y,
+                      const u128* g, const u128* e, comp_t* const* out);
+
 // ----------------------------------------------------------------------------
 // LeakyRelu (wire kind 20, docs/LEAKY_RELU.md): y = 2^s x (x >= 0), n_c x (x < 0), n_c in [0, 2^s) per
 // channel c = e / bc, which is n_c x + (2^s - n_c) relu(x). A public multiple and a sum of labels of one

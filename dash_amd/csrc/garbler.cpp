@@ -38,6 +38,7 @@ const char* kind_name(int kind) {
         case K_CLIP: return "clip";
         case K_ARGMAX: return "argmax";
         case K_MUL: return "mul";
+        case K_MATMUL: return "matmul";
         case K_LEAKY: return "leaky_relu";
         case K_PWL: return "pwl";
         case K_CONVT: return "conv_transpose2d";
@@ -652,6 +653,11 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
             DASH_CHECK(s >= -1 && s < static_cast<i64>(layers.size()), "mul: bad source layer");
             keep[s + 1] = 1;
         }
+        if (l.kind == K_MATMUL) {
+            const i64 s = param1(l.p, "src");
+            DASH_CHECK(s >= -1 && s < static_cast<i64>(layers.size()), "matmul: bad source layer");
+            keep[s + 1] = 1;
+        }
         if (l.kind == K_CONCAT)
             for (i64 s : paramv(l.p, "srcs")) {
                 DASH_CHECK(s >= -1 && s < static_cast<i64>(layers.size()), "concat: bad source layer");
@@ -753,6 +759,9 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
                                     spec.kind == K_CLIP || spec.kind == K_ARGMAX || spec.kind == K_PWL ||
                                     (spec.kind == K_MUL && GpuGarbler::mul_fits(k, param1(spec.p, "sq", 0) != 0)) ||
+                                    (spec.kind == K_MATMUL &&
+                                     GpuGarbler::matmul_fits(k, param1(spec.p, "M") * param1(spec.p, "T") *
+                                                                    param1(spec.p, "N"))) ||
                                     (spec.kind == K_RESCALE && (param1(spec.p, "mode", 0) != 0 || crt_[0] == 2)))));
         const bool passthru = spec.kind == K_FLATTEN;
         if (on_gpu && !dev_ok) {
@@ -1829,6 +1838,57 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                     g.a["g"] = ga;
                     g.a["e"] = ea;
                 }
+                break;
+            }
+            case K_MATMUL: {
+                // gadgets.h MatMulPlan: x = cur (M x T), y = the saved output of layer src (T x N)
+                DASH_CHECK(is_crt(), "matmul needs CRT-base labels");
+                DASH_CHECK(hard, "matmul: the MatMul layer exists in the hardened encoding only");
+                const i64 src = param1(spec.p, "src");
+                const MatMulPlan mp(crt_, param1(spec.p, "M"), param1(spec.p, "T"), param1(spec.p, "N"),
+                                    param1(spec.p, "ta", 0) != 0, param1(spec.p, "tb", 0) != 0);
+                DASH_CHECK(src >= -1 && src < static_cast<i64>(li), "matmul: bad source layer");
+                DASH_CHECK(saved_mod[src + 1] == crt_, "matmul: the operand is not on the CRT base");
+                i64 ny = 1;
+                for (i64 v : saved_dims[src + 1]) ny *= v;
+                DASH_CHECK(Nin == mp.nx() && ny == mp.ny(), "matmul: operand size mismatch");
+                const i64 No = mp.nout(), T = mp.T;
+                Array ga(DType::u128, {No * T, sum_crt}), ea(DType::u128, {No * T, sum_crt});
+                if (on_gpu) {
+                    sinkify(ga, "g");
+                    sinkify(ea, "e");
+                    gpu->matmul(L, mp, static_cast<size_t>(src + 1), cur, ga, ea);
+                } else {
+                    CrtLabels other;
+                    if (gpu) {  // the saved outputs live on the device: fetch this one (the device cur is stale)
+                        gpu->restore(static_cast<size_t>(src + 1), other);
+                        gpu->to_host(other);
+                    }
+                    const CrtLabels& ys = gpu ? other : saved[src + 1];
+                    DASH_CHECK(!ys.empty() && ys[0].N == mp.ny(), "matmul: operand size mismatch");
+                    CrtLabels nxt;
+                    for (int j = 0; j < k; ++j) nxt.emplace_back(crt_[j], No);
+                    parallel_for(No, [&](i64 b0, i64 b1) {
+                        std::vector<const comp_t*> xp(T * k), yp(T * k);
+                        std::vector<comp_t*> op(k);
+                        for (i64 o = b0; o < b1; ++o) {
+                            for (i64 t = 0; t < T; ++t)
+                                for (int j = 0; j < k; ++j) {
+                                    xp[t * k + j] = cur[j].at(mp.xidx(o, t));
+                                    yp[t * k + j] = ys[j].at(mp.yidx(o, t));
+                                }
+                            for (int j = 0; j < k; ++j) op[j] = nxt[j].at(o);
+                            matmul_garble_elem(mp, R_, prg_, L, o, xp.data(), yp.data(), ga.ptr<u128>() + o * T * sum_crt,
+                                               ea.ptr<u128>() + o * T * sum_crt, op.data());
+                        }
+                    }, nt);
+                    cur = std::move(nxt);
+                }
+                g.a["g"] = ga;
+                g.a["e"] = ea;
+                // the matrix shape: the spec does not carry the layer's out_dims (e.g. (C, H, W)), and saved_dims is
+                // only ever read for its product
+                dims = {mp.M, mp.N};
                 break;
             }
             case K_MMULT: {

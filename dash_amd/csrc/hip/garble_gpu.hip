@@ -3026,6 +3026,7 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     clip_joint_hook() = &GpuGarbler::clip_joint_dev;
     argmax_hook() = &GpuGarbler::argmax_level_dev;
     mul_hook() = &GpuGarbler::mul_dev;
+    matmul_hook() = &GpuGarbler::matmul_dev;
     pwl_hook() = &GpuGarbler::pwl_dev;
     leaky_keep_hook() = &GpuGarbler::leaky_keep_dev;
     leaky_map_hook() = &GpuGarbler::leaky_map_dev;
@@ -4469,34 +4470,17 @@ void GpuGarbler::concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& i
 // x with r = the colour of y's base label (rows (TW_MMG, j), table 4), the evaluator half gate F_NEGR keyed by y
 // with the same r and x's base label as its payload offset (rows (TW_GME, j), table 5); out = sk04 - sk03.
 // Square: the output label of residue j in slot j, one projection v -> v^2 (rows (TW_PROJ, j), table 4).
-void GpuGarbler::mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& ga,
-                         Array& ea) {
-    Impl& I = *self.impl_;
-    I.enter();
-    I.check_cur(cur);
-    PhaseTrace tr_("mul");
-    const int64_t N = I.cur_N;
+// mul_core: the N products (or squares) of the labels xl and yl (one label per element each; yl unused for a
+// square) into the tables ga / ea; returns the N output base labels. Shared by Mul and MatMul.
+static std::vector<DevBlock> mul_core(GpuGarbler::Impl& I, PhaseTrace& tr_, uint64_t layer, const MulPlan& mp,
+                                      const std::vector<DevBlock>& xl, const std::vector<DevBlock>* yl, int64_t N,
+                                      Array& ga, Array& ea) {
     const int k = I.k;
-    DASH_CHECK(I.c.hard, "gpu garbler: the Mul layer exists in the hardened encoding only");
-    DASH_CHECK(I.cur_mod == I.crt && mp.k() == k, "gpu garbler: mul needs CRT-base labels");
     static_assert(kMaxRes == 16, "GpuGarbler::mul_fits states the input set's size");
-    DASH_CHECK(mul_fits(k, mp.square), "gpu garbler: mul: x and y do not fit the 16 input residues of one projection set");
-    gg::In in = labels_in(I.cur, I.crt, N);
-    std::vector<DevBlock> ybc;  // a broadcast operand, one label per output element
+    DASH_CHECK(GpuGarbler::mul_fits(k, mp.square),
+               "gpu garbler: mul: x and y do not fit the 16 input residues of one projection set");
+    gg::In in = labels_in(xl, I.crt, N);
     if (!mp.square) {
-        auto it = I.saved.find(src_idx);
-        DASH_CHECK(it != I.saved.end() && it->second.mods == I.crt && it->second.N == mp.ny(N) &&
-                       (mp.bc == 0 || N % mp.bc == 0),
-                   "gpu garbler: mul operand missing, off the CRT base or of another shape");
-        const std::vector<DevBlock>* yl = &it->second.L;
-        if (mp.bc) {
-            ybc = I.alloc_labels(I.crt, N);
-            std::vector<int32_t> map(static_cast<size_t>(N));
-            for (int64_t e = 0; e < N; ++e) map[static_cast<size_t>(e)] = static_cast<int32_t>(e / mp.bc);
-            launch_gsum(I.c, ybc, *yl, I.crt, N, it->second.N, gg::dconst(map.data(), map.size()), 1, false,
-                        [](int, int) { return 1; });
-            yl = &ybc;
-        }
         for (int j = 0; j < k; ++j) {
             in.p[k + j] = (*yl)[j].as<int16_t>();
             in.n[k + j] = nr_comps(I.crt[j]);
@@ -4594,8 +4578,86 @@ void GpuGarbler::mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, si
     tr_.mark("kernels");
     tG.to_array(ga, I.device);
     if (!mp.square) tE.to_array(ea, I.device);
+    return out;
+}
+
+void GpuGarbler::mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& ga,
+                         Array& ea) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("mul");
+    const int64_t N = I.cur_N;
+    DASH_CHECK(I.c.hard, "gpu garbler: the Mul layer exists in the hardened encoding only");
+    DASH_CHECK(I.cur_mod == I.crt && mp.k() == I.k, "gpu garbler: mul needs CRT-base labels");
+    std::vector<DevBlock> ybc;  // a broadcast operand, one label per output element
+    const std::vector<DevBlock>* yl = nullptr;
+    if (!mp.square) {
+        auto it = I.saved.find(src_idx);
+        DASH_CHECK(it != I.saved.end() && it->second.mods == I.crt && it->second.N == mp.ny(N) &&
+                       (mp.bc == 0 || N % mp.bc == 0),
+                   "gpu garbler: mul operand missing, off the CRT base or of another shape");
+        yl = &it->second.L;
+        if (mp.bc) {
+            ybc = I.alloc_labels(I.crt, N);
+            std::vector<int32_t> map(static_cast<size_t>(N));
+            for (int64_t e = 0; e < N; ++e) map[static_cast<size_t>(e)] = static_cast<int32_t>(e / mp.bc);
+            launch_gsum(I.c, ybc, *yl, I.crt, N, it->second.N, gg::dconst(map.data(), map.size()), 1, false,
+                        [](int, int) { return 1; });
+            yl = &ybc;
+        }
+    }
+    std::vector<DevBlock> out = mul_core(I, tr_, layer, mp, I.cur, yl, N, ga, ea);
     I.cur = std::move(out);
     set_stale(cur, I.crt, N);
+}
+
+// MatMul (garbler.cpp K_MATMUL, gadgets.h MatMulPlan), byte-identical to matmul_garble_elem. Product (o, t) is
+// element o T + t of a Mul over M N T elements: both operands are gathered to one zero label per product (x by
+// MatMulPlan::xidx, y by yidx), mul_core garbles the products under stream_id(layer, 1, o T + t) into the
+// layer's tables (whose rows are output-major with t innermost, as mul_core's are element-major), and each
+// output's T product labels are summed in groups of kMaxTerms.
+void GpuGarbler::matmul_dev(GpuGarbler& self, uint64_t layer, const MatMulPlan& mp, size_t src_idx, CrtLabels& cur,
+                            Array& ga, Array& ea) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("matmul");
+    DASH_CHECK(I.c.hard, "gpu garbler: the MatMul layer exists in the hardened encoding only");
+    DASH_CHECK(I.cur_mod == I.crt && mp.k() == I.k, "gpu garbler: matmul needs CRT-base labels");
+    const int64_t No = mp.nout(), T = mp.T, P = No * T;
+    DASH_CHECK(matmul_fits(I.k, P), "gpu garbler: matmul: too many products for one pass, or too many residues");
+    auto it = I.saved.find(src_idx);
+    DASH_CHECK(I.cur_N == mp.nx() && it != I.saved.end() && it->second.mods == I.crt && it->second.N == mp.ny(),
+               "gpu garbler: matmul operand missing, off the CRT base or of another shape");
+    std::vector<DevBlock> xg = I.alloc_labels(I.crt, P), yg = I.alloc_labels(I.crt, P);
+    {
+        std::vector<int32_t> mx(static_cast<size_t>(P)), my(static_cast<size_t>(P));
+        for (int64_t o = 0; o < No; ++o)
+            for (int64_t t = 0; t < T; ++t) {
+                mx[static_cast<size_t>(o * T + t)] = static_cast<int32_t>(mp.xidx(o, t));
+                my[static_cast<size_t>(o * T + t)] = static_cast<int32_t>(mp.yidx(o, t));
+            }
+        launch_gsum(I.c, xg, I.cur, I.crt, P, I.cur_N, gg::dconst(mx.data(), mx.size()), 1, false,
+                    [](int, int) { return 1; });
+        launch_gsum(I.c, yg, it->second.L, I.crt, P, it->second.N, gg::dconst(my.data(), my.size()), 1, false,
+                    [](int, int) { return 1; });
+    }
+    std::vector<DevBlock> prod = mul_core(I, tr_, layer, MulPlan(I.crt, 0, false), xg, &yg, P, ga, ea);
+    std::vector<DevBlock> out = I.alloc_labels(I.crt, No);
+    for (int64_t t0 = 0; t0 < T; t0 += gg::kMaxTerms) {
+        const int Kt = static_cast<int>(std::min<int64_t>(gg::kMaxTerms, T - t0));
+        std::vector<int32_t> mt(static_cast<size_t>(No) * Kt);
+        for (int64_t o = 0; o < No; ++o)
+            for (int t = 0; t < Kt; ++t) mt[static_cast<size_t>(o) * Kt + t] = static_cast<int32_t>(o * T + t0 + t);
+        launch_gsum(I.c, out, prod, I.crt, No, P, gg::dconst(mt.data(), mt.size()), Kt, t0 > 0,
+                    [](int, int) { return 1; });
+    }
+    HIPCHECK(hipGetLastError());
+    tr_.mark("sum");
+    I.cur = std::move(out);
+    I.cur_N = No;
+    set_stale(cur, I.crt, No);
 }
 
 // dense base labels (garbler.cpp K_DENSE): y_o = sum_{w != 0 mod p} w x_src(i) + (1 + #zero weights) Z_p

@@ -171,6 +171,22 @@ class GpuGarbler {
         DASH_CHECK(mul_hook() != nullptr, "gpu garbler: mul is not linked in");
         mul_hook()(*this, layer, mp, src_idx, cur, g, e);
     }
+    // MatMul (gadgets.h MatMulPlan): x = the device cur (M T elements), y = the saved output `src_idx` (T N); tables
+    // g, e [M N T][P]; device cur -> the M N outputs. Both operands are gathered to one zero label per product, the
+    // products are Mul's (stream element o T + t) and each output's T product labels are summed. A hook as for mul.
+    using MatMulFn = void (*)(GpuGarbler&, uint64_t, const MatMulPlan&, size_t, CrtLabels&, Array&, Array&);
+    static MatMulFn& matmul_hook() {
+        static MatMulFn f = nullptr;
+        return f;
+    }
+    // The gathered operands and the products' slots live in device memory all at once: layers of more products
+    // than this (and bases beyond mul_fits) garble on the host
+    static constexpr i64 kMatMulMaxProducts = i64(1) << 18;  // about 5 KiB of labels and slots per product at k = 7
+    static bool matmul_fits(int k, i64 products) { return mul_fits(k, false) && products <= kMatMulMaxProducts; }
+    void matmul(uint64_t layer, const MatMulPlan& mp, size_t src_idx, CrtLabels& cur, Array& g, Array& e) {
+        DASH_CHECK(matmul_hook() != nullptr, "gpu garbler: matmul is not linked in");
+        matmul_hook()(*this, layer, mp, src_idx, cur, g, e);
+    }
     // PiecewiseLinear (gadgets.h PwlPlan): per kept breakpoint i the device cur shifted to x0 + T_i R, the sign's
     // draw / derive / fan-out passes on stream slot 1 + 2i (pm: exact, pa: approximate fused) and the ReLU half
     // gates on slot 2 + 2i, each breakpoint's output zero labels added into the combination
@@ -239,6 +255,8 @@ class GpuGarbler {
     static void leaky_map_dev(GpuGarbler& self, const LeakyPlan& lp, CrtLabels& cur);
     static void mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& g,
                         Array& e);
+    static void matmul_dev(GpuGarbler& self, uint64_t layer, const MatMulPlan& mp, size_t src_idx, CrtLabels& cur,
+                           Array& g, Array& e);
     std::unique_ptr<Impl> impl_;
 };
 

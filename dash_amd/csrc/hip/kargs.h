@@ -242,5 +242,24 @@ struct MulArgs {
     uint64_t gate0;
 };
 
+// A MatMul layer (gadgets.h MatMulPlan; hardened only): out[i N + l] = sum_t x[i xsi + t xst] * y[t yst + l ysl]
+// over M N outputs per GC. Neither operand's label is read by the multiply: kx / ky hold their compressed labels
+// and cx / cy their colours, [B][k][M T] and [B][k][T N], written once per run by the key pre-pass
+// (launch_label_key). The digits of x come from kx itself.
+struct MatMulArgs {
+    CrtInfo crt;
+    int64_t M, T, N;
+    int64_t xsi, xst, yst, ysl;  // the transposes, as strides
+    const u128* g;               // [B][M N T][sum] rows (TW_MMG, j) keyed by x, t innermost
+    const u128* e;               // [B][M N T][sum] rows (TW_GME, j) keyed by y
+    const u128 *kx, *ky;
+    const uint16_t *cx, *cy;
+    uint64_t gate0;
+    int lds_n;    // the widest label of an odd residue: rows of the accumulator image (and of the blocked form's digits)
+    int blocked;  // the planner's pick: k_matmul_b (matmul.blocked) instead of k_matmul (matmul.lane)
+};
+// The blocked form's tile: kMmI x kMmL outputs per block, kMmTC products of t per staged chunk
+constexpr int kMmI = 16, kMmL = 16, kMmTC = 16;
+
 }  // namespace dev
 }  // namespace dash

@@ -2249,6 +2249,10 @@ void launch_clip_mult(const ClipArgs& a, const Act& x, const Act& y, int B, cons
 void launch_pwl_key(const PwlArgs& a, u128* kx, uint16_t* colx, const Act& x, int B, const ModC* mc, hipStream_t st) {
     hipLaunchKernelGGL(k_label_key, grid_for(a.N, 256, a.crt.k, B), dim3(256), 0, st, x, a.crt, a.N, kx, colx, mc);
 }
+void launch_label_key(const CrtInfo& crt, int64_t N, u128* kx, uint16_t* colx, const Act& x, int B, const ModC* mc,
+                      hipStream_t st) {
+    hipLaunchKernelGGL(k_label_key, grid_for(N, 256, crt.k, B), dim3(256), 0, st, x, crt, N, kx, colx, mc);
+}
 template <int M>
 static void launch_pwl_mult_m(const PwlArgs& a, const Act& x, const Act& y, int B, const ModC* mc, hipStream_t st) {
     dim3 grid;

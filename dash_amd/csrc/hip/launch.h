@@ -114,6 +114,12 @@ void launch_proj(const ProjArgs& a, const Act& x, const Act& y, int B, const Mod
 // pick) or "mul.sq".
 void launch_mul(const MulArgs& a, bool square, const Act& x, const Act& ys, const Act& y, int B, const ModC* mc,
                 hipStream_t st);
+// MatMul layer (kernels_matmul.hip): the compressed labels and colours of an operand's N elements, once per run
+// (k_label_key, [B][k][N]), and the contraction itself, which reads only those. Logs "matmul.lane" or
+// "matmul.blocked" (MatMulArgs::blocked, the planner's pick).
+void launch_label_key(const CrtInfo& crt, int64_t N, u128* kx, uint16_t* colx, const Act& x, int B, const ModC* mc,
+                      hipStream_t st);
+void launch_matmul(const MatMulArgs& a, const Act& y, int B, const ModC* mc, hipStream_t st);
 void launch_mult(const MultArgs& a, const Act& x, const Act& y, int B, const ModC* mc, const AesGlobals& g,
                  hipStream_t st);
 

@@ -673,6 +673,7 @@ class HipEvaluator {
                 return N;
             }
             case K_MULT: case K_MMULT: return N_in / 2;
+            case K_MATMUL: return l.param("M") * l.param("N");
             default: return N_in;
         }
     }
@@ -718,6 +719,21 @@ class HipEvaluator {
                 mmax = std::max(mmax, PwlPlan(crt_, l.param("s"), l.vec("T"), l.vec("A"), l.param("V")).m());
         for (int i = 0; i < mmax; ++i)
             if (!kpwl_[i]) kpwl_[i] = dalloc<u128>(static_cast<size_t>(B_) * w.caps.maxSignN);
+    }
+    // a MatMul's operand keys and colours ([B][k][M T] and [B][k][T N]): sized by the model's largest operands
+    void ensure_matmul() {
+        i64 nx = 0, ny = 0;
+        for (const GLayer& l : tmpl_->layers)
+            if (l.kind == K_MATMUL) {
+                nx = std::max(nx, l.param("M") * l.param("T"));
+                ny = std::max(ny, l.param("T") * l.param("N"));
+            }
+        if (!mm_kx_) {
+            mm_kx_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * nx);
+            mm_cx_ = dalloc<uint16_t>(static_cast<size_t>(B_) * k_ * nx);
+            mm_ky_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * ny);
+            mm_cy_ = dalloc<uint16_t>(static_cast<size_t>(B_) * k_ * ny);
+        }
     }
     // The exact mixed-radix sign's chain (mode 1, gadgets.h SignMrsPlan) over N elements with layer li's table
     // `table`: a ReLU's (ny = ny_: the sign label's y-row pads), or with the label itself kept in `ks` and ny = 0
@@ -814,6 +830,7 @@ class HipEvaluator {
     void plan_proj(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_mult(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_mul(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_matmul(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_leaky(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_pwl(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname);
@@ -890,6 +907,8 @@ class HipEvaluator {
     const int16_t* zero_rows_ = nullptr;
     const int16_t* up_rows_ = nullptr;
     u128* mrs_ps_ = nullptr;  // mixed-radix rescale chain scratch (allocated by the first such layer)
+    u128 *mm_kx_ = nullptr, *mm_ky_ = nullptr;  // a MatMul's operand keys and colours (ensure_matmul)
+    uint16_t *mm_cx_ = nullptr, *mm_cy_ = nullptr;
     u128* kpwl_[kPwlMax] = {};  // [B][maxSignN] a PiecewiseLinear's sign labels (allocated by the first such layer)
     u128* ks_[2] = {nullptr, nullptr};  // [B][maxSignN] a Clip's two sign labels (allocated by the first Clip)
     // ArgMax scratch (allocated by the first ArgMax): candidate values / index labels of the odd levels, the value
@@ -931,6 +950,11 @@ void HipEvaluator::build() {
             DASH_CHECK(s >= -1 && s < static_cast<i64>(L), "mul: bad source layer");
             w.keep[s + 1] = 1;
         }
+        if (l.kind == K_MATMUL) {
+            const i64 s = l.param("src");
+            DASH_CHECK(s >= -1 && s < static_cast<i64>(L), "matmul: bad source layer");
+            w.keep[s + 1] = 1;
+        }
         if (l.kind == K_CONCAT)
             for (i64 s : l.vec("srcs")) w.keep[s + 1] = 1;
         if (l.p.count("in_src")) w.keep[l.param("in_src") + 1] = 1;
@@ -964,6 +988,7 @@ void HipEvaluator::build() {
             case K_PROJ: plan_proj(w, li, g, lname); break;
             case K_MULT: case K_MMULT: plan_mult(w, li, g, lname); break;
             case K_MUL: plan_mul(w, li, g, lname); break;
+            case K_MATMUL: plan_matmul(w, li, g, lname); break;
             case K_LEAKY: plan_leaky(w, li, g, lname); break;
             case K_PWL: plan_pwl(w, li, g, lname); break;
             case K_BASEEXT: plan_base_ext(w, li, g, lname); break;
@@ -2130,6 +2155,74 @@ void HipEvaluator::plan_mul(Walk& w, size_t li, const GLayer& g, const std::stri
     const Env e = w.env;
     add_op(lname, [a, sq, x, ys, y, e](hipStream_t st) { launch_mul(a, sq, x, ys, y, e.B, e.mc, st); });
     set_out(w, g, w.N, w.nxt());
+}
+
+// gadgets.h MatMulPlan: x = the current activation (M x T), y = the saved copy of layer src's output (T x N), read
+// in place as plan_mul reads it; a src that is the layer's own input reads the current activation. The key
+// pre-pass compresses every element of both operands once; the contraction reads only the keys and colours.
+void HipEvaluator::plan_matmul(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
+    DASH_CHECK(hard_, "the MatMul layer exists in the hardened encoding only");
+    DASH_CHECK(w.mods == crt_, "matmul: the input is not on the CRT base");
+    const MatMulPlan mp(crt_, g.param("M"), g.param("T"), g.param("N"), g.param("ta", 0) != 0, g.param("tb", 0) != 0);
+    const i64 src = g.param("src");
+    DASH_CHECK(src >= -1 && src < static_cast<i64>(li) && !saved_[src + 1].empty(), "matmul: operand not saved");
+    DASH_CHECK(w.saved_mods[src + 1] == crt_, "matmul: the operand is not on the CRT base");
+    DASH_CHECK(w.N == mp.nx() && w.saved_n[src + 1] == mp.ny(), "matmul: operand size mismatch");
+    const Array& ga = g.arr("g");
+    const Array& ea = g.arr("e");
+    DASH_CHECK(ga.shape.size() == 2 && ga.shape[0] == mp.nout() * mp.T && ga.shape[1] == w.crt.sum &&
+                   ea.shape == ga.shape, "matmul: table shape");
+    ensure_matmul();
+    MatMulArgs a{};
+    a.crt = w.crt;
+    a.M = mp.M;
+    a.T = mp.T;
+    a.N = mp.N;
+    a.xsi = mp.xsi;
+    a.xst = mp.xst;
+    a.yst = mp.yst;
+    a.ysl = mp.ysl;
+    a.kx = mm_kx_;
+    a.ky = mm_ky_;
+    a.cx = mm_cx_;
+    a.cy = mm_cy_;
+    a.gate0 = gate_base(li + 1, 1);
+    for (int j = 0; j < k_; ++j)
+        if (crt_[j] != 2) a.lds_n = std::max(a.lds_n, nr_comps(crt_[j]));
+    a.g = upload_tables(li, "g");
+    a.e = upload_tables(li, "e");
+    Act x = act_of(w.cur), y = act_of(w.nxt()), ys{};
+    const i64 x_src = g.p.count("in_src") ? g.param("in_src") : static_cast<i64>(li) - 1;
+    if (src == x_src) {
+        ys = x;
+    } else {
+        for (int j = 0; j < k_; ++j) ys.p[j] = saved_[src + 1][j];
+    }
+    ys.N = mp.ny();
+    // The grid rule: the blocked form where at least one kMmI x kMmL tile is full, else the lane form (a tile of a
+    // thinner product would be mostly idle lanes). DASH_MATMUL_FORM=lane|blocked overrides it (A/B runs).
+    a.blocked = mp.M >= kMmI && mp.N >= kMmL;
+    if (const char* f = std::getenv("DASH_MATMUL_FORM")) {
+        if (std::string(f) == "lane") a.blocked = 0;
+        if (std::string(f) == "blocked") a.blocked = 1;
+    }
+    const Env e = w.env;
+    const i64 nx = mp.nx(), ny = mp.ny();
+    // All MatMul layers share the key buffers: the ops of one evaluator run in order on one stream (or as one chain
+    // of a captured graph), so a layer's contraction has read them before the next layer's pre-pass writes them.
+    u128 *kxw = mm_kx_, *kyw = mm_ky_;
+    uint16_t *cxw = mm_cx_, *cyw = mm_cy_;
+    const bool same = src == x_src;  // x x^T: one tensor, keyed once
+    if (same) {
+        a.ky = a.kx;
+        a.cy = a.cx;
+    }
+    add_op(lname + ".K", [a, x, ys, nx, ny, e, kxw, kyw, cxw, cyw, same](hipStream_t st) {
+        launch_label_key(a.crt, nx, kxw, cxw, x, e.B, e.mc, st);
+        if (!same) launch_label_key(a.crt, ny, kyw, cyw, ys, e.B, e.mc, st);
+    });
+    add_op(lname, [a, y, e](hipStream_t st) { launch_matmul(a, y, e.B, e.mc, st); });
+    set_out(w, g, mp.nout(), w.nxt());
 }
 
 void HipEvaluator::plan_base_ext(Walk& w, size_t li, const GLayer& g, const std::string& lname) {

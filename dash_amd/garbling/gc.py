@@ -30,6 +30,7 @@ _ARGMAX = _Kind.ARGMAX
 _MUL = _Kind.MUL
 _CONVT = _Kind.CONVT
 _PWL = _Kind.PWL
+_MATMUL = _Kind.MATMUL
 
 Labels = list  # list[(modulus, np.ndarray int16 [N, n_p])]
 
@@ -223,6 +224,13 @@ class GarbledCircuit:
         if pwls and not (supported if hardened is None else hardened):
             raise ValueError("layer %d (pwl): the PiecewiseLinear layer exists in the hardened encoding only (%s)" % (
                 pwls[0], "hardened=False was asked for" if supported else
+                "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
+        # a MatMul is T Mul products per output: each operand label keys N (or M) half gates, told apart only by the
+        # hardened encoding's gate tweak
+        matmuls = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _MATMUL]
+        if matmuls and not (supported if hardened is None else hardened):
+            raise ValueError("layer %d (matmul): the MatMul layer exists in the hardened encoding only (%s)" % (
+                matmuls[0], "hardened=False was asked for" if supported else
                 "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
         if argmaxes and not mrs_capable(self.crt_base):
             raise ValueError("layer %d (argmax): the ArgMax layer's exact sign needs a CRT base with residue 0 = 2 "

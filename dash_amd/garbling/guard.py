@@ -25,8 +25,8 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
   int64 activations and 32 x 32 -> 64-bit products, on its own high-priority stream beside the garbled
   evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
   bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
-  has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no LeakyRelu, no PiecewiseLinear and no padded / ceil-mode
-  pooling:
+  has no Concat, no Clip, no ArgMax, no Mul, no MatMul, no ConvTranspose2d, no Upsample, no LeakyRelu, no
+  PiecewiseLinear and no padded / ceil-mode pooling:
   circuits with any of them take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
@@ -35,7 +35,10 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
 
 A ``Mul`` sets no limit of its own: its product is checked where a gadget or the output next reads it. The torch
 path multiplies in int64, exact like the numpy model; operands whose product could reach 2^62, where the numpy
-model raises ``OverflowError`` instead of wrapping, are flagged.
+model raises ``OverflowError`` instead of wrapping, are flagged. A ``MatMul`` is treated the same way: no limit
+of its own, an int64 broadcast multiply and sum over the contracted axis in the torch path (no int64 matmul exists
+on the GPU), operands whose T products could sum to 2^62 flagged; guard.hip has none, so such circuits take the
+torch path.
 """
 from __future__ import annotations
 
@@ -71,12 +74,13 @@ class RangeGuard:
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Mul, L.Projection,
                                           L.BaseExtension, L.ConvTranspose2d, L.Upsample, L.LeakyRelu,
-                                          L.PiecewiseLinear))
+                                          L.PiecewiseLinear, L.MatMul))
                            for l in circuit.layers)
         # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no
-        # LeakyRelu, no PiecewiseLinear, no dilated conv and no padded / ceil-mode pooling: such circuits take the batched torch path
+        # LeakyRelu, no PiecewiseLinear, no MatMul, no dilated conv and no padded / ceil-mode pooling: such circuits take
+        # the batched torch path
         self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.Mul, L.ConvTranspose2d, L.Upsample,
-                                                   L.LeakyRelu, L.PiecewiseLinear)) or
+                                                   L.LeakyRelu, L.PiecewiseLinear, L.MatMul)) or
                                     (isinstance(l, L.Conv2d) and (l.dh > 1 or l.dw > 1)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
@@ -286,6 +290,19 @@ class RangeGuard:
                 big = (ay > 0) & (ax > torch.div((1 << 62) - 1, ay.clamp_min(1), rounding_mode="floor"))
                 bad |= big
                 out = torch.where(big[:, None], 0, inp) * y
+            elif isinstance(l, L.MatMul):
+                a = inp.reshape((B,) + L._as_matrix(l.in_dims))
+                y = ctx[l.src + 1].reshape((B,) + L._as_matrix(l.src_dims))
+                a = a.transpose(1, 2) if l.trans_a else a
+                y = y.transpose(1, 2) if l.trans_b else y
+                # T max|x| max|y| >= 2^62 in exact integers: ax > floor(floor((2^62 - 1) / T) / ay). Such inputs are
+                # flagged (the numpy model raises OverflowError) and their x zeroed so nothing wraps
+                ax, ay = inp.abs().amax(dim=1), y.abs().amax(dim=(1, 2))
+                big = (ay > 0) & (ax > torch.div(((1 << 62) - 1) // l.T, ay.clamp_min(1), rounding_mode="floor"))
+                bad |= big
+                a = torch.where(big[:, None, None], 0, a)
+                # an int64 matmul does not exist on the GPU: a broadcast multiply and an integer sum over t
+                out = (a[:, :, :, None] * y[:, None, :, :]).sum(dim=2).reshape(B, -1)
             elif isinstance(l, L.Concat):
                 out = torch.cat([ctx[s + 1].reshape(B, -1) for s in l.srcs], dim=1)
             else:  # Flatten, Projection, BaseExtension: value-preserving

@@ -42,6 +42,7 @@ class Kind:
     MUL = 19
     LEAKY = 20
     PWL = 21
+    MATMUL = 22
 
 
 def _size(d: Sequence[int]) -> int:
@@ -1229,6 +1230,88 @@ class Mul(Layer):
     def __repr__(self) -> str:
         return (f"Mul.square({self.in_dims})" if self.is_square else
                 f"Mul({self.in_dims}, src={self.src}, src_dims={self.src_dims})")
+
+
+def _as_matrix(d: Sequence[int]) -> tuple[int, int]:
+    """Dims (d0, d1, ...) as the matrix d0 x prod(d1...) of the flat [C][H][W] order; (n,) is 1 x n."""
+    d = tuple(int(v) for v in d)
+    if not d:
+        raise ValueError("matmul: an operand needs at least one axis")
+    return (1, d[0]) if len(d) == 1 else (d[0], _size(d[1:]))
+
+
+class MatMul(Layer):
+    """Contraction of two secret tensors: out[i, l] = sum_t x[i, t] * y[t, l].
+    x is the layer's input, y the output of layer `src` (-1 = circuit input), as
+    for Add and Mul. A tensor of dims (d0, d1, ...) is read as the matrix
+    d0 x prod(d1...) in its flat order, a 1-D tensor (n,) as 1 x n; `trans_a` /
+    `trans_b` transpose that view (strides only, no data moves). After the flags
+    x is M x T and y is T x N. The output has dims (M, N), or `out_dims` of equal
+    size. `src` may name the layer's own input (x x^T with trans_b): it is
+    garbled as the general product. Scale-free: whoever builds the circuit puts
+    the scheme's rescale behind it, as after a Mul. Garbled as T generalized half
+    gates per output element and residue, summed (csrc/gadgets.h MatMulPlan);
+    hardened encoding only."""
+
+    kind = Kind.MATMUL
+    name = "matmul"
+
+    def __init__(self, dims, src: int, src_dims, trans_a: bool = False, trans_b: bool = False, out_dims=None):
+        dims = tuple(int(d) for d in dims)
+        sd = tuple(int(d) for d in src_dims)
+        self.trans_a, self.trans_b = bool(trans_a), bool(trans_b)
+        xr, xc = _as_matrix(dims)
+        yr, yc = _as_matrix(sd)
+        M, T = (xc, xr) if self.trans_a else (xr, xc)
+        T2, N = (yc, yr) if self.trans_b else (yr, yc)
+        if T != T2:
+            raise ValueError(f"matmul: x of dims {dims} is {M} x {T}{' (transposed)' if self.trans_a else ''} and y of "
+                             f"dims {sd} is {T2} x {N}{' (transposed)' if self.trans_b else ''}: the inner sizes differ")
+        od = (M, N) if out_dims is None else tuple(int(d) for d in out_dims)
+        if _size(od) != M * N:
+            raise ValueError(f"matmul: out_dims {od} do not hold the {M} x {N} product of dims {dims} and {sd}")
+        super().__init__(dims, od)
+        self.src_dims = sd
+        self.src = int(src)
+        self.M, self.T, self.N = M, T, N
+
+    def _views(self, x, ctx, dtype):
+        x = np.asarray(x, dtype=dtype).reshape(_as_matrix(self.in_dims))
+        y = np.asarray(ctx[self.src + 1], dtype=dtype).reshape(-1)
+        assert y.size == _size(self.src_dims), "matmul operand size mismatch"
+        y = y.reshape(_as_matrix(self.src_dims))
+        return (x.T if self.trans_a else x), (y.T if self.trans_b else y)
+
+    def plain_eval(self, x, track=True, ctx=None):
+        a, b = self._views(x, ctx, np.float32)
+        out = (a @ b).astype(np.float32).reshape(-1)
+        if track:
+            self._track_f(out)
+        return out
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        a, b = self._views(x, ctx, np.int64)
+        if a.size and b.size:
+            ax = max(abs(int(a.min())), abs(int(a.max())))
+            ay = max(abs(int(b.min())), abs(int(b.max())))
+            if self.T * ax * ay >= 1 << 62:
+                raise OverflowError(f"matmul: {self.T} products of operands up to {ax} and {ay} do not fit 62 bits")
+        out = (a[:, :, None] * b[None, :, :]).sum(axis=1, dtype=np.int64).reshape(-1)
+        if track:
+            self._track_q(a, b, out)
+        return out
+
+    def garble_spec(self):
+        p = {"src": self.src, "M": self.M, "T": self.T, "N": self.N}
+        if self.trans_a:
+            p["ta"] = 1
+        if self.trans_b:
+            p["tb"] = 1
+        return self.kind, p
+
+    def __repr__(self) -> str:
+        return (f"MatMul({self.in_dims}, src={self.src}, src_dims={self.src_dims}, trans_a={self.trans_a}, "
+                f"trans_b={self.trans_b}, out_dims={self.out_dims})")
 
 
 # ---- test-only layers (reference: projection.h, mult_layer.h, mixed_mod_mult_layer.h, max.h, base_extension.h)

@@ -58,6 +58,19 @@ follows the layer exactly as after a conv. A `Mul` with an initializer
 operand, any other broadcast and any other exponent are refused with the
 node's name.
 
+`MatMul` of two produced tensors, and `Gemm` of two produced tensors with
+`alpha = 1` and no `C` (its `transA` / `transB` become the flags), becomes a
+`MatMul` layer (docs/MATMUL.md) followed by the scheme's rescale, as after a
+`Mul`. Operands are rank 2 behind the batch axis: a `Reshape` of a produced
+`(C, H, W)` tensor to `(C, H W)` that feeds only such nodes is the same tensor
+under new dims (the flat layout already is that matrix), and so is the only
+`Reshape` of the node's result, e.g. back to `(C, H, W)`; every other `Reshape`
+flattens as before. A `Transpose` that swaps the last two axes and feeds only
+such nodes folds into `trans_a` / `trans_b`; any other `Transpose` is refused
+with its name. An operand of higher rank (a batch of matrices, heads), or one
+with a pending average factor or pending scale bits, is refused with the node's
+name. A `MatMul` / `Gemm` with an initializer operand is a `Dense`, as before.
+
 `ReduceSum` over (2, 3) is the plane `SumPool2d` itself (the exporter writes a
 global sum pool that no linear layer follows this way).
 
@@ -116,8 +129,8 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul,
-                     PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _convt_check, _pool_out)
+from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MatMul, MaxPool2d, Mul,
+                     PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _as_matrix, _convt_check, _pool_out)
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -232,6 +245,43 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         if uses and all(o == "Pow" and pos == 1 for o, pos in uses) and vals.size == 1:
             pow_consts[out] = float(vals[0])
 
+    # MatMul / Gemm of two produced tensors (no initializer operand): a MatMul layer. Around such a node a Transpose
+    # of the last two axes that feeds only such nodes folds into trans_a / trans_b, a Reshape that feeds only such
+    # nodes (or such a Transpose) is the same tensor under matrix dims, and so is the only Reshape of its result.
+    def uses_of(name: str) -> list:
+        return [k for k, n in enumerate(nodes) if name in n["inputs"]]
+
+    secret_mm = {k for k, n in enumerate(nodes) if n["op_type"] in ("MatMul", "Gemm") and len(n["inputs"]) >= 2
+                 and n["inputs"][0] not in inits and n["inputs"][1] not in inits}
+    fold_tr = set()
+    for k, n in enumerate(nodes):
+        perm = [int(v) for v in n["attrs"].get("perm", [])] if n["op_type"] == "Transpose" else []
+        r = len(perm)
+        if r >= 2 and perm == list(range(r - 2)) + [r - 1, r - 2] and uses_of(n["outputs"][0]) and \
+                all(u in secret_mm for u in uses_of(n["outputs"][0])):
+            fold_tr.add(k)
+    mm_feed = {k for k, n in enumerate(nodes) if n["op_type"] == "Reshape" and uses_of(n["outputs"][0])
+               and all(u in secret_mm or u in fold_tr for u in uses_of(n["outputs"][0]))}
+    mm_back = {k for k, n in enumerate(nodes) if n["op_type"] == "Reshape" and any(
+        nodes[m]["outputs"][0] == n["inputs"][0] and uses_of(n["inputs"][0]) == [k] for m in secret_mm)}
+    tr_of: dict[str, str] = {}    # a folded Transpose's output -> its input
+    vdims: dict[str, tuple] = {}  # a matrix-view Reshape's output -> its dims (the tensor itself is an alias)
+
+    def view_shape(node, size: int) -> tuple:
+        """The target of a Reshape without its batch axis, 0 and -1 resolved against `size` elements."""
+        name = node.get("name") or node["op_type"]
+        if len(node["inputs"]) < 2 or node["inputs"][1] not in inits:
+            raise NotImplementedError(f"onnx: {name}: the shape of a Reshape next to a MatMul must be an initializer")
+        shp = [int(v) for v in np.asarray(inits[node["inputs"][1]]["values"]).reshape(-1)][1:]
+        if any(v == 0 for v in shp):
+            raise NotImplementedError(f"onnx: {name}: a Reshape next to a MatMul must state its dims (no 0 entries)")
+        if shp.count(-1) == 1:
+            known = int(np.prod([v for v in shp if v != -1], dtype=np.int64))
+            shp[shp.index(-1)] = size // max(known, 1)
+        if not shp or any(v < 1 for v in shp) or int(np.prod(shp, dtype=np.int64)) != size:
+            raise NotImplementedError(f"onnx: {name}: Reshape of {size} elements to {shp}")
+        return tuple(shp)
+
     def res(name: str) -> str:
         return alias.get(name, name)
 
@@ -280,7 +330,51 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             alias[outs[0]] = res(ins[0])
             continue
         eb = bits(ins[0]) if ins else 0  # the data input's pending scale bits
-        if op == "Flatten" or op == "Reshape":
+        if op == "Reshape" and (ni in mm_feed or ni in mm_back):
+            j, dims, fac = data_in(node, ins[0])
+            shp = view_shape(node, int(np.prod(dims)))
+            alias[outs[0]] = res(ins[0])
+            if ni in mm_back:  # the product continues under these dims, e.g. (C, H, W)
+                specs[j].kw["out_dims"] = shp
+                tdims[res(ins[0])] = shp
+            else:
+                vdims[outs[0]] = shp
+        elif op == "Transpose" and ni in fold_tr:
+            data_in(node, ins[0])
+            alias[outs[0]] = res(ins[0])
+            tr_of[outs[0]] = ins[0]
+        elif op == "Transpose":
+            raise NotImplementedError(f"onnx: {node.get('name') or op}: a Transpose is supported only where it swaps "
+                                      "the last two axes and feeds only a MatMul / Gemm of two produced tensors")
+        elif ni in secret_mm:
+            name = node.get("name") or op
+            if op == "Gemm" and (float(a.get("alpha", 1.0)) != 1.0 or (len(ins) > 2 and ins[2])):
+                raise NotImplementedError(f"onnx: {name}: a Gemm of two produced tensors is supported with alpha = 1 "
+                                          "and no C only")
+            flags, opnd = [], []
+            for pos, key in ((0, "transA"), (1, "transB")):
+                nm, t = ins[pos], bool(int(a.get(key, 0))) if op == "Gemm" else False
+                if nm in tr_of:
+                    nm, t = tr_of[nm], not t
+                j, dims, fac = data_in(node, nm)
+                dims = vdims.get(nm, dims)
+                if len(dims) > 2:
+                    raise NotImplementedError(f"onnx: {name}: operand {pos} has dims {tuple(dims)} behind the batch "
+                                              "axis: a batch of more than one matrix per operand (heads) is not "
+                                              "supported; Reshape a (C, H, W) tensor to (C, H W) first")
+                if fac != 1.0 or bits(nm):
+                    raise NotImplementedError(f"onnx: {name}: operand {pos} carries a pending average factor or pending "
+                                              f"scale bits ({fac:g}, 2^{bits(nm)}) that no Conv/Gemm absorbed")
+                flags.append(t)
+                opnd.append((j, tuple(dims)))
+            (jx, dx), (jy, dy) = opnd
+            try:
+                probe = MatMul(dx, 0, dy, flags[0], flags[1])
+            except ValueError as ex:
+                raise ValueError(f"onnx: {name}: {ex}") from None
+            emit(_Spec("matmul", dims=dx, src=jy, src_dims=dy, ta=flags[0], tb=flags[1], out_dims=None), outs[0], jx,
+                 probe.out_dims)
+        elif op == "Flatten" or op == "Reshape":
             j, dims, fac = data_in(node, ins[0])
             if op == "Reshape" and len(dims) == 1:
                 alias[outs[0]] = res(ins[0])
@@ -718,10 +812,13 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         elif s.kind == "mul":
             layers.append(Mul.square(kw["dims"]) if kw["sq"] else
                           Mul(kw["dims"], spec_to_layer[kw["src"]], kw["src_dims"]))
+        elif s.kind == "matmul":
+            layers.append(MatMul(kw["dims"], spec_to_layer[kw["src"]], kw["src_dims"], kw["ta"], kw["tb"],
+                                 kw["out_dims"]))
         if kw.get("in_src") is not None:
             layers[-1].in_src = spec_to_layer[kw["in_src"]]
         spec_to_layer[i] = len(layers) - 1
-        if s.kind in ("dense", "conv", "convt", "mul"):  # a product carries both operands' scales, as a conv's does
+        if s.kind in ("dense", "conv", "convt", "mul", "matmul"):  # a product carries both operands' scales, as a conv's does
             out = layers[-1].out_dims
             if q_method == QuantizationMethod.ScaleQuant:  # + the input's pending scale bits
                 layers.append(Rescale(q_parameter + kw.get("e", 0), out))
@@ -931,6 +1028,29 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             other = cur if l.is_square else names[l.src]
             nodes.append(_node("Mul", [cur, other], [out], name))
             scale[out] = K * scale[other]
+        elif isinstance(l, MatMul):
+            # Reshape (where the tensor is no matrix yet) / Transpose / MatMul, and a Reshape of the result where the
+            # layer continues under other dims: what the importer folds back into one layer
+            if K != 1 or scale[names[l.src]] != 1:
+                raise NotImplementedError(f"onnx export: the average before layer {i} ({l.name}) has no linear layer "
+                                          "to fold its window size into")
+            opnds = []
+            for tag, tname, d_, tr in (("a", cur, l.in_dims, l.trans_a), ("b", names[l.src], l.src_dims, l.trans_b)):
+                if len(d_) != 2:
+                    inits.append(_tensor_i64(f"{name}.{tag}.shape", (1,) + _as_matrix(d_)))
+                    nodes.append(_node("Reshape", [tname, f"{name}.{tag}.shape"], [f"{name}.{tag}.m"], f"{name}.{tag}.reshape"))
+                    tname = f"{name}.{tag}.m"
+                if tr:
+                    nodes.append(_node("Transpose", [tname], [f"{name}.{tag}.t"], f"{name}.{tag}.transpose",
+                                       _attr_ints("perm", [0, 2, 1])))
+                    tname = f"{name}.{tag}.t"
+                opnds.append(tname)
+            if l.out_dims == (l.M, l.N):
+                nodes.append(_node("MatMul", opnds, [out], name))
+            else:
+                inits.append(_tensor_i64(f"{name}.shape", (1,) + l.out_dims))
+                nodes.append(_node("MatMul", opnds, [f"{name}.mm"], name))
+                nodes.append(_node("Reshape", [f"{name}.mm", f"{name}.shape"], [out], f"{name}.reshape"))
         elif isinstance(l, Concat):
             nodes.append(_node("Concat", [names[s] for s in l.srcs], [out], name, _attr_int("axis", 1)))
         else:

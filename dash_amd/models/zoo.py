@@ -12,8 +12,8 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, PiecewiseLinear,
-                         Relu,
+from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MatMul, MaxPool2d, Mul,
+                         PiecewiseLinear, Relu,
                          Rescale, Sign, SumPool2d, Upsample)
 from ..ir.quant import QuantizationMethod, quantize_input
 
@@ -43,6 +43,11 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   | ("se", r) squeeze-and-excitation: the current (C, H, W) tensor is kept, then gap, a 1x1 conv to
 #                   C / r + ReLU, a 1x1 conv to C, Clip(0, 1) (a hard sigmoid's range) and the channel-broadcast Mul
 #                   of the kept tensor with that gate + the scheme's rescale (refused under SimpleQuant, as a clip)
+#                   | ("nonlocal", r) the dot-product non-local block of Wang et al. (normaliser 1 / N, no softmax) on
+#                   a (C, H, W) tensor with H W <= 64: 1x1 convs phi, g, theta to C / r channels (each + the scheme's
+#                   rescale), f = MatMul(theta^T, phi) of dims (H W, H W) + rescale, y = MatMul(g, f^T) of dims
+#                   (C / r, H, W) + rescale, a 1x1 conv back to C whose weights carry the 1 / (H W), and the Add of
+#                   the block's input (docs/MATMUL.md)
 #                   | ("sigmoid",) | ("tanh",) | ("hsigmoid", alpha, beta) piecewise-linear activations
 #                   (PiecewiseLinear.sigmoid / .tanh / .hard_sigmoid, slope bits pwl_bits): ScaleQuant only, no
 #                   pending scale on their input; the output's 2^pwl_bits travels like a leaky ReLU's (docs/PWL.md)
@@ -104,6 +109,11 @@ ARCHS: dict[str, dict] = {
         ("dwconv", 3, 2, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("relu6",),
         ("dwconv", 3, 1, 1), ("relu6",), ("conv", 64, 1, 1, 0), ("relu6",),
         ("gap",), ("flatten",), ("fc", 10)]},
+    # a small CIFAR net with one dot-product non-local block (reduction 2) on its 8 x 8 stage: f is a
+    # (64, 16, 64) contraction, y a (16, 64, 64) one
+    "NONLOCAL_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 1, 1), ("relu",), ("maxpool", 2, 2), ("conv", 32, 3, 2, 1), ("relu",), ("nonlocal", 2),
+        ("relu",), ("gap",), ("flatten",), ("fc", 10)]},
     # MOBILENET_CIFAR with a squeeze-and-excitation gate (reduction 4) behind every pointwise conv
     "SE_MOBILENET_CIFAR": {"input": (3, 32, 32), "ops": [
         ("conv", 16, 3, 1, 1), ("relu6",),
@@ -202,9 +212,9 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         elif qm == QuantizationMethod.ScaleQuantPlus:
             layers.append(Rescale([q_parameter], d))
 
-    def conv(cout, k, s, p, cin, h, w, groups=1, dil=1):
+    def conv(cout, k, s, p, cin, h, w, groups=1, dil=1, wscale=1.0):
         fan_in = cin // groups * k * k
-        wt = _init(rng, (cout, cin // groups, k, k), fan_in)
+        wt = _init(rng, (cout, cin // groups, k, k), fan_in) * np.float32(wscale)
         bs = _init(rng, (cout,), fan_in)
         c = Conv2d(wt, bs, w, h, cin, cout, k, k, s, s, q_parameter, qm, q_const, pad_width=p, pad_height=p,
                    groups=groups, dilation_width=dil, dilation_height=dil, in_scale_bits=pend[0])
@@ -332,6 +342,36 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             mul.in_src = full  # the full tensor is the Mul's input, the gate its operand
             layers.append(mul)
             rescale_after(fd, pwl_bits if gate == "sigmoid" else 0)  # the gate's 2^s leaves with the product's
+        elif kind == "nonlocal":
+            r = op[1]
+            if len(dims) != 3 or dims[0] % r:
+                raise ValueError(f"{name}: op {len(layers)} (nonlocal): needs a (C, H, W) tensor whose channels {r} "
+                                 "divides")
+            cin, h, w = dims
+            if h * w > 64:
+                raise ValueError(f"{name}: op {len(layers)} (nonlocal): the affinity matrix has (H W)^2 entries of C / r "
+                                 f"products each; pool first so that H W <= 64, got {h} x {w}")
+            src, cr = len(layers) - 1, cin // r
+            d_e = conv(cr, 1, 1, 0, cin, h, w)  # phi reads the previous layer
+            phi = len(layers) - 1
+            first = len(layers)
+            conv(cr, 1, 1, 0, cin, h, w)
+            layers[first].in_src = src
+            g_out = len(layers) - 1
+            first = len(layers)
+            conv(cr, 1, 1, 0, cin, h, w)
+            layers[first].in_src = src
+            # f = theta^T phi, (H W, H W): the pairwise affinities
+            f = MatMul(d_e, phi, d_e, trans_a=True)
+            layers.append(f)
+            rescale_after(f.out_dims)
+            # y = g f^T, back to (C / r, H, W)
+            y = MatMul(d_e, len(layers) - 1, f.out_dims, trans_b=True, out_dims=d_e)
+            y.in_src = g_out
+            layers.append(y)
+            rescale_after(d_e)
+            conv(cin, 1, 1, 0, cr, h, w, wscale=1.0 / (h * w))  # the normaliser 1 / N rides on the weights
+            layers.append(Add(dims, src))
         elif kind == "argmax":
             am = ArgMax(dims)
             layers.append(am)
