@@ -841,7 +841,7 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 // gadgets.h MatMulPlan
                 DASH_CHECK(hard, "matmul: the MatMul layer exists in the hardened encoding only");
                 const MatMulPlan mp(crt, g.param("M"), g.param("T"), g.param("N"), g.param("ta", 0) != 0,
-                                    g.param("tb", 0) != 0);
+                                    g.param("tb", 0) != 0, g.param("G", 1));
                 const i64 src = g.param("src");
                 DASH_CHECK(src >= -1 && src < static_cast<i64>(li), "matmul: bad source layer");
                 const CrtLabels& ys = saved[src + 1];

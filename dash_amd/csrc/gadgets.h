@@ -594,19 +594,25 @@ void mul_eval_elem(const MulPlan& P, u64 gate, const comp_t* const* x, const com
 // (TW_MMG / TW_GME), so a label that is both operands (x x^T) still gets two
 // distinct pads. Tables g, e [M N T][P], output-major with t innermost: one
 // output's rows are contiguous. Hardened encoding only, for MulPlan's reasons.
+// Heads (param G, default 1): both operands are G contiguous slabs of M T and
+// T N elements, head g contracts slab g of x with slab g of y, and the output
+// is head-major, o = (g M + i) N + l. M, T, N and the strides stay per head; the
+// gate ids, the draws and the table layout follow o as they stand, over
+// G M N T products.
 struct MatMulPlan {
     std::vector<int> crt;
     i64 M = 0, T = 0, N = 0;
     bool ta = false, tb = false;
+    i64 G = 1;
     i64 xsi = 0, xst = 0, yst = 0, ysl = 0;
     i64 sum_crt = 0;
     std::vector<i64> prefix;  // table offset of residue j
     MatMulPlan() = default;
-    MatMulPlan(const std::vector<int>& crt_, i64 M_, i64 T_, i64 N_, bool ta_, bool tb_)
-        : crt(crt_), M(M_), T(T_), N(N_), ta(ta_), tb(tb_) {
-        DASH_CHECK(M >= 1 && T >= 1 && N >= 1, "matmul: empty operand");
-        DASH_CHECK(M <= (i64(1) << 36) / T && M * T <= (i64(1) << 36) / N && M * T * N <= (i64(1) << 36),
-                   "matmul: M N T products do not fit the 36-bit element field of a stream id");
+    MatMulPlan(const std::vector<int>& crt_, i64 M_, i64 T_, i64 N_, bool ta_, bool tb_, i64 G_ = 1)
+        : crt(crt_), M(M_), T(T_), N(N_), ta(ta_), tb(tb_), G(G_) {
+        DASH_CHECK(M >= 1 && T >= 1 && N >= 1 && G >= 1, "matmul: empty operand");
+        DASH_CHECK(M <= (i64(1) << 36) / T && M * T <= (i64(1) << 36) / N && M * T * N <= (i64(1) << 36) / G,
+                   "matmul: G M N T products do not fit the 36-bit element field of a stream id");
         xsi = ta ? 1 : T;
         xst = ta ? M : 1;
         yst = tb ? 1 : N;
@@ -617,11 +623,12 @@ struct MatMulPlan {
         }
     }
     int k() const { return static_cast<int>(crt.size()); }
-    i64 nout() const { return M * N; }
-    i64 nx() const { return M * T; }
-    i64 ny() const { return T * N; }
-    i64 xidx(i64 o, i64 t) const { return (o / N) * xsi + t * xst; }  // x's flat element of product (o, t)
-    i64 yidx(i64 o, i64 t) const { return t * yst + (o % N) * ysl; }  // y's
+    i64 nout() const { return G * M * N; }
+    i64 nx() const { return G * M * T; }
+    i64 ny() const { return G * T * N; }
+    // x's and y's flat element of product (o, t): the head's slab, then the strides within it
+    i64 xidx(i64 o, i64 t) const { return (o / (M * N)) * (M * T) + ((o / N) % M) * xsi + t * xst; }
+    i64 yidx(i64 o, i64 t) const { return (o / (M * N)) * (T * N) + t * yst + (o % N) * ysl; }
     i64 entries() const { return 2 * sum_crt * T; }                   // per output element
     static i64 entries(const std::vector<int>& crt, i64 T) { return MatMulPlan(crt, 1, T, 1, false, false).entries(); }
 };

@@ -760,8 +760,8 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                                     spec.kind == K_CLIP || spec.kind == K_ARGMAX || spec.kind == K_PWL ||
                                     (spec.kind == K_MUL && GpuGarbler::mul_fits(k, param1(spec.p, "sq", 0) != 0)) ||
                                     (spec.kind == K_MATMUL &&
-                                     GpuGarbler::matmul_fits(k, param1(spec.p, "M") * param1(spec.p, "T") *
-                                                                    param1(spec.p, "N"))) ||
+                                     GpuGarbler::matmul_fits(k, param1(spec.p, "G", 1) * param1(spec.p, "M") *
+                                                                    param1(spec.p, "T") * param1(spec.p, "N"))) ||
                                     (spec.kind == K_RESCALE && (param1(spec.p, "mode", 0) != 0 || crt_[0] == 2)))));
         const bool passthru = spec.kind == K_FLATTEN;
         if (on_gpu && !dev_ok) {
@@ -1841,12 +1841,12 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 break;
             }
             case K_MATMUL: {
-                // gadgets.h MatMulPlan: x = cur (M x T), y = the saved output of layer src (T x N)
+                // gadgets.h MatMulPlan: x = cur (G slabs M x T), y = the saved output of layer src (G slabs T x N)
                 DASH_CHECK(is_crt(), "matmul needs CRT-base labels");
                 DASH_CHECK(hard, "matmul: the MatMul layer exists in the hardened encoding only");
                 const i64 src = param1(spec.p, "src");
                 const MatMulPlan mp(crt_, param1(spec.p, "M"), param1(spec.p, "T"), param1(spec.p, "N"),
-                                    param1(spec.p, "ta", 0) != 0, param1(spec.p, "tb", 0) != 0);
+                                    param1(spec.p, "ta", 0) != 0, param1(spec.p, "tb", 0) != 0, param1(spec.p, "G", 1));
                 DASH_CHECK(src >= -1 && src < static_cast<i64>(li), "matmul: bad source layer");
                 DASH_CHECK(saved_mod[src + 1] == crt_, "matmul: the operand is not on the CRT base");
                 i64 ny = 1;
@@ -1888,7 +1888,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 g.a["e"] = ea;
                 // the matrix shape: the spec does not carry the layer's out_dims (e.g. (C, H, W)), and saved_dims is
                 // only ever read for its product
-                dims = {mp.M, mp.N};
+                dims = {mp.G * mp.M, mp.N};
                 break;
             }
             case K_MMULT: {

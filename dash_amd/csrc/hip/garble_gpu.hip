@@ -4616,7 +4616,8 @@ void GpuGarbler::mul_dev(GpuGarbler& self, uint64_t layer, const MulPlan& mp, si
 // element o T + t of a Mul over M N T elements: both operands are gathered to one zero label per product (x by
 // MatMulPlan::xidx, y by yidx), mul_core garbles the products under stream_id(layer, 1, o T + t) into the
 // layer's tables (whose rows are output-major with t innermost, as mul_core's are element-major), and each
-// output's T product labels are summed in groups of kMaxTerms.
+// output's T product labels are summed in groups of kMaxTerms. With heads the maps xidx / yidx carry the head's slab
+// offsets and o runs over the G M N head-major outputs; nothing else knows about them.
 void GpuGarbler::matmul_dev(GpuGarbler& self, uint64_t layer, const MatMulPlan& mp, size_t src_idx, CrtLabels& cur,
                             Array& ga, Array& ea) {
     Impl& I = *self.impl_;

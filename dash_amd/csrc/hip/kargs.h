@@ -245,10 +245,13 @@ struct MulArgs {
 // A MatMul layer (gadgets.h MatMulPlan; hardened only): out[i N + l] = sum_t x[i xsi + t xst] * y[t yst + l ysl]
 // over M N outputs per GC. Neither operand's label is read by the multiply: kx / ky hold their compressed labels
 // and cx / cy their colours, [B][k][M T] and [B][k][T N], written once per run by the key pre-pass
-// (launch_label_key). The digits of x come from kx itself.
+// (launch_label_key). The digits of x come from kx itself. With G > 1 heads the operands are G slabs of M T and
+// T N elements and the outputs G slabs of M N, head-major: every array above has G times the elements, and M, T, N
+// and the strides stay per head.
 struct MatMulArgs {
     CrtInfo crt;
     int64_t M, T, N;
+    int64_t G;  // heads, >= 1
     int64_t xsi, xst, yst, ysl;  // the transposes, as strides
     const u128* g;               // [B][M N T][sum] rows (TW_MMG, j) keyed by x, t innermost
     const u128* e;               // [B][M N T][sum] rows (TW_GME, j) keyed by y

@@ -54,31 +54,40 @@ __device__ __forceinline__ void matmul_store(act_t* Y, int64_t No, int n, const 
 // E + colour(y) x - G of every product: p = 2 as bit logic on one 128-bit word in registers (the compressed label
 // of x is its bits), every other residue in the lane's own column of an LDS image of kMmBS-byte rows, one byte
 // per digit, reduced at every step. The finished column is written once. Lanes never read each other's columns:
-// no barrier. grid (ceil(M N / kMmBS), k, B), dynamic LDS a.lds_n * kMmBS bytes.
+// no barrier. grid (ceil(G M N / kMmBS), k, B), dynamic LDS a.lds_n * kMmBS bytes.
+// kHeads (a.G > 1): the lanes run over the flat G M N outputs, a lane derives its head and offsets its operand bases
+// by the head's slabs; a wave may straddle a head boundary. The table row and e0 follow o in both instantiations, and
+// the single-head one compiles as it did before heads existed.
+template <bool kHeads>
 __global__ __launch_bounds__(kMmBS) void k_matmul(MatMulArgs a, Act y, const ModC* mc) {
     extern __shared__ __attribute__((aligned(16))) uint8_t mm_acc[];
     const int j = blockIdx.y, b = blockIdx.z;
     const int tid = static_cast<int>(threadIdx.x);
-    const int64_t No = a.M * a.N;
+    const int64_t Nh = a.M * a.N;  // outputs per head
+    const int64_t No = kHeads ? a.G * Nh : Nh;
     const int64_t o = static_cast<int64_t>(blockIdx.x) * kMmBS + tid;
     if (o >= No) return;
     const int p = a.crt.p[j];
     const ModC m = mc[p];
     const int n = static_cast<int>(m.n);
-    const int64_t i = o / a.N, l = o - i * a.N;
+    const int64_t hg = kHeads ? o / Nh : 0, oh = o - hg * Nh;
+    const int64_t i = oh / a.N, l = oh - i * a.N;
     const int64_t bk = static_cast<int64_t>(b) * a.crt.k + j;
-    const u128* kx = a.kx + bk * (a.M * a.T) + i * a.xsi;
-    const uint16_t* cx = a.cx + bk * (a.M * a.T) + i * a.xsi;
-    const u128* ky = a.ky + bk * (a.T * a.N) + l * a.ysl;
-    const uint16_t* cy = a.cy + bk * (a.T * a.N) + l * a.ysl;
+    const int64_t nx = a.M * a.T, ny = a.T * a.N;  // a head's slabs
+    const int64_t xb = (kHeads ? bk * a.G + hg : bk) * nx + i * a.xsi;
+    const int64_t yb = (kHeads ? bk * a.G + hg : bk) * ny + l * a.ysl;
+    const u128* kx = a.kx + xb;
+    const uint16_t* cx = a.cx + xb;
+    const u128* ky = a.ky + yb;
+    const uint16_t* cy = a.cy + yb;
     const int64_t row = (static_cast<int64_t>(b) * No + o) * a.T * a.crt.sum + a.crt.prefix[j];
     const uint64_t e0 = static_cast<uint64_t>(o) * static_cast<uint64_t>(a.T);
     uint8_t* col = mm_acc + tid;
     u128 W = 0;
-    MatMulOps nx = matmul_ops(a, kx, cx, ky, cy, row, 0);
+    MatMulOps nxt = matmul_ops(a, kx, cx, ky, cy, row, 0);
     for (int64_t t = 0; t < a.T; ++t) {
-        const MatMulOps c = nx;
-        if (t + 1 < a.T) nx = matmul_ops(a, kx, cx, ky, cy, row, t + 1);
+        const MatMulOps c = nxt;
+        if (t + 1 < a.T) nxt = matmul_ops(a, kx, cx, ky, cy, row, t + 1);
         const uint64_t gt = a.gate0 ^ (e0 + static_cast<uint64_t>(t));
         u128 G = c.Graw - hard_pad(c.Kx, gt, tw_sub(kTwMmg, j), 0);
         u128 E = c.Eraw - hard_pad(c.Ky, gt, tw_sub(kTwGme, j), 0);
@@ -122,8 +131,12 @@ __global__ __launch_bounds__(kMmBS) void k_matmul(MatMulArgs a, Act y, const Mod
 // lanes of an output row share one x label's key, colour and digits (the lane form fetches the key and extracts the
 // digits in every one of them), the kMmI lanes of an output column one y label's key and colour. Each lane streams
 // its own output's contiguous table rows and accumulates as the lane form does. Lanes past the tile's edge stage
-// and wait at the barriers but gather, hash and store nothing. grid (tiles, k, B), dynamic LDS
+// and wait at the barriers but gather, hash and store nothing. grid (G tiles-per-head, k, B), dynamic LDS
 // 2 a.lds_n kMmBS + 36 kMmBS bytes.
+// kHeads (a.G > 1): blockIdx.x = head * tiles-per-head + tile, so a tile never spans heads; i0, l0, the edge tests
+// and the staging indices are the head's own, against operand bases offset by the head's slabs, and a tile on a
+// head's edge touches nothing of the next head.
+template <bool kHeads>
 __global__ __launch_bounds__(kMmBS) void k_matmul_b(MatMulArgs a, Act y, const ModC* mc) {
     static_assert(kMmI * kMmL == kMmBS && kMmI * kMmTC == kMmBS && kMmTC * kMmL == kMmBS, "one staged label per lane");
     extern __shared__ __attribute__((aligned(16))) uint8_t mm_lds[];
@@ -139,17 +152,22 @@ __global__ __launch_bounds__(kMmBS) void k_matmul_b(MatMulArgs a, Act y, const M
     uint16_t* cxs = reinterpret_cast<uint16_t*>(kys + kMmBS);
     uint16_t* cys = cxs + kMmBS;
     const int64_t tilesL = (a.N + kMmL - 1) / kMmL;
-    const int64_t i0 = (static_cast<int64_t>(blockIdx.x) / tilesL) * kMmI;
-    const int64_t l0 = (static_cast<int64_t>(blockIdx.x) % tilesL) * kMmL;
+    const int64_t tilesH = kHeads ? ((a.M + kMmI - 1) / kMmI) * tilesL : 0;  // tiles per head
+    const int64_t hg = kHeads ? static_cast<int64_t>(blockIdx.x) / tilesH : 0;
+    const int64_t tile = static_cast<int64_t>(blockIdx.x) - hg * tilesH;
+    const int64_t i0 = (tile / tilesL) * kMmI;
+    const int64_t l0 = (tile % tilesL) * kMmL;
     const int li = tid / kMmL, ll = tid % kMmL;
     const bool live = i0 + li < a.M && l0 + ll < a.N;
-    const int64_t No = a.M * a.N;
-    const int64_t o = live ? (i0 + li) * a.N + l0 + ll : 0;
+    const int64_t No = kHeads ? a.G * a.M * a.N : a.M * a.N;
+    const int64_t o = live ? (hg * a.M + i0 + li) * a.N + l0 + ll : 0;
     const int64_t bk = static_cast<int64_t>(b) * a.crt.k + j;
-    const u128* kx = a.kx + bk * (a.M * a.T);
-    const uint16_t* cx = a.cx + bk * (a.M * a.T);
-    const u128* ky = a.ky + bk * (a.T * a.N);
-    const uint16_t* cy = a.cy + bk * (a.T * a.N);
+    const int64_t xb = (kHeads ? bk * a.G + hg : bk) * (a.M * a.T);
+    const int64_t yb = (kHeads ? bk * a.G + hg : bk) * (a.T * a.N);
+    const u128* kx = a.kx + xb;
+    const uint16_t* cx = a.cx + xb;
+    const u128* ky = a.ky + yb;
+    const uint16_t* cy = a.cy + yb;
     const int64_t row = (static_cast<int64_t>(b) * No + o) * a.T * a.crt.sum + a.crt.prefix[j];
     const uint64_t e0 = static_cast<uint64_t>(o) * static_cast<uint64_t>(a.T);
     const int sxi = tid / kMmTC, sxt = tid % kMmTC;  // this lane stages x[i0 + sxi, t0 + sxt]
@@ -227,24 +245,31 @@ __global__ __launch_bounds__(kMmBS) void k_matmul_b(MatMulArgs a, Act y, const M
 }
 
 void launch_matmul(const MatMulArgs& a, const Act& y, int B, const ModC* mc, hipStream_t st) {
-    const int64_t No = a.M * a.N;
+    const int64_t No = a.G * a.M * a.N;
+    const bool heads = a.G > 1;
     if (a.blocked) {
-        const int64_t tiles = ((a.M + kMmI - 1) / kMmI) * ((a.N + kMmL - 1) / kMmL);
+        const int64_t tiles = a.G * ((a.M + kMmI - 1) / kMmI) * ((a.N + kMmL - 1) / kMmL);
         const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(a.crt.k), static_cast<unsigned>(B));
         if (launch_log_on()) launch_log_add("matmul.blocked", grid, dim3(kMmBS));
         // 49 KiB at k = 7: above the default dynamic LDS limit of a kernel (raised once, as for the staged chain)
         static const bool raised = [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_matmul_b),
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_matmul_b<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10) == hipSuccess &&
+                   hipFuncSetAttribute(reinterpret_cast<const void*>(&k_matmul_b<true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10) == hipSuccess;
         }();
         (void)raised;
-        hipLaunchKernelGGL(k_matmul_b, grid, dim3(kMmBS), (2 * static_cast<size_t>(a.lds_n) + 36) * kMmBS, st, a, y, mc);
+        const size_t lds = (2 * static_cast<size_t>(a.lds_n) + 36) * kMmBS;
+        if (heads) hipLaunchKernelGGL(k_matmul_b<true>, grid, dim3(kMmBS), lds, st, a, y, mc);
+        else hipLaunchKernelGGL(k_matmul_b<false>, grid, dim3(kMmBS), lds, st, a, y, mc);
         return;
     }
     const dim3 grid(static_cast<unsigned>((No + kMmBS - 1) / kMmBS), static_cast<unsigned>(a.crt.k),
                     static_cast<unsigned>(B));
     if (launch_log_on()) launch_log_add("matmul.lane", grid, dim3(kMmBS));
-    hipLaunchKernelGGL(k_matmul, grid, dim3(kMmBS), static_cast<size_t>(a.lds_n) * kMmBS, st, a, y, mc);
+    const size_t lds = static_cast<size_t>(a.lds_n) * kMmBS;
+    if (heads) hipLaunchKernelGGL(k_matmul<true>, grid, dim3(kMmBS), lds, st, a, y, mc);
+    else hipLaunchKernelGGL(k_matmul<false>, grid, dim3(kMmBS), lds, st, a, y, mc);
 }
 
 }  // namespace dev

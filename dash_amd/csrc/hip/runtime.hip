@@ -673,7 +673,7 @@ class HipEvaluator {
                 return N;
             }
             case K_MULT: case K_MMULT: return N_in / 2;
-            case K_MATMUL: return l.param("M") * l.param("N");
+            case K_MATMUL: return l.param("G", 1) * l.param("M") * l.param("N");
             default: return N_in;
         }
     }
@@ -720,13 +720,13 @@ class HipEvaluator {
         for (int i = 0; i < mmax; ++i)
             if (!kpwl_[i]) kpwl_[i] = dalloc<u128>(static_cast<size_t>(B_) * w.caps.maxSignN);
     }
-    // a MatMul's operand keys and colours ([B][k][M T] and [B][k][T N]): sized by the model's largest operands
+    // a MatMul's operand keys and colours ([B][k][G M T] and [B][k][G T N]): sized by the model's largest operands
     void ensure_matmul() {
         i64 nx = 0, ny = 0;
         for (const GLayer& l : tmpl_->layers)
             if (l.kind == K_MATMUL) {
-                nx = std::max(nx, l.param("M") * l.param("T"));
-                ny = std::max(ny, l.param("T") * l.param("N"));
+                nx = std::max(nx, l.param("G", 1) * l.param("M") * l.param("T"));
+                ny = std::max(ny, l.param("G", 1) * l.param("T") * l.param("N"));
             }
         if (!mm_kx_) {
             mm_kx_ = dalloc<u128>(static_cast<size_t>(B_) * k_ * nx);
@@ -2157,13 +2157,15 @@ void HipEvaluator::plan_mul(Walk& w, size_t li, const GLayer& g, const std::stri
     set_out(w, g, w.N, w.nxt());
 }
 
-// gadgets.h MatMulPlan: x = the current activation (M x T), y = the saved copy of layer src's output (T x N), read
-// in place as plan_mul reads it; a src that is the layer's own input reads the current activation. The key
-// pre-pass compresses every element of both operands once; the contraction reads only the keys and colours.
+// gadgets.h MatMulPlan: x = the current activation (M x T), y = the saved copy of layer src's output (T x N), each G
+// head slabs of that shape, read in place as plan_mul reads it; a src that is the layer's own input reads the current
+// activation. The key pre-pass compresses every element of both operands once; the contraction reads only the keys
+// and colours.
 void HipEvaluator::plan_matmul(Walk& w, size_t li, const GLayer& g, const std::string& lname) {
     DASH_CHECK(hard_, "the MatMul layer exists in the hardened encoding only");
     DASH_CHECK(w.mods == crt_, "matmul: the input is not on the CRT base");
-    const MatMulPlan mp(crt_, g.param("M"), g.param("T"), g.param("N"), g.param("ta", 0) != 0, g.param("tb", 0) != 0);
+    const MatMulPlan mp(crt_, g.param("M"), g.param("T"), g.param("N"), g.param("ta", 0) != 0, g.param("tb", 0) != 0,
+                        g.param("G", 1));
     const i64 src = g.param("src");
     DASH_CHECK(src >= -1 && src < static_cast<i64>(li) && !saved_[src + 1].empty(), "matmul: operand not saved");
     DASH_CHECK(w.saved_mods[src + 1] == crt_, "matmul: the operand is not on the CRT base");
@@ -2178,6 +2180,7 @@ void HipEvaluator::plan_matmul(Walk& w, size_t li, const GLayer& g, const std::s
     a.M = mp.M;
     a.T = mp.T;
     a.N = mp.N;
+    a.G = mp.G;
     a.xsi = mp.xsi;
     a.xst = mp.xst;
     a.yst = mp.yst;
@@ -2200,8 +2203,18 @@ void HipEvaluator::plan_matmul(Walk& w, size_t li, const GLayer& g, const std::s
     }
     ys.N = mp.ny();
     // The grid rule: the blocked form where at least one kMmI x kMmL tile is full, else the lane form (a tile of a
-    // thinner product would be mostly idle lanes). DASH_MATMUL_FORM=lane|blocked overrides it (A/B runs).
+    // thinner product would be mostly idle lanes). It is taken per head: a tile never spans heads, so M and N here
+    // are a head's. DASH_MATMUL_FORM=lane|blocked overrides it (A/B runs).
     a.blocked = mp.M >= kMmI && mp.N >= kMmL;
+    // Heads whose tiles are half full in M (kMmI / 2 <= M < kMmI, N >= kMmL) also take the blocked form while the
+    // lane form's grid would leave the device partly filled: at least one block per CU, fewer than the 5 a CU holds
+    // (5 waves per SIMD, 4 SIMDs, 4 waves per block). There the idle half of a tile costs nothing and a lane's shared
+    // x digits win (docs/MATMUL.md, Heads: (4, 8, 16, 16) against (4, 8, 64, 64)); with fewer blocks than CUs
+    // nothing was measured and the per-head rule stands.
+    if (mp.G > 1 && !a.blocked && 2 * mp.M >= kMmI && mp.N >= kMmL) {
+        const i64 lane_blocks = (mp.nout() + 255) / 256 * k_ * B_;
+        a.blocked = lane_blocks >= num_cus() && lane_blocks < 5 * static_cast<i64>(num_cus());
+    }
     if (const char* f = std::getenv("DASH_MATMUL_FORM")) {
         if (std::string(f) == "lane") a.blocked = 0;
         if (std::string(f) == "blocked") a.blocked = 1;

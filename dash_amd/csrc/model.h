@@ -40,7 +40,7 @@ enum Kind : int {
     K_MUL = 19,  // params src, bc (broadcast only), sq (square only); arrays g, e (product) or t (square)
     K_LEAKY = 20,  // params s, n (one or one per channel), bc; arrays and smode exactly a K_RELU's
     K_PWL = 21,  // params s, T, A, V, fn; smode 0 | 1; per kept breakpoint i arrays b<i>.mrs | b<i>.s.*, b<i>.mm.g, b<i>.mm.e
-    K_MATMUL = 22,  // params src, M, T, N, ta / tb (only when set); arrays g, e [M N T][P]
+    K_MATMUL = 22,  // params src, M, T, N, ta / tb, G (heads; only when set / above 1); arrays g, e [G M N T][P]
 };
 const char* kind_name(int kind);
 

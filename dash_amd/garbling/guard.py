@@ -291,18 +291,19 @@ class RangeGuard:
                 bad |= big
                 out = torch.where(big[:, None], 0, inp) * y
             elif isinstance(l, L.MatMul):
-                a = inp.reshape((B,) + L._as_matrix(l.in_dims))
-                y = ctx[l.src + 1].reshape((B,) + L._as_matrix(l.src_dims))
-                a = a.transpose(1, 2) if l.trans_a else a
-                y = y.transpose(1, 2) if l.trans_b else y
+                # per head: [B][G][M][T] and [B][G][T][N] (G = 1 for the single contraction)
+                a = inp.reshape((B, l.heads) + L._head_matrix(l.in_dims, l.heads))
+                y = ctx[l.src + 1].reshape((B, l.heads) + L._head_matrix(l.src_dims, l.heads))
+                a = a.transpose(2, 3) if l.trans_a else a
+                y = y.transpose(2, 3) if l.trans_b else y
                 # T max|x| max|y| >= 2^62 in exact integers: ax > floor(floor((2^62 - 1) / T) / ay). Such inputs are
                 # flagged (the numpy model raises OverflowError) and their x zeroed so nothing wraps
-                ax, ay = inp.abs().amax(dim=1), y.abs().amax(dim=(1, 2))
+                ax, ay = inp.abs().amax(dim=1), y.abs().amax(dim=(1, 2, 3))
                 big = (ay > 0) & (ax > torch.div(((1 << 62) - 1) // l.T, ay.clamp_min(1), rounding_mode="floor"))
                 bad |= big
-                a = torch.where(big[:, None, None], 0, a)
+                a = torch.where(big[:, None, None, None], 0, a)
                 # an int64 matmul does not exist on the GPU: a broadcast multiply and an integer sum over t
-                out = (a[:, :, :, None] * y[:, None, :, :]).sum(dim=2).reshape(B, -1)
+                out = (a[:, :, :, :, None] * y[:, :, None, :, :]).sum(dim=3).reshape(B, -1)
             elif isinstance(l, L.Concat):
                 out = torch.cat([ctx[s + 1].reshape(B, -1) for s in l.srcs], dim=1)
             else:  # Flatten, Projection, BaseExtension: value-preserving

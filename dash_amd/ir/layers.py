@@ -1240,6 +1240,19 @@ def _as_matrix(d: Sequence[int]) -> tuple[int, int]:
     return (1, d[0]) if len(d) == 1 else (d[0], _size(d[1:]))
 
 
+def _head_matrix(d: Sequence[int], heads: int) -> tuple[int, int]:
+    """One head's matrix of a tensor of dims d split into `heads` contiguous slabs along its leading axis: slab
+    dims (d[0] // heads, *d[1:]), read by _as_matrix."""
+    d = tuple(int(v) for v in d)
+    if heads == 1:
+        return _as_matrix(d)
+    if len(d) < 2:
+        raise ValueError(f"matmul: a 1-D operand of dims {d} cannot be split into {heads} heads")
+    if d[0] % heads:
+        raise ValueError(f"matmul: the leading axis of dims {d} does not split into {heads} heads")
+    return _as_matrix((d[0] // heads,) + d[1:])
+
+
 class MatMul(Layer):
     """Contraction of two secret tensors: out[i, l] = sum_t x[i, t] * y[t, l].
     x is the layer's input, y the output of layer `src` (-1 = circuit input), as
@@ -1251,40 +1264,55 @@ class MatMul(Layer):
     garbled as the general product. Scale-free: whoever builds the circuit puts
     the scheme's rescale behind it, as after a Mul. Garbled as T generalized half
     gates per output element and residue, summed (csrc/gadgets.h MatMulPlan);
-    hardened encoding only."""
+    hardened encoding only.
+    `heads` = G > 1 contracts G independent matrix pairs: both operands split
+    along their leading axis (dims[0] % G == 0) into G contiguous slabs of dims
+    (dims[0] // G, *dims[1:]), each read as a matrix and transposed as above, and
+    out[g, i, l] = sum_t x_g[i, t] * y_g[t, l], flat head-major, default dims
+    (G M, N). M, T, N are per head. G = 1 is the single contraction."""
 
     kind = Kind.MATMUL
     name = "matmul"
 
-    def __init__(self, dims, src: int, src_dims, trans_a: bool = False, trans_b: bool = False, out_dims=None):
+    def __init__(self, dims, src: int, src_dims, trans_a: bool = False, trans_b: bool = False, out_dims=None,
+                 heads: int = 1):
         dims = tuple(int(d) for d in dims)
         sd = tuple(int(d) for d in src_dims)
         self.trans_a, self.trans_b = bool(trans_a), bool(trans_b)
-        xr, xc = _as_matrix(dims)
-        yr, yc = _as_matrix(sd)
+        G = int(heads)
+        if G < 1:
+            raise ValueError(f"matmul: heads = {heads} of dims {dims} and {sd}: at least one head")
+        xr, xc = _head_matrix(dims, G)
+        yr, yc = _head_matrix(sd, G)
         M, T = (xc, xr) if self.trans_a else (xr, xc)
         T2, N = (yc, yr) if self.trans_b else (yr, yc)
+        per = " per head" if G > 1 else ""
         if T != T2:
             raise ValueError(f"matmul: x of dims {dims} is {M} x {T}{' (transposed)' if self.trans_a else ''} and y of "
-                             f"dims {sd} is {T2} x {N}{' (transposed)' if self.trans_b else ''}: the inner sizes differ")
-        od = (M, N) if out_dims is None else tuple(int(d) for d in out_dims)
-        if _size(od) != M * N:
-            raise ValueError(f"matmul: out_dims {od} do not hold the {M} x {N} product of dims {dims} and {sd}")
+                             f"dims {sd} is {T2} x {N}{' (transposed)' if self.trans_b else ''}{per}: the inner sizes "
+                             f"differ")
+        od = (G * M, N) if out_dims is None else tuple(int(d) for d in out_dims)
+        if _size(od) != G * M * N:
+            raise ValueError(f"matmul: out_dims {od} do not hold the {M} x {N} product{per} of dims {dims} and {sd}"
+                             f"{f' in {G} heads' if G > 1 else ''}")
         super().__init__(dims, od)
         self.src_dims = sd
         self.src = int(src)
+        self.heads = G
         self.M, self.T, self.N = M, T, N
 
     def _views(self, x, ctx, dtype):
-        x = np.asarray(x, dtype=dtype).reshape(_as_matrix(self.in_dims))
+        """The operands as [G][M][T] and [G][T][N]."""
+        G = self.heads
+        x = np.asarray(x, dtype=dtype).reshape((G,) + _head_matrix(self.in_dims, G))
         y = np.asarray(ctx[self.src + 1], dtype=dtype).reshape(-1)
         assert y.size == _size(self.src_dims), "matmul operand size mismatch"
-        y = y.reshape(_as_matrix(self.src_dims))
-        return (x.T if self.trans_a else x), (y.T if self.trans_b else y)
+        y = y.reshape((G,) + _head_matrix(self.src_dims, G))
+        return (x.transpose(0, 2, 1) if self.trans_a else x), (y.transpose(0, 2, 1) if self.trans_b else y)
 
     def plain_eval(self, x, track=True, ctx=None):
         a, b = self._views(x, ctx, np.float32)
-        out = (a @ b).astype(np.float32).reshape(-1)
+        out = np.stack([a[g] @ b[g] for g in range(self.heads)]).astype(np.float32).reshape(-1)
         if track:
             self._track_f(out)
         return out
@@ -1296,7 +1324,7 @@ class MatMul(Layer):
             ay = max(abs(int(b.min())), abs(int(b.max())))
             if self.T * ax * ay >= 1 << 62:
                 raise OverflowError(f"matmul: {self.T} products of operands up to {ax} and {ay} do not fit 62 bits")
-        out = (a[:, :, None] * b[None, :, :]).sum(axis=1, dtype=np.int64).reshape(-1)
+        out = (a[:, :, :, None] * b[:, None, :, :]).sum(axis=2, dtype=np.int64).reshape(-1)
         if track:
             self._track_q(a, b, out)
         return out
@@ -1307,11 +1335,13 @@ class MatMul(Layer):
             p["ta"] = 1
         if self.trans_b:
             p["tb"] = 1
+        if self.heads > 1:
+            p["G"] = self.heads
         return self.kind, p
 
     def __repr__(self) -> str:
         return (f"MatMul({self.in_dims}, src={self.src}, src_dims={self.src_dims}, trans_a={self.trans_a}, "
-                f"trans_b={self.trans_b}, out_dims={self.out_dims})")
+                f"trans_b={self.trans_b}, out_dims={self.out_dims}{f', heads={self.heads}' if self.heads > 1 else ''})")
 
 
 # ---- test-only layers (reference: projection.h, mult_layer.h, mixed_mod_mult_layer.h, max.h, base_extension.h)

@@ -67,9 +67,23 @@ under new dims (the flat layout already is that matrix), and so is the only
 `Reshape` of the node's result, e.g. back to `(C, H, W)`; every other `Reshape`
 flattens as before. A `Transpose` that swaps the last two axes and feeds only
 such nodes folds into `trans_a` / `trans_b`; any other `Transpose` is refused
-with its name. An operand of higher rank (a batch of matrices, heads), or one
-with a pending average factor or pending scale bits, is refused with the node's
-name. A `MatMul` / `Gemm` with an initializer operand is a `Dense`, as before.
+with its name. An operand with a pending average factor or pending scale bits
+is refused with the node's name. A `MatMul` / `Gemm` with an initializer
+operand is a `Dense`, as before.
+
+Heads. An operand of rank 3 behind the batch axis, `(h, a, b)`, is `h` head
+slabs of the flat tensor and is accepted where it is such a `Reshape` alias
+(e.g. a channel-major `(C, H, W)` tensor viewed as `(h, C / h, H W)`) or a
+multi-head `MatMul` result as it stands (also behind a Relu, LeakyRelu, PRelu
+or Clip), and the other operand has the same
+`h`: the tensor is tracked as dims `(h a, b)` and the layer gets `heads = h`.
+A `Transpose` with perm `[0, 1, 3, 2]` folds into the flags; the only `Reshape`
+of the `(h, M, N)` result gives `out_dims`. This is what a channel-major
+PyTorch attention exports (1x1 convs, `.view(N, h, dh, L)`,
+`transpose(-1, -2)`, `matmul`), and it moves no data. Different head counts, a
+rank-3 operand that is neither kind, rank above 3 and a `Transpose` that moves
+the head axis (token-major exports) are refused with the node's name. The
+export writes this form for `heads > 1`.
 
 `ReduceSum` over (2, 3) is the plane `SumPool2d` itself (the exporter writes a
 global sum pool that no linear layer follows this way).
@@ -130,7 +144,8 @@ import numpy as np
 from ..native import native
 from .circuit import Circuit
 from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MatMul, MaxPool2d, Mul,
-                     PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _as_matrix, _convt_check, _pool_out)
+                     PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _as_matrix, _convt_check, _head_matrix,
+                     _pool_out)
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -266,6 +281,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
         nodes[m]["outputs"][0] == n["inputs"][0] and uses_of(n["inputs"][0]) == [k] for m in secret_mm)}
     tr_of: dict[str, str] = {}    # a folded Transpose's output -> its input
     vdims: dict[str, tuple] = {}  # a matrix-view Reshape's output -> its dims (the tensor itself is an alias)
+    mheads: dict[str, int] = {}   # a multi-head MatMul's result (tracked as dims (h M, N)) -> h
 
     def view_shape(node, size: int) -> tuple:
         """The target of a Reshape without its batch axis, 0 and -1 resolved against `size` elements."""
@@ -330,6 +346,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             alias[outs[0]] = res(ins[0])
             continue
         eb = bits(ins[0]) if ins else 0  # the data input's pending scale bits
+        if op in ("Relu", "LeakyRelu", "PRelu", "Clip") and ins and res(ins[0]) in mheads:
+            mheads[outs[0]] = mheads[res(ins[0])]  # an elementwise activation keeps the heads' slabs
         if op == "Reshape" and (ni in mm_feed or ni in mm_back):
             j, dims, fac = data_in(node, ins[0])
             shp = view_shape(node, int(np.prod(dims)))
@@ -337,7 +355,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             if ni in mm_back:  # the product continues under these dims, e.g. (C, H, W)
                 specs[j].kw["out_dims"] = shp
                 tdims[res(ins[0])] = shp
-            else:
+                mheads.pop(res(ins[0]), None)
+            if ni in mm_feed:
                 vdims[outs[0]] = shp
         elif op == "Transpose" and ni in fold_tr:
             data_in(node, ins[0])
@@ -351,29 +370,46 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             if op == "Gemm" and (float(a.get("alpha", 1.0)) != 1.0 or (len(ins) > 2 and ins[2])):
                 raise NotImplementedError(f"onnx: {name}: a Gemm of two produced tensors is supported with alpha = 1 "
                                           "and no C only")
-            flags, opnd = [], []
+            flags, opnd, heads = [], [], []
             for pos, key in ((0, "transA"), (1, "transB")):
                 nm, t = ins[pos], bool(int(a.get(key, 0))) if op == "Gemm" else False
                 if nm in tr_of:
                     nm, t = tr_of[nm], not t
                 j, dims, fac = data_in(node, nm)
-                dims = vdims.get(nm, dims)
-                if len(dims) > 2:
+                h = 1
+                if nm in vdims:
+                    # a Reshape alias: (r, c), or (h, a, b) = h head slabs, tracked as dims (h a, b) with heads = h
+                    dims = vdims[nm]
+                    if len(dims) > 3:
+                        raise NotImplementedError(f"onnx: {name}: operand {pos} has dims {tuple(dims)} behind the batch "
+                                                  "axis: rank above 3 (more than one axis of heads) is not supported")
+                    if len(dims) == 3:
+                        h, dims = int(dims[0]), (int(dims[0]) * int(dims[1]), int(dims[2]))
+                elif res(nm) in mheads:  # a multi-head MatMul's result as it stands, (h, M, N)
+                    h = mheads[res(nm)]
+                elif len(dims) > 2:
                     raise NotImplementedError(f"onnx: {name}: operand {pos} has dims {tuple(dims)} behind the batch "
-                                              "axis: a batch of more than one matrix per operand (heads) is not "
-                                              "supported; Reshape a (C, H, W) tensor to (C, H W) first")
+                                              "axis: a batch of more than one matrix per operand (heads) is accepted "
+                                              "only as a Reshape alias (h, a, b) or a MatMul result; Reshape a "
+                                              "(C, H, W) tensor to (C, H W), or to (h, C / h, H W) for h heads, first")
+                heads.append(h)
                 if fac != 1.0 or bits(nm):
                     raise NotImplementedError(f"onnx: {name}: operand {pos} carries a pending average factor or pending "
                                               f"scale bits ({fac:g}, 2^{bits(nm)}) that no Conv/Gemm absorbed")
                 flags.append(t)
                 opnd.append((j, tuple(dims)))
             (jx, dx), (jy, dy) = opnd
+            if heads[0] != heads[1]:
+                raise NotImplementedError(f"onnx: {name}: the operands have different head counts ({heads[0]} and "
+                                          f"{heads[1]}); both must be (h, a, b) with the same h")
             try:
-                probe = MatMul(dx, 0, dy, flags[0], flags[1])
+                probe = MatMul(dx, 0, dy, flags[0], flags[1], heads=heads[0])
             except ValueError as ex:
                 raise ValueError(f"onnx: {name}: {ex}") from None
-            emit(_Spec("matmul", dims=dx, src=jy, src_dims=dy, ta=flags[0], tb=flags[1], out_dims=None), outs[0], jx,
-                 probe.out_dims)
+            emit(_Spec("matmul", dims=dx, src=jy, src_dims=dy, ta=flags[0], tb=flags[1], out_dims=None, heads=heads[0]),
+                 outs[0], jx, probe.out_dims)
+            if heads[0] > 1:
+                mheads[outs[0]] = heads[0]
         elif op == "Flatten" or op == "Reshape":
             j, dims, fac = data_in(node, ins[0])
             if op == "Reshape" and len(dims) == 1:
@@ -814,7 +850,7 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                           Mul(kw["dims"], spec_to_layer[kw["src"]], kw["src_dims"]))
         elif s.kind == "matmul":
             layers.append(MatMul(kw["dims"], spec_to_layer[kw["src"]], kw["src_dims"], kw["ta"], kw["tb"],
-                                 kw["out_dims"]))
+                                 kw["out_dims"], heads=kw["heads"]))
         if kw.get("in_src") is not None:
             layers[-1].in_src = spec_to_layer[kw["in_src"]]
         spec_to_layer[i] = len(layers) - 1
@@ -1034,18 +1070,22 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             if K != 1 or scale[names[l.src]] != 1:
                 raise NotImplementedError(f"onnx export: the average before layer {i} ({l.name}) has no linear layer "
                                           "to fold its window size into")
+            # With heads the operands are reshaped to (1, h, a, b), the Transpose swaps the last two of four axes and
+            # the rank-4 result is always reshaped to the layer's out_dims.
             opnds = []
+            G = l.heads
             for tag, tname, d_, tr in (("a", cur, l.in_dims, l.trans_a), ("b", names[l.src], l.src_dims, l.trans_b)):
-                if len(d_) != 2:
-                    inits.append(_tensor_i64(f"{name}.{tag}.shape", (1,) + _as_matrix(d_)))
+                if len(d_) != 2 or G > 1:
+                    shp = (1, G) + _head_matrix(d_, G) if G > 1 else (1,) + _as_matrix(d_)
+                    inits.append(_tensor_i64(f"{name}.{tag}.shape", shp))
                     nodes.append(_node("Reshape", [tname, f"{name}.{tag}.shape"], [f"{name}.{tag}.m"], f"{name}.{tag}.reshape"))
                     tname = f"{name}.{tag}.m"
                 if tr:
                     nodes.append(_node("Transpose", [tname], [f"{name}.{tag}.t"], f"{name}.{tag}.transpose",
-                                       _attr_ints("perm", [0, 2, 1])))
+                                       _attr_ints("perm", [0, 1, 3, 2] if G > 1 else [0, 2, 1])))
                     tname = f"{name}.{tag}.t"
                 opnds.append(tname)
-            if l.out_dims == (l.M, l.N):
+            if G == 1 and l.out_dims == (l.M, l.N):
                 nodes.append(_node("MatMul", opnds, [out], name))
             else:
                 inits.append(_tensor_i64(f"{name}.shape", (1,) + l.out_dims))

@@ -126,6 +126,9 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
         elif k == "nonlocal":
             raise NotImplementedError(f"training: op {k} (a non-local block reads its input four times) not supported "
                                       "by the sequential trainer")
+        elif k == "attention":
+            raise NotImplementedError(f"training: op {k} (an attention block reads its input four times) not supported "
+                                      "by the sequential trainer")
         elif k == "relu6":
             mods.append(nn.ReLU6())
         elif k == "clip":

@@ -48,6 +48,12 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   rescale), f = MatMul(theta^T, phi) of dims (H W, H W) + rescale, y = MatMul(g, f^T) of dims
 #                   (C / r, H, W) + rescale, a 1x1 conv back to C whose weights carry the 1 / (H W), and the Add of
 #                   the block's input (docs/MATMUL.md)
+#                   | ("attention", heads) softmax-free multi-head attention, relu(Q K^T / sqrt(dh)) / L V (Wortsman et
+#                   al. 2023), on a (C, H, W) tensor with heads | C and L = H W <= 64: 1x1 convs k, v, q to C channels
+#                   (each + the scheme's rescale; q's weights carry 1 / sqrt(dh), dh = C / heads), the scores
+#                   S = MatMul(q^T, k) per head of dims (heads L, L) + rescale + ReLU, the mix O = MatMul(v, S^T) per
+#                   head of dims (C, H, W) + rescale, a 1x1 conv back to C whose weights carry the 1 / L, and the Add
+#                   of the block's input (docs/MATMUL.md, Heads)
 #                   | ("sigmoid",) | ("tanh",) | ("hsigmoid", alpha, beta) piecewise-linear activations
 #                   (PiecewiseLinear.sigmoid / .tanh / .hard_sigmoid, slope bits pwl_bits): ScaleQuant only, no
 #                   pending scale on their input; the output's 2^pwl_bits travels like a leaky ReLU's (docs/PWL.md)
@@ -113,6 +119,11 @@ ARCHS: dict[str, dict] = {
     # (64, 16, 64) contraction, y a (16, 64, 64) one
     "NONLOCAL_CIFAR": {"input": (3, 32, 32), "ops": [
         ("conv", 16, 3, 1, 1), ("relu",), ("maxpool", 2, 2), ("conv", 32, 3, 2, 1), ("relu",), ("nonlocal", 2),
+        ("relu",), ("gap",), ("flatten",), ("fc", 10)]},
+    # a small CIFAR net with one 4-head ReLU-attention block on its 4 x 4 stage of 32 channels (dh = 8, L = 16): the
+    # scores are a (16, 8, 16) contraction per head (the blocked kernel form), the mix an (8, 16, 16) one (the lane form)
+    "RELU_ATTN_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 2, 1), ("relu",), ("conv", 32, 3, 2, 1), ("relu",), ("maxpool", 2, 2), ("attention", 4),
         ("relu",), ("gap",), ("flatten",), ("fc", 10)]},
     # MOBILENET_CIFAR with a squeeze-and-excitation gate (reduction 4) behind every pointwise conv
     "SE_MOBILENET_CIFAR": {"input": (3, 32, 32), "ops": [
@@ -371,6 +382,38 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             layers.append(y)
             rescale_after(d_e)
             conv(cin, 1, 1, 0, cr, h, w, wscale=1.0 / (h * w))  # the normaliser 1 / N rides on the weights
+            layers.append(Add(dims, src))
+        elif kind == "attention":
+            nh = int(op[1])
+            if len(dims) != 3 or nh < 1 or dims[0] % nh:
+                raise ValueError(f"{name}: op {len(layers)} (attention): needs a (C, H, W) tensor whose channels "
+                                 f"{nh} heads divide, got {dims}")
+            cin, h, w = dims
+            L_ = h * w
+            if L_ > 64:
+                raise ValueError(f"{name}: op {len(layers)} (attention): the scores have heads (H W)^2 entries of C / "
+                                 f"heads products each; pool first so that H W <= 64, got {h} x {w}")
+            src, dh = len(layers) - 1, cin // nh
+            conv(cin, 1, 1, 0, cin, h, w)  # k reads the previous layer
+            k_out = len(layers) - 1
+            first = len(layers)
+            conv(cin, 1, 1, 0, cin, h, w)
+            layers[first].in_src = src
+            v_out = len(layers) - 1
+            first = len(layers)
+            conv(cin, 1, 1, 0, cin, h, w, wscale=1.0 / np.sqrt(dh))  # q carries the 1 / sqrt(dh)
+            layers[first].in_src = src
+            # S_g = q_g^T k_g, (L, L) per head: row = query token, column = key token
+            sc = MatMul(dims, k_out, dims, trans_a=True, heads=nh, out_dims=(nh * L_, L_))
+            layers.append(sc)
+            rescale_after(sc.out_dims)
+            layers.append(Relu(sc.out_dims))
+            # O_g = v_g S_g^T, (dh, L) per head, back to (C, H, W)
+            mix = MatMul(dims, len(layers) - 1, sc.out_dims, trans_b=True, heads=nh, out_dims=dims)
+            mix.in_src = v_out
+            layers.append(mix)
+            rescale_after(dims)
+            conv(cin, 1, 1, 0, cin, h, w, wscale=1.0 / L_)  # the normaliser 1 / L rides on the weights
             layers.append(Add(dims, src))
         elif kind == "argmax":
             am = ArgMax(dims)
