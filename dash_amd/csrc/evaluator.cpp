@@ -316,6 +316,19 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 cur = std::move(nxt);
                 break;
             }
+            case K_GATHER: {
+                // active labels moved by the public map, on whatever moduli the walk carries here
+                const GatherGeom G(g.p, Nin);
+                CrtLabels nxt;
+                for (size_t j = 0; j < cur.size(); ++j) {
+                    Labels O(cur[j].p, G.out_size());
+                    for (i64 o = 0; o < G.out_size(); ++o)
+                        std::memcpy(O.at(o), cur[j].at(G.src(o)), sizeof(comp_t) * O.n);
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
+                break;
+            }
             case K_RELU:
             case K_LEAKY: {
                 if (trace) trace->relu_in[li] = cur;

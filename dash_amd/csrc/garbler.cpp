@@ -43,6 +43,7 @@ const char* kind_name(int kind) {
         case K_PWL: return "pwl";
         case K_CONVT: return "conv_transpose2d";
         case K_UPSAMPLE: return "upsample";
+        case K_GATHER: return "gather";
     }
     return "unknown";
 }
@@ -140,6 +141,21 @@ UpGeom::UpGeom(const Params& p) {
     fh = param1(p, "fh");
     fw = param1(p, "fw");
     DASH_CHECK(C > 0 && H > 0 && W > 0 && fh >= 1 && fw >= 1 && fh * fw > 1, "bad upsample geometry");
+}
+
+GatherGeom::GatherGeom(const Params& p, i64 Nin) : idx(&paramv(p, "idx")), od(&paramv(p, "od")) {
+    DASH_CHECK(!idx->empty() && idx->size() < (size_t(1) << 31) && Nin > 0 && Nin < (i64(1) << 31),
+               "gather: sizes must lie in [1, 2^31)");
+    i64 n = 1;
+    for (i64 d : *od) {
+        DASH_CHECK(d > 0, "gather: bad output dims");
+        n *= d;
+    }
+    DASH_CHECK(n == out_size(), "gather: output dims do not match the index map");
+    for (size_t o = 0; o < idx->size(); ++o)
+        DASH_CHECK((*idx)[o] >= 0 && (*idx)[o] < Nin,
+                   "gather: index " + std::to_string((*idx)[o]) + " at position " + std::to_string(o) +
+                       " lies outside the input of " + std::to_string(Nin));
 }
 
 PoolGeom::PoolGeom(const Params& p) {
@@ -753,7 +769,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         // is present (the legacy rescale's sign base extension needs residue 0 = 2)
         const bool lin_kind = spec.kind == K_CONV || spec.kind == K_DENSE || spec.kind == K_SUMPOOL ||
                               spec.kind == K_ADD || spec.kind == K_CONCAT || spec.kind == K_CONVT ||
-                              spec.kind == K_UPSAMPLE;
+                              spec.kind == K_UPSAMPLE || spec.kind == K_GATHER;
         const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
                                     (spec.kind == K_RELU || spec.kind == K_SIGN || spec.kind == K_LEAKY ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
@@ -984,6 +1000,24 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                 }
                 CrtLabels nxt;
                 for (int j = 0; j < k; ++j) {
+                    Labels O(cur[j].p, G.out_size());
+                    for (i64 o = 0; o < G.out_size(); ++o)
+                        std::memcpy(O.at(o), cur[j].at(G.src(o)), sizeof(comp_t) * O.n);
+                    nxt.push_back(std::move(O));
+                }
+                cur = std::move(nxt);
+                break;
+            }
+            case K_GATHER: {
+                // free in the label domain: the zero labels moved by the public map (any moduli)
+                const GatherGeom G(spec.p, Nin);
+                dims = *G.od;
+                if (on_gpu) {
+                    gpu->gather(*G.idx, cur);
+                    break;
+                }
+                CrtLabels nxt;
+                for (size_t j = 0; j < cur.size(); ++j) {
                     Labels O(cur[j].p, G.out_size());
                     for (i64 o = 0; o < G.out_size(); ++o)
                         std::memcpy(O.at(o), cur[j].at(G.src(o)), sizeof(comp_t) * O.n);

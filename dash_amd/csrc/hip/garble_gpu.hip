@@ -3032,6 +3032,7 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     leaky_map_hook() = &GpuGarbler::leaky_map_dev;
     convt_hook() = &GpuGarbler::convt_dev;
     upsample_hook() = &GpuGarbler::upsample_dev;
+    gather_hook() = &GpuGarbler::gather_dev;
     Impl& I = *impl_;
     I.enter();
     I.c.hard = hardened ? 1 : 0;
@@ -4821,6 +4822,27 @@ void GpuGarbler::upsample_dev(GpuGarbler& self, const UpGeom& G, CrtLabels& cur)
     const int64_t Nout = G.out_size();
     std::vector<int32_t> map(static_cast<size_t>(Nout));
     for (int64_t o = 0; o < Nout; ++o) map[static_cast<size_t>(o)] = static_cast<int32_t>(G.src(o));
+    std::vector<DevBlock> y = I.alloc_labels(I.cur_mod, Nout);
+    launch_gsum(I.c, y, I.cur, I.cur_mod, Nout, I.cur_N, gg::dconst(map.data(), map.size()), 1, false,
+                [](int, int) { return 1; });
+    HIPCHECK(hipGetLastError());
+    I.cur = std::move(y);
+    I.cur_N = Nout;
+    set_stale(cur, I.cur_mod, Nout);
+}
+
+// Gather (garbler.cpp K_GATHER): cur = the device cur moved by the public map, upsample_dev's route
+void GpuGarbler::gather_dev(GpuGarbler& self, const std::vector<i64>& idx, CrtLabels& cur) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("gather");
+    const int64_t Nout = static_cast<int64_t>(idx.size());
+    std::vector<int32_t> map(idx.size());
+    for (size_t o = 0; o < idx.size(); ++o) {
+        DASH_CHECK(idx[o] >= 0 && idx[o] < I.cur_N, "gpu garbler: gather index outside the input");
+        map[o] = static_cast<int32_t>(idx[o]);
+    }
     std::vector<DevBlock> y = I.alloc_labels(I.cur_mod, Nout);
     launch_gsum(I.c, y, I.cur, I.cur_mod, Nout, I.cur_N, gg::dconst(map.data(), map.size()), 1, false,
                 [](int, int) { return 1; });

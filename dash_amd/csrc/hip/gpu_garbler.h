@@ -136,6 +136,16 @@ class GpuGarbler {
         DASH_CHECK(upsample_hook() != nullptr, "gpu garbler: upsample is not linked in");
         upsample_hook()(*this, G, cur);
     }
+    // Gather (K_GATHER): cur[o] = the device cur[idx[o]], on whatever moduli cur carries. A hook as for upsample.
+    using GatherFn = void (*)(GpuGarbler&, const std::vector<i64>&, CrtLabels&);
+    static GatherFn& gather_hook() {
+        static GatherFn f = nullptr;
+        return f;
+    }
+    void gather(const std::vector<i64>& idx, CrtLabels& cur) {
+        DASH_CHECK(gather_hook() != nullptr, "gpu garbler: gather is not linked in");
+        gather_hook()(*this, idx, cur);
+    }
     // max pool / max: window values, one ReLU-gadget tree level per call (relu_garble_elem on streams
     // 20 + 2 lv / 21 + 2 lv), then the reduced values become cur
     void maxpool_begin(const std::vector<std::vector<i64>>& win, CrtLabels& cur);
@@ -238,6 +248,7 @@ class GpuGarbler {
     void conv_run(const ConvGeom& G, const ConvTGeom* T, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur);
     static void convt_dev(GpuGarbler& self, const ConvTGeom& G, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur);
     static void upsample_dev(GpuGarbler& self, const UpGeom& G, CrtLabels& cur);
+    static void gather_dev(GpuGarbler& self, const std::vector<i64>& idx, CrtLabels& cur);
     static void concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& idx, CrtLabels& cur);
     static void clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
                          CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,

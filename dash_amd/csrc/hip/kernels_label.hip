@@ -20,6 +20,46 @@ __global__ __launch_bounds__(256) void k_copy_gather(Act in, int64_t Nin, Act ou
     out.p[j][(static_cast<int64_t>(b) * n + c) * Nout + o] = in.p[j][(static_cast<int64_t>(b) * n + c) * Nin + idx[o]];
 }
 
+// The Gather layer's form of the same move, four consecutive outputs per lane: grid (ceil(Nout/1024), k, B).
+// The map is the same for every component row and every circuit, so a lane loads its four int32 indices once
+// (one 16-byte load; idx is padded to a multiple of four) and then walks the n_j rows (n_j is uniform over the
+// block): four byte loads, packed into one dword store, 4 B per lane and coalesced. Preconditions, checked by the
+// planner: Nout % 4 == 0 and out.p[j] 4-byte aligned, so every row start (b n_j + c) Nout stays dword aligned;
+// 0 <= idx[o] < Nin.
+constexpr int kGatherRows = 4;
+__global__ __launch_bounds__(256) void k_gather4(Act in, int64_t Nin, Act out, int64_t Nout, const int32_t* idx,
+                                                 CrtInfo crt) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int n = crt.n[j];
+    const int64_t o = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (o >= Nout) return;
+    const int4 s = *reinterpret_cast<const int4*>(idx + o);
+    // the planner never passes one buffer as both (ping-pong buffers, or a saved copy as the source)
+    const act_t* __restrict__ src = in.p[j] + static_cast<int64_t>(b) * n * Nin;
+    act_t* __restrict__ dst = out.p[j] + static_cast<int64_t>(b) * n * Nout + o;
+    auto row = [&](const act_t* r) {
+        return static_cast<uint32_t>(r[s.x]) | static_cast<uint32_t>(r[s.y]) << 8 |
+               static_cast<uint32_t>(r[s.z]) << 16 | static_cast<uint32_t>(r[s.w]) << 24;
+    };
+    // kGatherRows rows at a time, all their byte loads issued before the first store: act_t is a byte type, so
+    // the compiler would otherwise keep each row's loads behind the row before's store
+    int c = 0;
+    for (; c + kGatherRows <= n; c += kGatherRows) {
+        uint32_t v[kGatherRows];
+#pragma unroll
+        for (int r = 0; r < kGatherRows; ++r) v[r] = row(src + r * Nin);
+#pragma unroll
+        for (int r = 0; r < kGatherRows; ++r) *reinterpret_cast<uint32_t*>(dst + r * Nout) = v[r];
+        src += kGatherRows * Nin;
+        dst += kGatherRows * Nout;
+    }
+    for (; c < n; ++c) {
+        *reinterpret_cast<uint32_t*>(dst) = row(src);
+        src += Nin;
+        dst += Nout;
+    }
+}
+
 // d[..][o*ops+q] = v[..][o*cnt+2q+1] - v[..][o*cnt+2q]
 __global__ __launch_bounds__(256) void k_pair_diff(Act v, int64_t Nv, Act d, int64_t Nout, int ops, int cnt,
                                                    CrtInfo crt) {
@@ -174,6 +214,17 @@ static inline int64_t nmax(const CrtInfo& c) {
 void launch_copy_gather(const Act& in, int64_t Nin, const Act& out, int64_t Nout, const int64_t* idx,
                         const CrtInfo& crt, int B, hipStream_t st) {
     hipLaunchKernelGGL(k_copy_gather, g1(Nout * nmax(crt), crt.k, B), dim3(256), 0, st, in, Nin, out, Nout, idx, crt);
+}
+void launch_gather(const Act& in, int64_t Nin, const Act& out, int64_t Nout, const int32_t* idx4, const int64_t* idx8,
+                   const CrtInfo& crt, int B, hipStream_t st) {
+    if (idx4) {
+        const dim3 grid(static_cast<unsigned>((Nout + 1023) / 1024), crt.k, B);
+        if (launch_log_on()) launch_log_add("gather.dword", grid, dim3(256));
+        hipLaunchKernelGGL(k_gather4, grid, dim3(256), 0, st, in, Nin, out, Nout, idx4, crt);
+        return;
+    }
+    if (launch_log_on()) launch_log_add("gather.byte", g1(Nout * nmax(crt), crt.k, B), dim3(256));
+    launch_copy_gather(in, Nin, out, Nout, idx8, crt, B, st);
 }
 void launch_pair_diff(const Act& v, int64_t Nv, const Act& d, int64_t Nout, int ops, int cnt, const CrtInfo& crt,
                       int B, hipStream_t st) {

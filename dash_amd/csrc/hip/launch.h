@@ -126,6 +126,11 @@ void launch_mult(const MultArgs& a, const Act& x, const Act& y, int B, const Mod
 // label kernels (kernels_label.hip)
 void launch_copy_gather(const Act& in, int64_t Nin, const Act& out, int64_t Nout, const int64_t* idx,
                         const CrtInfo& crt, int B, hipStream_t st);
+// Gather layer: the dword form (k_gather4, idx4 = the int32 map padded to a multiple of four; needs Nout % 4 == 0 and
+// 4-byte aligned out.p[j]) or, with idx4 null, the byte form (launch_copy_gather on the int64 map idx8). Logs
+// "gather.dword" / "gather.byte".
+void launch_gather(const Act& in, int64_t Nin, const Act& out, int64_t Nout, const int32_t* idx4, const int64_t* idx8,
+                   const CrtInfo& crt, int B, hipStream_t st);
 void launch_pair_diff(const Act& v, int64_t Nv, const Act& d, int64_t Nout, int ops, int cnt, const CrtInfo& crt, int B,
                       hipStream_t st);
 void launch_pair_add(const Act& v, int64_t Nv, const Act& r, const Act& nv, int64_t Nout, int ops, int cnt, int cnt1,

@@ -661,6 +661,7 @@ class HipEvaluator {
             case K_CONV: return ConvGeom(l).out_size();
             case K_CONVT: return ConvTGeom(l).out_size();
             case K_UPSAMPLE: return UpGeom(l.p).out_size();
+            case K_GATHER: return static_cast<i64>(l.vec("idx").size());
             case K_MAXPOOL: case K_SUMPOOL: return PoolGeom(l.p).out_size();
             case K_MAX: return 1;
             case K_ARGMAX: return l.param("P");
@@ -814,6 +815,7 @@ class HipEvaluator {
     void plan_conv(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_convt(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_upsample(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_gather(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_relu(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_clip(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_sign(Walk& w, size_t li, const GLayer& g, const std::string& lname);
@@ -969,13 +971,15 @@ void HipEvaluator::build() {
         const GLayer& g = m0.layers[li];
         if (stream_) add_op("stage", [this, li](hipStream_t st) { stage_layer(li, st); });
         const std::string lname = std::string(kind_name(g.kind)) + "#" + std::to_string(li);
-        if (g.p.count("in_src")) restore_in_src(w, g);
+        // a Gather reads its in_src source in place (plan_gather): no copy back into the current buffer
+        if (g.p.count("in_src") && g.kind != K_GATHER) restore_in_src(w, g);
         switch (g.kind) {
             case K_FLATTEN: break;
             case K_DENSE: plan_dense(w, li, g, lname); break;
             case K_CONV: plan_conv(w, li, g, lname); break;
             case K_CONVT: plan_convt(w, li, g, lname); break;
             case K_UPSAMPLE: plan_upsample(w, li, g, lname); break;
+            case K_GATHER: plan_gather(w, li, g, lname); break;
             case K_RELU: plan_relu(w, li, g, lname); break;
             case K_CLIP: plan_clip(w, li, g, lname); break;
             case K_SIGN: plan_sign(w, li, g, lname); break;
@@ -1371,6 +1375,42 @@ void HipEvaluator::plan_upsample(Walk& w, size_t, const GLayer& g, const std::st
     Act x = act_of(w.cur), y = act_of(w.nxt());
     const int B = B_;
     add_op(lname, [x, NN, y, No, didx, ci, B](hipStream_t st) { launch_copy_gather(x, NN, y, No, didx, ci, B, st); });
+    set_out(w, g, No, w.nxt());
+}
+
+// Gather: the labels moved by a public index map (free: no tables), any moduli. A layer with in_src reads the
+// saved copy of that output where it lies, as plan_mul reads its operand; N and the moduli come from the slot.
+// The form rule: the dword kernel where Nout % 4 == 0 and every base pointer is 4-byte aligned, else the byte
+// kernel; DASH_GATHER_FORM=byte forces the byte form (A/B runs).
+void HipEvaluator::plan_gather(Walk& w, size_t, const GLayer& g, const std::string& lname) {
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    if (g.p.count("in_src")) {
+        const i64 src = g.param("in_src");
+        DASH_CHECK(src >= -1 && src + 1 < static_cast<i64>(saved_.size()) && !saved_[src + 1].empty(),
+                   "in_src source not saved");
+        w.N = w.saved_n[src + 1];
+        w.mods = w.saved_mods[src + 1];
+        for (int j = 0; j < k_; ++j) x.p[j] = saved_[src + 1][j];
+    }
+    const GatherGeom G(g.p, w.N);
+    const i64 No = G.out_size(), NN = w.N;
+    bool dword = No % 4 == 0;
+    for (int j = 0; j < k_; ++j)
+        dword = dword && reinterpret_cast<uintptr_t>(x.p[j]) % 4 == 0 && reinterpret_cast<uintptr_t>(y.p[j]) % 4 == 0;
+    if (const char* f = std::getenv("DASH_GATHER_FORM"))
+        if (std::string(f) == "byte") dword = false;
+    const int32_t* d4 = nullptr;
+    const int64_t* d8 = nullptr;
+    if (dword) {
+        std::vector<int32_t> i4(static_cast<size_t>((No + 3) / 4 * 4), 0);
+        for (i64 o = 0; o < No; ++o) i4[static_cast<size_t>(o)] = static_cast<int32_t>(G.src(o));
+        d4 = upload(i4.data(), i4.size());
+    } else {
+        d8 = upload(G.idx->data(), G.idx->size());
+    }
+    const CrtInfo ci = crt_info(w.mods);
+    const int B = B_;
+    add_op(lname, [x, NN, y, No, d4, d8, ci, B](hipStream_t st) { launch_gather(x, NN, y, No, d4, d8, ci, B, st); });
     set_out(w, g, No, w.nxt());
 }
 

@@ -51,6 +51,16 @@ struct UpGeom {
     }
 };
 
+// General gather of a flat tensor by a public index map: y[o] = x[idx[o]], 0 <= idx[o] < Nin (repeats allowed,
+// inputs may go unread); od: the output dims, their product is idx's length
+struct GatherGeom {
+    const std::vector<i64>* idx;
+    const std::vector<i64>* od;
+    GatherGeom(const Params& p, i64 Nin);
+    i64 out_size() const { return static_cast<i64>(idx->size()); }
+    i64 src(i64 o) const { return (*idx)[static_cast<size_t>(o)]; }
+};
+
 struct PoolGeom {
     // ph/pw: symmetric padding (at most half the kernel); ceil: ONNX/PyTorch ceil_mode output size
     i64 C, H, W, kh, kw, sh, sw, ph, pw, ceil, OH, OW;

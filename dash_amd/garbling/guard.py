@@ -26,7 +26,7 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
   evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
   bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
   has no Concat, no Clip, no ArgMax, no Mul, no MatMul, no ConvTranspose2d, no Upsample, no LeakyRelu, no
-  PiecewiseLinear and no padded / ceil-mode pooling:
+  PiecewiseLinear, no Gather and no padded / ceil-mode pooling:
   circuits with any of them take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
@@ -74,13 +74,13 @@ class RangeGuard:
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Mul, L.Projection,
                                           L.BaseExtension, L.ConvTranspose2d, L.Upsample, L.LeakyRelu,
-                                          L.PiecewiseLinear, L.MatMul))
+                                          L.PiecewiseLinear, L.MatMul, L.Gather))
                            for l in circuit.layers)
         # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no
-        # LeakyRelu, no PiecewiseLinear, no MatMul, no dilated conv and no padded / ceil-mode pooling: such circuits take
-        # the batched torch path
+        # LeakyRelu, no PiecewiseLinear, no MatMul, no Gather, no dilated conv and no padded / ceil-mode pooling: such
+        # circuits take the batched torch path
         self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.Mul, L.ConvTranspose2d, L.Upsample,
-                                                   L.LeakyRelu, L.PiecewiseLinear, L.MatMul)) or
+                                                   L.LeakyRelu, L.PiecewiseLinear, L.MatMul, L.Gather)) or
                                     (isinstance(l, L.Conv2d) and (l.dh > 1 or l.dw > 1)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
@@ -180,6 +180,8 @@ class RangeGuard:
                         perm = torch.as_tensor(i // ch + (i % ch) * (K // ch), device=dev)
                     ws.append((torch.tensor(np.array(l.q_weights), dtype=torch.float64, device=dev),
                                torch.tensor(np.array(l.q_biases), dtype=torch.float64, device=dev), perm))
+                elif isinstance(l, L.Gather):
+                    ws.append(torch.as_tensor(np.array(l.idx), device=dev))
                 else:
                     ws.append(None)
             self._w = (dev, ws)
@@ -221,6 +223,8 @@ class RangeGuard:
             elif isinstance(l, L.Upsample):
                 v = inp.view(B, l.C, l.H, l.W)
                 out = v.repeat_interleave(l.fh, dim=2).repeat_interleave(l.fw, dim=3).reshape(B, -1)
+            elif isinstance(l, L.Gather):  # sets no limit: the moved values are checked where a gadget next reads them
+                out = inp.index_select(1, ws[i])
             elif isinstance(l, L.Dense):
                 W, b, perm = ws[i]
                 xin = inp if perm is None else inp[:, perm]

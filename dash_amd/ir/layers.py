@@ -43,6 +43,7 @@ class Kind:
     LEAKY = 20
     PWL = 21
     MATMUL = 22
+    GATHER = 23
 
 
 def _size(d: Sequence[int]) -> int:
@@ -510,6 +511,131 @@ class Upsample(Layer):
 
     def __repr__(self) -> str:
         return f"Upsample(in={self.in_dims}, factors=({self.fh}, {self.fw}))"
+
+
+def _slice_bounds(d: int, start: int, stop: int) -> tuple:
+    """ONNX Slice with a positive step on an axis of d elements: a negative start / stop counts from the end, then
+    both are clamped to [0, d] (so INT64_MAX means "to the end")."""
+    return tuple(min(max(int(v) + d if int(v) < 0 else int(v), 0), d) for v in (start, stop))
+
+
+class Gather(Layer):
+    """General reordering of a tensor by a public index map on the flat [C][H][W] order:
+    out.flat[o] = x.flat[idx[o]]. Repeats are allowed (fan-out, as Upsample has) and elements may go unread. Free in
+    the label domain: no tables, no PRG draws, no constants, so it works under both encodings and every
+    quantization scheme. The constructors below build the maps of Transpose, Slice, channel shuffle,
+    DepthToSpace and SpaceToDepth."""
+
+    kind = Kind.GATHER
+    name = "gather"
+
+    def __init__(self, dims, idx, out_dims=None):
+        dims = tuple(int(d) for d in dims)
+        nin = _size(dims)
+        a = np.asarray(idx)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"gather: idx is a 1-D integer array, got shape {a.shape} of {a.dtype}")
+        if a.size == 0:
+            raise ValueError("gather: idx is empty")
+        if not 0 < nin < 2 ** 31 or a.size >= 2 ** 31:
+            raise ValueError(f"gather: sizes must lie in [1, 2^31), got Nin={nin}, Nout={a.size}")
+        a = a.astype(np.int64)
+        bad = np.nonzero((a < 0) | (a >= nin))[0]
+        if bad.size:
+            o = int(bad[0])
+            what = "is negative (reserved)" if a[o] < 0 else f"is not below the input size {nin}"
+            raise ValueError(f"gather: idx[{o}] = {int(a[o])} {what}")
+        od = (int(a.size),) if out_dims is None else tuple(int(d) for d in out_dims)
+        if _size(od) != a.size or any(d < 1 for d in od):
+            raise ValueError(f"gather: out_dims {od} do not hold the {a.size} elements of idx")
+        super().__init__(dims, od)
+        a.setflags(write=False)  # garble_spec hands the array itself to the native specs (Circuit.garble_specs_native)
+        self.idx = a
+
+    # ---- the maps, written with numpy on np.arange(Nin).reshape(dims)
+    @staticmethod
+    def _ids(dims):
+        dims = tuple(int(d) for d in dims)
+        return np.arange(_size(dims), dtype=np.int64).reshape(dims)
+
+    @classmethod
+    def _of(cls, dims, ids):
+        return cls(dims, ids.reshape(-1), ids.shape)
+
+    @classmethod
+    def transpose(cls, dims, perm):
+        perm = tuple(int(p) for p in perm)
+        if sorted(perm) != list(range(len(tuple(dims)))):
+            raise ValueError(f"gather.transpose: perm {perm} is no permutation of the axes of {tuple(dims)}")
+        return cls._of(dims, np.transpose(cls._ids(dims), perm))
+
+    @classmethod
+    def slice(cls, dims, axis, start, stop, step=1):
+        """ONNX Slice along one axis: negative start / stop count from the end, both are clamped to [0, d]."""
+        dims = tuple(int(d) for d in dims)
+        axis, step = int(axis), int(step)
+        if not -len(dims) <= axis < len(dims):
+            raise ValueError(f"gather.slice: axis {axis} outside the {len(dims)} axes")
+        if step < 1:
+            raise ValueError(f"gather.slice: step must be >= 1, got {step}")
+        axis %= len(dims)
+        d = dims[axis]
+        lo, hi = _slice_bounds(d, start, stop)
+        if hi <= lo:
+            raise ValueError(f"gather.slice: empty slice [{start}:{stop}:{step}] of an axis of {d}")
+        sl = [np.s_[:]] * len(dims)
+        sl[axis] = np.s_[lo:hi:step]
+        return cls._of(dims, cls._ids(dims)[tuple(sl)])
+
+    @classmethod
+    def channel_shuffle(cls, dims, groups):
+        dims = tuple(int(d) for d in dims)
+        g = int(groups)
+        if g < 1 or dims[0] % g:
+            raise ValueError(f"gather.channel_shuffle: {g} groups do not divide {dims[0]} channels")
+        ids = cls._ids(dims).reshape((g, dims[0] // g) + dims[1:])
+        return cls(dims, np.swapaxes(ids, 0, 1).reshape(-1), dims)
+
+    @classmethod
+    def depth_to_space(cls, dims, r, mode="DCR"):
+        dims = tuple(int(d) for d in dims)
+        r = int(r)
+        if len(dims) != 3 or r < 1 or dims[0] % (r * r):
+            raise ValueError(f"gather.depth_to_space: (C, H, W) with C a multiple of r^2, got {dims}, r={r}")
+        C, H, W = dims
+        c = C // (r * r)
+        if mode == "DCR":
+            ids = cls._ids(dims).reshape(r, r, c, H, W).transpose(2, 3, 0, 4, 1)
+        elif mode == "CRD":
+            ids = cls._ids(dims).reshape(c, r, r, H, W).transpose(0, 3, 1, 4, 2)
+        else:
+            raise ValueError(f"gather.depth_to_space: mode is 'DCR' or 'CRD', got {mode!r}")
+        return cls(dims, ids.reshape(-1), (c, H * r, W * r))
+
+    @classmethod
+    def space_to_depth(cls, dims, r):
+        dims = tuple(int(d) for d in dims)
+        r = int(r)
+        if len(dims) != 3 or r < 1 or dims[1] % r or dims[2] % r:
+            raise ValueError(f"gather.space_to_depth: (C, H, W) with H and W multiples of r, got {dims}, r={r}")
+        C, H, W = dims
+        ids = cls._ids(dims).reshape(C, H // r, r, W // r, r).transpose(2, 4, 0, 1, 3)
+        return cls(dims, ids.reshape(-1), (C * r * r, H // r, W // r))
+
+    def plain_eval(self, x, track=True, ctx=None):
+        return np.asarray(x, dtype=np.float32).reshape(-1)[self.idx]
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        y = np.asarray(x, dtype=np.int64).reshape(-1)[self.idx]
+        if track:
+            self._track_q(y)
+        return y
+
+    def garble_spec(self):
+        return self.kind, {"idx": self.idx, "od": list(self.out_dims)}
+
+    def __repr__(self) -> str:
+        return f"Gather(in={self.in_dims}, out={self.out_dims})"
 
 
 class Relu(Layer):

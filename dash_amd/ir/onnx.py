@@ -122,11 +122,35 @@ name); its output carries e = `pwl_bits`, consumed like a LeakyRelu's:
     LeakyRelu / PRelu                e + leaky_bits
     Sigmoid / HardSigmoid / Tanh     0 required -> pwl_bits
     Relu, pools, Flatten, Upsample   passed through
+    Slice, Split, Gather, ...        passed through (Gather layers)
     Conv / ConvTranspose / Gemm      consumed: in_scale_bits = e, Rescale(l + e)
     Mul                              e0 + e1 consumed: Rescale(l + e0 + e1)
     Add / Concat                     equal on all operands
     Sign / ArgMax                    dropped
     Clip, graph output               0 required
+
+`Slice` (opset 1 attributes or opset >= 10 inputs, positive steps), `Split`
+(equal parts, or `split` as attribute or input; every output its own layer
+reading the Split's input), `DepthToSpace` (modes DCR and CRD), `SpaceToDepth`
+and `Gather` with initializer indices along one axis (a scalar index drops the
+axis) become `Gather` layers (docs/GATHER.md). All act on axes behind the
+batch axis and take their parameters from attributes or initializers; anything
+else is refused with the node's name. A map that is the identity under
+unchanged dims is an alias, not a layer. A Gather is value-preserving: the
+pending factor and the pending scale bits pass through. The flat form the
+export writes, `Flatten -> Gather(axis=1) -> Reshape`, is read back as one layer
+on the Flatten's input with the Reshape's dims as `out_dims`. A `Slice`, `Split`
+or `Gather` whose input comes (also through elementwise nodes) from a `Reshape`
+that is imported as a Flatten although its target has more than one axis
+behind the batch axis is refused by name: its axes are not the tracked ones.
+
+With the keyword `transpose="gather"` a `Transpose` that does not fold into a
+MatMul and permutes a produced tensor's own tracked axes with `perm[0] == 0`
+becomes a Gather too, and the chain `Reshape -> Transpose -> Reshape` whose
+shapes are initializers and whose intermediates have no other consumer
+(PyTorch's channel shuffle) becomes one Gather with the composed map. A
+Transpose of a Reshape view next to a MatMul is still refused. The default
+`transpose="matmul"` keeps every Transpose outside the MatMul fold refused.
 
 `save_onnx_model(path, circuit)` writes a pytorch-style ONNX graph of a float
 circuit with a small protobuf encoder (the python `onnx` package is not
@@ -143,9 +167,9 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MatMul, MaxPool2d, Mul,
-                     PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _as_matrix, _convt_check, _head_matrix,
-                     _pool_out)
+from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Gather, LeakyRelu, MatMul, MaxPool2d,
+                     Mul, PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _as_matrix, _convt_check, _head_matrix,
+                     _pool_out, _slice_bounds)
 from .quant import QuantizationMethod
 
 DEFAULT_Q_CONST = 0.02  # onnx_modelloader.h:377
@@ -209,10 +233,12 @@ def _pool_attrs(node) -> tuple:
 
 def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
                              q_const: float = DEFAULT_Q_CONST, q_parameter: int = -1, leaky_bits: int = 4,
-                             tanh: str = "sign", pwl_bits: int = 8) -> Circuit:
+                             tanh: str = "sign", pwl_bits: int = 8, transpose: str = "matmul") -> Circuit:
     q_method = QuantizationMethod(q_method)
     if tanh not in ("sign", "pwl"):
         raise ValueError(f"onnx: tanh must be 'sign' or 'pwl', got {tanh!r}")
+    if transpose not in ("matmul", "gather"):
+        raise ValueError(f"onnx: transpose must be 'matmul' or 'gather', got {transpose!r}")
     inits = {t["name"]: t for t in model["initializers"]}
     tf = model["producer_name"] == "tf2onnx"
 
@@ -283,14 +309,70 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
     vdims: dict[str, tuple] = {}  # a matrix-view Reshape's output -> its dims (the tensor itself is an alias)
     mheads: dict[str, int] = {}   # a multi-head MatMul's result (tracked as dims (h M, N)) -> h
 
-    def view_shape(node, size: int) -> tuple:
-        """The target of a Reshape without its batch axis, 0 and -1 resolved against `size` elements."""
+    # Gather layers (docs/GATHER.md). The flat form the export writes, Flatten -> Gather(axis=1) -> Reshape: a
+    # Flatten that feeds only such a Gather is the same tensor seen flat, and the only Reshape of the Gather's result
+    # gives the layer's out_dims. With transpose="gather", the chain Reshape -> Transpose -> Reshape whose
+    # intermediates have no other consumer (PyTorch's channel shuffle) becomes one Gather with the composed map.
+    def init_shape(n) -> bool:
+        return n["op_type"] == "Reshape" and len(n["inputs"]) > 1 and n["inputs"][1] in inits
+
+    made_by = {n["outputs"][0]: k for k, n in enumerate(nodes) if n["outputs"]}
+    gouts = {o["name"] for o in model.get("outputs", [])}  # an intermediate that is a graph output stays a tensor
+    flat_feed: set = set()         # Flatten nodes that only feed a flat Gather
+    flat_back: dict[int, int] = {}  # flat Gather -> the Reshape behind it
+    for k, n in enumerate(nodes):
+        m = made_by.get(n["inputs"][0]) if n["op_type"] == "Gather" and len(n["inputs"]) > 1 else None
+        if m is not None and int(n["attrs"].get("axis", 0)) == 1 and n["inputs"][1] in inits and \
+                nodes[m]["op_type"] == "Flatten" and int(nodes[m]["attrs"].get("axis", 1)) == 1 and \
+                uses_of(nodes[m]["outputs"][0]) == [k] and nodes[m]["outputs"][0] not in gouts:
+            flat_feed.add(m)
+            u = uses_of(n["outputs"][0])
+            if len(u) == 1 and init_shape(nodes[u[0]]) and nodes[u[0]]["inputs"][0] == n["outputs"][0] and \
+                    n["outputs"][0] not in gouts:
+                flat_back[k] = u[0]
+    shuffle_chain: dict[int, tuple] = {}  # first Reshape -> (Transpose, second Reshape)
+    if transpose == "gather":
+        for k, n in enumerate(nodes):
+            if not init_shape(n) or k in mm_feed or k in mm_back:
+                continue
+            u = uses_of(n["outputs"][0])
+            if len(u) != 1 or nodes[u[0]]["op_type"] != "Transpose" or u[0] in fold_tr or \
+                    n["outputs"][0] in gouts or nodes[u[0]]["outputs"][0] in gouts:
+                continue
+            u2 = uses_of(nodes[u[0]]["outputs"][0])
+            if len(u2) == 1 and init_shape(nodes[u2[0]]) and u2[0] not in mm_feed and u2[0] not in mm_back and \
+                    nodes[u2[0]]["inputs"][0] == nodes[u[0]]["outputs"][0]:
+                shuffle_chain[k] = (u[0], u2[0])
+    fviews: set = set()  # outputs of the flat_feed Flattens: aliases of their (C, H, W) input, read flat
+    # A Reshape that is neither next to a MatMul nor part of a chain above is imported as a Flatten. Where its target
+    # has more than one axis behind the batch axis (or is not an initializer), the graph's axes no longer are the
+    # tracked ones: tensor name -> that Reshape's name, carried through elementwise nodes. An operator that names
+    # an axis (Slice, Split, Gather) refuses such an input.
+    unflat: dict[str, str] = {}
+    elementwise = ("Identity", "Dropout", "Relu", "LeakyRelu", "PRelu", "Clip", "Sigmoid", "HardSigmoid", "Tanh",
+                   "SignTanh", "Sign")
+
+    def tracked_axes(node):
+        nm = node["inputs"][0]
+        if nm in unflat:
+            raise NotImplementedError(
+                f"onnx: {node.get('name') or node['op_type']}: the input {nm!r} comes from the Reshape "
+                f"{unflat[nm]!r}, which is imported flat: a {node['op_type']} along an axis of the reshaped view is "
+                "not supported")
+
+    def view_shape(node, size: int, where: str = "next to a MatMul", batch_one: bool = False) -> tuple:
+        """The target of a Reshape without its batch axis, 0 and -1 resolved against `size` elements. batch_one: the
+        first entry must be the batch axis of one sample (1, 0 = copied, or the shape's only -1)."""
         name = node.get("name") or node["op_type"]
         if len(node["inputs"]) < 2 or node["inputs"][1] not in inits:
-            raise NotImplementedError(f"onnx: {name}: the shape of a Reshape next to a MatMul must be an initializer")
-        shp = [int(v) for v in np.asarray(inits[node["inputs"][1]]["values"]).reshape(-1)][1:]
+            raise NotImplementedError(f"onnx: {name}: the shape of a Reshape {where} must be an initializer")
+        shp = [int(v) for v in np.asarray(inits[node["inputs"][1]]["values"]).reshape(-1)]
+        if batch_one and (not shp or not (shp[0] in (0, 1) or (shp[0] == -1 and -1 not in shp[1:]))):
+            raise NotImplementedError(f"onnx: {name}: a Reshape {where} must keep the batch axis (first entry 1), got "
+                                      f"{shp}")
+        shp = shp[1:]
         if any(v == 0 for v in shp):
-            raise NotImplementedError(f"onnx: {name}: a Reshape next to a MatMul must state its dims (no 0 entries)")
+            raise NotImplementedError(f"onnx: {name}: a Reshape {where} must state its dims (no 0 entries)")
         if shp.count(-1) == 1:
             known = int(np.prod([v for v in shp if v != -1], dtype=np.int64))
             shp[shp.index(-1)] = size // max(known, 1)
@@ -337,18 +419,168 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                 f"onnx: {node.get('name') or node['op_type']}: the operands of this {node['op_type']} carry "
                 f"different LeakyRelu scales (2^e with e = {eb_}); no Conv/Gemm absorbed them")
 
+    def ints_of(node, pos: int, what: str) -> list:
+        """The integers of input `pos`, which must be an initializer."""
+        nm = node["inputs"][pos] if len(node["inputs"]) > pos else ""
+        if nm not in inits:
+            raise NotImplementedError(f"onnx: {node.get('name') or node['op_type']}: {what} must be an initializer")
+        t = inits[nm]
+        return [int(v) for v in (list(t["ivalues"]) or np.asarray(t["values"]).reshape(-1))]
+
+    def inner_axis(node, axis: int, dims) -> int:
+        """An ONNX axis of the [N, ...dims] tensor as an axis of dims; the batch axis is refused."""
+        nd = len(dims) + 1
+        if tf or not -nd <= axis < nd or axis % nd == 0:
+            raise NotImplementedError(f"onnx: {node.get('name') or node['op_type']}: {node['op_type']} along axis "
+                                      f"{axis} of a rank-{nd} tensor: only the axes behind the batch axis of an NCHW or "
+                                      "[N, K] tensor are supported")
+        return axis % nd - 1
+
+    def emit_gather(node, out_name: str, in_name: str, ids, out_dims=None):
+        """out = the tensor `in_name` moved by the index map `ids` (shaped as the output, or flat with out_dims):
+        a Gather layer, or an alias where the map is the identity under unchanged dims. Value-preserving: the
+        pending factor and scale bits pass through."""
+        j, dims, fac = data_in(node, in_name)
+        ids = np.asarray(ids, dtype=np.int64)
+        od = tuple(int(v) for v in (out_dims if out_dims is not None else (ids.shape or (1,))))
+        if ids.size == 0:
+            raise ValueError(f"onnx: {node.get('name') or node['op_type']}: the result is empty")
+        if od == tuple(dims) and np.array_equal(ids.reshape(-1), np.arange(ids.size)):
+            alias[out_name] = res(in_name)
+            return
+        emit(_Spec("gather", dims=tuple(dims), idx=ids.reshape(-1).copy(), out_dims=od), out_name, j, od, fac,
+             bits(in_name))
+
+    def ids_of(dims) -> np.ndarray:
+        return np.arange(int(np.prod(dims)), dtype=np.int64).reshape(tuple(dims))
+
     for ni, node in enumerate(nodes):
         if ni in skip:
             continue
         op, a = node["op_type"], node["attrs"]
         ins, outs = node["inputs"], node["outputs"]
+        if op in elementwise and ins and ins[0] in unflat:
+            unflat[outs[0]] = unflat[ins[0]]
         if op in ("Identity", "Dropout"):
             alias[outs[0]] = res(ins[0])
             continue
         eb = bits(ins[0]) if ins else 0  # the data input's pending scale bits
         if op in ("Relu", "LeakyRelu", "PRelu", "Clip") and ins and res(ins[0]) in mheads:
             mheads[outs[0]] = mheads[res(ins[0])]  # an elementwise activation keeps the heads' slabs
-        if op == "Reshape" and (ni in mm_feed or ni in mm_back):
+        if ni in shuffle_chain:  # Reshape -> Transpose -> Reshape under transpose="gather": one composed map
+            t_, r2 = shuffle_chain[ni]
+            tn, name = nodes[t_], nodes[t_].get("name") or "Transpose"
+            _, dims, _ = data_in(node, ins[0])
+            size = int(np.prod(dims))
+            s1 = view_shape(node, size, "in front of a Transpose", True)
+            perm = [int(v) for v in tn["attrs"].get("perm", [])]
+            if len(perm) != len(s1) + 1 or sorted(perm) != list(range(len(perm))) or perm[0] != 0:
+                raise NotImplementedError(f"onnx: {name}: a Transpose with perm {perm} of a tensor of dims "
+                                          f"{(1,) + s1}: only a permutation that keeps the batch axis is supported")
+            s2 = view_shape(nodes[r2], size, "behind a Transpose", True)
+            ids = np.transpose(np.arange(size, dtype=np.int64).reshape(s1), [p - 1 for p in perm[1:]])
+            emit_gather(tn, nodes[r2]["outputs"][0], ins[0], ids.reshape(-1), s2)
+            skip.update((t_, r2))
+        elif op == "Flatten" and ni in flat_feed:
+            data_in(node, ins[0])
+            alias[outs[0]] = res(ins[0])
+            fviews.add(outs[0])
+        elif op == "Gather":
+            name = node.get("name") or op
+            tracked_axes(node)
+            flat = ins[0] in fviews
+            _, dims, _ = data_in(node, ins[0])
+            if len(ins) < 2 or ins[1] not in inits:
+                raise NotImplementedError(f"onnx: {name}: the indices of a Gather must be an initializer")
+            ishape = [int(v) for v in inits[ins[1]]["dims"]]
+            if len(ishape) > 1:
+                raise NotImplementedError(f"onnx: {name}: Gather indices of shape {ishape}: only a scalar (the axis is "
+                                          "dropped) or a 1-D list along one axis is supported")
+            vdim = (int(np.prod(dims)),) if flat else tuple(dims)
+            ax = inner_axis(node, int(a.get("axis", 0)), vdim)
+            sel = np.asarray(ints_of(node, 1, "the indices of a Gather"), dtype=np.int64)
+            if sel.size == 0 or (sel < -vdim[ax]).any() or (sel >= vdim[ax]).any():
+                raise ValueError(f"onnx: {name}: Gather indices outside the axis of {vdim[ax]} elements (or none)")
+            sel = np.where(sel < 0, sel + vdim[ax], sel)
+            ids = np.take(ids_of(vdim), sel if ishape else int(sel[0]), axis=ax)
+            if flat:  # the export's form: the map acts on the flat tensor, the Reshape behind it gives out_dims
+                od = None
+                if ni in flat_back:
+                    od = view_shape(nodes[flat_back[ni]], ids.size, "behind a flat Gather", True)
+                    skip.add(flat_back[ni])
+                emit_gather(node, outs[0], ins[0], ids.reshape(-1), od or (ids.size,))
+                if ni in flat_back:
+                    alias[nodes[flat_back[ni]]["outputs"][0]] = res(outs[0])
+            else:
+                emit_gather(node, outs[0], ins[0], ids)
+        elif op == "Slice":
+            name = node.get("name") or op
+            tracked_axes(node)
+            _, dims, _ = data_in(node, ins[0])
+            if "starts" in a:  # opset 1: attributes
+                starts, ends = [int(v) for v in a["starts"]], [int(v) for v in a["ends"]]
+                axes = [int(v) for v in a["axes"]] if "axes" in a else list(range(len(starts)))
+                steps = [1] * len(starts)
+            else:  # opset >= 10: inputs
+                starts, ends = ints_of(node, 1, "the starts of a Slice"), ints_of(node, 2, "the ends of a Slice")
+                axes = ints_of(node, 3, "the axes of a Slice") if len(ins) > 3 and ins[3] else list(range(len(starts)))
+                steps = ints_of(node, 4, "the steps of a Slice") if len(ins) > 4 and ins[4] else [1] * len(starts)
+            if not (len(starts) == len(ends) == len(axes) == len(steps)):
+                raise ValueError(f"onnx: {name}: Slice starts, ends, axes and steps of different lengths")
+            if any(s < 1 for s in steps):
+                raise NotImplementedError(f"onnx: {name}: Slice steps {steps}: only positive steps are supported")
+            ids = ids_of(dims)
+            for s0, e0, ax0, st0 in zip(starts, ends, axes, steps):
+                ax = inner_axis(node, ax0, dims)
+                lo, hi = _slice_bounds(dims[ax], s0, e0)
+                ids = ids[(np.s_[:],) * ax + (np.s_[lo:max(hi, lo):st0],)]
+            emit_gather(node, outs[0], ins[0], ids)
+        elif op == "Split":
+            name = node.get("name") or op
+            tracked_axes(node)
+            _, dims, _ = data_in(node, ins[0])
+            ax = inner_axis(node, int(a.get("axis", 0)), dims)
+            if "split" in a:
+                parts = [int(v) for v in a["split"]]
+            elif len(ins) > 1 and ins[1]:
+                parts = ints_of(node, 1, "the split of a Split")
+            else:
+                n_out = len(outs)
+                if dims[ax] % n_out:
+                    raise NotImplementedError(f"onnx: {name}: Split of an axis of {dims[ax]} into {n_out} parts: only "
+                                              "equal parts (or a given split) are supported")
+                parts = [dims[ax] // n_out] * n_out
+            if len(parts) != len(outs) or sum(parts) != dims[ax] or any(p < 1 for p in parts):
+                raise ValueError(f"onnx: {name}: split {parts} does not cut the axis of {dims[ax]} into {len(outs)} "
+                                 "parts")
+            ids, lo = ids_of(dims), 0
+            for out_name, p in zip(outs, parts):  # every part its own layer, reading the Split's input
+                emit_gather(node, out_name, ins[0], ids[(np.s_[:],) * ax + (np.s_[lo:lo + p],)])
+                lo += p
+        elif op in ("DepthToSpace", "SpaceToDepth"):
+            name = node.get("name") or op
+            _, dims, _ = data_in(node, ins[0])
+            if tf or len(dims) != 3:
+                raise NotImplementedError(f"onnx: {name}: {op} of an NCHW image only")
+            try:
+                if op == "DepthToSpace":
+                    probe = Gather.depth_to_space(dims, int(a.get("blocksize", 0)), _sattr(a, "mode", "DCR"))
+                else:
+                    probe = Gather.space_to_depth(dims, int(a.get("blocksize", 0)))
+            except ValueError as ex:
+                raise NotImplementedError(f"onnx: {name}: {ex}") from None
+            emit_gather(node, outs[0], ins[0], probe.idx, probe.out_dims)
+        elif op == "Transpose" and transpose == "gather" and ni not in fold_tr:
+            name = node.get("name") or op
+            _, dims, _ = data_in(node, ins[0])
+            perm = [int(v) for v in a.get("perm", [])] or list(range(len(dims), -1, -1))
+            if ins[0] in vdims or ins[0] in fviews or len(perm) != len(dims) + 1 or \
+                    sorted(perm) != list(range(len(perm))) or perm[0] != 0:
+                raise NotImplementedError(f"onnx: {name}: a Transpose with perm {perm} of a tensor tracked under dims "
+                                          f"{(1,) + tuple(dims)}: only a permutation of a produced tensor's own axes that "
+                                          "keeps the batch axis becomes a Gather (a Reshape view is no such tensor)")
+            emit_gather(node, outs[0], ins[0], np.transpose(ids_of(dims), [p - 1 for p in perm[1:]]))
+        elif op == "Reshape" and (ni in mm_feed or ni in mm_back):
             j, dims, fac = data_in(node, ins[0])
             shp = view_shape(node, int(np.prod(dims)))
             alias[outs[0]] = res(ins[0])
@@ -412,6 +644,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                 mheads[outs[0]] = heads[0]
         elif op == "Flatten" or op == "Reshape":
             j, dims, fac = data_in(node, ins[0])
+            if op == "Reshape" and not (init_shape(node) and int(np.asarray(inits[ins[1]]["values"]).size) == 2):
+                unflat[outs[0]] = node.get("name") or op  # imported flat, but the graph goes on under other dims
             if op == "Reshape" and len(dims) == 1:
                 alias[outs[0]] = res(ins[0])
                 continue
@@ -813,6 +1047,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                                           out_pad_height=kw["opad"][0], in_scale_bits=kw["e"]))
         elif s.kind == "upsample":
             layers.append(Upsample(kw["dims"], kw["f"][0], kw["f"][1]))
+        elif s.kind == "gather":
+            layers.append(Gather(kw["dims"], kw["idx"], kw["out_dims"]))
         elif s.kind in ("maxpool", "sumpool"):
             C, H, W = kw["dims"]
             cls = MaxPool2d if s.kind == "maxpool" else SumPool2d
@@ -867,11 +1103,14 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
 
 def load_onnx_model(path, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant, q_parameter: int = -1,
                     q_const: float = DEFAULT_Q_CONST, leaky_bits: int = 4, tanh: str = "sign",
-                    pwl_bits: int = 8) -> Circuit:
+                    pwl_bits: int = 8, transpose: str = "matmul") -> Circuit:
     """Reference: load_onnx_model (onnx_modelloader.h:371-406). leaky_bits: the slope bits of imported LeakyRelu /
     PRelu nodes (docs/LEAKY_RELU.md). tanh: "sign" imports Tanh as Sign (the reference's convention), "pwl" as a
-    PiecewiseLinear; pwl_bits: the slope bits of imported Sigmoid / HardSigmoid / Tanh nodes (docs/PWL.md)."""
-    return create_circuit_from_onnx(parse_onnx(path), q_method, q_const, q_parameter, leaky_bits, tanh, pwl_bits)
+    PiecewiseLinear; pwl_bits: the slope bits of imported Sigmoid / HardSigmoid / Tanh nodes (docs/PWL.md).
+    transpose: "matmul" accepts a Transpose only where it folds into a MatMul, "gather" also turns every other
+    Transpose that keeps the batch axis into a Gather layer (docs/GATHER.md)."""
+    return create_circuit_from_onnx(parse_onnx(path), q_method, q_const, q_parameter, leaky_bits, tanh, pwl_bits,
+                                    transpose)
 
 
 # ------------------------------------------------------------------ export
@@ -993,6 +1232,19 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             attrs = (_attr_str("coordinate_transformation_mode", "asymmetric") + _attr_str("mode", "nearest")
                      + _attr_str("nearest_mode", "floor"))
             nodes.append(_node("Resize", [cur, "", f"{name}.scales"], [out], name, attrs))
+            scale[out] = K
+        elif isinstance(l, Gather):
+            # the map on the flat tensor: Flatten -> Gather(axis=1) -> Reshape(out_dims); value-preserving, so a
+            # pending average ratio passes through
+            inits.append(_tensor_i64(f"{name}.indices", l.idx))
+            nodes.append(_node("Flatten", [cur], [f"{name}.flat"], f"{name}.flatten", _attr_int("axis", 1)))
+            if len(l.out_dims) == 1:
+                nodes.append(_node("Gather", [f"{name}.flat", f"{name}.indices"], [out], name, _attr_int("axis", 1)))
+            else:
+                inits.append(_tensor_i64(f"{name}.shape", (1,) + l.out_dims))
+                nodes.append(_node("Gather", [f"{name}.flat", f"{name}.indices"], [f"{name}.g"], name,
+                                   _attr_int("axis", 1)))
+                nodes.append(_node("Reshape", [f"{name}.g", f"{name}.shape"], [out], f"{name}.reshape"))
             scale[out] = K
         elif isinstance(l, MaxPool2d):
             attrs = _attr_ints("kernel_shape", [l.kh, l.kw]) + _attr_ints("pads", [l.ph, l.pw, l.ph, l.pw]) + \

@@ -129,6 +129,10 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
         elif k == "attention":
             raise NotImplementedError(f"training: op {k} (an attention block reads its input four times) not supported "
                                       "by the sequential trainer")
+        elif k in ("shuffle", "d2s", "shuffle_unit"):
+            raise NotImplementedError(f"training: op {k} (a Gather layer: channel shuffle, depth-to-space and the "
+                                      "ShuffleNet unit's split have no module here) not supported by the sequential "
+                                      "trainer")
         elif k == "relu6":
             mods.append(nn.ReLU6())
         elif k == "clip":

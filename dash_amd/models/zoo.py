@@ -12,7 +12,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MatMul, MaxPool2d, Mul,
+from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Gather, LeakyRelu, MatMul, MaxPool2d, Mul,
                          PiecewiseLinear, Relu,
                          Rescale, Sign, SumPool2d, Upsample)
 from ..ir.quant import QuantizationMethod, quantize_input
@@ -59,6 +59,12 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   pending scale on their input; the output's 2^pwl_bits travels like a leaky ReLU's (docs/PWL.md)
 #                   | ("se", r, "sigmoid") the same block gated by the piecewise-linear sigmoid instead of
 #                   Clip(0, 1): the Mul's rescale is then l + pwl_bits (ScaleQuant only)
+#                   | ("shuffle", g) channel shuffle with g groups and ("d2s", r) depth-to-space by r (PixelShuffle, the
+#                   ONNX mode CRD; ("d2s", r, "DCR") for the other): Gather layers, free and value-preserving
+#                   | ("shuffle_unit",) the ShuffleNetV2 basic unit on a (C, H, W) tensor with C even: the first half
+#                   of the channels is kept (a Gather), the second half (a Gather reading the unit's input) goes
+#                   through a 1x1 conv + ReLU, a depthwise 3x3 and a 1x1 conv + ReLU (each conv + the scheme's
+#                   rescale), then the Concat of both and a shuffle with 2 groups (docs/GATHER.md)
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     # MODEL_A whose decoded output is the class alone, not the ten logits
@@ -176,6 +182,16 @@ ARCHS: dict[str, dict] = {
         ("aspp", 16, (1, 2, 4)),
         ("conv", 16, 1, 1, 0), ("relu",),
         ("conv", 4, 1, 1, 0), ("argmax",), ("up", 2)]},
+    # ShuffleNetV2-style CIFAR net: a strided stem (32 -> 16 -> 8), two basic units on the (16, 8, 8) stage, a global
+    # average and a dense head
+    "SHUFFLENET_V2_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 8, 3, 2, 1), ("relu",), ("conv", 16, 3, 2, 1), ("relu",),
+        ("shuffle_unit",), ("shuffle_unit",), ("gap",), ("flatten",), ("fc", 10)]},
+    # sub-pixel segmentation head: a stride-2 encoder (32 -> 16), a 1x1 conv to 4 r^2 = 16 channels, PixelShuffle by
+    # r = 2 back to the (4, 32, 32) score map of 4 classes and the per-pixel class (1, 32, 32)
+    "SUBPIXEL_SEG_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 8, 3, 2, 1), ("relu",), ("conv", 16, 3, 1, 1), ("relu",),
+        ("conv", 16, 1, 1, 0), ("d2s", 2), ("argmax",)]},
 }
 
 ALIASES = {"MINIONN": "MODEL_F_MINIONN_POOL_REPL", "GNNP": "MODEL_F_GNNP_POOL_REPL", "MLP": "MODEL_A",
@@ -238,7 +254,7 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
     for op in arch["ops"]:
         kind = op[0]
         if pend[0] and kind not in ("conv", "dwconv", "fc", "relu", "leaky", "prelu", "maxpool", "sumpool", "gap",
-                                    "flatten", "up"):
+                                    "flatten", "up", "shuffle", "d2s"):
             raise NotImplementedError(f"{name}: op {len(layers)} ({kind}): a leaky ReLU's 2^{pend[0]} scale reaches it "
                                       "before a conv or fc could absorb it")
         if kind == "convt":
@@ -255,6 +271,32 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             up = Upsample(dims, op[1])
             layers.append(up)
             dims = up.out_dims
+        elif kind == "shuffle":
+            layers.append(Gather.channel_shuffle(dims, op[1]))
+        elif kind == "d2s":
+            ps = Gather.depth_to_space(dims, op[1], op[2] if len(op) > 2 else "CRD")
+            layers.append(ps)
+            dims = ps.out_dims
+        elif kind == "shuffle_unit":
+            if len(dims) != 3 or dims[0] % 2:
+                raise ValueError(f"{name}: op {len(layers)} (shuffle_unit): needs a (C, H, W) tensor of an even channel "
+                                 f"count, got {dims}")
+            cin, h, w = dims
+            src, half = len(layers) - 1, cin // 2
+            keep = Gather.slice(dims, 0, 0, half)
+            layers.append(keep)
+            left = len(layers) - 1
+            right = Gather.slice(dims, 0, half, cin)
+            right.in_src = src  # both halves read the tensor the unit was given
+            layers.append(right)
+            d_b = conv(half, 1, 1, 0, half, h, w)
+            layers.append(Relu(d_b))
+            d_b = conv(half, 3, 1, 1, half, h, w, groups=half)
+            d_b = conv(half, 1, 1, 0, half, h, w)
+            layers.append(Relu(d_b))
+            cat = Concat([keep.out_dims, d_b], [left, len(layers) - 1])
+            layers.append(cat)
+            layers.append(Gather.channel_shuffle(cat.out_dims, 2))
         elif kind == "skip":
             skips.append((len(layers) - 1, dims))
         elif kind == "cat":
