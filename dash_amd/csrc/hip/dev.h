@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace dash {
 namespace dev {
 
@@ -193,6 +195,169 @@ __device__ __forceinline__ uint32_t chunk_digit(uint32_t& r, const ModC& m) {
     r = div32_q(r, m.q, m.mq, d);
 #endif
     return d;
+}
+
+// ---------------------------------------------------------------------------
+// Constant-modulus digit arithmetic. ModK<Q> holds, as compile-time constants, what make_modc (host_util.h)
+// derives for an odd modulus at run time, from the same formulas; hostutil::modk_table_ok ties the two together
+// when an evaluator uploads its ModC table. The kernels that know their modulus at compile time (the joint output
+// kernel per residue, the staged chain of a first-primes base) walk whole chunks with these forms:
+//  * two digits per extraction: one multiply-high (a quarter-rate instruction) by Q^2, the pair split with
+//    full-rate 24-bit multiplies;
+//  * reductions of small sums by one 24-bit multiply and a shift;
+//  * chunk compress with constant powers, in two halves of 24-bit multiply-adds joined by one 32-bit multiply.
+// Every hand-written multiply / shift reduction is checked over its whole operand range by a static_assert at
+// its use; where the range cannot be enumerated (r < D) the division is written as C++ division by the constant.
+constexpr uint32_t kFirstPrimes[12] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};
+constexpr uint32_t modk_pow(uint32_t q, int t) {
+    uint32_t v = 1;
+    for (int i = 0; i < t; ++i) v *= q;
+    return v;
+}
+constexpr uint32_t modk_n(uint32_t q) {  // core.h nr_comps for an odd modulus: the largest n with q^n < 2^128
+    u128 v = 1;
+    uint32_t n = 0;
+    while (v <= ~static_cast<u128>(0) / q) {
+        v *= q;
+        ++n;
+    }
+    return n;
+}
+constexpr uint32_t modk_c(uint32_t q) {  // make_modc: the most digits with q^c <= 2^DASH_CHUNK_BITS
+    uint64_t D = q;
+    uint32_t c = 1;
+    while (D * q <= (1ull << DASH_CHUNK_BITS)) {
+        D *= q;
+        ++c;
+    }
+    return c;
+}
+// Between the digit pairs of a written-out chunk: the instruction scheduler keeps the pairs in program order. Left
+// free it interleaves a whole chunk's LDS reads and digit extractions, and the kernels that were at their register
+// budget with the rolled loop spill (the K = 7 joint chain: 44 -> 208 B of scratch per lane).
+__device__ __forceinline__ void pair_fence() { __builtin_amdgcn_sched_barrier(0); }
+template <int I0, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I0 < N) {
+        f(std::integral_constant<int, I0>{});
+        static_for<I0 + 1, N>(f);
+    }
+}
+template <uint32_t Q>
+struct ModK {
+    static_assert(Q >= 3 && (Q & 1u) && Q < 256, "odd moduli below 2^8");
+    static constexpr uint32_t q = Q, QQ = Q * Q;
+    static constexpr uint32_t n = modk_n(Q), c = modk_c(Q), D = modk_pow(Q, static_cast<int>(c));
+    static constexpr uint32_t sh = static_cast<uint32_t>(__builtin_clz(D));
+    static constexpr uint32_t Dn = D << sh;
+    static constexpr uint32_t v = static_cast<uint32_t>(~0ull / static_cast<uint64_t>(Dn) - (1ull << 32));
+    static_assert(c >= 2 && D < (1u << 31) && sh >= 1, "the chunk divides as make_modc's (D < 2^31)");
+    // floor(x / Q) = (x * km) >> ks with one 24-bit multiply, for x < X: both factors below 2^24, the product
+    // below 2^32; checked for every x < X where it is used (div_ok)
+    static constexpr uint32_t ks = 20, km = (1u << ks) / Q + 1u;
+    template <uint32_t X>
+    static constexpr bool div_ok() {
+        if (X > (1u << 24) || km >= (1u << 24) || static_cast<uint64_t>(X) * km > (1ull << 32)) return false;
+        for (uint32_t x = 0; x < X; ++x)
+            if (((x * km) >> ks) != x / Q) return false;
+        return true;
+    }
+    template <uint32_t X>
+    static __device__ __forceinline__ uint32_t quot(uint32_t x) {  // floor(x / Q), x < X
+        static_assert(div_ok<X>(), "24-bit reciprocal of Q over the whole operand range");
+        return __umul24(x, km) >> ks;
+    }
+    // x - t Q for a result in [0, 2^23): one signed 24-bit multiply-add (v_mad_i32_i24). Written as x - umul24(t, Q)
+    // the compiler picks the 64-bit multiply-add, a quarter-rate instruction.
+    static __device__ __forceinline__ uint32_t msub(uint32_t x, uint32_t t) {
+        return static_cast<uint32_t>(__mul24(static_cast<int>(t), -static_cast<int>(Q)) + static_cast<int>(x));
+    }
+    template <uint32_t X>
+    static __device__ __forceinline__ uint32_t mod(uint32_t x) {  // x mod Q, x < X
+        return msub(x, quot<X>(x));
+    }
+    // the chunk remainder's next digit, r < D (chunk_digit's digit)
+    static __device__ __forceinline__ uint32_t digit(uint32_t& r) {
+        const uint32_t t = r / Q;
+        const uint32_t d = (r - __umul24(t, Q)) & 0xFFFFFFu;  // d < Q: the low 24 bits of the difference suffice
+        r = t;
+        return d;
+    }
+    // its next two digits, d0 then d1: rem = r mod Q^2 < 2^16 from the low 24 bits, split with 24-bit multiplies
+    static __device__ __forceinline__ void digit2(uint32_t& r, uint32_t& d0, uint32_t& d1) {
+        const uint32_t t = r / QQ;
+        const uint32_t rem = (r - __umul24(t, QQ)) & 0xFFFFFFu;
+        d1 = quot<QQ>(rem);
+        d0 = msub(rem, d1);
+        r = t;
+    }
+    // divmod128 with the modulus' constants: Q128 /= D, the remainder (a chunk of c digits) returned
+    static __device__ __forceinline__ uint32_t divmod(u128& Q128);
+    // Chunk compress, digits pushed bottom-up with a constant index T < CNT <= c: sum_t d_t Q^t as lo + Q^H hi,
+    // both halves sums of 24-bit multiply-adds (d < 2^24, Q^t < 2^24 for t < H), one 32-bit multiply to join.
+    template <int CNT>
+    struct Acc {
+        static constexpr int H = (CNT + 1) / 2;
+        static_assert(CNT >= 1 && CNT <= static_cast<int>(c) && modk_pow(Q, H > 0 ? H - 1 : 0) < (1u << 24), "half-chunk powers fit 24 bits");
+        uint32_t lo = 0, hi = 0;
+        template <int T>
+        __device__ __forceinline__ void push(uint32_t d) {  // d < Q
+            static_assert(T >= 0 && T < CNT, "digit index inside the chunk");
+            if constexpr (T < H) lo += __umul24(d, modk_pow(Q, T));
+            else hi += __umul24(d, modk_pow(Q, T - H));
+        }
+        __device__ __forceinline__ uint32_t value() const {
+            if constexpr (CNT > H) return lo + hi * modk_pow(Q, H);
+            else return lo;
+        }
+    };
+};
+template <uint32_t Q>
+__device__ __forceinline__ uint32_t ModK<Q>::divmod(u128& Q128) {
+    const uint32_t l3 = static_cast<uint32_t>(Q128 >> 96), l2 = static_cast<uint32_t>(Q128 >> 64);
+    const uint32_t l1 = static_cast<uint32_t>(Q128 >> 32), l0 = static_cast<uint32_t>(Q128);
+    constexpr uint32_t rs = 32u - sh;
+    const uint32_t u4 = l3 >> rs;
+    const uint32_t u3 = __builtin_amdgcn_alignbit(l3, l2, rs), u2 = __builtin_amdgcn_alignbit(l2, l1, rs);
+    const uint32_t u1 = __builtin_amdgcn_alignbit(l1, l0, rs), u0 = l0 << sh;
+    uint32_t r, q3 = 0, q2 = 0;
+    if (l3 | l2) {
+        q3 = mg_step(u4, u3, Dn, v, r);
+        q2 = mg_step(r, u2, Dn, v, r);
+    } else {
+        r = u2;  // as divmod128: no quotient bits above 2^64
+    }
+    const uint32_t q1 = mg_step(r, u1, Dn, v, r);
+    const uint32_t q0 = mg_step(r, u0, Dn, v, r);
+    Q128 = (static_cast<u128>((static_cast<uint64_t>(q3) << 32) | q2) << 64) | ((static_cast<uint64_t>(q1) << 32) | q0);
+    return r >> sh;
+}
+// Run f(ModK<p>{}) for the odd primes the constant forms are compiled for; false (f not run) for any other p.
+// p is block-uniform where this is used: one scalar branch per block.
+// WIDE adds the other odd primes of the shipped bases (up to 37): the helpers' test kernel only.
+constexpr uint32_t kModKMax = 17;
+template <bool WIDE = false, class F>
+__device__ __forceinline__ bool modk_dispatch(uint32_t p, F&& f) {
+    switch (p) {
+        case 3: f(ModK<3>{}); return true;
+        case 5: f(ModK<5>{}); return true;
+        case 7: f(ModK<7>{}); return true;
+        case 11: f(ModK<11>{}); return true;
+        case 13: f(ModK<13>{}); return true;
+        case 17: f(ModK<17>{}); return true;
+        default: break;
+    }
+    if constexpr (WIDE) {
+        switch (p) {
+            case 19: f(ModK<19>{}); return true;
+            case 23: f(ModK<23>{}); return true;
+            case 29: f(ModK<29>{}); return true;
+            case 31: f(ModK<31>{}); return true;
+            case 37: f(ModK<37>{}); return true;
+            default: break;
+        }
+    }
+    return false;
 }
 
 // top digit needs a final reduction (matches host decompress for any payload)

@@ -326,6 +326,99 @@ struct ChunkKey {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Constant-modulus forms of the two chunk-major walks above (MK = ModK<p>, dev.h), for kernels whose block knows
+// its residue: the label width, the chunk length and the last chunk's length are constants, so the chunk loop
+// stays rolled and a chunk's digits are written out with no loop bookkeeping, two digits per extraction. The
+// same digits, rows and key as ChunkKey::walk / lds_mult_chunks (tests/test_gpu_const_mod.py).
+
+// rows [0, CNT) of col: one chunk of ChunkKey::walk (not payload); returns the chunk's value sum_t Y_t Q^t
+template <class MK, int BS, int CNT>
+__device__ __forceinline__ uint32_t rescale_chunk_k(uint8_t* col, uint32_t r, uint32_t inv) {
+    typename MK::template Acc<CNT> acc;
+    static_for<0, (CNT + 1) / 2>([&](auto tt) __attribute__((always_inline)) {
+        constexpr int t = 2 * decltype(tt)::value;
+        uint32_t p0, p1 = 0;
+        if constexpr (t + 1 < CNT) MK::digit2(r, p0, p1);
+        else p0 = MK::digit(r);
+        // S^-1 L + digit < (Q - 1)^2 + Q
+        const uint32_t v0 = MK::template mod<MK::QQ + 3 * MK::q>(__umul24(col[t * BS], inv) + p0);
+        col[t * BS] = static_cast<uint8_t>(v0);
+        acc.template push<t>(v0);
+        if constexpr (t + 1 < CNT) {
+            const uint32_t v1 = MK::template mod<MK::QQ + 3 * MK::q>(__umul24(col[(t + 1) * BS], inv) + p1);
+            col[(t + 1) * BS] = static_cast<uint8_t>(v1);
+            acc.template push<t + 1>(v1);
+        }
+        pair_fence();
+    });
+    return acc.value();
+}
+// ChunkKey::walk over a whole label of MK::n rows; returns the key compress(Y)
+template <class MK, int BS>
+__device__ __forceinline__ u128 rescale_walk_k(uint8_t* col, u128 P, uint32_t inv) {
+    constexpr int c = static_cast<int>(MK::c), n = static_cast<int>(MK::n), nfull = n / c, tail = n % c;
+    u128 C = 0, PW = 1;
+#pragma unroll 1
+    for (int ch = 0; ch < nfull; ++ch) {
+        const uint32_t r = MK::divmod(P);
+        C += PW * static_cast<u128>(rescale_chunk_k<MK, BS, c>(col + ch * c * BS, r, inv));
+        PW *= static_cast<u128>(MK::D);
+    }
+    if constexpr (tail > 0) {
+        const uint32_t r = MK::divmod(P);
+        C += PW * static_cast<u128>(rescale_chunk_k<MK, BS, tail>(col + nfull * c * BS, r, inv));
+    }
+    return C;
+}
+// rows [0, CNT) of col: one chunk of lds_mult_chunks. The digit sums stay below the bounds of mult_digit
+// (Q^2 + 3 Q, the Clip's second entry digit included) and leaky_digit ((Q - 1)(3 Q - 2)).
+template <class MK, int BS, int CNT, bool CLIP, bool LEAKY>
+__device__ __forceinline__ void mult_chunk_k(uint8_t* col, uint32_t rg, uint32_t re, uint32_t rc, uint32_t ypr,
+                                             uint32_t yl, uint32_t fc) {
+    constexpr uint32_t Q = MK::q;
+    auto one = [&](uint8_t& w, uint32_t g, uint32_t ev) {
+        const uint32_t x = w;
+        if constexpr (LEAKY)
+            w = static_cast<uint8_t>(MK::template mod<(Q - 1) * (3 * Q - 2) + 1>(__umul24(fc, ev + Q - g) + __umul24(yl, x)));
+        else
+            w = static_cast<uint8_t>(MK::template mod<MK::QQ + 3 * Q>(ev + __umul24(ypr, x) + Q - g));
+    };
+    static_for<0, (CNT + 1) / 2>([&](auto tt) __attribute__((always_inline)) {
+        constexpr int t = 2 * decltype(tt)::value;
+        uint32_t g0, g1 = 0, e0, e1 = 0, c0 = 0, c1 = 0;
+        if constexpr (t + 1 < CNT) {
+            MK::digit2(rg, g0, g1);
+            MK::digit2(re, e0, e1);
+            if constexpr (CLIP) MK::digit2(rc, c0, c1);
+        } else {
+            g0 = MK::digit(rg);
+            e0 = MK::digit(re);
+            if constexpr (CLIP) c0 = MK::digit(rc);
+        }
+        one(col[t * BS], g0, e0 + c0);
+        if constexpr (t + 1 < CNT) one(col[(t + 1) * BS], g1, e1 + c1);
+        pair_fence();
+    });
+}
+template <class MK, int BS, bool CLIP, bool LEAKY = false>
+__device__ __forceinline__ void lds_mult_chunks_k(uint8_t* col, u128 G, u128 E, u128 C, uint32_t ypr,
+                                                  LeakyLane lk = LeakyLane{0u, 0u}) {
+    static_assert(!(CLIP && LEAKY), "no leaky Clip");
+    constexpr int c = static_cast<int>(MK::c), n = static_cast<int>(MK::n), nfull = n / c, tail = n % c;
+    // leaky_mult: c ypr + b < Q^2
+    const uint32_t yl = LEAKY ? MK::template mod<MK::QQ>(__umul24(lk.fc, ypr) + lk.fb) : 0u;
+#pragma unroll 1
+    for (int ch = 0; ch < nfull; ++ch) {
+        const uint32_t rg = MK::divmod(G), re = MK::divmod(E), rc = CLIP ? MK::divmod(C) : 0u;
+        mult_chunk_k<MK, BS, c, CLIP, LEAKY>(col + ch * c * BS, rg, re, rc, ypr, yl, lk.fc);
+    }
+    if constexpr (tail > 0) {
+        const uint32_t rg = MK::divmod(G), re = MK::divmod(E), rc = CLIP ? MK::divmod(C) : 0u;
+        mult_chunk_k<MK, BS, tail, CLIP, LEAKY>(col + nfull * c * BS, rg, re, rc, ypr, yl, lk.fc);
+    }
+}
+
 // Grouped walk: row c < n becomes f(c, row c), G rows per group (load: rows are read; else f gets 0). The
 // group's LDS reads are issued together, one exposed latency per group instead of per digit: a digit's
 // write-back may alias the next digit's read, so the compiler cannot hoist it.

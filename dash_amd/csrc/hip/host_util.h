@@ -146,6 +146,41 @@ inline dev::ModC make_modc(int q) {
     return m;
 }
 
+// The compile-time constants of dev::ModK<q> in ModC's fields (q, n, c, D, Dn, v, sh; the rest zero), for the odd
+// primes up to 37; false for any other q. The constant-modulus kernels use these, the generic ones make_modc's.
+inline bool modk_constants(int q, dev::ModC& m) {
+    m = dev::ModC{};
+    auto fill = [&](auto mk) {
+        using MK = decltype(mk);
+        m.q = MK::q; m.n = MK::n; m.c = MK::c; m.D = MK::D; m.Dn = MK::Dn; m.v = MK::v; m.sh = MK::sh;
+    };
+    switch (q) {
+        case 3: fill(dev::ModK<3>{}); return true;
+        case 5: fill(dev::ModK<5>{}); return true;
+        case 7: fill(dev::ModK<7>{}); return true;
+        case 11: fill(dev::ModK<11>{}); return true;
+        case 13: fill(dev::ModK<13>{}); return true;
+        case 17: fill(dev::ModK<17>{}); return true;
+        case 19: fill(dev::ModK<19>{}); return true;
+        case 23: fill(dev::ModK<23>{}); return true;
+        case 29: fill(dev::ModK<29>{}); return true;
+        case 31: fill(dev::ModK<31>{}); return true;
+        case 37: fill(dev::ModK<37>{}); return true;
+        default: return false;
+    }
+}
+// The load-time tie between the two: every modulus the constant forms are compiled for (dev::modk_dispatch,
+// kModKMax) has the constants the ModC table gives the generic forms.
+inline bool modk_table_ok() {
+    for (int q = 3; q <= static_cast<int>(dev::kModKMax); q += 2) {
+        dev::ModC k;
+        if (!modk_constants(q, k)) continue;
+        const dev::ModC m = make_modc(q);
+        if (k.q != m.q || k.n != m.n || k.c != m.c || k.D != m.D || k.Dn != m.Dn || k.v != m.v || k.sh != m.sh) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 

@@ -156,6 +156,8 @@ struct MrsArgs {
     u128* ks;         // mode 1, a Clip's sign: [B][N] the sign label itself (with ny = 0: no y-row pads); else null
     int qpack;        // k_mrs_chain_q: bit 0 four digits per quad reduction (moduli <= 63); >> 1: positions
                       // I < that value take chunk-split keys
+    int cmod;         // joint output kernels (k_rescale_*_out_t): 1 takes the constant-modulus walks (launch.h
+                      // const_mod_on; the launcher sets it at every launch)
 };
 
 // Clip multiply (gadgets.h ClipPlan): the two sign labels, the half gates' tables and the cap rows

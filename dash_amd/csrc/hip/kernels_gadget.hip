@@ -1473,17 +1473,33 @@ __device__ __forceinline__ void rescale_relu_out_t_body(uint8_t* stg, const MrsA
         const uint32_t pd0 = chunk_digit(r, m);
         Graw = grow[modq(static_cast<uint32_t>(stg[tid]) * inv + pd0, m)];
     }
-    // pass 1: Y_j = S^-1 L_j + digits(P) in place, key = compress(Y_j) summed per chunk
-    ChunkKey ck;
-    ck.init(P);
-    ck.walk<kRrtBS>(col, n, inv, false, m);
-    const u128 G = Graw - hard_pad(ck.C, gate, tw_sub(kTwMmg, j), 0);
+    // pass 1: Y_j = S^-1 L_j + digits(P) in place, key = compress(Y_j) summed per chunk. The residue is
+    // block-uniform: with a.cmod the odd primes up to kModKMax take the constant-modulus walks (one scalar branch
+    // per pass), every other modulus the run-time forms
+    u128 key = 0;
+    const bool kform = a.cmod && modk_dispatch(static_cast<uint32_t>(p), [&](auto mk) __attribute__((always_inline)) {
+        key = rescale_walk_k<decltype(mk), kRrtBS>(col, P, inv);
+    });
+    if (!kform) {
+        ChunkKey ck;
+        ck.init(P);
+        ck.walk<kRrtBS>(col, n, inv, false, m);
+        key = ck.C;
+    }
+    const u128 G = Graw - hard_pad(key, gate, tw_sub(kTwMmg, j), 0);
     // pass 2: relu_j = E + ypr Y_j - G in place
-    if (LEAKY)
-        lds_mult_chunks<kRrtBS, false, true>(col, n, G, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m), p, m,
-                                             leaky_lane(lk, e, j, k));
-    else
-        lds_mult_chunks<kRrtBS, false>(col, n, G, o.Eraw - o.HS, 0, mini_mult(o.mini, o.cS, o.HM, p, m), p, m);
+    const u128 E = o.Eraw - o.HS;
+    const uint32_t ypr = mini_mult(o.mini, o.cS, o.HM, p, m);
+    if (kform) {
+        modk_dispatch(static_cast<uint32_t>(p), [&](auto mk) __attribute__((always_inline)) {
+            if constexpr (LEAKY) lds_mult_chunks_k<decltype(mk), kRrtBS, false, true>(col, G, E, 0, ypr, leaky_lane(lk, e, j, k));
+            else lds_mult_chunks_k<decltype(mk), kRrtBS, false>(col, G, E, 0, ypr);
+        });
+    } else if (LEAKY) {
+        lds_mult_chunks<kRrtBS, false, true>(col, n, G, E, 0, ypr, p, m, leaky_lane(lk, e, j, k));
+    } else {
+        lds_mult_chunks<kRrtBS, false>(col, n, G, E, 0, ypr, p, m);
+    }
     __syncthreads();
     lds_store_rows<kRrtBS>(Y, stg, N, e0, 0, n);
 }
@@ -1504,7 +1520,7 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_leaky_out_t(MrsArgs a, SignA
 // (mode 2, ca.klo) and the Clip's upper sign chain (mode 1, ca.khi), which both ran on the rescale's input; the
 // lane derives the pads of u and of s_hi (clip_keyed) while the rows are staged. Pass 2 adds the cap stream;
 // residue 0 is (G ^ E ^ C) ^ (ypr ? P : 0) on 128-bit registers. The rescaled label is never written.
-__global__ __launch_bounds__(kRrtBS) void k_rescale_clip_out_t(MrsArgs a, ClipArgs ca, Act x, Act y, const ModC* mc) {
+__global__ __launch_bounds__(kRrtBS, 5) void k_rescale_clip_out_t(MrsArgs a, ClipArgs ca, Act x, Act y, const ModC* mc) {
     __shared__ __attribute__((aligned(16))) uint8_t stg[kRrtCap * kRrtBS];
     const int j = blockIdx.y, b = blockIdx.z;
     const int64_t N = a.N;
@@ -1561,12 +1577,25 @@ __global__ __launch_bounds__(kRrtBS) void k_rescale_clip_out_t(MrsArgs a, ClipAr
     }
     const ClipLane c = clip_keyed(ca, j, b, e, p, m);
     // pass 1: Y_j = S^-1 L_j + digits(P) in place, key = compress(Y_j) summed per chunk
-    ChunkKey ck;
-    ck.init(P);
-    ck.walk<kRrtBS>(col, n, inv, false, m);
-    const u128 G = Graw - hard_pad(ck.C, gate, tw_sub(kTwMmg, j), 0);
+    // (constant-modulus walks as in rescale_relu_out_t_body)
+    u128 key = 0;
+    const bool kform = a.cmod && modk_dispatch(static_cast<uint32_t>(p), [&](auto mk) __attribute__((always_inline)) {
+        key = rescale_walk_k<decltype(mk), kRrtBS>(col, P, inv);
+    });
+    if (!kform) {
+        ChunkKey ck;
+        ck.init(P);
+        ck.walk<kRrtBS>(col, n, inv, false, m);
+        key = ck.C;
+    }
+    const u128 G = Graw - hard_pad(key, gate, tw_sub(kTwMmg, j), 0);
     // pass 2: clip_j = E + C + ypr Y_j - G in place
-    lds_mult_chunks<kRrtBS, true>(col, n, G, c.E, c.C, c.ypr, p, m);
+    if (kform)
+        modk_dispatch(static_cast<uint32_t>(p), [&](auto mk) __attribute__((always_inline)) {
+            lds_mult_chunks_k<decltype(mk), kRrtBS, true>(col, G, c.E, c.C, c.ypr);
+        });
+    else
+        lds_mult_chunks<kRrtBS, true>(col, n, G, c.E, c.C, c.ypr, p, m);
     __syncthreads();
     lds_store_rows<kRrtBS>(Y, stg, N, e0, 0, n);
 }
@@ -1676,6 +1705,22 @@ __global__ __launch_bounds__(256) void k_rescale_relu_out_q(MrsArgs a, SignArgs 
     }
 }
 
+// Constant-modulus kernel forms (launch.h): the mode, initially DASH_CONST_MOD or kConstModDefault, and the counts
+// of host-side launches that took a constant form (the launch log's lines are the same for both forms)
+static std::atomic<int>& const_mod_state() {
+    static std::atomic<int> mode{[] {
+        const char* e = std::getenv("DASH_CONST_MOD");
+        const int v = e ? std::atoi(e) : kConstModDefault;
+        return v < 0 ? 0 : (v > 2 ? 2 : v);
+    }()};
+    return mode;
+}
+static std::atomic<long> g_cmod_chain{0}, g_cmod_out{0};
+int const_mod_mode() { return const_mod_state().load(std::memory_order_relaxed); }
+void set_const_mod(int mode) { const_mod_state().store(mode < 0 ? 0 : (mode > 2 ? 2 : mode), std::memory_order_relaxed); }
+void const_mod_count(bool chain) { (chain ? g_cmod_chain : g_cmod_out).fetch_add(1, std::memory_order_relaxed); }
+long const_mod_launches(bool chain) { return (chain ? g_cmod_chain : g_cmod_out).load(std::memory_order_relaxed); }
+
 // The joint-fuse mode (launch.h): -1 auto, 0 off, 1 on; the DASH_JOINT_FUSE environment value is its initial state
 static std::atomic<int>& joint_fuse_state() {
     static std::atomic<int> mode{[] {
@@ -1719,7 +1764,10 @@ void launch_rescale_relu_out(const MrsArgs& a, const SignArgs& sa, const Act& x,
     if (rro_stage && B >= 3 && stage_ok(a.N, kRrtBS) && rrt_fits(a)) {  // throughput batches (own log name)
         const dim3 gt(static_cast<unsigned>((a.N + kRrtBS - 1) / kRrtBS), a.crt.k, B);
         if (launch_log_on()) launch_log_add("relu_out.tput", gt, dim3(kRrtBS));
-        hipLaunchKernelGGL(k_rescale_relu_out_t, gt, dim3(kRrtBS), 0, st, a, sa, x, y, gtab, etab, mc);
+        MrsArgs ak = a;
+        ak.cmod = const_mod_on() ? 1 : 0;
+        if (ak.cmod) const_mod_count(false);
+        hipLaunchKernelGGL(k_rescale_relu_out_t, gt, dim3(kRrtBS), 0, st, ak, sa, x, y, gtab, etab, mc);
         return;
     }
     if (rro_stage && stage_ok(a.N, kRroBS)) {
@@ -1745,7 +1793,10 @@ void launch_rescale_leaky_out(const MrsArgs& a, const SignArgs& sa, const LeakyT
     if (!out_quad_fits(a, B) && rro_stage && B >= 3 && stage_ok(a.N, kRrtBS) && rrt_fits(a)) {
         const dim3 gt(static_cast<unsigned>((a.N + kRrtBS - 1) / kRrtBS), a.crt.k, B);
         if (launch_log_on()) launch_log_add("leaky_out.tput", gt, dim3(kRrtBS));
-        hipLaunchKernelGGL(k_rescale_leaky_out_t, gt, dim3(kRrtBS), 0, st, a, sa, lk, x, y, gtab, etab, mc);
+        MrsArgs ak = a;
+        ak.cmod = const_mod_on() ? 1 : 0;
+        if (ak.cmod) const_mod_count(false);
+        hipLaunchKernelGGL(k_rescale_leaky_out_t, gt, dim3(kRrtBS), 0, st, ak, sa, lk, x, y, gtab, etab, mc);
         return;
     }
     launch_rescale_mrs_out(a, x, B, mc, g, st);
@@ -1773,7 +1824,10 @@ void launch_rescale_clip_out(const MrsArgs& a, const ClipArgs& ca, const Act& x,
     if (B >= 3 && stage_ok(a.N, kRrtBS) && rrt_fits(a)) {
         const dim3 gt(static_cast<unsigned>((a.N + kRrtBS - 1) / kRrtBS), a.crt.k, B);
         if (launch_log_on()) launch_log_add("clip_out.tput", gt, dim3(kRrtBS));
-        hipLaunchKernelGGL(k_rescale_clip_out_t, gt, dim3(kRrtBS), 0, st, a, ca, x, y, mc);
+        MrsArgs ak = a;
+        ak.cmod = const_mod_on() ? 1 : 0;
+        if (ak.cmod) const_mod_count(false);
+        hipLaunchKernelGGL(k_rescale_clip_out_t, gt, dim3(kRrtBS), 0, st, ak, ca, x, y, mc);
         return;
     }
     launch_rescale_mrs_out(a, x, B, mc, g, st);

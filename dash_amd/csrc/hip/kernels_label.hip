@@ -204,6 +204,60 @@ __global__ __launch_bounds__(256) void k_codec_test(const int16_t* L, int64_t N,
     if (f.finish() != C) decomp[e] = -1;
 }
 
+// The constant-modulus digit helpers (dev.h ModK<q>) on chunk remainders r[e] < D, kModkTestRow words per element:
+// [0, c) the digits by digit2 (a last single digit where c is odd), [20, 20 + c) the digits by digit, [40] the
+// digits recompressed (Acc<c>), [41] mod<Q^2 + 3Q> of r mod (Q^2 + 3Q), [42] the remainder and [43, 47) the
+// quotient of divmod on r (2^96 + 2^45 + 1) mod 2^128; [48 + I - 1] mod<(I + 1) Q> of r mod ((I + 1) Q) for
+// I = 1 .. 6 (the chain's lazy fold), [54] mod<(Q - 1)(3 Q - 2) + 1> (the leaky digit) and [55] mod<Q^2> (the
+// leaky multiplier) of r mod their ranges, [56] the remainder and [57, 59) the quotient of divmod on r (2^32 + 1),
+// a numerator below 2^64 (the two-step branch); [63] 1 when q has no constant form.
+template <class MK>
+__device__ __forceinline__ void modk_test_one(uint32_t r, uint32_t* o) {
+    constexpr int c = static_cast<int>(MK::c);
+    static_assert(c <= 20, "row layout");
+    uint32_t rr = r;
+    typename MK::template Acc<c> acc;
+    static_for<0, (c + 1) / 2>([&](auto tt) __attribute__((always_inline)) {
+        constexpr int t = 2 * decltype(tt)::value;
+        uint32_t d0, d1 = 0;
+        if constexpr (t + 1 < c) MK::digit2(rr, d0, d1);
+        else d0 = MK::digit(rr);
+        o[t] = d0;
+        acc.template push<t>(d0);
+        if constexpr (t + 1 < c) {
+            o[t + 1] = d1;
+            acc.template push<t + 1>(d1);
+        }
+    });
+    o[40] = acc.value();
+    rr = r;
+    for (int t = 0; t < c; ++t) o[20 + t] = MK::digit(rr);
+    constexpr uint32_t X = MK::QQ + 3 * MK::q;
+    o[41] = MK::template mod<X>(r % X);
+    u128 P = static_cast<u128>(r) * ((static_cast<u128>(1) << 96) + (static_cast<u128>(1) << 45) + 1);
+    o[42] = MK::divmod(P);
+    for (int w = 0; w < 4; ++w) o[43 + w] = static_cast<uint32_t>(P >> (32 * w));
+    static_for<1, 7>([&](auto ii) __attribute__((always_inline)) {
+        constexpr uint32_t I = decltype(ii)::value, XI = (I + 1) * MK::q;
+        o[48 + I - 1] = MK::template mod<XI>(r % XI);
+    });
+    constexpr uint32_t XL = (MK::q - 1) * (3 * MK::q - 2) + 1;
+    o[54] = MK::template mod<XL>(r % XL);
+    o[55] = MK::template mod<MK::QQ>(r % MK::QQ);
+    u128 S = static_cast<u128>(r) * ((static_cast<u128>(1) << 32) + 1);  // < 2^64
+    o[56] = MK::divmod(S);
+    o[57] = static_cast<uint32_t>(S);
+    o[58] = static_cast<uint32_t>(S >> 32);
+}
+__global__ __launch_bounds__(256) void k_modk_test(int q, const uint32_t* r, int64_t N, uint32_t* out) {
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    uint32_t* o = out + e * kModkTestRow;
+    const uint32_t re = r[e];
+    const bool known = modk_dispatch<true>(static_cast<uint32_t>(q), [&](auto mk) __attribute__((always_inline)) { modk_test_one<decltype(mk)>(re, o); });
+    if (!known) o[kModkTestRow - 1] = 1u;
+}
+
 static inline dim3 g1(int64_t n, int y, int z) { return dim3(static_cast<unsigned>((n + 255) / 256), y, z); }
 static inline int64_t nmax(const CrtInfo& c) {
     int m = 0;
@@ -514,6 +568,9 @@ void launch_hard_test(const u128* key, const uint64_t* gate, const uint32_t* sub
                       int64_t n, hipStream_t st) {
     hipLaunchKernelGGL(k_hard_test, dim3(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 1024))), dim3(256), 0,
                        st, key, gate, sub, blk, out, n);
+}
+void launch_modk_test(int q, const uint32_t* r, int64_t N, uint32_t* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_modk_test, g1(N, 1, 1), dim3(256), 0, st, q, r, N, out);
 }
 void launch_codec_test(const int16_t* labels, int64_t N, int q, const ModC* mc, u128* comp, int16_t* decomp,
                        hipStream_t st) {

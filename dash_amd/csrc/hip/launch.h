@@ -43,6 +43,30 @@ bool joint_fuse(int64_t N, int B);  // the mode applied to the rule
 bool leaky_fuse(int64_t N, int B);
 bool clip_fuse_pick(int64_t N, int B);
 bool clip_fuse(int64_t N, int B);
+// Constant-modulus kernel forms (dev.h ModK). Mode 0: none, the run-time-modulus forms of the same build (A/B on one
+// device); 1: the joint output kernels' per-residue walks; 2: also the staged chain of a first-primes base of 7
+// residues. The DASH_CONST_MOD environment value is the initial mode, kConstModDefault without one. The chain's
+// form is opt-in: it spills more than the generic chain and was not faster (profiles/ab/const_mod/README.md). The
+// mode is read at every host-side launch; an evaluator's launches are frozen when its graph is captured, so set it
+// before the evaluator's first run. Results are bit-identical in every mode. const_mod_launches counts the
+// host-side launches that took a constant form (chain: the staged chain, else an output kernel): the launch log's
+// lines do not tell the forms apart. (Defined in kernels_gadget.hip.)
+constexpr int kConstModDefault = 1;
+int const_mod_mode();
+void set_const_mod(int mode);
+inline bool const_mod_on() { return const_mod_mode() >= 1; }
+inline bool const_mod_chain() { return const_mod_mode() >= 2; }
+void const_mod_count(bool chain);
+long const_mod_launches(bool chain);
+// The staged chain's rule (pure host arithmetic): the base is the first 7 primes, the one K whose constant-modulus
+// chain is compiled (mrs_chain.h kChainFpK). The joint output kernels need no rule: they dispatch per residue.
+constexpr int kChainFpK = 7;  // the headline base; another K costs its chain unit's build time again (docs/BUILD.md)
+inline bool chain_const_mod_pick(const int* p, int k) {
+    if (k != kChainFpK) return false;
+    for (int r = 0; r < k; ++r)
+        if (p[r] != static_cast<int>(kFirstPrimes[r])) return false;
+    return true;
+}
 // Launch log: off by default (one relaxed load per host-side launch, nothing under graph replay, where no picker
 // runs). When on, every picker appends the form it launched as "<form> grid=(x,y,z) block=n".
 extern std::atomic<bool> g_launch_log_on;
@@ -150,6 +174,9 @@ void launch_aes_bench(u128* out, int blocks, int iters, const AesGlobals& g, hip
 void launch_aes_test(const u128* in, u128* out, int64_t n, const AesGlobals& g, hipStream_t st);
 void launch_hard_test(const u128* key, const uint64_t* gate, const uint32_t* sub, const uint32_t* blk, u128* out,
                       int64_t n, hipStream_t st);
+// dev.h ModK<q>'s helpers on N chunk remainders r (k_modk_test): kModkTestRow zero-initialised words per element
+constexpr int kModkTestRow = 64;
+void launch_modk_test(int q, const uint32_t* r, int64_t N, uint32_t* out, hipStream_t st);
 void launch_codec_test(const int16_t* labels, int64_t N, int q, const ModC* mc, u128* comp, int16_t* decomp,
                        hipStream_t st);
 

@@ -332,8 +332,43 @@ constexpr int kStageU = DASH_STAGE_U;
 #define DASH_STAGE_RD 4  // LDS component reads batched per lane
 #endif
 constexpr int kStageRd = DASH_STAGE_RD;
-// one position of k_mrs_chain_s, I a compile-time constant (constant stream counts and pair indices)
-template <int K, int MODE, int I>
+// One chunk of CNT digits of position I's key with a constant modulus (MK = ModK<p>, dev.h): sc is the lane's
+// column of the chunk's staged rows, rr the I payload streams' chunk remainders. Two digits per extraction from
+// every stream; a position's I stream digits fold lazily, d = L + I Q - sum(s) in [I, (I + 1) Q), with one
+// reduction per key digit instead of a compare-select per stream. Returns the chunk's value sum_t d_t Q^t, the
+// chunk's first digit in d0.
+template <class MK, int I, int CNT>
+__device__ __forceinline__ uint32_t chain_chunk_k(const uint8_t* sc, bool valid, uint32_t (&rr)[I > 0 ? I : 1], uint32_t& d0) {
+    typename MK::template Acc<CNT> acc;
+    static_for<0, (CNT + 1) / 2>([&](auto tt) __attribute__((always_inline)) {
+        constexpr int t = 2 * decltype(tt)::value;
+        constexpr bool two = t + 1 < CNT;
+        uint32_t s0 = 0, s1 = 0;
+        static_for<0, I>([&](auto ll) __attribute__((always_inline)) {
+            constexpr int l = decltype(ll)::value;
+            uint32_t a0, a1 = 0;
+            if constexpr (two) MK::digit2(rr[l], a0, a1);
+            else a0 = MK::digit(rr[l]);
+            s0 += a0;
+            s1 += a1;
+        });
+        uint32_t da = valid ? sc[t * kMrsBS] : 0u;  // spare lanes read no staged bytes
+        if constexpr (I > 0) da = MK::template mod<(I + 1) * MK::q>(da + I * MK::q - s0);
+        if constexpr (t == 0) d0 = da;
+        acc.template push<t>(da);
+        if constexpr (two) {
+            uint32_t db = valid ? sc[(t + 1) * kMrsBS] : 0u;
+            if constexpr (I > 0) db = MK::template mod<(I + 1) * MK::q>(db + I * MK::q - s1);
+            acc.template push<t + 1>(db);
+        }
+        pair_fence();
+    });
+    return acc.value();
+}
+// one position of k_mrs_chain_s, I a compile-time constant (constant stream counts and pair indices). FP: the base
+// is the first K primes (the launch checked it), so the position's modulus is the constant kFirstPrimes[r] and its
+// odd residues walk with the constant-modulus chunk above.
+template <int K, int MODE, int I, bool FP = false>
 __device__ __forceinline__ void chain_s_pos(const MrsArgs& a, uint64_t gate, const ModC* mc, const Act& x,
                                             uint8_t* stg, int b, int64_t N, int64_t e0, int tid, bool valid,
                                             const u128* row0, u128* PS, u128* psl, u128& acc, u128& sx) {
@@ -384,6 +419,52 @@ __device__ __forceinline__ void chain_s_pos(const MrsArgs& a, uint64_t gate, con
                     }
                 }
                 key = cf.finish();
+            } else if constexpr (FP) {
+                // the chunk-major walk below with the modulus, label width, chunk length and last chunk's length
+                // constant: the same passes of whole chunks; the pass and chunk loops stay rolled, a chunk's
+                // digits are written out (chain_chunk_k). The row gather starts after chunk 0.
+                using MK = ModK<kFirstPrimes[r]>;
+                constexpr int mcn = static_cast<int>(MK::c), nk = static_cast<int>(MK::n);
+                constexpr int PC = kMrsCap / mcn, nfull = nk / mcn, tail = nk % mcn;
+                static_assert(nfull >= 1 && PC >= 1, "a label holds a whole chunk, and so does a staging pass");
+                u128 Q[NQ];
+                chain_s_get<K, MODE, I, false>(Q, PS, psl, N);
+                u128 C = 0, PW = 1;
+#pragma unroll 1
+                for (int ch0 = 0; ch0 * mcn < nk; ch0 += PC) {  // one staging pass: chunks [ch0, ch0 + PC)
+                    const int p0 = ch0 * mcn, pcnt = min(PC * mcn, nk - p0);
+                    __syncthreads();
+                    lds_stage_rows<kMrsBS, kStageU, true>(stg, L, N, e0, p0, pcnt);
+                    __syncthreads();
+                    if (ch0 == 0) chain_s_get<K, MODE, I, true>(Q, PS, psl, N);
+                    const int fe = min(ch0 + PC, nfull);
+#pragma unroll 1
+                    for (int ch = ch0; ch < fe; ++ch) {
+                        uint32_t rr[NQ];
+#pragma unroll
+                        for (int l = 0; l < i; ++l) rr[l] = MK::divmod(Q[l]);
+                        uint32_t d0 = 0;
+                        const uint32_t v = chain_chunk_k<MK, I, mcn>(stg + (ch - ch0) * mcn * kMrsBS + tid, valid, rr, d0);
+                        if (ch == 0) {  // (uniform) the row index is the key's first digit
+                            col = d0;
+                            const u128* rowp = row0 + a.dig_off[i] + static_cast<int64_t>(col) * nt;
+                            pf0 = rowp[0];
+                            pf1 = rowp[nt - 1];
+                        }
+                        C += PW * static_cast<u128>(v);
+                        PW *= static_cast<u128>(MK::D);
+                    }
+                    if constexpr (tail > 0) {
+                        if (nfull < ch0 + PC) {  // the last, shorter chunk lies in this pass
+                            uint32_t rr[NQ];
+#pragma unroll
+                            for (int l = 0; l < i; ++l) rr[l] = MK::divmod(Q[l]);
+                            uint32_t d0 = 0;
+                            C += PW * static_cast<u128>(chain_chunk_k<MK, I, tail>(stg + (nfull - ch0) * mcn * kMrsBS + tid, valid, rr, d0));
+                        }
+                    }
+                }
+                key = C;
             } else {
                 // chunk-major walk (as k_mrs_chain_w): passes of whole chunks, one divmod per stream per chunk of
                 // m.c digits, wave-uniform digit loops, one compress flush per chunk
@@ -449,11 +530,11 @@ __device__ __forceinline__ void chain_s_pos(const MrsArgs& a, uint64_t gate, con
             chain_s_put<K, MODE, I>(E, PS, psl, N, valid, sx);
             if constexpr (MODE != 1) acc = add_packed(acc, E[K - 1 - i], a.hmask);
         }
-        chain_s_pos<K, MODE, I + 1>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, psl, acc, sx);
+        chain_s_pos<K, MODE, I + 1, FP>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, psl, acc, sx);
     }
 }
 
-template <int K, int MODE>
+template <int K, int MODE, bool FP = false>
 __global__ __launch_bounds__(kMrsBS, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_MINBLOCKS) void k_mrs_chain_s(
     MrsArgs a, Act x, const ModC* mc, const uint32_t* te0, const uint32_t* rk) {
     (void)te0;
@@ -473,7 +554,7 @@ __global__ __launch_bounds__(kMrsBS, MODE == 2 ? DASH_CHAIN2_WAVES : DASH_UA_MIN
         u128 acc = 0;
         u128 sx = 0;  // modes 1, 2: XOR of the payloads aimed at the sign position (reset per tile)
         const uint64_t gate = a.gate0 ^ static_cast<uint64_t>(e);
-        chain_s_pos<K, MODE, 0>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, psl, acc, sx);
+        chain_s_pos<K, MODE, 0, FP>(a, gate, mc, x, stg, b, N, e0, tid, valid, row0, PS, psl, acc, sx);
         if (MODE >= 1) {
             const ModC m = mc[a.crt.p[0]];
             const int n = static_cast<int>(m.n);
@@ -1252,6 +1333,22 @@ static inline bool mrs_staged(const MrsArgs& a, int B) {
 }
 
 
+// the staged chain, in its first-primes form (constant moduli) where the base and the build have it. Mode 1 (the
+// exact sign alone) keeps the generic form: its first-primes form needs 128 registers for the generic's 88, 4 waves
+// per SIMD for 5.
+template <int K, int MODE>
+static void launch_chain_s(const MrsArgs& a, const Act& x, dim3 gc, dim3 bc, const ModC* mc, const AesGlobals& g,
+                           hipStream_t st) {
+    if constexpr (K == kChainFpK && MODE != 1) {
+        if (const_mod_chain() && chain_const_mod_pick(a.crt.p, a.crt.k)) {
+            const_mod_count(true);
+            hipLaunchKernelGGL((k_mrs_chain_s<K, MODE, true>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_mrs_chain_s<K, MODE>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
+}
+
 // One chain launch for K residues: the wave-staged form for launches of at most one block per CU (batch-1
 // latency), the LDS-staged form for large ones, the per-lane form between; a.mode picks rescale / sign / joint.
 template <int K>
@@ -1263,15 +1360,15 @@ void launch_mrs_chain_k(const MrsArgs& a, const Act& x, int B, const ModC* mc, c
     if (!wl) chain_log(stg ? "staged" : "lane", K, a.mode == 1 || a.mode == 2 ? a.mode : 0, gc, bc);
     if (a.mode == 1) {
         if (wl) launch_chain_w<K, 1>(a, x, B, wl, mc, g, st);
-        else if (stg) hipLaunchKernelGGL((k_mrs_chain_s<K, 1>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
+        else if (stg) launch_chain_s<K, 1>(a, x, gc, bc, mc, g, st);
         else hipLaunchKernelGGL((k_mrs_chain<K, 1>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
     } else if (a.mode == 2) {
         if (wl) launch_chain_w<K, 2>(a, x, B, wl, mc, g, st);
-        else if (stg) hipLaunchKernelGGL((k_mrs_chain_s<K, 2>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
+        else if (stg) launch_chain_s<K, 2>(a, x, gc, bc, mc, g, st);
         else hipLaunchKernelGGL((k_mrs_chain<K, 2>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
     } else {
         if (wl) launch_chain_w<K, 0>(a, x, B, wl, mc, g, st);
-        else if (stg) hipLaunchKernelGGL((k_mrs_chain_s<K, 0>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
+        else if (stg) launch_chain_s<K, 0>(a, x, gc, bc, mc, g, st);
         else hipLaunchKernelGGL((k_mrs_chain<K, 0>), gc, bc, 0, st, a, x, mc, g.te0, g.rk);
     }
 }

@@ -1015,6 +1015,7 @@ void HipEvaluator::upload_constants() {
     const int maxmod = m0.h.max_mod;
     std::vector<ModC> mc(maxmod + 1);
     for (int q = 2; q <= maxmod; ++q) mc[q] = make_modc(q);
+    DASH_CHECK(modk_table_ok(), "dev::ModK constants differ from the ModC table");  // the constant-modulus kernels
     mc_ = upload(mc.data(), mc.size());
     auto te = make_te0();
     auto rk = fixed_round_key_words();
@@ -2862,6 +2863,50 @@ void register_hip_bindings(py::module_& m) {
         (void)hipFree(dte); (void)hipFree(dout);
         const double n = 2.0 * iters * blocks * 512.0;
         return py::make_tuple(ms, n / (ms * 1e-3));
+    });
+    // Constant-modulus kernel forms (launch.h const_mod_mode): 0 none, 1 the joint output kernels, 2 also the staged
+    // chain. Read at every host-side launch: set it before an evaluator's first run. hip_chain_const_mod_pick is
+    // the staged chain's rule on a base (host arithmetic only); hip_const_mod_launches counts the host-side launches
+    // that took a constant form, (staged chain, output kernels).
+    m.def("hip_set_const_mod", [](int mode) {
+        DASH_CHECK(mode >= 0 && mode <= 2, "hip_set_const_mod: mode must be 0 (off), 1 (output kernels) or 2 (and the chain)");
+        dev::set_const_mod(mode);
+    });
+    m.def("hip_const_mod", []() { return dev::const_mod_mode(); });
+    m.def("hip_const_mod_launches", []() {
+        return py::make_tuple(dev::const_mod_launches(true), dev::const_mod_launches(false));
+    });
+    m.def("hip_chain_const_mod_pick", [](const std::vector<int>& primes) {
+        return dev::chain_const_mod_pick(primes.data(), static_cast<int>(primes.size()));
+    });
+    // (q, n, c, D, Dn, v, sh) of dev::ModK<q> (None where q has no constant form) and of the ModC table's entry
+    m.def("hip_modk_constants", [](int q) -> py::object {
+        ModC k;
+        if (!modk_constants(q, k)) return py::none();
+        return py::make_tuple(k.q, k.n, k.c, k.D, k.Dn, k.v, k.sh);
+    });
+    m.def("hip_modc_constants", [](int q) {
+        DASH_CHECK(q >= 2 && q < (1 << 16), "hip_modc_constants: modulus out of range");
+        const ModC k = make_modc(q);
+        return py::make_tuple(k.q, k.n, k.c, k.D, k.Dn, k.v, k.sh);
+    });
+    m.def("hip_modk_digits", [](int q, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> r) {
+        // dev::ModK<q>'s helpers on chunk remainders r < D (k_modk_test): (N, kModkTestRow) uint32 rows
+        DASH_CHECK(r.ndim() == 1 && r.shape(0) >= 1, "expected a non-empty 1-d array");
+        const int64_t N = r.shape(0);
+        const size_t ob = static_cast<size_t>(N) * dev::kModkTestRow * 4;
+        struct Bufs {  // freed on every way out
+            uint32_t *r = nullptr, *out = nullptr;
+            ~Bufs() { (void)hipFree(r); (void)hipFree(out); }
+        } d;
+        HIPCHECK(hipMalloc(&d.r, N * 4));
+        HIPCHECK(hipMalloc(&d.out, ob));
+        HIPCHECK(hipMemcpy(d.r, r.data(), N * 4, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemset(d.out, 0, ob));
+        launch_modk_test(q, d.r, N, d.out, nullptr);
+        py::array_t<uint32_t> out({static_cast<py::ssize_t>(N), static_cast<py::ssize_t>(dev::kModkTestRow)});
+        HIPCHECK(hipMemcpy(out.mutable_data(), d.out, ob, hipMemcpyDeviceToHost));
+        return out;
     });
     m.def("hip_codec", [](py::array_t<int16_t, py::array::c_style | py::array::forcecast> labels, int q) {
         // labels (N, n) label-major -> (compressed (N,2) u64, decompressed (N, n))
