@@ -8,7 +8,7 @@ and a HIP/CDNA4 evaluator for gfx950 with RCCL batch data parallelism.
 """
 from .ir.bases import first_primes, get_mrs_base  # noqa: F401
 from .ir.circuit import Circuit  # noqa: F401
-from .ir.layers import (Add, ArgMax, BaseExtension, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Max,  # noqa: F401
+from .ir.layers import (Add, ArgMax, BaseExtension, Bilinear, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Max,  # noqa: F401
                         Gather, LeakyRelu, MatMul, MaxPool2d, MixedModMultLayer, Mul, MultLayer, PiecewiseLinear, Projection, Relu,
                         Rescale, Sign, SumPool2d, Upsample)
 from .ir.quant import QuantizationMethod  # noqa: F401

@@ -50,7 +50,7 @@ def _circuit_and_inputs(cfg):
         xq = [quantize_input(x, qm, -1, circuit.get_q_const()) for x in imgs]
     else:
         xq = [quantize_input(x, qm, qp, cfg.q_const) for x in imgs]
-        if any(l.name in ("clip", "argmax", "conv_transpose2d", "mul", "leaky_relu", "pwl", "matmul")
+        if any(l.name in ("clip", "argmax", "conv_transpose2d", "mul", "leaky_relu", "pwl", "matmul", "bilinear")
                for l in circuit.layers):
             # these layers exist in the hardened encoding only: track the ranges so that rescale="auto" can resolve
             # to the mixed-radix rescale (the legacy one cannot be hardened)

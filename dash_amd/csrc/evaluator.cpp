@@ -329,6 +329,14 @@ CrtLabels cpu_evaluate(const GarbledModel& m, const CrtLabels& inputs, int nt, s
                 cur = std::move(nxt);
                 break;
             }
+            case K_BILINEAR: {
+                // the same public map on the active labels (hardened only: zero-mod-p weights contribute 0)
+                DASH_CHECK(hard, "bilinear exists in the hardened encoding only");
+                const BilinearGeom G(g.p);
+                DASH_CHECK(G.in_size() == Nin, "bilinear input size mismatch");
+                cur = bilinear_labels(G, cur, nt);
+                break;
+            }
             case K_RELU:
             case K_LEAKY: {
                 if (trace) trace->relu_in[li] = cur;

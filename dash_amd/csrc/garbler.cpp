@@ -44,6 +44,7 @@ const char* kind_name(int kind) {
         case K_CONVT: return "conv_transpose2d";
         case K_UPSAMPLE: return "upsample";
         case K_GATHER: return "gather";
+        case K_BILINEAR: return "bilinear";
     }
     return "unknown";
 }
@@ -156,6 +157,68 @@ GatherGeom::GatherGeom(const Params& p, i64 Nin) : idx(&paramv(p, "idx")), od(&p
         DASH_CHECK((*idx)[o] >= 0 && (*idx)[o] < Nin,
                    "gather: index " + std::to_string((*idx)[o]) + " at position " + std::to_string(o) +
                        " lies outside the input of " + std::to_string(Nin));
+}
+
+BilinearGeom::BilinearGeom(const Params& p)
+    : y0(&paramv(p, "y0")), y1(&paramv(p, "y1")), ny(&paramv(p, "ny")), x0(&paramv(p, "x0")), x1(&paramv(p, "x1")),
+      nx(&paramv(p, "nx")) {
+    C = param1(p, "C");
+    H = param1(p, "H");
+    W = param1(p, "W");
+    OH = param1(p, "OH");
+    OW = param1(p, "OW");
+    by = param1(p, "by");
+    bx = param1(p, "bx");
+    const i64 lim = i64(1) << 31;
+    DASH_CHECK(C > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C < lim && H < lim && W < lim && OH < lim && OW < lim &&
+                   C * H < lim && C * H * W < lim && C * OH < lim && C * OH * OW < lim,
+               "bilinear: sizes must lie in [1, 2^31)");
+    DASH_CHECK(by >= 0 && by <= kMaxBits && bx >= 0 && bx <= kMaxBits, "bilinear: fraction bits must lie in [0, 8]");
+    auto axis = [](const char* name, const std::vector<i64>& i0, const std::vector<i64>& i1, const std::vector<i64>& n,
+                   i64 in, i64 out, i64 b) {
+        DASH_CHECK(static_cast<i64>(i0.size()) == out && static_cast<i64>(i1.size()) == out &&
+                       static_cast<i64>(n.size()) == out,
+                   std::string("bilinear: the ") + name + " tables do not have one entry per output position");
+        for (size_t o = 0; o < i0.size(); ++o) {
+            DASH_CHECK(i0[o] >= 0 && i0[o] < in && i1[o] >= 0 && i1[o] < in,
+                       std::string("bilinear: ") + name + " tap at position " + std::to_string(o) +
+                           " lies outside the input of " + std::to_string(in));
+            DASH_CHECK(n[o] >= 0 && n[o] <= (i64(1) << b),
+                       std::string("bilinear: ") + name + " weight " + std::to_string(n[o]) + " at position " +
+                           std::to_string(o) + " lies outside [0, 2^" + std::to_string(b) + "]");
+        }
+    };
+    axis("row", *y0, *y1, *ny, H, OH, by);
+    axis("column", *x0, *x1, *nx, W, OW, bx);
+}
+
+CrtLabels bilinear_labels(const BilinearGeom& G, const CrtLabels& cur, int nt) {
+    CrtLabels nxt;
+    for (size_t j = 0; j < cur.size(); ++j) {
+        const Labels& I = cur[j];
+        const i64 p = I.p;
+        DASH_CHECK(I.N == G.in_size(), "bilinear input size mismatch");
+        Labels O(I.p, G.out_size());
+        parallel_for(G.C * G.OH, [&](i64 b0, i64 b1) {
+            for (i64 r = b0; r < b1; ++r) {
+                const i64 c = r / G.OH, oy = r % G.OH;
+                const i64 w0y = G.wy(oy, 0, p), w1y = G.wy(oy, 1, p);
+                const i64 r0 = (c * G.H + (*G.y0)[static_cast<size_t>(oy)]) * G.W;
+                const i64 r1 = (c * G.H + (*G.y1)[static_cast<size_t>(oy)]) * G.W;
+                for (i64 ox = 0; ox < G.OW; ++ox) {
+                    const i64 c0 = (*G.x0)[static_cast<size_t>(ox)], c1 = (*G.x1)[static_cast<size_t>(ox)];
+                    const i64 w0x = G.wx(ox, 0, p), w1x = G.wx(ox, 1, p);
+                    const i64 w00 = w0y * w0x % p, w01 = w0y * w1x % p, w10 = w1y * w0x % p, w11 = w1y * w1x % p;
+                    const comp_t *a = I.at(r0 + c0), *b = I.at(r0 + c1), *d = I.at(r1 + c0), *e = I.at(r1 + c1);
+                    comp_t* y = O.at(r * G.OW + ox);
+                    for (int cc = 0; cc < I.n; ++cc)
+                        y[cc] = static_cast<comp_t>((w00 * a[cc] + w01 * b[cc] + w10 * d[cc] + w11 * e[cc]) % p);
+                }
+            }
+        }, nt);
+        nxt.push_back(std::move(O));
+    }
+    return nxt;
 }
 
 PoolGeom::PoolGeom(const Params& p) {
@@ -711,6 +774,7 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
     layer_ms_.assign(layers.size(), 0.0);
     // joint rescale + ReLU sign: the rescale leaves the sign base labels here (host) or in the GPU garbler
     bool sig_next = false;
+    bool sig_on_host = false;  // with a GPU garbler: that rescale garbled on the host, and so must the layer it signs
     Labels sig_host;
     // joint Clip: its upper sign's base labels and table, garbled at the rescale on that layer's input labels
     Labels shi_host;
@@ -769,8 +833,13 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
         // is present (the legacy rescale's sign base extension needs residue 0 = 2)
         const bool lin_kind = spec.kind == K_CONV || spec.kind == K_DENSE || spec.kind == K_SUMPOOL ||
                               spec.kind == K_ADD || spec.kind == K_CONCAT || spec.kind == K_CONVT ||
-                              spec.kind == K_UPSAMPLE || spec.kind == K_GATHER;
-        const bool on_gpu = gpu && (lin_kind || ((!hard || gpu_hardened()) &&
+                              spec.kind == K_UPSAMPLE || spec.kind == K_GATHER || spec.kind == K_BILINEAR;
+        // a mixed-radix rescale whose last table row exceeds the device's staging garbles on the host, and the ReLU /
+        // Clip that takes its sign from it follows (the sign's base labels then live on the host)
+        const bool mrs_on_host = mrs_rescale && gpu && !GpuGarbler::rescale_mrs_fits(crt_, param1(spec.p, "l"));
+        const bool follows_host = sig_in && sig_on_host;
+        sig_on_host = mrs_on_host && joint_out;
+        const bool on_gpu = gpu && !mrs_on_host && !follows_host && (lin_kind || ((!hard || gpu_hardened()) &&
                                     (spec.kind == K_RELU || spec.kind == K_SIGN || spec.kind == K_LEAKY ||
                                     spec.kind == K_MAXPOOL || spec.kind == K_MAX || spec.kind == K_BASEEXT ||
                                     spec.kind == K_CLIP || spec.kind == K_ARGMAX || spec.kind == K_PWL ||
@@ -1024,6 +1093,21 @@ GarbledModel Garbler::garble(const std::vector<LayerSpec>& layers, const std::ve
                     nxt.push_back(std::move(O));
                 }
                 cur = std::move(nxt);
+                break;
+            }
+            case K_BILINEAR: {
+                // free in the label domain: public multiples and sums of the zero labels, no tables, no constants,
+                // no draws. Hardened only: a zero-mod-p weight contributes 0 (the reference encoding would add Z_p,
+                // a count that differs per output position)
+                DASH_CHECK(hard, "bilinear exists in the hardened encoding only");
+                const BilinearGeom G(spec.p);
+                DASH_CHECK(G.in_size() == Nin, "bilinear input size mismatch");
+                dims = {G.C, G.OH, G.OW};
+                if (on_gpu) {
+                    gpu->bilinear(G, cur);
+                    break;
+                }
+                cur = bilinear_labels(G, cur, nt);
                 break;
             }
             case K_RELU:

@@ -3033,6 +3033,7 @@ GpuGarbler::GpuGarbler(const std::vector<int>& crt, const std::vector<int>& mrs,
     convt_hook() = &GpuGarbler::convt_dev;
     upsample_hook() = &GpuGarbler::upsample_dev;
     gather_hook() = &GpuGarbler::gather_dev;
+    bilinear_hook() = &GpuGarbler::bilinear_dev;
     Impl& I = *impl_;
     I.enter();
     I.c.hard = hardened ? 1 : 0;
@@ -4850,6 +4851,72 @@ void GpuGarbler::gather_dev(GpuGarbler& self, const std::vector<i64>& idx, CrtLa
     I.cur = std::move(y);
     I.cur_N = Nout;
     set_stale(cur, I.cur_mod, Nout);
+}
+
+// Bilinear (garbler.cpp K_BILINEAR): the zero labels through the evaluator's own stencil kernels (launch_bilinear,
+// one launch for all residues), as conv_run reuses launch_conv: the garbler's chunked int16 labels are unchunked
+// into component-major byte activations and the output chunked back. Hardened only, so no zero-label terms.
+void GpuGarbler::bilinear_dev(GpuGarbler& self, const BilinearGeom& G, CrtLabels& cur) {
+    Impl& I = *self.impl_;
+    I.enter();
+    I.check_cur(cur);
+    PhaseTrace tr_("bilinear");
+    DASH_CHECK(I.c.hard, "gpu garbler: bilinear exists in the hardened encoding only");
+    DASH_CHECK(G.in_size() == I.cur_N, "gpu garbler: bilinear input size mismatch");
+    const std::vector<int> mods = I.cur_mod;
+    const int k = static_cast<int>(mods.size());
+    DASH_CHECK(k <= kMaxRes, "gpu garbler: too many residues");
+    const int64_t Nin = I.cur_N, Nout = G.out_size();
+    dev::CrtInfo ci{};
+    ci.k = k;
+    for (int j = 0; j < k; ++j) {
+        DASH_CHECK(mods[j] <= dev::kActMaxModulus, "gpu garbler: bilinear residue modulus above 255");
+        ci.p[j] = mods[j];
+        ci.n[j] = nr_comps(mods[j]);
+        ci.prefix[j] = ci.sum;
+        ci.sum += mods[j];
+    }
+    dev::BilinearArgs a{};
+    const dev::BilinearTables t = dev::bilinear_tables(a, G, mods.data(), k);
+    a.rows = gg::dconst(t.rows.data(), t.rows.size());
+    a.cols = gg::dconst(t.cols.data(), t.cols.size());
+    a.wrow = gg::dconst(t.wrow.data(), t.wrow.size());
+    a.wcol = gg::dconst(t.wcol.data(), t.wcol.size());
+    std::vector<DevBlock> out = I.alloc_labels(mods, Nout);
+    std::vector<DevBlock> xin(mods.size()), yout(mods.size());
+    dev::Act x{}, y{};
+    x.N = Nin;
+    y.N = Nout;
+    dev::TrRes ti{}, to{};
+    ti.k = to.k = k;
+    bool dword = G.OW % 4 == 0;
+    for (int j = 0; j < k; ++j) {
+        const int n = ci.n[j];
+        xin[j].alloc(I.device, static_cast<size_t>(Nin) * n);
+        yout[j].alloc(I.device, static_cast<size_t>(Nout) * n);
+        ti.in[j] = I.cur[j].as<int16_t>();
+        ti.out[j] = xin[j].as<dev::act_t>();
+        ti.rows[j] = n;
+        ti.cols[j] = Nin;
+        to.in[j] = yout[j].as<dev::act_t>();
+        to.out[j] = out[j].as<int16_t>();
+        to.rows[j] = n;
+        to.cols[j] = Nout;
+        x.p[j] = xin[j].as<dev::act_t>();
+        y.p[j] = yout[j].as<dev::act_t>();
+        dword = dword && reinterpret_cast<uintptr_t>(y.p[j]) % 4 == 0;
+    }
+    dev::launch_unchunk_to_act_res(ti, gg::tl_st);
+    dev::launch_bilinear(a, dword, x, y, ci, 1, gg::tl_st);
+    dev::launch_chunk_from_act_res(to, gg::tl_st);
+    // xin / yout return to the block cache; later users are ordered behind these kernels on the stream
+    HIPCHECK(hipGetLastError());
+    std::vector<void*> tmp;
+    gg::end_layer(tmp);
+    tr_.mark("kernels");
+    I.cur = std::move(out);
+    I.cur_N = Nout;
+    set_stale(cur, mods, Nout);
 }
 
 // max pool / max (garbler.cpp K_MAXPOOL / K_MAX): the window values, then per tree level the pair differences,

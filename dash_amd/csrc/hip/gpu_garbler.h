@@ -146,6 +146,17 @@ class GpuGarbler {
         DASH_CHECK(gather_hook() != nullptr, "gpu garbler: gather is not linked in");
         gather_hook()(*this, idx, cur);
     }
+    // Bilinear (K_BILINEAR): cur = the layer's public two-tap stencil on the device cur, through the evaluator's own
+    // kernels (launch_bilinear). A hook as for upsample.
+    using BilinearFn = void (*)(GpuGarbler&, const BilinearGeom&, CrtLabels&);
+    static BilinearFn& bilinear_hook() {
+        static BilinearFn f = nullptr;
+        return f;
+    }
+    void bilinear(const BilinearGeom& G, CrtLabels& cur) {
+        DASH_CHECK(bilinear_hook() != nullptr, "gpu garbler: bilinear is not linked in");
+        bilinear_hook()(*this, G, cur);
+    }
     // max pool / max: window values, one ReLU-gadget tree level per call (relu_garble_elem on streams
     // 20 + 2 lv / 21 + 2 lv), then the reduced values become cur
     void maxpool_begin(const std::vector<std::vector<i64>>& win, CrtLabels& cur);
@@ -177,6 +188,19 @@ class GpuGarbler {
     // x and y enter the projection descriptors as input residues j and k + j of one 16-entry set: a product needs
     // 2 k <= 16, a square k <= 16. The host garbler takes the layers that do not fit.
     static bool mul_fits(int k, bool square) { return (square ? k : 2 * k) <= 16; }
+    // Mixed-radix rescale (gadgets.h RescaleMrsPlan): the emit kernel stages one element's last table row, T = 2^(l+1)
+    // colors by k targets, in LDS with its position map, bank indices, pad runs and two elements' key hashes. An upper
+    // estimate of that scope against the 64 KiB less the projection descriptors: k = 7 fits up to l = 8. A rescale
+    // beyond it (a Rescale(l + e) that absorbs pending scale bits) garbles on the host, byte-identical.
+    static bool rescale_mrs_fits(const std::vector<int>& crt, i64 l) {
+        if (l < 0 || l > 11) return false;
+        const i64 T = i64(2) << l, k = static_cast<i64>(crt.size());
+        i64 nb = 0;
+        for (int p : crt) nb += std::min<i64>(T, p);
+        const i64 per = T * 20 + nb * 16;
+        const i64 fixed = T * k * 6 + 16 + T * ((k + 3) / 4 + 1) * 4 + 4;
+        return 2 * per + fixed <= (i64(64) << 10) - 32 * 224;
+    }
     void mul(uint64_t layer, const MulPlan& mp, size_t src_idx, CrtLabels& cur, Array& g, Array& e) {
         DASH_CHECK(mul_hook() != nullptr, "gpu garbler: mul is not linked in");
         mul_hook()(*this, layer, mp, src_idx, cur, g, e);
@@ -249,6 +273,7 @@ class GpuGarbler {
     static void convt_dev(GpuGarbler& self, const ConvTGeom& G, const i64* w, size_t nw, uint64_t wh, CrtLabels& cur);
     static void upsample_dev(GpuGarbler& self, const UpGeom& G, CrtLabels& cur);
     static void gather_dev(GpuGarbler& self, const std::vector<i64>& idx, CrtLabels& cur);
+    static void bilinear_dev(GpuGarbler& self, const BilinearGeom& G, CrtLabels& cur);
     static void concat_saved_dev(GpuGarbler& self, const std::vector<size_t>& idx, CrtLabels& cur);
     static void clip_dev(GpuGarbler& self, uint64_t layer, const SignMrsPlan* pm, const SignPlan* pa, i64 lo, i64 hi,
                          CrtLabels& cur, Array* const (*st)[3], const std::vector<i64>* prefix, Array& mmg, Array& mme,

@@ -60,6 +60,102 @@ __global__ __launch_bounds__(256) void k_gather4(Act in, int64_t Nin, Act out, i
     }
 }
 
+// Bilinear layer (launch.h BilinearArgs): out[c][oy][ox] = sum over the two row and two column taps of
+// (wy_a wx_b) in[c][y_a][x_b] mod p_j, per component row. The weights are public, reduced mod p_j on the host; the
+// products wy wx stay unreduced: four terms of three factors below 256 fit the int32 accumulator, and one
+// reduction (div32_q, p_j is uniform over the block) closes each output.
+struct BilinearTap {
+    int x0, x1;
+    uint32_t w00, w01, w10, w11;
+};
+__device__ __forceinline__ BilinearTap bilinear_tap(int2 col, uint32_t wy, uint32_t wx) {
+    const uint32_t wy0 = wy & 255u, wy1 = wy >> 8, wx0 = wx & 255u, wx1 = wx >> 8;
+    return BilinearTap{col.x, col.y, wy0 * wx0, wy0 * wx1, wy1 * wx0, wy1 * wx1};
+}
+__device__ __forceinline__ uint32_t bilinear_acc(const BilinearTap& t, const act_t* r0, const act_t* r1) {
+    return t.w00 * r0[t.x0] + t.w01 * r0[t.x1] + t.w10 * r1[t.x0] + t.w11 * r1[t.x1];
+}
+
+// The byte form, one output per lane: grid (ceil(Nout*n_max/256), k, B)
+__global__ __launch_bounds__(256) void k_bilinear(Act in, Act out, BilinearArgs g, CrtInfo crt) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int n = crt.n[j];
+    const uint32_t p = static_cast<uint32_t>(crt.p[j]);
+    const int64_t Nin = static_cast<int64_t>(g.C) * g.H * g.W, Nout = static_cast<int64_t>(g.C) * g.OH * g.OW;
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= Nout * n) return;
+    const int64_t c = t / Nout, o = t % Nout;
+    const int ox = static_cast<int>(o % g.OW), r = static_cast<int>(o / g.OW), oy = r % g.OH, ch = r / g.OH;
+    const int2 ry = g.rows[oy];
+    const BilinearTap tp = bilinear_tap(g.cols[ox], g.wrow[static_cast<int64_t>(j) * g.OH + oy],
+                                        g.wcol[static_cast<int64_t>(j) * g.OWp + ox]);
+    const act_t* I = in.p[j] + (static_cast<int64_t>(b) * n + c) * Nin + static_cast<int64_t>(ch) * g.H * g.W;
+    uint32_t rem;
+    div32_q(bilinear_acc(tp, I + static_cast<int64_t>(ry.x) * g.W, I + static_cast<int64_t>(ry.y) * g.W), p, g.mq[j],
+            rem);
+    out.p[j][(static_cast<int64_t>(b) * n + c) * Nout + o] = static_cast<act_t>(rem);
+}
+
+// The dword form, four consecutive ox of one output row per lane: grid (ceil(Nout/1024), k, B). A lane loads its row
+// entry and its four column entries once (two 16-byte loads and one 8-byte load of the padded tables), forms the
+// sixteen tap weights, then walks the n_j component rows: sixteen byte loads from two input rows, four
+// accumulates and reductions, one dword store, 4 B per lane and coalesced. The input is re-read from L2 (it is
+// 1 / (fh fw) of the output); no LDS staging. Preconditions, checked by the planner: OW % 4 == 0 and out.p[j]
+// 4-byte aligned, so every row start (b n_j + c) Nout + (ch OH + oy) OW stays dword aligned.
+constexpr int kBilinearRows = 2;
+__global__ __launch_bounds__(256) void k_bilinear4(Act in, Act out, BilinearArgs g, CrtInfo crt) {
+    const int j = blockIdx.y, b = blockIdx.z;
+    const int n = crt.n[j];
+    const uint32_t p = static_cast<uint32_t>(crt.p[j]), mq = g.mq[j];
+    const int64_t Nin = static_cast<int64_t>(g.C) * g.H * g.W, Nout = static_cast<int64_t>(g.C) * g.OH * g.OW;
+    const int64_t o = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (o >= Nout) return;
+    const int ox = static_cast<int>(o % g.OW), r = static_cast<int>(o / g.OW), oy = r % g.OH, ch = r / g.OH;
+    const int2 ry = g.rows[oy];
+    const uint32_t wy = g.wrow[static_cast<int64_t>(j) * g.OH + oy];
+    const int4 ca = *reinterpret_cast<const int4*>(g.cols + ox), cb = *reinterpret_cast<const int4*>(g.cols + ox + 2);
+    const uint2 wc = *reinterpret_cast<const uint2*>(g.wcol + static_cast<int64_t>(j) * g.OWp + ox);
+    const BilinearTap tp[4] = {bilinear_tap(make_int2(ca.x, ca.y), wy, wc.x & 0xFFFFu),
+                               bilinear_tap(make_int2(ca.z, ca.w), wy, wc.x >> 16),
+                               bilinear_tap(make_int2(cb.x, cb.y), wy, wc.y & 0xFFFFu),
+                               bilinear_tap(make_int2(cb.z, cb.w), wy, wc.y >> 16)};
+    // the planner never passes one buffer as both (ping-pong buffers)
+    const act_t* __restrict__ s0 =
+        in.p[j] + static_cast<int64_t>(b) * n * Nin + (static_cast<int64_t>(ch) * g.H + ry.x) * g.W;
+    const act_t* __restrict__ s1 =
+        in.p[j] + static_cast<int64_t>(b) * n * Nin + (static_cast<int64_t>(ch) * g.H + ry.y) * g.W;
+    act_t* __restrict__ dst = out.p[j] + static_cast<int64_t>(b) * n * Nout + o;
+    auto row = [&](const act_t* r0, const act_t* r1) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t rem;
+            div32_q(bilinear_acc(tp[q], r0, r1), p, mq, rem);
+            v |= rem << (8 * q);
+        }
+        return v;
+    };
+    // kBilinearRows rows at a time, all their byte loads issued before the first store: act_t is a byte type, so
+    // the compiler would otherwise keep each row's loads behind the row before's store (as in k_gather4)
+    int c = 0;
+    for (; c + kBilinearRows <= n; c += kBilinearRows) {
+        uint32_t v[kBilinearRows];
+#pragma unroll
+        for (int q = 0; q < kBilinearRows; ++q) v[q] = row(s0 + q * Nin, s1 + q * Nin);
+#pragma unroll
+        for (int q = 0; q < kBilinearRows; ++q) *reinterpret_cast<uint32_t*>(dst + q * Nout) = v[q];
+        s0 += kBilinearRows * Nin;
+        s1 += kBilinearRows * Nin;
+        dst += kBilinearRows * Nout;
+    }
+    for (; c < n; ++c) {
+        *reinterpret_cast<uint32_t*>(dst) = row(s0, s1);
+        s0 += Nin;
+        s1 += Nin;
+        dst += Nout;
+    }
+}
+
 // d[..][o*ops+q] = v[..][o*cnt+2q+1] - v[..][o*cnt+2q]
 __global__ __launch_bounds__(256) void k_pair_diff(Act v, int64_t Nv, Act d, int64_t Nout, int ops, int cnt,
                                                    CrtInfo crt) {
@@ -279,6 +375,19 @@ void launch_gather(const Act& in, int64_t Nin, const Act& out, int64_t Nout, con
     }
     if (launch_log_on()) launch_log_add("gather.byte", g1(Nout * nmax(crt), crt.k, B), dim3(256));
     launch_copy_gather(in, Nin, out, Nout, idx8, crt, B, st);
+}
+void launch_bilinear(const BilinearArgs& g, bool dword, const Act& in, const Act& out, const CrtInfo& crt, int B,
+                     hipStream_t st) {
+    const int64_t Nout = static_cast<int64_t>(g.C) * g.OH * g.OW;
+    if (dword) {
+        const dim3 grid(static_cast<unsigned>((Nout + 1023) / 1024), crt.k, B);
+        if (launch_log_on()) launch_log_add("bilinear.dword", grid, dim3(256));
+        hipLaunchKernelGGL(k_bilinear4, grid, dim3(256), 0, st, in, out, g, crt);
+        return;
+    }
+    const dim3 grid = g1(Nout * nmax(crt), crt.k, B);
+    if (launch_log_on()) launch_log_add("bilinear.byte", grid, dim3(256));
+    hipLaunchKernelGGL(k_bilinear, grid, dim3(256), 0, st, in, out, g, crt);
 }
 void launch_pair_diff(const Act& v, int64_t Nv, const Act& d, int64_t Nout, int ops, int cnt, const CrtInfo& crt,
                       int B, hipStream_t st) {

@@ -155,6 +155,53 @@ void launch_copy_gather(const Act& in, int64_t Nin, const Act& out, int64_t Nout
 // "gather.dword" / "gather.byte".
 void launch_gather(const Act& in, int64_t Nin, const Act& out, int64_t Nout, const int32_t* idx4, const int64_t* idx8,
                    const CrtInfo& crt, int B, hipStream_t st);
+// Bilinear layer (layers.h BilinearGeom): the separable two-tap label stencil. rows / cols: the taps (i0, i1) per
+// output row / column; wrow / wcol: per residue the tap weights reduced mod p_j, w0 | w1 << 8 ([k][OH] and
+// [k][OWp]); cols and wcol are padded to OWp = OW rounded up to a multiple of 4, so that the dword form's vector
+// loads stay aligned and in bounds; mq[j] = floor(2^32 / p_j) (dev.h div32_q). Every modulus is at most
+// kActMaxModulus: four products of three bytes fit the int32 accumulator.
+struct BilinearArgs {
+    int C, H, W, OH, OW, OWp;
+    const int2* rows;
+    const int2* cols;
+    const uint16_t* wrow;
+    const uint16_t* wcol;
+    uint32_t mq[kMaxRes];
+};
+// The host side of those tables, for the caller to put into device memory (the evaluator's planner and the GPU
+// garbler own their uploads); sets every field of `a` but the four pointers.
+struct BilinearTables {
+    std::vector<int2> rows, cols;
+    std::vector<uint16_t> wrow, wcol;
+};
+template <class Geom>  // layers.h BilinearGeom (validated: taps in range, weights in [0, 2^b])
+BilinearTables bilinear_tables(BilinearArgs& a, const Geom& G, const int* mods, int k) {
+    a.C = static_cast<int>(G.C); a.H = static_cast<int>(G.H); a.W = static_cast<int>(G.W);
+    a.OH = static_cast<int>(G.OH); a.OW = static_cast<int>(G.OW);
+    a.OWp = (a.OW + 3) / 4 * 4;
+    BilinearTables t;
+    t.rows.resize(static_cast<size_t>(a.OH));
+    t.cols.assign(static_cast<size_t>(a.OWp), make_int2(0, 0));
+    t.wrow.resize(static_cast<size_t>(k) * a.OH);
+    t.wcol.assign(static_cast<size_t>(k) * a.OWp, 0);
+    for (int oy = 0; oy < a.OH; ++oy)
+        t.rows[oy] = make_int2(static_cast<int>((*G.y0)[oy]), static_cast<int>((*G.y1)[oy]));
+    for (int ox = 0; ox < a.OW; ++ox)
+        t.cols[ox] = make_int2(static_cast<int>((*G.x0)[ox]), static_cast<int>((*G.x1)[ox]));
+    for (int j = 0; j < k; ++j) {
+        const int p = mods[j];
+        a.mq[j] = static_cast<uint32_t>((uint64_t(1) << 32) / static_cast<uint64_t>(p));
+        for (int oy = 0; oy < a.OH; ++oy)
+            t.wrow[static_cast<size_t>(j) * a.OH + oy] = static_cast<uint16_t>(G.wy(oy, 0, p) | G.wy(oy, 1, p) << 8);
+        for (int ox = 0; ox < a.OW; ++ox)
+            t.wcol[static_cast<size_t>(j) * a.OWp + ox] = static_cast<uint16_t>(G.wx(ox, 0, p) | G.wx(ox, 1, p) << 8);
+    }
+    return t;
+}
+// dword: k_bilinear4, a lane owns four consecutive ox of one output row (needs OW % 4 == 0 and 4-byte aligned
+// out.p[j]); else k_bilinear, one output per lane. Logs "bilinear.dword" / "bilinear.byte".
+void launch_bilinear(const BilinearArgs& g, bool dword, const Act& in, const Act& out, const CrtInfo& crt, int B,
+                     hipStream_t st);
 void launch_pair_diff(const Act& v, int64_t Nv, const Act& d, int64_t Nout, int ops, int cnt, const CrtInfo& crt, int B,
                       hipStream_t st);
 void launch_pair_add(const Act& v, int64_t Nv, const Act& r, const Act& nv, int64_t Nout, int ops, int cnt, int cnt1,

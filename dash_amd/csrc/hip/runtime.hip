@@ -662,6 +662,7 @@ class HipEvaluator {
             case K_CONVT: return ConvTGeom(l).out_size();
             case K_UPSAMPLE: return UpGeom(l.p).out_size();
             case K_GATHER: return static_cast<i64>(l.vec("idx").size());
+            case K_BILINEAR: return BilinearGeom(l.p).out_size();
             case K_MAXPOOL: case K_SUMPOOL: return PoolGeom(l.p).out_size();
             case K_MAX: return 1;
             case K_ARGMAX: return l.param("P");
@@ -816,6 +817,7 @@ class HipEvaluator {
     void plan_convt(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_upsample(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_gather(Walk& w, size_t li, const GLayer& g, const std::string& lname);
+    void plan_bilinear(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_relu(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_clip(Walk& w, size_t li, const GLayer& g, const std::string& lname);
     void plan_sign(Walk& w, size_t li, const GLayer& g, const std::string& lname);
@@ -980,6 +982,7 @@ void HipEvaluator::build() {
             case K_CONVT: plan_convt(w, li, g, lname); break;
             case K_UPSAMPLE: plan_upsample(w, li, g, lname); break;
             case K_GATHER: plan_gather(w, li, g, lname); break;
+            case K_BILINEAR: plan_bilinear(w, li, g, lname); break;
             case K_RELU: plan_relu(w, li, g, lname); break;
             case K_CLIP: plan_clip(w, li, g, lname); break;
             case K_SIGN: plan_sign(w, li, g, lname); break;
@@ -1413,6 +1416,31 @@ void HipEvaluator::plan_gather(Walk& w, size_t, const GLayer& g, const std::stri
     const int B = B_;
     add_op(lname, [x, NN, y, No, d4, d8, ci, B](hipStream_t st) { launch_gather(x, NN, y, No, d4, d8, ci, B, st); });
     set_out(w, g, No, w.nxt());
+}
+
+// Bilinear: the separable two-tap label stencil with public weights (free: no tables), any moduli of at most
+// kActMaxModulus. The form rule: the dword kernel where OW % 4 == 0 and every base pointer is 4-byte aligned, else
+// the byte kernel; DASH_BILINEAR_FORM=byte forces the byte form (A/B runs).
+void HipEvaluator::plan_bilinear(Walk& w, size_t, const GLayer& g, const std::string& lname) {
+    DASH_CHECK(hard_, "bilinear exists in the hardened encoding only");
+    const BilinearGeom G(g.p);
+    DASH_CHECK(G.in_size() == w.N, "bilinear input size mismatch");
+    for (int p : w.mods) DASH_CHECK(p <= kActMaxModulus, "bilinear: residue modulus above 255");
+    Act x = act_of(w.cur), y = act_of(w.nxt());
+    bool dword = G.OW % 4 == 0;
+    for (int j = 0; j < k_; ++j) dword = dword && reinterpret_cast<uintptr_t>(y.p[j]) % 4 == 0;
+    if (const char* f = std::getenv("DASH_BILINEAR_FORM"))
+        if (std::string(f) == "byte") dword = false;
+    BilinearArgs a{};
+    const BilinearTables t = bilinear_tables(a, G, w.mods.data(), static_cast<int>(w.mods.size()));
+    a.rows = upload(t.rows.data(), t.rows.size());
+    a.cols = upload(t.cols.data(), t.cols.size());
+    a.wrow = upload(t.wrow.data(), t.wrow.size());
+    a.wcol = upload(t.wcol.data(), t.wcol.size());
+    const CrtInfo ci = crt_info(w.mods);
+    const int B = B_;
+    add_op(lname, [a, dword, x, y, ci, B](hipStream_t st) { launch_bilinear(a, dword, x, y, ci, B, st); });
+    set_out(w, g, G.out_size(), w.nxt());
 }
 
 void HipEvaluator::plan_relu(Walk& w, size_t li, const GLayer& g, const std::string& lname) {

@@ -61,6 +61,30 @@ struct GatherGeom {
     i64 src(i64 o) const { return (*idx)[static_cast<size_t>(o)]; }
 };
 
+// Separable two-tap interpolation of a (C, H, W) tensor by public tables (bilinear Resize, docs/BILINEAR.md):
+//   y[c][oy][ox] = sum_{a, b in {0, 1}} wy_a[oy] wx_b[ox] x[c][y_a[oy]][x_b[ox]],
+// wy_1 = ny[oy] in [0, 2^by], wy_0 = 2^by - ny[oy], likewise in x: 2^(by + bx) times the interpolated value. The
+// tables are taken as they are (the coordinate modes exist in the IR only); by, bx <= 8.
+struct BilinearGeom {
+    static constexpr i64 kMaxBits = 8;
+    i64 C, H, W, OH, OW, by, bx;
+    const std::vector<i64>*y0, *y1, *ny, *x0, *x1, *nx;
+    explicit BilinearGeom(const Params& p);
+    i64 in_size() const { return C * H * W; }
+    i64 out_size() const { return C * OH * OW; }
+    // the two row / column weights of an output row / column, reduced mod p
+    i64 wy(i64 oy, int a, i64 p) const {
+        const i64 n = (*ny)[static_cast<size_t>(oy)];
+        return (a ? n : (i64(1) << by) - n) % p;
+    }
+    i64 wx(i64 ox, int a, i64 p) const {
+        const i64 n = (*nx)[static_cast<size_t>(ox)];
+        return (a ? n : (i64(1) << bx) - n) % p;
+    }
+};
+// the layer's map on labels of any moduli: out = sum of (weight mod p) * tap per residue (zero weights add nothing)
+CrtLabels bilinear_labels(const BilinearGeom& G, const CrtLabels& cur, int nt);
+
 struct PoolGeom {
     // ph/pw: symmetric padding (at most half the kernel); ceil: ONNX/PyTorch ceil_mode output size
     i64 C, H, W, kh, kw, sh, sw, ph, pw, ceil, OH, OW;

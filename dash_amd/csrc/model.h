@@ -42,6 +42,7 @@ enum Kind : int {
     K_PWL = 21,  // params s, T, A, V, fn; smode 0 | 1; per kept breakpoint i arrays b<i>.mrs | b<i>.s.*, b<i>.mm.g, b<i>.mm.e
     K_MATMUL = 22,  // params src, M, T, N, ta / tb, G (heads; only when set / above 1); arrays g, e [G M N T][P]
     K_GATHER = 23,  // params idx [Nout] (0 <= idx < Nin), od (output dims); no arrays
+    K_BILINEAR = 24,  // params C, H, W, OH, OW, by, bx, y0 / y1 / ny [OH], x0 / x1 / nx [OW]; no arrays (hardened only)
 };
 const char* kind_name(int kind);
 

@@ -29,6 +29,7 @@ _CLIP = _Kind.CLIP
 _ARGMAX = _Kind.ARGMAX
 _MUL = _Kind.MUL
 _CONVT = _Kind.CONVT
+_BILINEAR = _Kind.BILINEAR
 _PWL = _Kind.PWL
 _MATMUL = _Kind.MATMUL
 
@@ -211,6 +212,13 @@ class GarbledCircuit:
                              "only (%s)" % (convts[0], "hardened=False was asked for" if supported else
                                             "the resolved constructions cannot be hardened: fused sign and no legacy "
                                             "DASH rescale are needed"))
+        # a Bilinear has no reference encoding either, for the ConvTranspose2d's reason: the number of tap weights that
+        # vanish mod p differs per output position
+        bilinears = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _BILINEAR]
+        if bilinears and not (supported if hardened is None else hardened):
+            raise ValueError("layer %d (bilinear): the Bilinear layer exists in the hardened encoding only (%s)" % (
+                bilinears[0], "hardened=False was asked for" if supported else
+                "the resolved constructions cannot be hardened: fused sign and no legacy DASH rescale are needed"))
         # a Mul's operands are read by other gates too (a skip tensor, a broadcast operand across a plane, one
         # tensor into two Muls): without the hardened encoding's gate tweak those reads would share a pad
         muls = [i for i, l in enumerate(circuit.layers) if getattr(l, "kind", -1) == _MUL]

@@ -26,7 +26,7 @@ Three implementations with one semantics (tests/test_range_guard.py pins them ag
   evaluation; inputs whose activations exceed a kernel's exact operand range (int32, or the 24-bit conv form's
   bound) are marked uncertain and decided by the numpy model alone, whatever the device flagged for them. It
   has no Concat, no Clip, no ArgMax, no Mul, no MatMul, no ConvTranspose2d, no Upsample, no LeakyRelu, no
-  PiecewiseLinear, no Gather and no padded / ceil-mode pooling:
+  PiecewiseLinear, no Gather, no Bilinear and no padded / ceil-mode pooling:
   circuits with any of them take the torch path on the GPU;
 * the batched torch evaluation (float64 GEMMs, exact below 2^53), used on the CPU and as the bench's batched
   verification oracle (``outputs``);
@@ -74,13 +74,13 @@ class RangeGuard:
         self.batched = all(isinstance(l, (L.Conv2d, L.Dense, L.Rescale, L.Relu, L.Sign, L.Flatten, L.MaxPool2d,
                                           L.SumPool2d, L.Add, L.Concat, L.Clip, L.ArgMax, L.Mul, L.Projection,
                                           L.BaseExtension, L.ConvTranspose2d, L.Upsample, L.LeakyRelu,
-                                          L.PiecewiseLinear, L.MatMul, L.Gather))
+                                          L.PiecewiseLinear, L.MatMul, L.Gather, L.Bilinear))
                            for l in circuit.layers)
         # DevRangeGuard (guard.hip) has no Concat, no Clip, no ArgMax, no Mul, no ConvTranspose2d, no Upsample, no
-        # LeakyRelu, no PiecewiseLinear, no MatMul, no Gather, no dilated conv and no padded / ceil-mode pooling: such
-        # circuits take the batched torch path
+        # LeakyRelu, no PiecewiseLinear, no MatMul, no Gather, no Bilinear, no dilated conv and no padded / ceil-mode
+        # pooling: such circuits take the batched torch path
         self.native_forms = not any(isinstance(l, (L.Concat, L.Clip, L.ArgMax, L.Mul, L.ConvTranspose2d, L.Upsample,
-                                                   L.LeakyRelu, L.PiecewiseLinear, L.MatMul, L.Gather)) or
+                                                   L.LeakyRelu, L.PiecewiseLinear, L.MatMul, L.Gather, L.Bilinear)) or
                                     (isinstance(l, L.Conv2d) and (l.dh > 1 or l.dw > 1)) or
                                     (isinstance(l, (L.MaxPool2d, L.SumPool2d)) and l.padded) for l in circuit.layers)
         self._w = None
@@ -182,6 +182,9 @@ class RangeGuard:
                                torch.tensor(np.array(l.q_biases), dtype=torch.float64, device=dev), perm))
                 elif isinstance(l, L.Gather):
                     ws.append(torch.as_tensor(np.array(l.idx), device=dev))
+                elif isinstance(l, L.Bilinear):  # taps and the four weight vectors, int64
+                    ws.append(tuple(torch.as_tensor(np.array(a), device=dev) for a in (
+                        l.y0, l.y1, (1 << l.by) - l.ny, l.ny, l.x0, l.x1, (1 << l.bx) - l.nx, l.nx)))
                 else:
                     ws.append(None)
             self._w = (dev, ws)
@@ -225,6 +228,11 @@ class RangeGuard:
                 out = v.repeat_interleave(l.fh, dim=2).repeat_interleave(l.fw, dim=3).reshape(B, -1)
             elif isinstance(l, L.Gather):  # sets no limit: the moved values are checked where a gadget next reads them
                 out = inp.index_select(1, ws[i])
+            elif isinstance(l, L.Bilinear):  # exact in int64 (index_select and integer multiplies); no limit of its own
+                y0, y1, wy0, wy1, x0, x1, wx0, wx1 = ws[i]
+                v = inp.view(B, l.C, l.H, l.W)
+                r = v.index_select(2, y0) * wy0[None, None, :, None] + v.index_select(2, y1) * wy1[None, None, :, None]
+                out = (r.index_select(3, x0) * wx0 + r.index_select(3, x1) * wx1).reshape(B, -1)
             elif isinstance(l, L.Dense):
                 W, b, perm = ws[i]
                 xin = inp if perm is None else inp[:, perm]

@@ -44,6 +44,7 @@ class Kind:
     PWL = 21
     MATMUL = 22
     GATHER = 23
+    BILINEAR = 24
 
 
 def _size(d: Sequence[int]) -> int:
@@ -636,6 +637,125 @@ class Gather(Layer):
 
     def __repr__(self) -> str:
         return f"Gather(in={self.in_dims}, out={self.out_dims})"
+
+
+class Bilinear(Layer):
+    """Bilinear resize of a (C, H, W) tensor to (C, OH, OW) (docs/BILINEAR.md): separable, one public two-tap table
+    per axis. For output index o on an axis of n inputs and m outputs, in exact rational arithmetic,
+      half_pixel:    src = (o + 1/2) n / m - 1/2, clamped to [0, n - 1]
+      align_corners: src = o (n - 1) / (m - 1), 0 when m = 1
+      asymmetric:    src = o n / m
+    i0 = floor(src), i1 = min(i0 + 1, n - 1), lam = src - i0, n1 = floor(lam 2^b + 1/2), n0 = 2^b - n1. The axis'
+    fraction bits b are the smallest value in 0..8 that makes every lam 2^b an integer (exact weights), else `bits`.
+    With s = by + bx the quantized output is the exact integer
+      y[c][oy][ox] = sum_{a, b in {0, 1}} ny_a[oy] nx_b[ox] x[c][iy_a[oy]][ix_b[ox]] = 2^s (interpolated value):
+    it carries a scale 2^s larger than the input (pending scale bits, as a LeakyRelu's), which the next linear
+    layer absorbs (in_scale_bits). Free in the label domain: public multiples and sums of labels, no tables, no PRG
+    draws. Hardened encoding only, as ConvTranspose2d (the zero-mod-p weights differ per output position).
+
+    factors: one number or (fh, fw), each with an integer n f (OH = H fh); or size = (OH, OW)."""
+
+    kind = Kind.BILINEAR
+    name = "bilinear"
+    MODES = ("half_pixel", "align_corners", "asymmetric")
+    MAX_BITS = 8
+
+    def __init__(self, dims, factors=None, size=None, mode: str = "half_pixel", bits: int = 6):
+        from fractions import Fraction
+
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 3 or min(dims) < 1:
+            raise ValueError(f"bilinear: the input is (C, H, W), got {dims}")
+        if mode not in self.MODES:
+            raise ValueError(f"bilinear: mode is one of {self.MODES}, got {mode!r}")
+        if int(bits) != bits or not 1 <= int(bits) <= self.MAX_BITS:
+            raise ValueError(f"bilinear: bits must be an integer in [1, {self.MAX_BITS}], got {bits}")
+        if (factors is None) == (size is None):
+            raise ValueError("bilinear: give either factors or size")
+        self.C, self.H, self.W = dims
+        if size is not None:
+            size = tuple(size)
+            if len(size) != 2 or any(int(v) != v or int(v) < 1 for v in size):
+                raise ValueError(f"bilinear: size is (OH, OW) with positive integers, got {size}")
+            oh, ow = (int(v) for v in size)
+        else:
+            f = tuple(factors) if isinstance(factors, (tuple, list)) else (factors, factors)
+            if len(f) != 2:
+                raise ValueError(f"bilinear: factors is one number or (fh, fw), got {factors}")
+            out = []
+            for n, v in zip((self.H, self.W), f):
+                m = Fraction(v) * n
+                if m.denominator != 1 or m < 1:
+                    raise ValueError(f"bilinear: factor {v} does not take an axis of {n} to a whole size; give size")
+                out.append(int(m))
+            oh, ow = out
+        if (oh, ow) == (self.H, self.W):
+            raise ValueError(f"bilinear: the output {(oh, ow)} equals the input")
+        self.OH, self.OW, self.mode, self.bits = oh, ow, mode, int(bits)
+        super().__init__(dims, (self.C, oh, ow))
+        self.y0, self.y1, self.ny, self.by = self.axis_table(self.H, oh, mode, self.bits)
+        self.x0, self.x1, self.nx, self.bx = self.axis_table(self.W, ow, mode, self.bits)
+        for a in (self.y0, self.y1, self.ny, self.x0, self.x1, self.nx):
+            a.setflags(write=False)  # garble_spec hands the arrays themselves to the native specs
+
+    @staticmethod
+    def axis_table(n: int, m: int, mode: str, bits: int):
+        """(i0, i1, n1, b) of one axis: int64 arrays of length m and the axis' fraction bits."""
+        from fractions import Fraction
+
+        half = Fraction(1, 2)
+        src = []
+        for o in range(m):
+            if mode == "half_pixel":
+                s = min(max((o + half) * Fraction(n, m) - half, Fraction(0)), Fraction(n - 1))
+            elif mode == "align_corners":
+                s = Fraction(o * (n - 1), m - 1) if m > 1 else Fraction(0)
+            else:
+                s = Fraction(o * n, m)
+            src.append(s)
+        i0 = [s.numerator // s.denominator for s in src]
+        lam = [s - i for s, i in zip(src, i0)]
+        b = next((t for t in range(Bilinear.MAX_BITS + 1) if all((l * (1 << t)).denominator == 1 for l in lam)), bits)
+        n1 = [int((l * (1 << b) + half).numerator // (l * (1 << b) + half).denominator) for l in lam]
+        return (np.array(i0, dtype=np.int64), np.array([min(i + 1, n - 1) for i in i0], dtype=np.int64),
+                np.array(n1, dtype=np.int64), b)
+
+    @property
+    def scale_bits(self) -> int:
+        """s = by + bx: the output is 2^s times the interpolated value."""
+        return self.by + self.bx
+
+    def _taps(self, x, wy0, wy1, wx0, wx1):
+        x = x.reshape(self.C, self.H, self.W)
+        r = x[:, self.y0, :] * wy0[None, :, None] + x[:, self.y1, :] * wy1[None, :, None]
+        return (r[:, :, self.x0] * wx0[None, None, :] + r[:, :, self.x1] * wx1[None, None, :]).reshape(-1)
+
+    def plain_eval(self, x, track=True, ctx=None):
+        sy, sx = float(1 << self.by), float(1 << self.bx)
+        y = self._taps(np.asarray(x, dtype=np.float64), 1.0 - self.ny / sy, self.ny / sy, 1.0 - self.nx / sx,
+                       self.nx / sx).astype(np.float32)
+        if track:
+            self._track_f(y)
+        return y
+
+    def plain_q_eval(self, x, track=True, ctx=None, crt_modulus=None):
+        y = self._taps(np.asarray(x, dtype=np.int64), (1 << self.by) - self.ny, self.ny, (1 << self.bx) - self.nx,
+                       self.nx)
+        if track:
+            self._track_q(y)  # 2^s times a convex combination: the output's own range bounds every partial sum
+        return y
+
+    def quantize(self, q_const):
+        self.reset_ranges()
+
+    def garble_spec(self):
+        return self.kind, {"C": self.C, "H": self.H, "W": self.W, "OH": self.OH, "OW": self.OW, "by": self.by,
+                           "bx": self.bx, "y0": self.y0, "y1": self.y1, "ny": self.ny, "x0": self.x0, "x1": self.x1,
+                           "nx": self.nx}
+
+    def __repr__(self) -> str:
+        return (f"Bilinear(in={self.in_dims}, out={self.out_dims}, mode={self.mode}, "
+                f"bits=({self.by}, {self.bx}))")
 
 
 class Relu(Layer):

@@ -49,6 +49,19 @@ asymmetric pads are refused with the node's name. `Resize` (opset >= 11) and
 PyTorch exports for nn.Upsample(mode="nearest")), become an `Upsample` layer;
 everything else is refused with the node's name. A pending factor passes through.
 
+With the keyword `resize="bilinear"` a `Resize` (opset >= 11) in mode `linear`
+becomes a `Bilinear` layer (docs/BILINEAR.md): `coordinate_transformation_mode`
+`half_pixel` (the default), `pytorch_half_pixel` (output sizes above 1, where
+both agree), `align_corners` or `asymmetric`; constant `scales` [1, 1, fh, fw]
+whose products with the input sizes are whole numbers (the layer's coordinates
+are the size ratios; non-integer factors such as 1.5 are fine) or constant
+`sizes`. An `Upsample` (opset <= 9) in mode `linear` becomes a `Bilinear` in
+mode asymmetric. ScaleQuant only: the output carries by + bx pending scale
+bits more than the input. A pending average factor passes through (the map is
+linear). Everything else (cubic, a `roi` crop via `tf_crop_and_resize`,
+non-constant scales, a batch or channel scale) is refused with the node's name.
+The default `resize="nearest"` keeps every `linear` node refused.
+
 `Mul` of two produced tensors becomes a `Mul` layer: equal dims multiply
 elementwise, `[N, C, 1, 1]` or `[N, C]` against `[N, C, H, W]` (either order;
 the full tensor becomes the layer's input) broadcasts over the plane, and the
@@ -122,6 +135,7 @@ name); its output carries e = `pwl_bits`, consumed like a LeakyRelu's:
     LeakyRelu / PRelu                e + leaky_bits
     Sigmoid / HardSigmoid / Tanh     0 required -> pwl_bits
     Relu, pools, Flatten, Upsample   passed through
+    Resize linear (resize="bilinear") e + by + bx (the Bilinear layer's fraction bits)
     Slice, Split, Gather, ...        passed through (Gather layers)
     Conv / ConvTranspose / Gemm      consumed: in_scale_bits = e, Rescale(l + e)
     Mul                              e0 + e1 consumed: Rescale(l + e0 + e1)
@@ -167,7 +181,7 @@ import numpy as np
 
 from ..native import native
 from .circuit import Circuit
-from .layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Gather, LeakyRelu, MatMul, MaxPool2d,
+from .layers import (Add, ArgMax, Bilinear, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Gather, LeakyRelu, MatMul, MaxPool2d,
                      Mul, PiecewiseLinear, Relu, Rescale, Sign, SumPool2d, Upsample, _as_matrix, _convt_check, _head_matrix,
                      _pool_out, _slice_bounds)
 from .quant import QuantizationMethod
@@ -233,8 +247,11 @@ def _pool_attrs(node) -> tuple:
 
 def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant,
                              q_const: float = DEFAULT_Q_CONST, q_parameter: int = -1, leaky_bits: int = 4,
-                             tanh: str = "sign", pwl_bits: int = 8, transpose: str = "matmul") -> Circuit:
+                             tanh: str = "sign", pwl_bits: int = 8, transpose: str = "matmul",
+                             resize: str = "nearest") -> Circuit:
     q_method = QuantizationMethod(q_method)
+    if resize not in ("nearest", "bilinear"):
+        raise ValueError(f"onnx: resize must be 'nearest' or 'bilinear', got {resize!r}")
     if tanh not in ("sign", "pwl"):
         raise ValueError(f"onnx: tanh must be 'sign' or 'pwl', got {tanh!r}")
     if transpose not in ("matmul", "gather"):
@@ -753,21 +770,28 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             name = node.get("name") or op
             if tf or len(dims) != 3:
                 raise NotImplementedError(f"onnx: {name}: {op} of an NCHW image only")
-            if _sattr(a, "mode", "nearest") != "nearest":
+            linear = resize == "bilinear" and _sattr(a, "mode", "nearest") == "linear"
+            if _sattr(a, "mode", "nearest") != "nearest" and not linear:
                 raise NotImplementedError(f"onnx: {name}: {op} mode {_sattr(a, 'mode', 'nearest')!r} is not supported "
-                                          "(nearest only)")
+                                          + ("(nearest and linear only)" if resize == "bilinear" else "(nearest only)"))
             if op == "Resize":
                 if int(model.get("opset", 11)) < 11:
                     raise NotImplementedError(f"onnx: {name}: Resize needs opset >= 11")
                 ctm, nm = _sattr(a, "coordinate_transformation_mode", "half_pixel"), \
                     _sattr(a, "nearest_mode", "round_prefer_floor")
-                if ctm != "asymmetric" or nm != "floor":
+                if linear:
+                    if ctm not in ("half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"):
+                        raise NotImplementedError(f"onnx: {name}: a linear Resize is supported with "
+                                                  "coordinate_transformation_mode half_pixel, pytorch_half_pixel, "
+                                                  f"align_corners or asymmetric, got {ctm!r}")
+                elif ctm != "asymmetric" or nm != "floor":
                     raise NotImplementedError(f"onnx: {name}: Resize is supported with coordinate_transformation_mode="
                                               f"asymmetric and nearest_mode=floor only, got {ctm!r} / {nm!r}")
                 s_in, z_in = (ins[2] if len(ins) > 2 else ""), (ins[3] if len(ins) > 3 else "")
             else:
                 s_in, z_in = (ins[1] if len(ins) > 1 else ""), ""
             full = (1,) + tuple(dims)
+            lin_size = None  # a linear Resize given by sizes: they need not be multiples of the input
             if s_in and s_in in inits and inits[s_in]["values"].size:
                 sc = [float(v) for v in np.asarray(inits[s_in]["values"]).reshape(-1)]
             elif op == "Upsample" and "scales" in a:  # opset 7: an attribute
@@ -775,11 +799,40 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
             elif z_in and z_in in inits:
                 t = inits[z_in]
                 sz = [int(v) for v in (list(t["ivalues"]) or np.asarray(t["values"]).reshape(-1))]
-                if len(sz) != 4 or any(z % d for z, d in zip(sz, full)):
+                if linear:
+                    if len(sz) != 4 or sz[0] != 1 or sz[1] != dims[0] or min(sz[2:]) < 1:
+                        raise NotImplementedError(f"onnx: {name}: sizes {sz} do not keep the batch and channel axes of "
+                                                  f"the input {full}")
+                    lin_size = (sz[2], sz[3])
+                elif len(sz) != 4 or any(z % d for z, d in zip(sz, full)):
                     raise NotImplementedError(f"onnx: {name}: sizes {sz} are no integer multiples of the input {full}")
-                sc = [z / d for z, d in zip(sz, full)]
+                sc = [1.0, 1.0, 0.0, 0.0] if lin_size else [z / d for z, d in zip(sz, full)]
             else:
                 raise NotImplementedError(f"onnx: {name}: {op} needs constant scales or sizes")
+            if linear:
+                from fractions import Fraction
+
+                if q_method != QuantizationMethod.ScaleQuant:
+                    raise ValueError(f"onnx: {name}: a linear {op} is imported as a Bilinear layer under ScaleQuant only: "
+                                     "its output carries a power-of-two scale that the next power-of-two Rescale absorbs")
+                if len(sc) != 4 or sc[0] != 1 or sc[1] != 1:
+                    raise NotImplementedError(f"onnx: {name}: {op} scales {sc} are not [1, 1, fh, fw]: the batch and "
+                                              "channel axes cannot be resized")
+                size = lin_size or [Fraction(v) * d for v, d in zip(sc[2:], dims[1:])]
+                if any(Fraction(m).denominator != 1 or m < 1 for m in size):
+                    raise NotImplementedError(f"onnx: {name}: {op} scales {sc} do not take the input {tuple(dims)} to whole "
+                                              "sizes (the layer's coordinates are the size ratios); export with sizes")
+                size = tuple(int(m) for m in size)
+                mode = "asymmetric" if op == "Upsample" else {"pytorch_half_pixel": "half_pixel"}.get(ctm, ctm)
+                if op == "Resize" and ctm == "pytorch_half_pixel" and min(size) <= 1:
+                    raise NotImplementedError(f"onnx: {name}: pytorch_half_pixel with an output size of 1 is not supported")
+                if size == tuple(dims[1:]):
+                    raise NotImplementedError(f"onnx: {name}: {op} scales {sc} leave the size unchanged")
+                spec = _Spec("bilinear", dims=dims, size=size, mode=mode)
+                # the fraction bits are the tables': build them once here, the layer itself is built from the spec
+                probe = Bilinear(dims, size=size, mode=mode)
+                emit(spec, outs[0], j, (dims[0],) + size, fac, eb + probe.scale_bits)
+                continue
             if len(sc) != 4 or sc[0] != 1 or sc[1] != 1 or any(v != int(v) or v < 1 for v in sc[2:]) or \
                     sc[2] * sc[3] == 1:
                 raise NotImplementedError(f"onnx: {name}: {op} scales {sc} are not [1, 1, fh, fw] with integer "
@@ -1047,6 +1100,8 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
                                           out_pad_height=kw["opad"][0], in_scale_bits=kw["e"]))
         elif s.kind == "upsample":
             layers.append(Upsample(kw["dims"], kw["f"][0], kw["f"][1]))
+        elif s.kind == "bilinear":
+            layers.append(Bilinear(kw["dims"], size=kw["size"], mode=kw["mode"]))
         elif s.kind == "gather":
             layers.append(Gather(kw["dims"], kw["idx"], kw["out_dims"]))
         elif s.kind in ("maxpool", "sumpool"):
@@ -1103,14 +1158,15 @@ def create_circuit_from_onnx(model: dict, q_method: QuantizationMethod = Quantiz
 
 def load_onnx_model(path, q_method: QuantizationMethod = QuantizationMethod.SimpleQuant, q_parameter: int = -1,
                     q_const: float = DEFAULT_Q_CONST, leaky_bits: int = 4, tanh: str = "sign",
-                    pwl_bits: int = 8, transpose: str = "matmul") -> Circuit:
+                    pwl_bits: int = 8, transpose: str = "matmul", resize: str = "nearest") -> Circuit:
     """Reference: load_onnx_model (onnx_modelloader.h:371-406). leaky_bits: the slope bits of imported LeakyRelu /
     PRelu nodes (docs/LEAKY_RELU.md). tanh: "sign" imports Tanh as Sign (the reference's convention), "pwl" as a
     PiecewiseLinear; pwl_bits: the slope bits of imported Sigmoid / HardSigmoid / Tanh nodes (docs/PWL.md).
     transpose: "matmul" accepts a Transpose only where it folds into a MatMul, "gather" also turns every other
-    Transpose that keeps the batch axis into a Gather layer (docs/GATHER.md)."""
+    Transpose that keeps the batch axis into a Gather layer (docs/GATHER.md). resize: "nearest" accepts a Resize /
+    Upsample in mode nearest only, "bilinear" also imports mode linear as a Bilinear layer (docs/BILINEAR.md)."""
     return create_circuit_from_onnx(parse_onnx(path), q_method, q_const, q_parameter, leaky_bits, tanh, pwl_bits,
-                                    transpose)
+                                    transpose, resize)
 
 
 # ------------------------------------------------------------------ export
@@ -1232,6 +1288,13 @@ def save_onnx_model(path, circuit: Circuit, producer: str = "dash_amd") -> None:
             attrs = (_attr_str("coordinate_transformation_mode", "asymmetric") + _attr_str("mode", "nearest")
                      + _attr_str("nearest_mode", "floor"))
             nodes.append(_node("Resize", [cur, "", f"{name}.scales"], [out], name, attrs))
+            scale[out] = K
+        elif isinstance(l, Bilinear):
+            # what PyTorch writes for F.interpolate(size=..., mode="bilinear"): Resize with an empty roi, no scales
+            # and constant sizes; linear, so a pending average ratio passes through
+            inits.append(_tensor_i64(f"{name}.sizes", (1, l.C, l.OH, l.OW)))
+            attrs = _attr_str("coordinate_transformation_mode", l.mode) + _attr_str("mode", "linear")
+            nodes.append(_node("Resize", [cur, "", "", f"{name}.sizes"], [out], name, attrs))
             scale[out] = K
         elif isinstance(l, Gather):
             # the map on the flat tensor: Flatten -> Gather(axis=1) -> Reshape(out_dims); value-preserving, so a

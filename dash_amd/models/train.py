@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Clip, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, PiecewiseLinear, Relu, Rescale, Sign, SumPool2d,
+from ..ir.layers import (Bilinear, Clip, Conv2d, ConvTranspose2d, Dense, Flatten, LeakyRelu, MaxPool2d, Mul, PiecewiseLinear, Relu, Rescale, Sign, SumPool2d,
                          Upsample, _pool_out)
 from ..ir.quant import QuantizationMethod
 from .zoo import ARCHS, canonical
@@ -110,6 +110,12 @@ def build_torch_model(name: str, fake_quant: float = 0.0):
         elif k == "up":
             mods.append(nn.Upsample(scale_factor=int(op[1]), mode="nearest"))
             dims = [dims[0], dims[1] * int(op[1]), dims[2] * int(op[1])]
+        elif k == "bilinear":
+            mode = op[2] if len(op) > 2 else "half_pixel"
+            if mode == "asymmetric":
+                raise NotImplementedError("training: nn.Upsample(mode='bilinear') has no asymmetric coordinate mode")
+            mods.append(nn.Upsample(scale_factor=op[1], mode="bilinear", align_corners=mode == "align_corners"))
+            dims = [dims[0], int(dims[1] * op[1]), int(dims[2] * op[1])]
         elif k in ("skip", "cat"):
             raise NotImplementedError(f"training: op {k} (skip connections) not supported by the sequential trainer")
         elif k == "relu":
@@ -241,9 +247,18 @@ def to_circuit(model, name: str, q_method=QuantizationMethod.ScaleQuant, q_param
             dims = c.out_dims
             rescale(dims)
         elif isinstance(m, nn.Upsample):
-            if m.mode != "nearest" or m.scale_factor is None:
-                raise NotImplementedError("training: only nn.Upsample(scale_factor=f, mode='nearest') maps to a layer")
+            if m.mode not in ("nearest", "bilinear") or m.scale_factor is None:
+                raise NotImplementedError("training: only nn.Upsample(scale_factor=f, mode='nearest' | 'bilinear') maps "
+                                          "to a layer")
             sf = m.scale_factor if isinstance(m.scale_factor, (tuple, list)) else (m.scale_factor, m.scale_factor)
+            if m.mode == "bilinear":  # docs/BILINEAR.md: half_pixel is PyTorch's align_corners=False
+                if qm != QuantizationMethod.ScaleQuant:
+                    raise ValueError("training: a bilinear upsampling exists under ScaleQuant only")
+                bl = Bilinear(dims, (sf[0], sf[1]), mode="align_corners" if m.align_corners else "half_pixel")
+                layers.append(bl)
+                dims = bl.out_dims
+                pend[0] += bl.scale_bits
+                continue
             if any(float(f) != int(f) for f in sf):
                 raise NotImplementedError("training: nn.Upsample needs integer scale factors")
             up = Upsample(dims, int(sf[0]), int(sf[1]))

@@ -12,7 +12,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from ..ir.circuit import Circuit
-from ..ir.layers import (Add, ArgMax, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Gather, LeakyRelu, MatMul, MaxPool2d, Mul,
+from ..ir.layers import (Add, ArgMax, Bilinear, Clip, Concat, Conv2d, ConvTranspose2d, Dense, Flatten, Gather, LeakyRelu, MatMul, MaxPool2d, Mul,
                          PiecewiseLinear, Relu,
                          Rescale, Sign, SumPool2d, Upsample)
 from ..ir.quant import QuantizationMethod, quantize_input
@@ -65,6 +65,10 @@ from ..ir.quant import QuantizationMethod, quantize_input
 #                   of the channels is kept (a Gather), the second half (a Gather reading the unit's input) goes
 #                   through a 1x1 conv + ReLU, a depthwise 3x3 and a 1x1 conv + ReLU (each conv + the scheme's
 #                   rescale), then the Concat of both and a shuffle with 2 groups (docs/GATHER.md)
+#                   | ("bilinear", f) bilinear upsampling by f in mode half_pixel (PyTorch's align_corners=False), or
+#                   ("bilinear", f, mode) with mode align_corners / asymmetric: ScaleQuant only; the output's
+#                   2^(by + bx) travels like a leaky ReLU's to the next conv or fc, an ("argmax",) or ("sign",) drops
+#                   it, and a ("cat",) needs the same pending bits on both operands (docs/BILINEAR.md)
 ARCHS: dict[str, dict] = {
     "MODEL_A": {"input": (1, 28, 28), "ops": [("flatten",), ("fc", 128), ("relu",), ("fc", 128), ("relu",), ("fc", 10)]},
     # MODEL_A whose decoded output is the class alone, not the ten logits
@@ -182,6 +186,25 @@ ARCHS: dict[str, dict] = {
         ("aspp", 16, (1, 2, 4)),
         ("conv", 16, 1, 1, 0), ("relu",),
         ("conv", 4, 1, 1, 0), ("argmax",), ("up", 2)]},
+    # UNET_CIFAR with both decoder steps written as the up-conv: bilinear upsampling, then a 3x3 conv (which absorbs
+    # the upsampling's pending scale bits before the concat) + ReLU
+    "UNET_BILINEAR_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 8, 3, 1, 1), ("relu",), ("skip",),
+        ("conv", 16, 3, 2, 1), ("relu",), ("skip",),
+        ("conv", 32, 3, 2, 1), ("relu",),
+        ("bilinear", 2), ("conv", 16, 3, 1, 1), ("relu",), ("cat",),
+        ("conv", 16, 3, 1, 1), ("relu",),
+        ("bilinear", 2), ("conv", 8, 3, 1, 1), ("relu",), ("cat",),
+        ("conv", 8, 3, 1, 1), ("relu",),
+        ("conv", 4, 1, 1, 0), ("argmax",)]},
+    # ASPP_SEG_CIFAR with DeepLab's head: the 4-class scores are upsampled bilinearly to the input grid, then the
+    # per-pixel class (1, 32, 32) is taken (the ArgMax drops the upsampling's scale)
+    "DEEPLAB_HEAD_CIFAR": {"input": (3, 32, 32), "ops": [
+        ("conv", 16, 3, 2, 1), ("relu",),
+        ("conv", 16, 3, 1, 1), ("relu",),
+        ("aspp", 16, (1, 2, 4)),
+        ("conv", 16, 1, 1, 0), ("relu",),
+        ("conv", 4, 1, 1, 0), ("bilinear", 2), ("argmax",)]},
     # ShuffleNetV2-style CIFAR net: a strided stem (32 -> 16 -> 8), two basic units on the (16, 8, 8) stage, a global
     # average and a dense head
     "SHUFFLENET_V2_CIFAR": {"input": (3, 32, 32), "ops": [
@@ -250,11 +273,11 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
         pend[0] = 0
         return c.out_dims
 
-    skips = []  # open ("skip",) marks: (layer index, dims)
+    skips = []  # open ("skip",) marks: (layer index, dims, pending scale bits)
     for op in arch["ops"]:
         kind = op[0]
         if pend[0] and kind not in ("conv", "dwconv", "fc", "relu", "leaky", "prelu", "maxpool", "sumpool", "gap",
-                                    "flatten", "up", "shuffle", "d2s"):
+                                    "flatten", "up", "shuffle", "d2s", "bilinear", "argmax", "sign", "skip", "cat"):
             raise NotImplementedError(f"{name}: op {len(layers)} ({kind}): a leaky ReLU's 2^{pend[0]} scale reaches it "
                                       "before a conv or fc could absorb it")
         if kind == "convt":
@@ -271,6 +294,14 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             up = Upsample(dims, op[1])
             layers.append(up)
             dims = up.out_dims
+        elif kind == "bilinear":
+            if qm != QuantizationMethod.ScaleQuant:
+                raise ValueError(f"{name}: op {len(layers)} (bilinear): a bilinear resize exists under ScaleQuant only "
+                                 "(its 2^s output scale needs a power-of-two rescale behind it)")
+            bl = Bilinear(dims, op[1], mode=op[2] if len(op) > 2 else "half_pixel")
+            layers.append(bl)
+            dims = bl.out_dims
+            pend[0] += bl.scale_bits
         elif kind == "shuffle":
             layers.append(Gather.channel_shuffle(dims, op[1]))
         elif kind == "d2s":
@@ -298,11 +329,14 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             layers.append(cat)
             layers.append(Gather.channel_shuffle(cat.out_dims, 2))
         elif kind == "skip":
-            skips.append((len(layers) - 1, dims))
+            skips.append((len(layers) - 1, dims, pend[0]))
         elif kind == "cat":
             if not skips:
                 raise ValueError(f"{name}: ('cat',) without an open ('skip',)")
-            src, sd = skips.pop()
+            src, sd, sbits = skips.pop()
+            if sbits != pend[0]:
+                raise NotImplementedError(f"{name}: op {len(layers)} (cat): the skip tensor carries 2^{sbits} pending "
+                                          f"scale and the current tensor 2^{pend[0]}: a Concat needs equal bits")
             cat = Concat([sd, dims], [src, len(layers) - 1])
             layers.append(cat)
             dims = cat.out_dims
@@ -360,6 +394,7 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             pend[0] += pwl_bits
         elif kind == "sign":
             layers.append(Sign(dims))
+            pend[0] = 0  # scale-free: a pending 2^e ends here
         elif kind in ("relu6", "clip"):
             lo, hi = (0.0, 6.0) if kind == "relu6" else (op[1], op[2])
             if qm == QuantizationMethod.SimpleQuant:
@@ -461,6 +496,7 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             am = ArgMax(dims)
             layers.append(am)
             dims = am.out_dims
+            pend[0] = 0  # scale-free: a pending 2^e ends here
         elif kind == "maxpool":
             k, s = op[1], op[2]
             pad, ceil = (op[3], op[4]) if len(op) > 3 else (0, False)
@@ -510,6 +546,8 @@ def build_circuit(name: str, q_method: QuantizationMethod = QuantizationMethod.S
             dims = d2
         else:
             raise ValueError(f"unknown op {kind}")
+    if pend[0]:
+        raise NotImplementedError(f"{name}: the output carries a pending 2^{pend[0]} scale that no conv or fc absorbed")
     return Circuit(layers, q_parameter)
 
 
@@ -554,6 +592,10 @@ BENCH_CONFIGS = {
                             mrs=100.0),
     "ASPP_SEG_CIFAR/DASH": dict(model="ASPP_SEG_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5, crt=7,
                                 mrs=100.0),
+    "UNET_BILINEAR_CIFAR/DASH": dict(model="UNET_BILINEAR_CIFAR", q_method=QuantizationMethod.ScaleQuant,
+                                     q_parameter=5, crt=7, mrs=100.0),
+    "DEEPLAB_HEAD_CIFAR/DASH": dict(model="DEEPLAB_HEAD_CIFAR", q_method=QuantizationMethod.ScaleQuant, q_parameter=5,
+                                    crt=7, mrs=100.0),
     "MODEL_A_ARGMAX/SIMPLE": dict(model="MODEL_A_ARGMAX", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8,
                                   mrs=100.0),
     "MODEL_A/SIMPLE": dict(model="MODEL_A", q_method=QuantizationMethod.SimpleQuant, q_parameter=-1, crt=8, mrs=100.0),
