@@ -623,6 +623,31 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u16x2 as_u16x2(uint32_t w) { return __builtin_bit_cast(u16x2, w); }
 __device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
 
+// Which form compress_xa / compress_xa2 take for a modulus (ModC::q, ModC::bits): chunk-aligned groups of 8 or 4
+// digits, runtime groups, or runtime groups of a power of two. The one predicate of the device dispatch below and
+// of the garbler's launch record (xa_class_name), so that the record cannot drift from the kernels.
+enum XaClass { XA_G8 = 0, XA_G4 = 1, XA_RT = 2, XA_PW2 = 3 };
+__host__ __device__ __forceinline__ XaClass xa_class(uint32_t q, uint32_t bits) {
+    if (kAlignedGroups && q <= 8) return XA_G8;
+    if (kAlignedGroups && q <= 64) return XA_G4;
+    return bits ? XA_PW2 : XA_RT;
+}
+// Digits per group of the runtime-group forms and the group's radix D: q^g <= 2^24 (power of two: 24 / b bits)
+__host__ __device__ __forceinline__ int xa_group(uint32_t q, uint32_t b, bool pw2, uint32_t& D) {
+    int g = 1;
+    D = q;
+    if (pw2) {
+        g = static_cast<int>(24 / b);
+        D = 1u << (b * g);
+    } else {
+        while (static_cast<uint64_t>(D) * q <= (1u << 24)) {
+            D *= q;
+            ++g;
+        }
+    }
+    return g;
+}
+
 // C * d + v for d, v < 2^24 (four 32-bit limbs, carries by 64-bit adds)
 __device__ __forceinline__ u128 mad128_24(u128 C, uint32_t d, uint32_t v) {
     const uint64_t lo = static_cast<uint64_t>(C), hi = static_cast<uint64_t>(C >> 64);
@@ -644,17 +669,8 @@ template <bool PW2>
 __device__ __forceinline__ u128 compress_xa_t(LRef x, const uint32_t* a, const ModC& m, uint32_t& d0) {
     const int nc = static_cast<int>(chunks_of(static_cast<int>(m.n)));
     const uint32_t q = m.q, b = m.bits;
-    int g = 1;  // digits per group: q^g <= 2^24 (power of two: 24 / b bits)
-    uint32_t D = q;
-    if (PW2) {
-        g = static_cast<int>(24 / b);
-        D = 1u << (b * g);
-    } else {
-        while (static_cast<uint64_t>(D) * q <= (1u << 24)) {
-            D *= q;
-            ++g;
-        }
-    }
+    uint32_t D;
+    const int g = xa_group(q, b, PW2, D);  // digits per group
     const u16x2 qq = {static_cast<unsigned short>(q), static_cast<unsigned short>(q)};
     const u16x2 msk = {static_cast<unsigned short>(q - 1), static_cast<unsigned short>(q - 1)};
     u128 C = 0;
@@ -759,9 +775,12 @@ __device__ __forceinline__ u128 compress_xa_g(LRef x, const uint32_t* a, const M
     return C;
 }
 __device__ __forceinline__ u128 compress_xa(LRef x, const uint32_t* a, const ModC& m, uint32_t& d0) {
-    if (kAlignedGroups && m.q <= 8) return compress_xa_g<8>(x, a, m, d0);
-    if (kAlignedGroups && m.q <= 64) return compress_xa_g<4>(x, a, m, d0);
-    return m.bits ? compress_xa_t<true>(x, a, m, d0) : compress_xa_t<false>(x, a, m, d0);
+    switch (xa_class(m.q, m.bits)) {
+        case XA_G8: return compress_xa_g<8>(x, a, m, d0);
+        case XA_G4: return compress_xa_g<4>(x, a, m, d0);
+        case XA_PW2: return compress_xa_t<true>(x, a, m, d0);
+        default: return compress_xa_t<false>(x, a, m, d0);
+    }
 }
 
 // Two keys of one label x with two uniform rows a1, a2 (two entry indices): x is read once, and the two
@@ -771,17 +790,8 @@ __device__ __forceinline__ void compress_xa2_t(LRef x, const uint32_t* a1, const
                                                u128& C2, uint32_t& d01, uint32_t& d02) {
     const int nc = static_cast<int>(chunks_of(static_cast<int>(m.n)));
     const uint32_t q = m.q, b = m.bits;
-    int g = 1;
-    uint32_t D = q;
-    if (PW2) {
-        g = static_cast<int>(24 / b);
-        D = 1u << (b * g);
-    } else {
-        while (static_cast<uint64_t>(D) * q <= (1u << 24)) {
-            D *= q;
-            ++g;
-        }
-    }
+    uint32_t D;
+    const int g = xa_group(q, b, PW2, D);
     const u16x2 qq = {static_cast<unsigned short>(q), static_cast<unsigned short>(q)};
     const u16x2 msk = {static_cast<unsigned short>(q - 1), static_cast<unsigned short>(q - 1)};
     C1 = 0;
@@ -897,10 +907,12 @@ __device__ __forceinline__ void compress_xa2_g(LRef x, const uint32_t* a1, const
 }
 __device__ __forceinline__ void compress_xa2(LRef x, const uint32_t* a1, const uint32_t* a2, const ModC& m, u128& C1,
                                              u128& C2, uint32_t& d01, uint32_t& d02) {
-    if (kAlignedGroups && m.q <= 8) compress_xa2_g<8>(x, a1, a2, m, C1, C2, d01, d02);
-    else if (kAlignedGroups && m.q <= 64) compress_xa2_g<4>(x, a1, a2, m, C1, C2, d01, d02);
-    else if (m.bits) compress_xa2_t<true>(x, a1, a2, m, C1, C2, d01, d02);
-    else compress_xa2_t<false>(x, a1, a2, m, C1, C2, d01, d02);
+    switch (xa_class(m.q, m.bits)) {
+        case XA_G8: compress_xa2_g<8>(x, a1, a2, m, C1, C2, d01, d02); break;
+        case XA_G4: compress_xa2_g<4>(x, a1, a2, m, C1, C2, d01, d02); break;
+        case XA_PW2: compress_xa2_t<true>(x, a1, a2, m, C1, C2, d01, d02); break;
+        default: compress_xa2_t<false>(x, a1, a2, m, C1, C2, d01, d02); break;
+    }
 }
 
 #ifndef DASH_GG_HASH_PAIRS
@@ -1020,6 +1032,23 @@ inline auto hash_jobs_kernel() { return gg_aes_copies() == 16 ? k_hash_jobs<16> 
 inline auto hash_iu_kernel(bool hard) {
     if (hard) return k_hash_iu<16, true>;
     return gg_aes_copies() == 16 ? k_hash_iu<16, false> : k_hash_iu<32, false>;
+}
+// the same picks by name, for the garbler's launch record
+inline const char* draw_kernel_name() { return gg_aes_copies() == 16 ? "k_draw<16>" : "k_draw<32>"; }
+inline const char* hash_kernel_name() { return gg_aes_copies() == 16 ? "k_hash<16>" : "k_hash<32>"; }
+inline const char* hash_jobs_kernel_name() { return gg_aes_copies() == 16 ? "k_hash_jobs<16>" : "k_hash_jobs<32>"; }
+inline const char* hash_iu_kernel_name(bool hard) {
+    if (hard) return "k_hash_iu<16,hard>";
+    return gg_aes_copies() == 16 ? "k_hash_iu<16>" : "k_hash_iu<32>";
+}
+// the record's name of a modulus' compress_xa form: g8, g4, rt<digits per group> or pw2
+inline std::string xa_class_name(uint32_t q, uint32_t bits) {
+    const XaClass cl = xa_class(q, bits);
+    if (cl == XA_G8) return "g8";
+    if (cl == XA_G4) return "g4";
+    if (cl == XA_PW2) return "pw2";
+    uint32_t D;
+    return "rt" + std::to_string(xa_group(q, bits, false, D));
 }
 // DASH_GG_KEYS (A/B knob): 2 (default) = uniform-i key hashes and bank payloads from the offsets' multiple rows
 // (compress_xa); 1 = multiple rows for the bank payloads only; 0 = the round-3 per-lane forms
@@ -2254,9 +2283,58 @@ size_t gpu_table_cache_bytes() {
     return c.cached;
 }
 
+// ---------------------------------------------------- garbler launch record
+// Off by default: one relaxed load where a line would be written. When on, the host side of the garbler appends
+//   entry <gadget> N=<elements> k=<residues>            one per gadget-level entry point. N is the number of
+//           elements the entry's gadget kernels run over: the layer's elements for sign, sign_relu,
+//           rescale_legacy_iter, rescale_mrs, relu_mrs, relu_mult, rescale_redash and base_ext; the level's pair
+//           differences (outputs x pairs per window) for maxpool_level; the OUTPUT count for sumpool; the INPUT
+//           count for dense (its labels on the device; the output count is the layer's)
+//   draw kernel=<name> grid=<g> blocks=<uncapped> cap=<c> lanes=<n>
+//   launch <kernel> grid=<g> blocks=<uncapped> cap=<c>  every capped launch (grid < blocks: the grid wrapped)
+//   project keys=<iu|jobs|entry|fused> hard=.. by_i=.. rin=.. N=.. scopes=.. tsh=a,b,.. emit_blocks=.. lds=..
+//           budget=<k_emit LDS budget, bytes>
+//           bank_paired=.. bank_single=.. hash=<kernel> xa=<q>:<class>,..
+// The evaluator's launch log (launch.h) is a separate list. Garbling contexts run on several threads: the list
+// is guarded by a mutex.
+namespace {
+std::atomic<bool> g_gglog_on{false};
+std::mutex g_gglog_mu;
+std::vector<std::string> g_gglog;
+inline bool gglog_on() { return g_gglog_on.load(std::memory_order_relaxed); }
+void gglog_add(std::string line) {
+    std::lock_guard<std::mutex> lk(g_gglog_mu);
+    g_gglog.push_back(std::move(line));
+}
+void gglog_entry(const char* gadget, int64_t N, int k) {
+    gglog_add(std::string("entry ") + gadget + " N=" + std::to_string(N) + " k=" + std::to_string(k));
+}
+}  // namespace
+
+void gpu_garbler_log_enable(bool on) { g_gglog_on.store(on, std::memory_order_relaxed); }
+std::vector<std::string> gpu_garbler_log_take() {
+    std::lock_guard<std::mutex> lk(g_gglog_mu);
+    std::vector<std::string> out;
+    out.swap(g_gglog);
+    return out;
+}
+std::string gpu_garbler_compress_class(int q) {
+    DASH_CHECK(q >= 2 && q < 32768, "gpu_garbler_compress_class: modulus outside [2, 32768)");
+    const dev::ModC m = make_modc(q);
+    return gg::xa_class_name(m.q, m.bits);
+}
+
 namespace {
 inline unsigned blocks_for(int64_t n, int bs, int cap = 65536) {
     return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + bs - 1) / bs, cap)));
+}
+// blocks_for of a capped, grid-strided launch, with its line in the launch record
+inline unsigned capped(const char* kernel, int64_t n, int bs, int cap) {
+    const unsigned g = blocks_for(n, bs, cap);
+    if (gglog_on())
+        gglog_add(std::string("launch ") + kernel + " grid=" + std::to_string(g) + " blocks=" +
+                  std::to_string(std::max<int64_t>(1, (n + bs - 1) / bs)) + " cap=" + std::to_string(cap));
+    return g;
 }
 
 // a cached device block with RAII return to the cache (or a borrowed buffer: never cached or freed)
@@ -2362,7 +2440,12 @@ inline int draw_block_cap() {
 }
 unsigned draw_grid(const gg::Gadget& g) {
     const int64_t lanes = (g.N + gg::kTile - 1) / gg::kTile * gg::kTile * g.ndraws;
-    return blocks_for(lanes, gg::kGB, draw_block_cap());
+    const unsigned grid = blocks_for(lanes, gg::kGB, draw_block_cap());
+    if (gglog_on())
+        gglog_add(std::string("draw kernel=") + gg::draw_kernel_name() + " grid=" + std::to_string(grid) + " blocks=" +
+                  std::to_string(std::max<int64_t>(1, (lanes + gg::kGB - 1) / gg::kGB)) + " cap=" +
+                  std::to_string(draw_block_cap()) + " lanes=" + std::to_string(lanes));
+    return grid;
 }
 
 // AES-CTR blocks per element: draws are laid out back to back in counter order
@@ -2381,6 +2464,8 @@ void check_desc(const gg::Gadget& g) {
 std::pair<u128*, uint16_t*> hc_scratch(size_t entries, int64_t N);
 u128* bank_scratch(size_t rows, int64_t N);
 const uint32_t* const* ensure_iR(const gg::Ctx& c, const std::vector<int>& mods);
+// the moduli ensure_iR builds a multiple row for (every modulus in use is within the context's ModC table)
+inline bool ir_row_modulus(int p) { return p >= 2 && p < 32768; }
 
 // Host-side function data of a projection set (the value f(i, d) of every entry): k_emit reads bank rows
 // and bank indices built from it here, so none of it is needed on the device.
@@ -2640,11 +2725,15 @@ void project(const gg::Ctx& c, gg::Gadget& g, const gg::In& in, const gg::Tables
     const bool iu = by_i;  // k_hash_iu writes the by-index layout k_emit then inverts
     em.by_i = by_i ? 1 : 0;
     em.fused = fused ? 1 : 0;
+    // key_mods: the key hashes' input moduli; bank_mods: the moduli of the bank rows with an R offset. Together the
+    // list ensure_iR gets; the launch record below names its compress_xa moduli from the same two vectors.
+    std::vector<int> key_mods, bank_mods;
+    for (const auto& p : pr) key_mods.push_back(p.pin);
+    for (const auto& r : rows)
+        if (r.res < 0) bank_mods.push_back(r.pout);
     {
-        std::vector<int> mods;
-        for (const auto& p : pr) mods.push_back(p.pin);
-        for (const auto& r : rows)
-            if (r.res < 0) mods.push_back(r.pout);
+        std::vector<int> mods = key_mods;
+        mods.insert(mods.end(), bank_mods.begin(), bank_mods.end());
         std::sort(mods.begin(), mods.end());
         mods.erase(std::unique(mods.begin(), mods.end()), mods.end());
         if (gg::gg_hash_mode() != 0) cc.iR = ensure_iR(c, mods);
@@ -2652,9 +2741,9 @@ void project(const gg::Ctx& c, gg::Gadget& g, const gg::In& in, const gg::Tables
     // (rejected, profiles/ab/README.md: one block per label group with the label staged in LDS, 7.2 -> 7.6-8.2 ms
     // per 4 GCs, and one wave per group stepping packed-byte payloads o + v*off incrementally, 10.7 ms)
     if (fused) DASH_CHECK(cc.iR != nullptr, "gpu garbler: fused emit without the offsets' multiple rows");
+    std::vector<gg::BankJob> bj;
     if (!rows.empty() && !fused) {
         // bank jobs: neighbouring rows of one slot label with R offsets pair up (one label read, two payloads)
-        std::vector<gg::BankJob> bj;
         const bool pairs = gg::gg_hash_mode() == 2;
         for (size_t r = 0; r < rows.size(); ++r) {
             const auto& a = rows[r];
@@ -2669,7 +2758,7 @@ void project(const gg::Ctx& c, gg::Gadget& g, const gg::In& in, const gg::Tables
             bj.push_back(gg::BankJob{static_cast<int>(r), -1});
         }
         const gg::BankJob* dbj = gg::dconst(bj.data(), bj.size());
-        hipLaunchKernelGGL(gg::k_bank, dim3(blocks_for(lanes * static_cast<int64_t>(bj.size()), 256, 32768)), dim3(256), 0,
+        hipLaunchKernelGGL(gg::k_bank, dim3(capped("k_bank", lanes * static_cast<int64_t>(bj.size()), 256, 32768)), dim3(256), 0,
                            gg::tl_st, cc, g, in, em.rows, dbj, static_cast<int>(bj.size()));
     }
     if (fused) {
@@ -2678,20 +2767,59 @@ void project(const gg::Ctx& c, gg::Gadget& g, const gg::In& in, const gg::Tables
         for (int pi = 0; pi < np; ++pi)
             for (int c0 = 0; c0 < pr[pi].pin; c0 += gg::kHJ) hj.push_back(gg::HashJob{pi, c0});
         const gg::HashJob* dj = gg::dconst(hj.data(), hj.size());
-        hipLaunchKernelGGL(gg::hash_iu_kernel(cc.hard != 0), dim3(blocks_for(lanes * static_cast<int64_t>(hj.size()), gg::kPB, 16384)),
+        hipLaunchKernelGGL(gg::hash_iu_kernel(cc.hard != 0),
+                           dim3(capped("k_hash_iu", lanes * static_cast<int64_t>(hj.size()), gg::kPB, 16384)),
                            dim3(gg::kPB), 0, gg::tl_st, cc, g, in, dj, static_cast<int>(hj.size()));
     } else if (gg::gg_hash_jobs()) {
         std::vector<gg::HashJob> hj;
         for (int pi = 0; pi < np; ++pi)
             for (int c0 = 0; c0 < pr[pi].pin; c0 += gg::kHJ) hj.push_back(gg::HashJob{pi, c0});
         const gg::HashJob* dj = gg::dconst(hj.data(), hj.size());
-        hipLaunchKernelGGL(gg::hash_jobs_kernel(), dim3(blocks_for(lanes * static_cast<int64_t>(hj.size()), gg::kPB, 16384)),
+        hipLaunchKernelGGL(gg::hash_jobs_kernel(),
+                           dim3(capped("k_hash_jobs", lanes * static_cast<int64_t>(hj.size()), gg::kPB, 16384)),
                            dim3(gg::kPB), 0, gg::tl_st, c, g, in, dj, static_cast<int>(hj.size()));
     } else {
-        hipLaunchKernelGGL(gg::hash_kernel(), dim3(blocks_for(lanes * g.entries, gg::kPB, 16384)), dim3(gg::kPB), 0,
+        hipLaunchKernelGGL(gg::hash_kernel(), dim3(capped("k_hash", lanes * g.entries, gg::kPB, 16384)), dim3(gg::kPB), 0,
                            gg::tl_st, c, g, in);
     }
-    hipLaunchKernelGGL(gg::k_emit, dim3(static_cast<unsigned>(std::min<int64_t>(em.blocks, 65536))), dim3(gg::kEB),
+    if (gglog_on()) {
+        const char* keys = fused ? "fused" : iu ? "iu" : gg::gg_hash_jobs() ? "jobs" : "entry";
+        const char* hash = fused ? "k_emit" : iu ? gg::hash_iu_kernel_name(cc.hard != 0)
+                                    : gg::gg_hash_jobs() ? gg::hash_jobs_kernel_name() : gg::hash_kernel_name();
+        // rin: a projection pays out an input label's multiple (R_INPUT), which keeps the set off the fused path
+        const bool rin = std::any_of(pr.begin(), pr.end(), [](const gg::Proj& p) { return p.outr_kind == gg::R_INPUT; });
+        std::string tshs;
+        for (const auto& S : sc) tshs += (tshs.empty() ? "" : ",") + std::to_string(S.tsh);
+        size_t bank_paired = 0, bank_single = 0;
+        for (const auto& j : bj) ++(j.r1 >= 0 ? bank_paired : bank_single);
+        // The moduli that reach compress_xa / compress_xa2, from the vectors ensure_iR was given:
+        //  * key_mods where the keys are hashed with a uniform entry index: k_hash_iu (iu) or k_emit's fused phase 1;
+        //    k_hash_jobs and k_hash (push_lin) never compress through a multiple row;
+        //  * bank_mods where the multiple rows exist (cc.iR set, i.e. DASH_GG_KEYS != 0) and ensure_iR built the
+        //    modulus' row (ir_row_modulus): bank_payload's `res < 0 && c.iR[pout]` branch, k_bank's pairs, and
+        //    k_emit's fused bank rows.
+        std::vector<int> xa;
+        if (iu || fused) xa = key_mods;
+        if (cc.iR != nullptr)
+            for (int q : bank_mods)
+                if (ir_row_modulus(q)) xa.push_back(q);
+        std::sort(xa.begin(), xa.end());
+        xa.erase(std::unique(xa.begin(), xa.end()), xa.end());
+        std::string xas;
+        for (int q : xa) {
+            const dev::ModC m = make_modc(q);
+            xas += (xas.empty() ? "" : ",") + std::to_string(q) + ":" + gg::xa_class_name(m.q, m.bits);
+        }
+        gglog_add(std::string("project keys=") + keys + " hard=" + std::to_string(c.hard ? 1 : 0) + " by_i=" +
+                  std::to_string(em.by_i) + " rin=" + (rin ? "1" : "0") + " N=" + std::to_string(g.N) + " scopes=" +
+                  std::to_string(sc.size()) +
+                  " tsh=" + tshs + " emit_blocks=" + std::to_string(em.blocks) + " lds=" + std::to_string(lds_max) +
+                  " budget=" + std::to_string(emit_lds_budget()) +
+                  " bank_paired=" + std::to_string(bank_paired) + " bank_single=" + std::to_string(bank_single) +
+                  " hash=" + hash + " xa=" + (xas.empty() ? "-" : xas));
+    }
+    // one block per (scope, tile of te elements), grid-strided past the cap (em.blocks >= 1)
+    hipLaunchKernelGGL(gg::k_emit, dim3(capped("k_emit", em.blocks, 1, 65536)), dim3(gg::kEB),
                        lds_max, gg::tl_st, fused ? cc : c, g, in, tb, em);
 }
 
@@ -2883,11 +3011,11 @@ const uint32_t* const* ensure_iR(const gg::Ctx& c, const std::vector<int>& mods)
         if (!a.n) return;
         int64_t mx = 1;
         for (int i = 0; i < a.n; ++i) mx = std::max<int64_t>(mx, static_cast<int64_t>(a.j[i].p) * a.j[i].words);
-        hipLaunchKernelGGL(gg::k_iR, dim3(blocks_for(mx, 256, 1024), a.n), dim3(256), 0, gg::tl_st, c, a);
+        hipLaunchKernelGGL(gg::k_iR, dim3(capped("k_iR", mx, 256, 1024), a.n), dim3(256), 0, gg::tl_st, c, a);
         a.n = 0;
     };
     for (int p : mods) {
-        if (p < 2 || p >= 32768 || p > d.mc_max) continue;
+        if (!ir_row_modulus(p) || p > d.mc_max) continue;
         auto& slot = d.iR_buf[p];
         if (slot.first && slot.second == d.iR_gen) continue;
         const int words = 4 * static_cast<int>(gg::chunks_of(nr_comps(p)));
@@ -3394,10 +3522,10 @@ static std::vector<DevBlock> sign_core(GpuGarbler::Impl& I, uint64_t layer, uint
         for (int j = 0; j < k; ++j) ma.out[j] = out[j].as<int16_t>();
         // the sign gadget's payload bank (>= 2 rows, its readers are done: same stream) now holds the two
         // mini-gate key hashes of the sign output
-        hipLaunchKernelGGL(gg::k_bin_keys, dim3(blocks_for(N, gg::kGB, 8192)), dim3(gg::kGB), 0, gg::tl_st, I.c,
+        hipLaunchKernelGGL(gg::k_bin_keys, dim3(capped("k_bin_keys", N, gg::kGB, 8192)), dim3(gg::kGB), 0, gg::tl_st, I.c,
                            static_cast<const int16_t*>(gg::slot_base(g, L.out_slot0)),
                            static_cast<const int16_t*>(nullptr), g.PB, N);
-        hipLaunchKernelGGL(gg::k_relu_finish, dim3(blocks_for(N, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c, gm, in,
+        hipLaunchKernelGGL(gg::k_relu_finish, dim3(capped("k_relu_finish", N, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c, gm, in,
                            tb, ma, static_cast<const u128*>(g.PB));
         tG.to_array(*mmg, I.device);
         tE.to_array(*mme, I.device);
@@ -3435,6 +3563,7 @@ void GpuGarbler::sign_layer(uint64_t layer, const SignPlan& sp, CrtLabels& cur, 
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_(relu_crt ? "relu" : "sign");
+    if (gglog_on()) gglog_entry(relu_crt ? "sign_relu" : "sign", I.cur_N, I.k);
     const int64_t N = I.cur_N;
     std::vector<void*> tmp;
     std::vector<int> omods;
@@ -3455,6 +3584,7 @@ void GpuGarbler::rescale_legacy_iter(uint64_t layer, int it, const RescalePlan& 
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_("rescale_iter");
+    if (gglog_on()) gglog_entry("rescale_legacy_iter", I.cur_N, I.k);
     const int64_t N = I.cur_N;
     const int k = I.k;
     std::vector<void*> tmp;
@@ -3496,9 +3626,9 @@ void GpuGarbler::rescale_legacy_iter(uint64_t layer, int it, const RescalePlan& 
     gg::SignLayout L = gg::sign_layout(P.sign, 0);
     // rows 0-1: the trans key hashes (k_bin_keys -> k_rescale_pre)
     u128* PB = I.pbank(2, N);
-    hipLaunchKernelGGL(gg::k_bin_keys, dim3(blocks_for(N, gg::kGB, 8192)), dim3(gg::kGB), 0, gg::tl_st, I.c,
+    hipLaunchKernelGGL(gg::k_bin_keys, dim3(capped("k_bin_keys", N, gg::kGB, 8192)), dim3(gg::kGB), 0, gg::tl_st, I.c,
                        static_cast<const int16_t*>(ra.L[0]), ra.up, PB, N);
-    hipLaunchKernelGGL(gg::k_rescale_pre, dim3(blocks_for(N, gg::kGB, 2048), k - 1), dim3(gg::kGB), 0, gg::tl_st, I.c,
+    hipLaunchKernelGGL(gg::k_rescale_pre, dim3(capped("k_rescale_pre", N, gg::kGB, 2048), k - 1), dim3(gg::kGB), 0, gg::tl_st, I.c,
                        ra, tb, PB, N);
     int16_t* S = I.scratch(static_cast<size_t>(N) * L.nslots * gg::kW * sizeof(int16_t));
     gg::In in{};
@@ -3521,7 +3651,7 @@ void GpuGarbler::rescale_legacy_iter(uint64_t layer, int it, const RescalePlan& 
     g.N = N;
     g.nslots = L.nslots;
     run_sign(I.c, L, g, in, tb, I.lut_fns());
-    hipLaunchKernelGGL(gg::k_rescale_post_g, dim3(blocks_for(N * 128, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c, ra,
+    hipLaunchKernelGGL(gg::k_rescale_post_g, dim3(capped("k_rescale_post_g", N * 128, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c, ra,
                        g, L.out_slot0);
     HIPCHECK(hipGetLastError());
     gg::end_layer(tmp);
@@ -3589,10 +3719,10 @@ static std::vector<DevBlock> relu_mult_gates(GpuGarbler::Impl& I, const gg::Gadg
     ma.sig_slot = sig_slot;
     ma.sk_slot0 = sk0;
     for (int j = 0; j < k; ++j) ma.out[j] = out[j].as<int16_t>();
-    hipLaunchKernelGGL(gg::k_bin_keys, dim3(blocks_for(N, gg::kGB, 8192)), dim3(gg::kGB), 0, gg::tl_st, I.c,
+    hipLaunchKernelGGL(gg::k_bin_keys, dim3(capped("k_bin_keys", N, gg::kGB, 8192)), dim3(gg::kGB), 0, gg::tl_st, I.c,
                        static_cast<const int16_t*>(gg::slot_base(g, sig_slot)), static_cast<const int16_t*>(nullptr),
                        gm.PB, N);
-    hipLaunchKernelGGL(gg::k_relu_finish, dim3(blocks_for(N, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c, gm, in,
+    hipLaunchKernelGGL(gg::k_relu_finish, dim3(capped("k_relu_finish", N, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c, gm, in,
                        tb, ma, static_cast<const u128*>(gm.PB));
     return out;
 }
@@ -3708,6 +3838,7 @@ void GpuGarbler::relu_mrs(uint64_t layer, const SignMrsPlan& P, CrtLabels& cur, 
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_("relu_mrs");
+    if (gglog_on()) gglog_entry("relu_mrs", I.cur_N, I.k);
     (void)relu_crt;
     const int64_t N = I.cur_N;
     std::vector<void*> tmp;
@@ -3817,7 +3948,7 @@ static void clip_core(GpuGarbler::Impl& I, uint64_t layer, const SignMrsPlan* pm
     tG.alloc(I.device, N, mmg.shape[1], mmg);
     tE.alloc(I.device, N, static_cast<int64_t>(k) * 3, mme, true);
     tC.alloc(I.device, N, static_cast<int64_t>(k) * 2, cap);
-    hipLaunchKernelGGL(gg::k_clip_u, dim3(blocks_for(static_cast<int64_t>(gg::kW / gg::kCh) * N, 256, 4096)), dim3(256), 0,
+    hipLaunchKernelGGL(gg::k_clip_u, dim3(capped("k_clip_u", static_cast<int64_t>(gg::kW / gg::kCh) * N, 256, 4096)), dim3(256), 0,
                        gg::tl_st, g, sig[0], sig[1], u_slot);
     gg::Tables tbm{};
     tbm.t[4] = tG.p(); tbm.row[4] = tG.row;
@@ -3876,7 +4007,7 @@ static void clip_core(GpuGarbler::Impl& I, uint64_t layer, const SignMrsPlan* pm
             ncmax = std::max(ncmax, cf.nc[j]);
         }
         cf.cap0 = cap0;
-        hipLaunchKernelGGL(gg::k_clip_finish, dim3(blocks_for(N * ncmax, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c,
+        hipLaunchKernelGGL(gg::k_clip_finish, dim3(capped("k_clip_finish", N * ncmax, 256, 4096), k), dim3(256), 0, gg::tl_st, I.c,
                            gc, cf);
     }
     HIPCHECK(hipGetLastError());
@@ -4039,6 +4170,7 @@ void GpuGarbler::rescale_mrs(uint64_t layer, const RescaleMrsPlan& P, CrtLabels&
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_("rescale_mrs");
+    if (gglog_on()) gglog_entry("rescale_mrs", I.cur_N, I.k);
     const int64_t N = I.cur_N;
     const int k = I.k;
     DASH_CHECK(P.k() == k && static_cast<int>(P.T) <= I.max_mod, "gpu garbler: mixed-radix rescale plan mismatch");
@@ -4169,6 +4301,7 @@ void GpuGarbler::relu_mult(uint64_t layer, CrtLabels& cur, const std::vector<i64
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_("relu_mult");
+    if (gglog_on()) gglog_entry("relu_mult", I.cur_N, I.k);
     const int64_t N = I.cur_N;
     const int k = I.k;
     DASH_CHECK(I.sig_slot >= 2 * k && I.sig_N == N, "gpu garbler: joint ReLU without a preceding sign-producing rescale");
@@ -4259,7 +4392,7 @@ void launch_lin(const gg::Ctx& c, const std::vector<gg::LinJob>& jobs, int64_t N
             a.j[i] = jobs[s0 + i];
             ncmax = std::max(ncmax, a.j[i].nc);
         }
-        hipLaunchKernelGGL(gg::k_lin, dim3(blocks_for(N * ncmax, 256, 8192), a.n), dim3(256), 0, gg::tl_st, c, a);
+        hipLaunchKernelGGL(gg::k_lin, dim3(capped("k_lin", N * ncmax, 256, 8192), a.n), dim3(256), 0, gg::tl_st, c, a);
     }
 }
 
@@ -4286,7 +4419,7 @@ void launch_gsum(const gg::Ctx& c, const std::vector<DevBlock>& dst, const std::
         for (int t = 0; t < K; ++t) a.j[j].cf[t] = static_cast<int>(pmod(coef(mods[j], t), mods[j]));
         ncmax = std::max(ncmax, a.j[j].nc);
     }
-    hipLaunchKernelGGL(gg::k_gsum, dim3(blocks_for(N * ncmax, 256, 8192), a.n), dim3(256), 0, gg::tl_st, c, a);
+    hipLaunchKernelGGL(gg::k_gsum, dim3(capped("k_gsum", N * ncmax, 256, 8192), a.n), dim3(256), 0, gg::tl_st, c, a);
 }
 
 struct DensePlanKey {
@@ -4669,6 +4802,7 @@ void GpuGarbler::dense(i64 in, i64 out, i64 ch, const i64* w, size_t nw, uint64_
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_("dense");
+    if (gglog_on()) gglog_entry("dense", I.cur_N, static_cast<int>(I.cur_mod.size()));
     DASH_CHECK(I.cur_N == in && static_cast<i64>(nw) == in * out, "gpu garbler: dense shape");
     const int k = static_cast<int>(I.cur_mod.size());
     DensePlan plan{};
@@ -4789,6 +4923,7 @@ void GpuGarbler::sumpool(const PoolGeom& G, CrtLabels& cur) {
     I.enter();
     I.check_cur(cur);
     DASH_CHECK(G.C * G.H * G.W == I.cur_N, "gpu garbler: sum pool input size");
+    if (gglog_on()) gglog_entry("sumpool", G.out_size(), static_cast<int>(I.cur_mod.size()));
     const int64_t Nout = G.out_size();
     const int K = static_cast<int>(G.kh * G.kw);
     // in-image taps first, then -1 (k_gsum skips those): padded / ceil-mode windows have fewer than K taps
@@ -4946,6 +5081,7 @@ void GpuGarbler::maxpool_level(uint64_t layer, int lv, i64 ops, const SignPlan& 
     I.enter();
     PhaseTrace tr_("maxpool_level");
     const int64_t Nout = I.mp_Nout, cnt = I.mp_cnt, cnt1 = ops + cnt % 2, Nd = Nout * ops;
+    if (gglog_on()) gglog_entry("maxpool_level", Nd, I.k);
     DASH_CHECK(ops >= 1 && 2 * ops <= cnt, "gpu garbler: max tree level shape");
     // pair differences D[o ops + q] = V[o cnt + 2q + 1] - V[o cnt + 2q]
     std::vector<int32_t> dm(static_cast<size_t>(Nd) * 2), am(static_cast<size_t>(Nout * cnt1)),
@@ -5207,6 +5343,7 @@ void GpuGarbler::rescale_redash(uint64_t layer, int it, const RescalePlan& P, Cr
     I.enter();
     I.check_cur(cur);
     PhaseTrace tr_("rescale_redash");
+    if (gglog_on()) gglog_entry("rescale_redash", I.cur_N, I.k);
     DASH_CHECK(!P.sign_be && I.cur_mod == I.crt, "gpu garbler: ReDash rescale plan mismatch");
     const int64_t N = I.cur_N;
     const int k = I.k;
@@ -5318,6 +5455,7 @@ void GpuGarbler::base_ext(uint64_t layer, const BEPlan& P, CrtLabels& cur, Array
     I.enter();
     I.check_cur(cur);
     DASH_CHECK(P.moduli == I.cur_mod, "gpu garbler: base extension plan mismatch");
+    if (gglog_on()) gglog_entry("base_ext", I.cur_N, static_cast<int>(P.moduli.size()));
     const int64_t N = I.cur_N;
     const int E = static_cast<int>(P.moduli.size());
     std::vector<gg::Draw> dr;

@@ -303,4 +303,14 @@ class GpuGarbler {
 void gpu_table_cache_trim();
 size_t gpu_table_cache_bytes();
 
+// The GPU garbler's launch record (garble_gpu.hip, host side only; off by default, one relaxed load per line
+// that would be written). A list of its own beside the evaluator's launch log (launch.h): one line per gadget
+// entry point, draw launch, capped launch and projection set (key path, scopes, compress_xa classes). take
+// returns the lines recorded so far and clears them. gpu_garbler_compress_class: the record's name of the
+// compress_xa form a modulus takes ("g8", "g4", "rt<digits per group>", "pw2"), from the
+// predicate the kernels dispatch on; it needs no device.
+void gpu_garbler_log_enable(bool on);
+std::vector<std::string> gpu_garbler_log_take();
+std::string gpu_garbler_compress_class(int q);
+
 }  // namespace dash

@@ -21,6 +21,7 @@
 #include "host_util.h"
 #include "launch.h"
 #include "fetch.h"
+#include "gpu_garbler.h"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 
@@ -2575,6 +2576,11 @@ void register_hip_bindings(py::module_& m) {
     });
     m.def("hip_launch_log", [](bool on) { dev::launch_log_enable(on); }, py::arg("on"));
     m.def("hip_launch_log_take", []() { return dev::launch_log_take(); });
+    // The GPU garbler's own launch record (gpu_garbler.h): a separate list, so the evaluator's log above keeps
+    // its contents. hip_garbler_compress_class is host arithmetic only.
+    m.def("hip_garbler_log", [](bool on) { gpu_garbler_log_enable(on); }, py::arg("on"));
+    m.def("hip_garbler_log_take", []() { return gpu_garbler_log_take(); });
+    m.def("hip_garbler_compress_class", [](int q) { return gpu_garbler_compress_class(q); }, py::arg("q"));
     // The conv kernel plan of a dense-conv layer, exactly as the evaluator (mfma: its switch) and the GPU garbler
     // plan it (launch.h conv_layer_plan). Host arithmetic only: works without a device.
     // dh, dw: dilation (a kernel axis of size 1 normalises its dilation to 1, as ConvGeom does). The result also
